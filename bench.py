@@ -2,6 +2,7 @@
 """bench.py -- docs/sec forward+backward through the CAGGC+MAGGC stack on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5|c1] [--mode graph|eager] [--global-batch G]
+                    [--dump-outputs DIR] [--full]
 
 One step = one forward + backward of GATAttention -> GraphConvolution -> MultiHeadAttention ->
 MultiGraphConvolution (the hop loop of GCGCN_glove.py:329-341) over one batch of B synthetic
@@ -14,9 +15,13 @@ along the batch axis -- weak scaling by default (B per GPU fixed), strong scalin
 (G / N documents per GPU; SURVEY 8d: G = 256) -- and the step ends with ONE RCCL all-reduce of the flat
 gradient bucket.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with two extra objects:
-  roofline     -- the dominant kernel's algorithmic HBM bytes / its HIP-event-timed duration
-  cpu_baseline -- the CPU oracle (a port of the reference's op sequence) timed on this host's cores
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline figure
+(`value` docs/s, `ms_per_step`).  With ``--full`` it also measures, outside the timed region:
+  roofline         -- the dominant kernel's algorithmic work / its HIP-event-timed duration (after a per-family pre-pass)
+  roofline_hbm     -- the same for the backward edge pass
+  extra            -- the cache-warm figure (one batch replayed back to back)
+  cpu_baseline     -- the CPU oracle (a port of the reference's op sequence) timed on this host's cores
+``--dump-outputs DIR`` writes what the last timed step computed (the hop stack's output and every gradient) to DIR/<name>.npy.
 """
 import argparse
 import ctypes
@@ -109,6 +114,26 @@ def cpu_baseline(cfg, budget_s=20.0):
                       "per-document tensors -- BASELINE.md 3 says os.cpu_count(), this is the deviation)"}
 
 
+DUMP_BUDGET = 15_000_000          # float32 elements over all dumped arrays: 60 MB
+
+
+def dump_outputs(out_dir, named):
+    """Write each (name, device tensor) to out_dir/<name>.npy as float32.  The budget is shared out smallest array first:
+    arrays that fit are written whole, the rest as a sample of sorted flat indices drawn by a generator seeded with the
+    array's position in `named` -- the same elements on every run with the same arguments, whatever the build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left, order = DUMP_BUDGET, sorted(range(len(named)), key=lambda i: named[i][1].numel())
+    for j, i in enumerate(order):
+        name, t = named[i]
+        a, take = t.detach(), min(t.numel(), left // (len(order) - j))
+        left -= take
+        if take < t.numel():
+            idx = torch.randint(t.numel(), (take,), generator=torch.Generator().manual_seed(i)).sort().values
+            a = a.reshape(-1)[idx.to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.float().cpu().numpy())
+
+
 def self_launch(ngpus):
     """``python bench.py --gpus N`` without a torch.distributed environment: start the N ranks as children of this process
     (which has not touched a GPU: no HIP call, no torch.cuda.is_available()), wait, and exit with their status.  Rank 0 of the
@@ -137,8 +162,14 @@ def main():
                          "bracketed by HIP events for the roofline (every 10th) run eagerly -- same kernels, same data. "
                          "eager: every step is issued from Python (the GPU time is the same; the host's jitter is not)")
     ap.add_argument("--prof-kernel", default="auto",
-                    help="kernel family timed with HIP events inside the timed region (auto = the one with the largest time share)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: kernel family timed with HIP events after the timed region (auto = the one with the largest time share)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the per-family time shares, the roofline objects, the cache-warm "
+                         "replay figure and the CPU baseline (extra steps and runs outside the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (output, input and parameter gradients) as DIR/<name>.npy, "
+                         "float32, a fixed seeded sample of the largest arrays (at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--eval-mode", action="store_true", help="A/B only: dropout off (the metric is defined in train mode)")
     ap.add_argument("--input-sets", type=int, default=3,
                     help="resident synthetic batches rotated through the steps (default 3: 3 x (E1 + E2) = 805 MB at cfg 2, "
@@ -225,6 +256,7 @@ def main():
             t.requires_grad_()
         sets.append((x, e1, e2, adj))
     cot = torch.ones(B, N, D, device=dev)         # d(sum(out))/d(out)
+    outs = [None] * nsets                         # the output of the last step on each batch (in graph mode: the captured one)
 
     def fwd_bwd(k):
         x, e1, e2, adj = sets[k]
@@ -232,8 +264,9 @@ def main():
         bucket.zero_grad()
         out = hops(x, [e1, e2], adj, n_valid=n_valid)[-1]
         torch.autograd.backward(out, cot)
+        outs[k] = out
 
-    graphs, graph_grads = [], []
+    graphs, graph_grads, graph_outs = [], [], []
     if args.mode == "graph":                      # capture the launch-bound step in one hipGraph per resident batch
         try:
             s = torch.cuda.Stream()
@@ -248,9 +281,10 @@ def main():
                     fwd_bwd(k)
                 graphs.append(g)
                 graph_grads.append([(p, p.grad) for p in bucket.params])   # the tensors that graph's replays write the gradients into
+                graph_outs.append([outs[k]] + [t.grad for t in sets[k][:3]])   # ... and the output and the input gradients into
         except Exception as ex:                   # never lose the measurement to a capture problem: issue the steps eagerly
             print(f"bench.py: hipGraph capture failed ({ex!r}); running --mode eager", file=sys.stderr)
-            graphs, graph_grads = [], []
+            graphs, graph_grads, graph_outs = [], [], []
             args.mode = "eager"
             torch.cuda.synchronize()
     counter = [0]
@@ -307,7 +341,7 @@ def main():
     for _ in range(2):                                         # first touches (allocator, code objects) before the pre-pass
         step()
     sync()
-    use_prof = True
+    use_prof = args.full
     # which kernel family dominates the step?  (untimed pre-pass, 3 steps per family)
     shares = {}
     dominant = args.prof_kernel
@@ -349,6 +383,12 @@ def main():
         print("per-step GPU ms:", [round(_evs[i][0].elapsed_time(_evs[i + 1][0]), 3) for i in range(len(_evs) - 1)], file=sys.stderr)
         print("host issue ms:", [round(t * 1e3, 2) for _, t in _evs], "total", round(dt * 1e3, 2), file=sys.stderr)
     gc.enable()
+    if args.dump_outputs and rank == 0:                        # before any step outside the region overwrites them
+        k = (args.steps - 1) % nsets                           # the timed steps ran on batches 0, 1, .. mod nsets
+        got = graph_outs[k] if graphs else [outs[k]] + [t.grad for t in sets[k][:3]]
+        named = list(zip(("out", "x.grad", "e1.grad", "e2.grad"), got))
+        named += [(n + ".grad", p.grad) for n, p in hops.named_parameters() if p.grad is not None]   # (flat_k gets none)
+        dump_outputs(args.dump_outputs, named)
     # the dominant kernel family, HIP events on its launches (hipExtLaunchKernelGGL start/stop events on the launch stream),
     # on `nsamp` eagerly issued steps right after the region
     nsamp = max(1, min(5, args.steps))
@@ -402,13 +442,13 @@ def main():
                     r["mfma_busy"] = round(avg("mfma_busy"), 4)
         return r
 
-    roofline = roof(dominant, kms, kn, kw, nsamp)
+    roofline = roof(dominant, kms, kn, kw, nsamp) if use_prof else None
     if roofline is not None:
         roofline["sampled_on"] = (f"{nsamp} eagerly issued steps directly after the {args.steps} timed steps (same kernels, same "
                                   "rotating inputs; the timed region itself is " + ("hipGraph replays only)" if graphs else "eager steps without events)"))
     # the cache-warm figure (one batch replayed back to back, E1 partly served from the Infinity Cache) for comparison
     warm = None
-    if nsets > 1 and rank == 0 and world == 1 and not force_dist:
+    if args.full and nsets > 1 and rank == 0 and world == 1 and not force_dist:
         for _ in range(3):
             step(k=0, collective=False)
         torch.cuda.synchronize()
@@ -459,18 +499,18 @@ def main():
                        "global_batch": B * world, "mode": args.mode, "input_sets": nsets,
                        "parallelism": f"dp{world}", "grad_allreduce": ("per-block, overlapped with backward (tensor hooks)"
                                                                        if args.overlap_grads else "one coalesced collective after backward")},
-            "roofline": roofline,
-            "roofline_hbm": roofline_hbm,
             "whole_step": {"hbm_frac": round(value / world * bytes_doc / HBM_PEAK, 4),
                            "mfma_frac": round(value / world * flops / MFMA_F32_PEAK, 4),
                            "algorithmic_bytes_per_doc": bytes_doc, "algorithmic_flops_per_doc": flops},
-            "time_shares_ms_per_step": {k: v for k, v in shares.items() if v["launches_per_step"]},
         }
+        if args.full:
+            line["roofline"], line["roofline_hbm"] = roofline, roofline_hbm
+            line["time_shares_ms_per_step"] = {k: v for k, v in shares.items() if v["launches_per_step"]}
         if warm is not None:
             line["extra"] = {"warm_replay_ms_per_step": round(warm * 1e3, 4), "warm_replay_docs_per_s": round(B / warm, 2),
                              "note": "one resident batch replayed back to back (the round-1 bench): its E1 is partly served from "
                                      "the 256 MiB Infinity Cache; `value` above is the rotating-input (cold) figure"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(cfg)
         real_stdout.write(json.dumps(line) + "\n")
         real_stdout.flush()

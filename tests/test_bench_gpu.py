@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -27,7 +28,7 @@ def _run(args, env=None, timeout=300):
 
 
 def test_bench_line_contract(gpu_device):
-    d = _run(["--config", "c1", "--steps", "6", "--warmup", "2"])
+    d = _run(["--config", "c1", "--steps", "6", "--warmup", "2", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -44,6 +45,25 @@ def test_bench_line_contract(gpu_device):
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "documents" in cb["sample"]
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(gpu_device, tmp_path):
+    """Without --full the line carries the headline figure and nothing measured outside the timed region; --dump-outputs
+    writes the output and every gradient of the last timed step, float32, within 64 MB, the same elements on every run."""
+    runs = []
+    for r in range(2):
+        d = _run(["--config", "c1", "--steps", "5", "--warmup", "1", "--dump-outputs", str(tmp_path / str(r))])
+        assert d["steps"] == 5 and d["ms_per_step"] > 0 and abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3
+        for k in ("roofline", "roofline_hbm", "time_shares_ms_per_step", "extra", "cpu_baseline"):
+            assert k not in d, k
+        runs.append({f: np.load(tmp_path / str(r) / f) for f in sorted(os.listdir(tmp_path / str(r)))})
+    a, b = runs
+    assert {"out.npy", "x.grad.npy", "e1.grad.npy", "e2.grad.npy", "graphcnn.1.flat.grad.npy"} <= set(a) and set(a) == set(b)
+    assert sum(os.path.getsize(tmp_path / "0" / f) for f in a) <= 64e6
+    assert a["out.npy"].shape == (8, 16, 128) and a["x.grad.npy"].shape == (8, 16, 128)
+    for f in a:
+        assert a[f].dtype == np.float32 and a[f].shape == b[f].shape and np.isfinite(a[f]).all(), f
+        assert np.abs(a[f] - b[f]).max() <= 1e-4 * max(1.0, np.abs(a[f]).max()), f
+
+
 def test_bench_distributed_path_on_one_rank_and_strong_scaling_flag(gpu_device):
     d = _run(["--config", "c1", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--global-batch", "16"], env={"GCGCN_FORCE_DIST": "1"})
     assert d["n_gpus"] == 1 and d["scaling"] == "strong" and d["config"]["global_batch"] == 16 and "B=16/GPU" in d["config"]["workload"]
@@ -56,7 +76,8 @@ def test_bench_two_ranks_complete_and_print_one_line(gpu_device):
     """Round-3 verdict: the sampling steps after the timed region all-reduced on rank 0 only, so any N > 1 run would have hung
     before its JSON line.  Two real ranks, self-launched through torch.distributed.run exactly like ``--gpus N`` without the
     driver's environment; the profiling / warm-replay steps (rank 0 only, or a per-rank count) now issue no collectives."""
-    d = _run(["--gpus", "2", "--dist-backend", "gloo", "--config", "c1", "--steps", "4", "--warmup", "1", "--no-cpu-baseline"], timeout=540)
+    d = _run(["--gpus", "2", "--dist-backend", "gloo", "--config", "c1", "--steps", "4", "--warmup", "1", "--full", "--no-cpu-baseline"],
+             timeout=540)
     assert d["n_gpus"] == 2 and d["config"]["global_batch"] == 16 and d["config"]["parallelism"] == "dp2"
     assert d["steps"] == 4 and d["warmup"] == 1 and d["scaling"] == "weak" and d["value"] > 0
     assert abs(d["value"] - 16 * 1e3 / d["ms_per_step"]) / d["value"] < 1e-3               # whole-job docs/s = global batch / step time
