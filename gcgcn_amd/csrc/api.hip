@@ -101,18 +101,15 @@ static long scratch_elems(int B, int N, int D, int H) { return gemm_scratch_elem
 
 // Run-time A/B switches.  option("head_v1", -1) reads gcgcn_set_option's value if one was set, else the environment
 // variable GCGCN_HEAD_V1 (read once), else the default.  Every knob a test has to flip lives here, so that one process
-// can run both sides of an A/B (function-local statics around getenv could not be switched by the test suite).
+// can run both sides of an A/B; the knobs whose A/B is settled are constants at their use.
 struct Opt {
   const char* name;
   int value;
   bool resolved;
 };
-static Opt g_opts[] = {{"head_v1", 0, false},      {"head_bil3", 0, false},    {"head_bil3_bwd", 0, false}, {"head_dw3", 0, false},
-                       {"chain_fuse", 0, false},   {"chain_carry", 0, false},  {"gat_ride", 0, false},      {"chain_t", 0, false},
-                       {"mha_ride", 0, false},     {"maggc_fuse", 0, false},   {"carry_spread", 0, false},  {"chain_spread", 0, false},
-                       {"carry_cohort", 0, false}, {"chain_cohort", 0, false}, {"carry_spread_min", 0, false},
-                       {"chain_spread_min", 0, false}, {"att_in_chain", 0, false}, {"fold_slices", 0, false}, {"head_sum_fold", 0, false},
-                       {"head_compact", 0, false}, {"chain_big", 0, false},   {"split_widen", 0, false}};
+static Opt g_opts[] = {{"head_v1", 0, false},      {"head_bil3", 0, false}, {"head_bil3_bwd", 0, false}, {"head_dw3", 0, false},
+                       {"head_compact", 0, false}, {"chain_t", 0, false},   {"chain_big", 0, false},     {"split_widen", 0, false},
+                       {"chain", 0, false},        {"mha_core", 0, false},  {"group_dump", 0, false}};
 int option(const char* name, int dflt) {
   for (Opt& o : g_opts) {
     if (strcmp(o.name, name) != 0) continue;
@@ -138,16 +135,9 @@ static bool set_opt(const char* name, int value) {
   return false;
 }
 
-// GCGCN_NO_CHAIN=1 (or gcgcn_set_option("chain", 0)) runs every per-(doc, head) product as its own batched
-// launch instead of inside the chain kernels (A/B testing of chain.hip).
-static int g_chain = -1;
-static bool use_chain() {
-  if (g_chain < 0) {
-    const char* e = getenv("GCGCN_NO_CHAIN");
-    g_chain = (e && e[0] == '1') ? 0 : 1;
-  }
-  return g_chain != 0;
-}
+// option chain = 0 (GCGCN_CHAIN=0) runs every per-(doc, head) product as its own batched launch instead of inside the chain
+// kernels (A/B testing of chain.hip).
+static bool use_chain() { return option("chain", 1) != 0; }
 
 // Graphs of more than 64 entities have no LDS-resident chain kernel: the generic chain kernels hand every product's tiles through
 // L2 inside one workgroup per (document, head) pair, and at that size each product is a full launch of its own anyway (cfg 5:
@@ -159,16 +149,9 @@ static bool use_chain_for(int N, bool fwd_with_ride) {
   return N <= 64 || fwd_with_ride || option("chain_big", 0) != 0;
 }
 
-// GCGCN_NO_MHA_CORE=1 (or gcgcn_set_option("mha_core", 0)) sends small graphs through the generic batched-GEMM +
-// row-softmax attention path as well (A/B testing of mha_core.hip).
-static int g_mha_core = -1;
-static bool use_mha_core() {
-  if (g_mha_core < 0) {
-    const char* e = getenv("GCGCN_NO_MHA_CORE");
-    g_mha_core = (e && e[0] == '1') ? 0 : 1;
-  }
-  return g_mha_core != 0;
-}
+// option mha_core = 0 (GCGCN_MHA_CORE=0) sends small graphs through the generic batched-GEMM + row-softmax attention path as
+// well (A/B testing of mha_core.hip).
+static bool use_mha_core() { return option("mha_core", 1) != 0; }
 
 // gcgcn_edge_ride -> EdgeRide (kind 1: edge mean forward, 2: its backward); NULL = no passenger
 static int make_ride(const char* who, const gcgcn_edge_ride* ride, int kind, EdgeRide& r) {
@@ -211,14 +194,6 @@ const char* gcgcn_last_error(void) { return g_err; }
 
 int gcgcn_set_option(const char* name, int value) {
   GC_REQUIRE(name, "set_option: null name");
-  if (strcmp(name, "chain") == 0) {
-    g_chain = value ? 1 : 0;
-    return 0;
-  }
-  if (strcmp(name, "mha_core") == 0) {
-    g_mha_core = value ? 1 : 0;
-    return 0;
-  }
   if (set_opt(name, value)) return 0;
   set_error("set_option: unknown option '%s'", name);
   return 1;
@@ -346,13 +321,10 @@ int gcgcn_gat_bwd(int B, int N, int D, int Dh, const float* X, const float* E, c
   const long M = (long)B * N;
   GC_REQUIRE(scratch, "gat_bwd: scratch is required");
   const bool small = gat_dlogit_ok(N);
-  const bool ride = option("gat_ride", 1) != 0;
   GatTail tail{P, dA, uvc, dX_in, ds, dX, drop, B, gat_dlogit_slices(D)};
-  if (small && ride) {
+  if (small) {
     // dlogit, ds and dX = ds u + dX_in ride in the edge pass below: its entity rows take their dlogit row from P and dA
     // themselves, B * slices passenger workgroups produce ds and dX (dlogit is never stored)
-  } else if (small) {  // the same in a launch of its own, one workgroup per (document, slice)
-    GC_TRY(gat_dlogit(P, dA, uvc, dX_in, dlogit, ds, dX, B, N, D, drop, st));
   } else {
     GC_TRY(softmax_bwd(P, dA, dlogit, M, N, drop, st));
     // ds[b, j] = sum_i dlogit[b, i, j]
@@ -360,7 +332,7 @@ int gcgcn_gat_bwd(int B, int N, int D, int Dh, const float* X, const float* E, c
     GC_TRY(node_score_bwd(ds, uvc, dX_in, dX, M, D, st));
   }
   GC_TRY(edge_bwd(E, uvc + D, n_valid, dlogit, dEbar, dE, dvpart, B, N, D, st, (DeferQueue*)defer_queue,  // + parked weight gradients
-                  small && ride ? &tail : nullptr));
+                  small ? &tail : nullptr));
   // du = sum_m ds[m] X[m,:],  dv = sum partials,  dc = sum_m ds[m]: row-slice partials in one launch; the fold's
   // backward sums the slices itself (duvc stays unused)
   long part_off[3];
@@ -709,9 +681,8 @@ int gcgcn_gcn_bwd(int B, int N, int D, int L, int H, const float* X, const float
     // launch: dY = dropout_bwd(dHO) is the product's own epilogue (the forward mask: same site, same element offsets), and the
     // residual gradient dXres = sum_h dHO_h = dout (sum_h Wlin_h) is one more small product (one head: dHO itself, written
     // beside dY).  At cfg 3 the extra product and the second store cost more than the launch they save (round 2: +8 us).
-    const long fold_opt = option("head_sum_fold", 1);   // 0 off, 1 up to 2 M elements of dHO, n > 1: up to n M elements (A/B)
-    const bool fold_hs = fold_opt != 0 && scratch && (H == 1 || wsum_fwd) && (long)M * HD <= (fold_opt > 1 ? fold_opt : 2) * (1L << 20) &&
-                         (((uintptr_t)dXres) & 15) == 0;
+    constexpr long fold_max = 2L << 20;   // elements of dHO up to which the fold pays
+    const bool fold_hs = scratch && (H == 1 || wsum_fwd) && (long)M * HD <= fold_max && (((uintptr_t)dXres) & 15) == 0;
     {  // one launch: dHO = dout Wlin  and  dWlin = dout^T HO
       GemmArgs gs[3];
       gs[0].ws = gs[1].ws = gs[2].ws = scratch, gs[0].ws_elems = gs[1].ws_elems = gs[2].ws_elems = wse;
@@ -853,7 +824,7 @@ int gcgcn_gcn_bwd(int B, int N, int D, int L, int H, const float* X, const float
     }
     // + the attention core's backward: as passenger workgroups of this launch where a (document, head) pair's scratch fits
     // the tile kernel's LDS (head width <= 32), as a launch of its own in front of it otherwise
-    const bool mha_rides = mha && gemm_group_can_carry_mha(D / H) && option("mha_ride", 1) != 0;
+    const bool mha_rides = mha && gemm_group_can_carry_mha(D / H);
     if (mha_rides) mp.kchunk = gemm_group_mha_chunk(D / H);
     if (mha && !mha_rides)
       GC_TRY(mha_core_bwd(mp.Q, mp.P, mp.dA, mp.dQ, B, N, D, H, mp.alpha, mp.drop, st));
@@ -867,7 +838,7 @@ int gcgcn_maggc_fusable(int N, int D, int H) {
   const int dh = D / H;
   // (the backward core rides in a group launch only for head widths up to 32; wider heads keep that launch, and still gain
   // the query projection inside the forward group launch and the forward core inside the chain workgroups)
-  return use_mha_core() && dh % 4 == 0 && D % 4 == 0 && option("maggc_fuse", 1) != 0 ? 1 : 0;
+  return use_mha_core() && dh % 4 == 0 && D % 4 == 0 ? 1 : 0;
 }
 
 // ---------------------------------------------------------------------------------------------

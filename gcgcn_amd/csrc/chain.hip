@@ -94,8 +94,8 @@ __global__ __launch_bounds__(64 * CW) void gcn_chain_fwd_kernel(const GcnCtx c) 
   __shared__ __attribute__((aligned(16))) float lds[CHAIN_LDS];
   if (blockIdx.x >= c.B * c.H) {  // passenger workgroup: one entity row of the riding edge mean
     const EdgeRide& r = c.ride;
-    edge_fwd_row<4, false, true, CW>(r.in, nullptr, r.n_valid, r.out, nullptr, nullptr, nullptr, Drop(), r.N, r.D,
-                                     blockIdx.x - c.B * c.H, lds);
+    edge_fwd_row<4, false, CW>(r.in, nullptr, r.n_valid, r.out, nullptr, nullptr, nullptr, Drop(), r.N, r.D,
+                               blockIdx.x - c.B * c.H, lds);
     return;
   }
   const int z = blockIdx.x;  // b * H + h
@@ -262,8 +262,8 @@ __global__ __launch_bounds__(64 * CW) void gcn_chain_s_fwd_kernel(const GcnCtx c
   __shared__ __attribute__((aligned(16))) float lds[S_FWD_LDS];
   if (blockIdx.x >= c.B * c.H) {  // passenger workgroup: one entity row of the riding edge mean
     const EdgeRide& r = c.ride;
-    edge_fwd_row<4, false, true, CW>(r.in, nullptr, r.n_valid, r.out, nullptr, nullptr, nullptr, Drop(), r.N, r.D,
-                                     blockIdx.x - c.B * c.H, lds);
+    edge_fwd_row<4, false, CW>(r.in, nullptr, r.n_valid, r.out, nullptr, nullptr, nullptr, Drop(), r.N, r.D,
+                               blockIdx.x - c.B * c.H, lds);
     return;
   }
   TS(0);
@@ -822,10 +822,9 @@ static bool chain_t_takes(const GcnCtx& c, bool bwd) {
   return chain_t_ok(c, bwd) && !chain_s_preferred(c, s_ok);
 }
 bool chain_bwd_fusable(const GcnCtx& c) {   // asked before c.dout is set
-  const bool on = option("chain_fuse", 1) != 0;
   auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  if (on && chain_t_takes(c, true)) return chain_t_bwd_fusable(c);
-  return on && chain_small_ok(c, true) && c.N == 64 && (c.H == 1 || c.H == 8) && al(c.A) && al(c.Pn) && al(c.Y) && al(c.dM) &&
+  if (chain_t_takes(c, true)) return chain_t_bwd_fusable(c);
+  return chain_small_ok(c, true) && c.N == 64 && (c.H == 1 || c.H == 8) && al(c.A) && al(c.Pn) && al(c.Y) && al(c.dM) &&
          al(c.dP) && al(c.dA) && al(c.flat + c.oWd) && al(c.flat + c.oWlin) && c.HD % 4 == 0;
 }
 
@@ -838,7 +837,6 @@ static bool chain_aligned(const GcnCtx& c, bool bwd) {
 }
 
 bool chain_fwd_computes_attention(const GcnCtx& c) {   // before c.mha is set: a question about the shape and the options
-  if (option("att_in_chain", 1) == 0) return false;
   if (chain_t_takes(c, false)) return chain_t_fwd_att_ok(c);
   return chain_aligned(c, false) && chain_small_ok(c, false) && mha_lds_bytes(c.D / c.H) <= sizeof(float) * 64 * S_LP &&
          (c.D / c.H) % 4 == 0;
@@ -849,17 +847,6 @@ bool chain_can_carry(const EdgeRide& r) {
   auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
   return r.kind != 0 && r.D % 4 == 0 && al(r.in) && al(r.out) && (long)CW * r.D <= CHAIN_LDS &&
          (long)r.B * r.N <= 0x3fffffffL;
-}
-
-// GCGCN_CHAIN_CARRY=0: no parked products in the chain launches (A/B knob)
-static bool chain_passengers() { return option("chain_carry", 1) != 0; }
-
-static long carry_budget_pct() {  // GCGCN_CHAIN_CARRY_PCT: tuning knob, default 50
-  static const long v = [] {
-    const char* e = getenv("GCGCN_CHAIN_CARRY_PCT");
-    return e ? atol(e) : 50L;
-  }();
-  return v;
 }
 
 static unsigned chain_grid(const GcnCtx& c, int kind) {
@@ -901,9 +888,9 @@ int gcn_chain_bwd(const GcnCtx& c, hipStream_t st, DeferQueue* carry) {
   // split at the budget, the rest of its tiles rides in GATAttention's edge pass.  K % 64 == 0 for equal halves.
   const bool s_ok = chain_aligned(c, true) && chain_small_ok(c, true);
   const bool use_t = chain_t_ok(c, true) && !chain_s_preferred(c, s_ok);
-  if (use_t) return gcn_chain_t_bwd(c, fl, st, chain_passengers() ? carry : nullptr);
+  if (use_t) return gcn_chain_t_bwd(c, fl, st, carry);
   int ng = 0;
-  if (carry && carry->n > 0 && (long)c.B * c.H <= 64 && ((long)c.B * c.N) % 64 == 0 && chain_passengers()) {
+  if (carry && carry->n > 0 && (long)c.B * c.H <= 64 && ((long)c.B * c.N) % 64 == 0) {
     const int passes = (((c.N + 63) / 64) * ((c.gh + 63) / 64) + 1) / 2;
     const double t_chain = 8.0 * (4 * c.L - 1) * passes;                  // us
     const double t_tile = 0.47 * ((double)c.B * c.N / 32.0);              // us: weight gradients have K = B N
@@ -912,7 +899,7 @@ int gcn_chain_bwd(const GcnCtx& c, hipStream_t st, DeferQueue* carry) {
     for (int i = 0; i < carry->n; ++i) halves = halves && carry->p[i].K % 64 == 0 && !carry->p[i].rb;   // (row-block products ride elsewhere)
     // the riding dE broadcast needs its share of the idle compute units too: with it aboard only half of them take a tile
     long budget = rounds * (256 - (long)c.B * c.H);
-    if (c.ride.kind == 2) budget = carry_budget_pct() * budget / 100;
+    if (c.ride.kind == 2) budget /= 2;
     if (rounds > 0 && halves && budget > 0) ng = gemm_take_deferred_pairs(carry, cg, &fl, budget);
   }
   dim3 grid(chain_grid(c, 2) + (unsigned)ng), block(64 * CW);
@@ -922,12 +909,13 @@ int gcn_chain_bwd(const GcnCtx& c, hipStream_t st, DeferQueue* carry) {
 }
 
 Spread chain_carry_spread(const GcnCtx& c, int ng) {
-  // options chain_spread / chain_cohort / chain_spread_min: as carry_spread / carry_cohort / carry_spread_min (edge.hip) for
-  // the tile workgroups of a chain launch in which dE-broadcast rows ride as well; these tile workgroups take a compute
-  // unit each, so a cohort is half the idle units (cfg 5: 7.89 -> 7.78 ms; neutral at cfg 3; cfg 2 has too few tiles)
+  // as the edge pass's tile cohorts (edge.hip) for the tile workgroups of a chain launch in which dE-broadcast rows ride as
+  // well; these tile workgroups take a compute unit each, so a cohort is half the idle units (cfg 5: 7.89 -> 7.78 ms; neutral
+  // at cfg 3; cfg 2 has too few tiles)
+  constexpr int spread_pct = 85, cohort = 128, spread_min = 256;
   const long rows = c.ride.kind == 2 ? (long)c.ride.B * c.ride.N : 0;
-  const bool on = rows > 0 && ng >= option("chain_spread_min", 256);
-  return make_spread(ng, rows, option("chain_cohort", 128), on ? option("chain_spread", 85) : 0);
+  const bool on = rows > 0 && ng >= spread_min;
+  return make_spread(ng, rows, cohort, on ? spread_pct : 0);
 }
 
 static int chain_bwd_launch(const GcnCtx& c, const GemmGroup4& cg, dim3 grid, dim3 block, double fl, hipStream_t st) {

@@ -42,9 +42,9 @@ bool chain_t_ok(const GcnCtx& c, bool bwd) {
 }
 
 // The backward kernel can compute the output projection's input gradient itself (chain_t.hpp FUSE): blocks of at most 256
-// features whose residual-gradient share divides over the waves (one head: no such product); option chain_fuse = 0: never
+// features whose residual-gradient share divides over the waves (one head: no such product)
 bool chain_t_bwd_fusable(const GcnCtx& c) {
-  if (option("chain_fuse", 1) == 0 || c.N > 64 || c.D != c.L * c.gh || c.D > 256 || c.D % 32 != 0 || c.gh > 128 || 16 % c.L != 0) return false;
+  if (c.N > 64 || c.D != c.L * c.gh || c.D > 256 || c.D % 32 != 0 || c.gh > 128 || 16 % c.L != 0) return false;
   bool shape = false;
 #define X(gh_, l_) shape = shape || (c.gh == gh_ && c.L == l_);
   GC_CHAIN_T_HOST_SHAPES(X)
@@ -90,7 +90,7 @@ int gcn_chain_t_bwd(const GcnCtx& c, double fl, hipStream_t st, DeferQueue* carr
   const int nteam = c.gh / 64;
   int npw = 0;
   const long idle = 256 - (long)c.B * c.H;
-  if (carry && carry->n > 0 && idle > 0 && nteam > 0 && option("chain_carry", 1) != 0) {   // (nteam == 0: a 128-thread workgroup hosts no tile team)
+  if (carry && carry->n > 0 && idle > 0 && nteam > 0) {   // (nteam == 0: a 128-thread workgroup hosts no tile team)
     bool ok = true;
     int kmax = 0;
     for (int i = 0; i < carry->n; ++i) {

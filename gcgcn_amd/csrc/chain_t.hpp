@@ -323,8 +323,8 @@ __global__ __launch_bounds__(4 * GH) void gcn_chain_t_fwd_kernel(const GcnCtx c)
   __shared__ __attribute__((aligned(16))) float lds[t_fwd_lds<GH, L>()];
   if (blockIdx.x >= c.B * c.H) {  // passenger workgroup: one entity row of the riding edge mean
     const EdgeRide& r = c.ride;
-    edge_fwd_row<4, false, true, W>(r.in, nullptr, r.n_valid, r.out, nullptr, nullptr, nullptr, Drop(), r.N, r.D,
-                                    blockIdx.x - c.B * c.H, lds);
+    edge_fwd_row<4, false, W>(r.in, nullptr, r.n_valid, r.out, nullptr, nullptr, nullptr, Drop(), r.N, r.D,
+                              blockIdx.x - c.B * c.H, lds);
     return;
   }
   const int z = blockIdx.x, b = z / c.H, h = z - b * c.H;

@@ -16,7 +16,6 @@
 //
 // Ragged batches: n_valid[b] <= N entities are real; padding rows/columns are neither read nor
 // averaged, and their outputs are zero.
-#include <stdlib.h>
 #include <string.h>
 
 #include "edge_body.hpp"
@@ -25,21 +24,21 @@
 
 namespace gc {
 
-template <int VEC, bool ATT, bool NTL>
+template <int VEC, bool ATT>
 __global__ __launch_bounds__(64 * EW) void edge_fwd_kernel(const float* __restrict__ E, const float* __restrict__ v,
                                                            const int* __restrict__ n_valid, float* __restrict__ Ebar,
                                                            const float* __restrict__ coladd, float* __restrict__ P,
                                                            float* __restrict__ Aout, Drop drop, int N, int D,
                                                            const unsigned char* __restrict__ mask) {
   extern __shared__ __attribute__((aligned(16))) float cs[];  // [EW][D] per-wave column sums, then [N] logits
-  edge_fwd_row<VEC, ATT, NTL, EW>(E, v, n_valid, Ebar, coladd, P, Aout, drop, N, D, blockIdx.x, cs, mask);
+  edge_fwd_row<VEC, ATT, EW>(E, v, n_valid, Ebar, coladd, P, Aout, drop, N, D, blockIdx.x, cs, mask);
 }
 
 // ---------------------------------------------------------------------------------------------
 // backward of the CAGGC hop: dE = dlogit (x) v + dEbar / n ;  dv partial per workgroup.
 // dynamic LDS: N + EW * D floats.
 // ---------------------------------------------------------------------------------------------
-template <int VEC, bool NTL>
+template <int VEC>
 __device__ __forceinline__ void edge_bwd_row(const float* __restrict__ E, const float* __restrict__ v,
                                              const int* __restrict__ n_valid, const float* __restrict__ dlogit,
                                              const float* __restrict__ dEbar, float* __restrict__ dE,
@@ -97,10 +96,7 @@ __device__ __forceinline__ void edge_bwd_row(const float* __restrict__ E, const 
       for (int u = 0; u < EUNR; ++u) {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) x[u][e] = 0.f;
-        if (act) {
-          if (NTL) vload_nt<VEC>(x[u], Er + (long)(j + u * EW) * D + c);
-          else vload<VEC>(x[u], Er + (long)(j + u * EW) * D + c);
-        }
+        if (act) vload_nt<VEC>(x[u], Er + (long)(j + u * EW) * D + c);
       }
 #pragma unroll
       for (int u = 0; u < EUNR; ++u) {
@@ -150,7 +146,7 @@ __device__ __forceinline__ void edge_bwd_row(const float* __restrict__ E, const 
   }
 }
 
-template <int VEC, bool NTL>
+template <int VEC>
 __global__ __launch_bounds__(64 * EW) void edge_bwd_kernel(const float* __restrict__ E, const float* __restrict__ v,
                                                            const int* __restrict__ n_valid,
                                                            const float* __restrict__ dlogit,
@@ -165,7 +161,7 @@ __global__ __launch_bounds__(64 * EW) void edge_bwd_kernel(const float* __restri
     gat_dlogit_doc(gt.P, gt.dA, gt.uvc, gt.dXin, nullptr, gt.ds, gt.dX, N, D, gt.drop, b, blockIdx.x - b * gt.slices, gt.slices, sm);
     return;
   }
-  edge_bwd_row<VEC, NTL>(E, v, n_valid, dlogit, dEbar, dE, dvpart, N, D, nt, blockIdx.x - ngat, sm, gt);
+  edge_bwd_row<VEC>(E, v, n_valid, dlogit, dEbar, dE, dvpart, N, D, nt, blockIdx.x - ngat, sm, gt);
 }
 
 // The same pass carrying deferred GEMM problems (gemm.hpp): the first gg.tile_begin[gg.nprob] workgroups each run one
@@ -173,7 +169,7 @@ __global__ __launch_bounds__(64 * EW) void edge_bwd_kernel(const float* __restri
 // the rest are the entity rows.  The tiles go out in cohorts spread through the launch (Spread, common.hpp): every compute
 // unit then hosts rows AND a tile for most of the launch, where tiles-first order fills the chip with tiles alone for
 // ntile / 1024 rounds before the first row starts (cfg 5: 1.5 rounds, no overlap at all).
-template <int VEC, bool NTL, bool RB>   // RB: a carried product runs on the row blocks of a ragged batch (GemmArgs::rb)
+template <int VEC, bool RB>   // RB: a carried product runs on the row blocks of a ragged batch (GemmArgs::rb)
 __global__ __launch_bounds__(64 * EW) void edge_bwd_carry_kernel(const float* __restrict__ E, const float* __restrict__ v,
                                                                  const int* __restrict__ n_valid,
                                                                  const float* __restrict__ dlogit,
@@ -198,7 +194,7 @@ __global__ __launch_bounds__(64 * EW) void edge_bwd_carry_kernel(const float* __
     gat_dlogit_doc(gt.P, gt.dA, gt.uvc, gt.dXin, nullptr, gt.ds, gt.dX, N, D, gt.drop, b, r - b * gt.slices, gt.slices, tile_lds);
     return;
   }
-  edge_bwd_row<VEC, NTL>(E, v, n_valid, dlogit, dEbar, dE, dvpart, N, D, nt, r - ngat, tile_lds, gt);
+  edge_bwd_row<VEC>(E, v, n_valid, dlogit, dEbar, dE, dvpart, N, D, nt, r - ngat, tile_lds, gt);
 }
 
 template <int VEC>
@@ -213,25 +209,11 @@ __global__ __launch_bounds__(64 * EW) void edge_bcast_kernel(const float* __rest
 // ---------------------------------------------------------------------------------------------
 static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 // E is read once per pass and never again before something else has flushed the caches (a training step feeds new
-// documents): all E loads are non-temporal.  GCGCN_NT_E1=0 restores ordinary loads for the attention pass over E1 --
-// that was the round-1 setting, tuned on a bench that replayed ONE batch (part of E1 still sat in the Infinity Cache
-// from the previous backward); with rotating batches ordinary loads cost 8 us in edge_fwd_att (33.6 -> 25.7 us) and
-// 3 us in the backward edge pass.  GCGCN_NT_STORE=1 switches the dE stores to non-temporal too (A/B knob; no gain
-// with rotating batches, slower stores with a replayed one: edge_bwd 56 -> 69 us).
-static int nt_e1() {
-  static const int v = [] {
-    const char* e = getenv("GCGCN_NT_E1");
-    return (e && e[0] == '0') ? 0 : 1;
-  }();
-  return v;
-}
-static int nt_store() {
-  static const int v = [] {
-    const char* e = getenv("GCGCN_NT_STORE");
-    return (e && e[0] == '1') ? 1 : 0;
-  }();
-  return v;
-}
+// documents): all E loads are non-temporal.  Ordinary loads for the attention pass over E1 were the round-1 setting, tuned
+// on a bench that replayed ONE batch (part of E1 still sat in the Infinity Cache from the previous backward); with rotating
+// batches they cost 8 us in edge_fwd_att (33.6 -> 25.7 us) and 3 us in the backward edge pass.  The dE stores stay ordinary
+// (nt = 0): non-temporal ones gained nothing with rotating batches and were slower with a replayed one (edge_bwd 56 -> 69 us).
+constexpr int NT_STORE = 0;
 
 int edge_fwd(const float* E, const float* v, const int* n_valid, float* Ebar, const float* coladd, float* P, float* A,
              Drop drop, int B, int N, int D, hipStream_t st, const unsigned char* mask) {
@@ -245,16 +227,14 @@ int edge_fwd(const float* E, const float* v, const int* n_valid, float* Ebar, co
   dim3 grid((unsigned)((long)B * N)), block(64 * EW);
   const char* tag = att ? "edge_fwd_att" : "edge_fwd_mean";
   const double bytes = 4.0 * B * N * N * D;
-  // the mean-only pass reads E once per step: always non-temporal; the attention pass over E1 too unless GCGCN_NT_E1=0
-  const bool ntl = !att || nt_e1();
-#define GC_EDGE_FWD(V, AT, NT) \
-  GC_LAUNCH_TIMED(tag, bytes, (edge_fwd_kernel<V, AT, NT>), grid, block, lds, st, E, v, n_valid, Ebar, coladd, P, A, drop, N, D, mask)
+#define GC_EDGE_FWD(V, AT) \
+  GC_LAUNCH_TIMED(tag, bytes, (edge_fwd_kernel<V, AT>), grid, block, lds, st, E, v, n_valid, Ebar, coladd, P, A, drop, N, D, mask)
   if (vec) {
-    if (att) { if (ntl) GC_EDGE_FWD(4, true, true); else GC_EDGE_FWD(4, true, false); }
-    else GC_EDGE_FWD(4, false, true);
+    if (att) GC_EDGE_FWD(4, true);
+    else GC_EDGE_FWD(4, false);
   } else {
-    if (att) { if (ntl) GC_EDGE_FWD(1, true, true); else GC_EDGE_FWD(1, true, false); }
-    else GC_EDGE_FWD(1, false, true);
+    if (att) GC_EDGE_FWD(1, true);
+    else GC_EDGE_FWD(1, false);
   }
 #undef GC_EDGE_FWD
   return check_launch("edge_fwd");
@@ -285,28 +265,28 @@ int edge_bwd(const float* E, const float* v, const int* n_valid, const float* dl
     const int col_base = gemm_take_deferred_col2(carry, gg.col) ? (int)((long)B * N + ngat + ntile) : 0;
     const int ncolwg = col_base ? cdiv(gg.col.C, 256) : 0;
     dim3 grid((unsigned)((long)B * N + ngat + ntile + ncolwg));
-    // options carry_spread: percentage of the launch the tile cohorts are spread over (0: all tiles first, the order until
-    // round 3), carry_cohort: tiles per cohort; launches of fewer than carry_spread_min tiles keep them in front
-    const Spread sp = make_spread(ntile, (long)B * N + ngat, option("carry_cohort", 256),
-                                  ntile >= option("carry_spread_min", 1024) ? option("carry_spread", 90) : 0);
+    // the tile cohorts (cohort tiles each) are spread over spread_pct % of the launch (0: all tiles first, the order until
+    // round 3); launches of fewer than spread_min tiles keep them in front
+    constexpr int spread_pct = 90, cohort = 256, spread_min = 1024;
+    const Spread sp = make_spread(ntile, (long)B * N + ngat, cohort, ntile >= spread_min ? spread_pct : 0);
     const double bytes = (dE ? 8.0 : 4.0) * B * N * N * D;
     bool any_rb = false;
     for (int i = 0; i < gg.nprob; ++i) any_rb = any_rb || gg.p[i].rb != nullptr;
-#define GC_EDGE_CARRY(NT, RBV)                                                                                                  \
-  GC_LAUNCH_TIMED("edge_bwd", bytes, (edge_bwd_carry_kernel<4, NT, RBV>), grid, block, 0, st, E, v, n_valid, dlogit, dEbar, dE, \
-                  dvpart, N, D, nt_store(), sp, gt, gg, col_base)
-    if (nt_e1()) { if (any_rb) GC_EDGE_CARRY(true, true); else GC_EDGE_CARRY(true, false); }
-    else { if (any_rb) GC_EDGE_CARRY(false, true); else GC_EDGE_CARRY(false, false); }
+#define GC_EDGE_CARRY(RBV)                                                                                                  \
+  GC_LAUNCH_TIMED("edge_bwd", bytes, (edge_bwd_carry_kernel<4, RBV>), grid, block, 0, st, E, v, n_valid, dlogit, dEbar, dE, \
+                  dvpart, N, D, NT_STORE, sp, gt, gg, col_base)
+    if (any_rb) GC_EDGE_CARRY(true);
+    else GC_EDGE_CARRY(false);
 #undef GC_EDGE_CARRY
     return check_launch("edge_bwd_carry");
   }
   dim3 grid((unsigned)((long)B * N + ngat));
   const double bytes = (dE ? 8.0 : 4.0) * B * N * N * D;
-#define GC_EDGE_BWD(V, NT)                                                                                                 \
-  GC_LAUNCH_TIMED("edge_bwd", bytes, (edge_bwd_kernel<V, NT>), grid, block, lds, st, E, v, n_valid, dlogit, dEbar, dE, dvpart, N, D, \
-                  nt_store(), gt)
-  if (vec) { if (nt_e1()) GC_EDGE_BWD(4, true); else GC_EDGE_BWD(4, false); }
-  else { if (nt_e1()) GC_EDGE_BWD(1, true); else GC_EDGE_BWD(1, false); }
+#define GC_EDGE_BWD(V)                                                                                                           \
+  GC_LAUNCH_TIMED("edge_bwd", bytes, (edge_bwd_kernel<V>), grid, block, lds, st, E, v, n_valid, dlogit, dEbar, dE, dvpart, N, D, \
+                  NT_STORE, gt)
+  if (vec) GC_EDGE_BWD(4);
+  else GC_EDGE_BWD(1);
 #undef GC_EDGE_BWD
   return check_launch("edge_bwd");
 }
@@ -316,8 +296,8 @@ int edge_bcast(const float* dEbar, const int* n_valid, float* dE, int B, int N, 
   const bool vec = (D % 4 == 0) && al16(dE) && al16(dEbar);
   dim3 grid((unsigned)((long)B * N)), block(64 * EW);
   ProfScope ps("edge_bcast", st, 4.0 * B * N * N * D);
-  if (vec) hipLaunchKernelGGL((edge_bcast_kernel<4>), grid, block, 0, st, dEbar, n_valid, dE, N, D, nt_store());
-  else hipLaunchKernelGGL((edge_bcast_kernel<1>), grid, block, 0, st, dEbar, n_valid, dE, N, D, nt_store());
+  if (vec) hipLaunchKernelGGL((edge_bcast_kernel<4>), grid, block, 0, st, dEbar, n_valid, dE, N, D, NT_STORE);
+  else hipLaunchKernelGGL((edge_bcast_kernel<1>), grid, block, 0, st, dEbar, n_valid, dE, N, D, NT_STORE);
   return check_launch("edge_bcast");
 }
 

@@ -60,7 +60,7 @@ constexpr int EUNR = 4;  // rows in flight per wave (8 was tried: no faster in t
 // wave 0 in the same launch (GATAttention glove:162-167), so P/A are the only attention outputs.
 // EWT waves (the whole workgroup) work on entity row bi; cs = EWT * D (+ N when ATT) floats of LDS.  Control flow is
 // uniform over the workgroup, so the body can also ride inside another kernel's spare workgroups (chain.hip).
-template <int VEC, bool ATT, bool NTL, int EWT>
+template <int VEC, bool ATT, int EWT>
 __device__ __forceinline__ void edge_fwd_row(const float* __restrict__ E, const float* __restrict__ v,
                                              const int* __restrict__ n_valid, float* __restrict__ Ebar,
                                              const float* __restrict__ coladd, float* __restrict__ P,
@@ -96,10 +96,7 @@ __device__ __forceinline__ void edge_fwd_row(const float* __restrict__ E, const 
       for (int u = 0; u < EUNR; ++u) {
 #pragma unroll
         for (int e = 0; e < VEC; ++e) x[u][e] = 0.f;
-        if (act) {
-          if (NTL) vload_nt<VEC>(x[u], Er + (long)(j + u * EWT) * D + c);
-          else vload<VEC>(x[u], Er + (long)(j + u * EWT) * D + c);
-        }
+        if (act) vload_nt<VEC>(x[u], Er + (long)(j + u * EWT) * D + c);
       }
 #pragma unroll
       for (int u = 0; u < EUNR; ++u) {

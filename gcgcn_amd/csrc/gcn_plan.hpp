@@ -1,5 +1,5 @@
 // The per-(document, head) products of the densely connected GraphConv stack, described once and
-// used twice: by the host (one batched launch per product: gcgcn_gcn_fwd/_bwd with GCGCN_NO_CHAIN=1)
+// used twice: by the host (one batched launch per product: gcgcn_gcn_fwd/_bwd with option chain = 0)
 // and by the chain kernels (chain.hip: one persistent workgroup per (b, h) runs them back to back).
 //
 // Tensors are [B*N, H, L, gh] row-major (row stride HD = H*D, D = L*gh); A is [B, H, N, N];

@@ -269,10 +269,7 @@ static int launch(const GemmArgs& g, hipStream_t stream) {
 // (a K = 2048 tile next to K = 256 tiles would otherwise drain alone), and a launch that cannot fill
 // the slots at all is cut until its blocks are ~8 k-steps long.
 static int pick_splits(int K, long work) {
-  static const int thr_pct = [] {  // GCGCN_SPLIT_PCT: tuning knob (percent of the average slot load), default 250
-    const char* e = getenv("GCGCN_SPLIT_PCT");
-    return e ? atoi(e) : 250;
-  }();
+  constexpr int thr_pct = 250;  // percent of the average slot load
   const long iters = cdiv(K, BK);
   long thr = work / 1024 * thr_pct / 100;
   if (thr < 8) thr = 8;
@@ -337,8 +334,7 @@ int gemm(const GemmArgs& g_in, hipStream_t stream, int tile, int splits) {
   GC_REQUIRE(nb * g.splits <= 65535, "gemm: batch %ld x splits %d exceeds grid.z", nb, g.splits);
   GC_REQUIRE(cdiv(g.M, 64) <= 65535, "gemm: M %d exceeds grid.y", g.M);
   const bool al = g.vecA && g.vecB && g.M % 64 == 0 && g.N % 64 == 0 && g.ksplit % BK == 0;
-  static const bool dump = getenv("GCGCN_GROUP_DUMP") != nullptr;   // diagnosis (with the group launches' dump)
-  if (dump)
+  if (option("group_dump", 0))   // diagnosis (with the group launches' dump)
     fprintf(stderr, "gemm: %-12s M %5d N %5d K %5d batch %3ld splits %2d a_kc %d b_kc %d rb_mode %d %s\n", g.tag, g.M, g.N, g.K, nb, g.splits,
             g.a_kc, g.b_kc, g.rb ? g.rb_mode : 0, al ? "interior" : "guarded");
   return al ? launch<1, 1, true>(g, stream) : launch<1, 1, false>(g, stream);
@@ -428,8 +424,7 @@ int gemm_group(const GemmArgs* probs, int n, hipStream_t stream, const ColRide* 
     flops += 2.0 * g.M * g.N * g.K * nb;
     gg.p[gg.nprob++] = g;
   }
-  static const bool dump = getenv("GCGCN_GROUP_DUMP") != nullptr;   // diagnosis: what each group launch is made of
-  if (dump) {
+  if (option("group_dump", 0)) {   // diagnosis: what each group launch is made of
     fprintf(stderr, "gemm_group: %d problems, %d tile workgroups, mha pairs %d\n", gg.nprob, tiles, mha ? mha->count : 0);
     for (int i = 0; i < gg.nprob; ++i) {
       const GemmArgs& g = gg.p[i];

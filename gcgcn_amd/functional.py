@@ -251,7 +251,6 @@ class MhaFn(torch.autograd.Function):
              _p(scratch), _p(rowblk), _stream())
         ctx.save_for_backward(x, flat, Q, P)
         ctx.H, ctx.p, ctx.snap, ctx.rowblk = H, float(p), snap, rowblk
-        ctx.flat_leaf = flat if (flat.is_leaf and not _under_ddp()) else None
         return (P if A is None else A), x.view_as(x)
 
     @staticmethod
@@ -266,14 +265,10 @@ class MhaFn(torch.autograd.Function):
         dS = torch.empty(B, H, N, N, device=dev)
         dQ = torch.empty(B, N, D, device=dev)
         scratch = torch.empty(max(_lib.lib().gcgcn_mha_scratch(B, N, D), 1), device=dev)
-        # dWq could be parked too (defer_mha_weight_grads); measured neutral at cfg 2 -- the carrying edge pass is already the
-        # longer side with the two convolutions' products (0.652 vs 0.648 ms) -- so it stays with its own group launch
-        bp = _pass_for_parking(ctx, 1) if defer_mha_weight_grads else None
+        # dWq is not parked: measured neutral at cfg 2 -- the carrying edge pass is already the longer side with the two
+        # convolutions' products (0.652 vs 0.648 ms) -- so it stays with its own group launch
         call("gcgcn_mha_bwd", B, N, D, H, _p(x), _p(flat), _p(ctx.snap), ctx.p, _p(Q), _p(P), _p(dA), _p(dXin), _p(dX),
-             _p(dflat), _p(dS), _p(dQ), _p(scratch), None if bp is None else bp.queue, 0, _p(ctx.rowblk), _stream())
-        if bp is not None:
-            bp.park(ctx.flat_leaf, dflat, (x, dQ, ctx.rowblk))
-            dflat = None                                # installed as .grad by the pass's end-of-backward callback
+             _p(dflat), _p(dS), _p(dQ), _p(scratch), None, 0, _p(ctx.rowblk), _stream())
         return dX, dflat, None, None, None, None, None
 
 
@@ -298,7 +293,6 @@ class MhaFn(torch.autograd.Function):
 # queued callback: a pass that raises half-way is destroyed with its graph task -- parked operands, queue and all --
 # and leaves nothing behind; passes of other models, devices or threads never share a queue.
 defer_weight_grads = os.environ.get("GCGCN_DEFER", "1") != "0"      # GCGCN_DEFER=0: A/B knob
-defer_mha_weight_grads = False
 defer_fused_mha_weight_grads = os.environ.get("GCGCN_DEFER_MHA", "1") != "0"   # the fused MAGGC hop's dWq + dbq second stage (A/B knob)
 _warned_ddp = [False]
 

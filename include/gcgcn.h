@@ -38,9 +38,10 @@ const char* gcgcn_last_error(void); /* message of the last failing call on this 
 /* Run-time switches for A/B tests.  "chain": 1 (default) = the per-(doc, head) products of a conv run inside the
  * chain kernels, 0 = one batched launch per product.  "mha_core": 1 (default) = graphs of N <= 64 entities take the
  * one-workgroup-per-(doc, head) attention kernels, 0 = batched GEMM + row softmax for every N.  Results are identical
- * up to fp32 summation order.  The other names -- "head_v1" (-1 = by problem size), "head_bil3", "head_bil3_bwd",
- * "head_dw3", "chain_s", "chain_fuse", "chain_carry", "gat_ride", ... -- select kernel generations; each also reads the
- * environment variable GCGCN_<NAME> once when nobody set it (DESIGN.md section 6 lists them). */
+ * up to fp32 summation order.  "head_v1" (-1 = by problem size), "head_bil3", "head_bil3_bwd", "head_dw3",
+ * "head_compact", "chain_t", "chain_big" and "split_widen" select kernel generations; "group_dump" (0 = off) prints what
+ * every GEMM launch is made of on stderr.  Each name also reads the environment variable GCGCN_<NAME> once when nobody set
+ * it (GCGCN_CHAIN=0, GCGCN_HEAD_V1=1, ...: DESIGN.md section 6 lists them).  Any other name fails. */
 int gcgcn_set_option(const char* name, int value);
 
 /* ---- ragged batches: the entity rows that exist (ABI v5; v7: one list serves every product) ------------------------------- */

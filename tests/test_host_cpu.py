@@ -23,6 +23,31 @@ def test_library_exports_every_declared_symbol():
     assert lib.gcgcn_version() == _lib.ABI_VERSION == 7
 
 
+# gcgcn_set_option's names (api.hip g_opts) with their defaults, and names of switches that are constants now
+OPTION_DEFAULTS = {"head_v1": -1, "head_bil3": 1, "head_bil3_bwd": 1, "head_dw3": 1, "head_compact": 1, "chain_t": 1,
+                   "chain_big": 0, "split_widen": 1, "chain": 1, "mha_core": 1, "group_dump": 0}
+RETIRED_OPTIONS = ["chain_fuse", "chain_carry", "att_in_chain", "maggc_fuse", "mha_ride", "gat_ride", "carry_spread",
+                   "carry_cohort", "carry_spread_min", "chain_spread", "chain_cohort", "chain_spread_min", "fold_slices",
+                   "head_sum_fold", "chain_s", "chain_t_wide_full"]
+
+
+def test_set_option_knows_exactly_the_kept_options():
+    """Every kept option is accepted (set to its default: the process is left as it was found), every retired one is refused,
+    and every option a test or tool sets by a literal name is a kept one."""
+    for name, dflt in OPTION_DEFAULTS.items():
+        _lib.call("gcgcn_set_option", name.encode(), dflt)
+    for name in RETIRED_OPTIONS:
+        with pytest.raises(RuntimeError, match="unknown option"):
+            _lib.call("gcgcn_set_option", name.encode(), 0)
+    used = set()
+    for d in ("tests", "tools"):
+        for f in sorted(os.listdir(os.path.join(ROOT, d))):
+            if f.endswith(".py"):
+                used |= set(re.findall(r'gcgcn_set_option", b"(\w+)"', open(os.path.join(ROOT, d, f)).read()))
+    used.discard("bogus")                        # (test_hip_parity's deliberately unknown name)
+    assert used and used <= set(OPTION_DEFAULTS), used - set(OPTION_DEFAULTS)
+
+
 @pytest.mark.parametrize("D,L,H", [(8, 2, 2), (128, 2, 8), (768, 4, 4), (512, 2, 8), (12, 4, 4)])
 def test_layouts_match_library(D, L, H):
     assert P.gat_layout(D) == _lib.layout("gat", D, D)

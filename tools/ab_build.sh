@@ -4,20 +4,19 @@
 # Only meaningful while both revisions speak the same C ABI (include/gcgcn.h).
 set -e
 rev=${1:-HEAD}
+root=$(cd $(dirname $0)/.. && pwd)
 d=/tmp/ab_src
-rm -rf $d && mkdir -p $d/csrc $d/include
-for f in $(git ls-tree --name-only $rev gcgcn_amd/csrc/ | grep -E '\.(hip|hpp)$'); do
-  git show $rev:$f > $d/csrc/$(basename $f)
+rm -rf $d && mkdir -p $d/gcgcn_amd/csrc $d/include   # the tree's layout: the sources include "../../include/gcgcn.h"
+for f in $(git ls-tree --name-only $rev gcgcn_amd/csrc/ | grep -E '\.(hip|hpp)$') include/gcgcn.h; do
+  git show $rev:$f > $d/$f
 done
-git show $rev:include/gcgcn.h > $d/include/gcgcn.h
-sed -i "s#\"../../include/gcgcn.h\"#\"$d/include/gcgcn.h\"#" $d/csrc/api.hip
-cd $d/csrc
+cd $d/gcgcn_amd/csrc
 objs=""
 for f in *.hip; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c $f -o ${f%.hip}.o &
   objs="$objs ${f%.hip}.o"
 done
 wait
-mkdir -p /root/repo/build
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o /root/repo/build/ab_old.so $objs
-ls -la /root/repo/build/ab_old.so
+mkdir -p $root/build
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $root/build/ab_old.so $objs
+ls -la $root/build/ab_old.so

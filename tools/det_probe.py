@@ -16,10 +16,6 @@ x = (torch.randn(B, N, D, generator=g) * mask[..., None]).to(dev)
 ebar = (torch.randn(B, N, D, generator=g) * 0.3 * mask[..., None]).to(dev)
 adj = (torch.rand(B, H, N, N, generator=g) * mask[:, None, :, None] * mask[:, None, None, :]).to(dev)
 cot = torch.randn(B, N, D, generator=g).to(dev)
-try:
-    _lib.call("gcgcn_set_option", b"chain_t_wide_full", 0)
-except Exception:
-    pass
 outs = []
 for r in range(int(os.environ.get("REPS", "8"))):
     xs = [t.clone().requires_grad_() for t in (x, ebar, adj, flat)]

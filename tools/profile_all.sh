@@ -1,6 +1,6 @@
 #!/bin/bash
-# All rocprofv3 evidence of a round in one gpurun call (tools/profile_workload.sh per workload); outputs in gpurun_out/prof/.
-#   gpurun --timeout 1200 -- 'bash tools/profile_all.sh r03 c2 c3 c5 head producer tail'
+# All rocprofv3 evidence of a round in one run (tools/profile_workload.sh per workload); outputs in $OUT/prof/ (default out/prof/):
+#   bash tools/profile_all.sh r03 c2 c3 c5 head producer tail
 set -e
 round=$1; shift
 for w in "$@"; do
@@ -16,4 +16,4 @@ for w in "$@"; do
   esac
   echo "== $w done"
 done
-ls -la gpurun_out/prof/
+ls -la ${OUT:-out}/prof/

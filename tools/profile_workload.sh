@@ -8,11 +8,11 @@
 # Run on the GPU box from the repo root:
 #   bash tools/profile_workload.sh r03_c3 bench.py --config c3 --steps 20 --warmup 5 --no-cpu-baseline
 #   bash tools/profile_workload.sh r03_head_n64 tools/head_bench.py --steps 5
-# Outputs land in gpurun_out/prof/ (gpurun merges only gpurun_out/): copy what is judged into profiles/.
+# Outputs land in $OUT/prof/ (default out/prof/): copy what is judged into profiles/.
 set -e
 tag=$1; shift
 root=$PWD
-out=$root/gpurun_out/prof
+out=$(realpath -m "${OUT:-$root/out}")/prof
 work=$out/work_$tag
 mkdir -p $out && rm -rf $work && mkdir -p $work
 prog=$root/$1; shift
