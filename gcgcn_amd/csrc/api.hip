@@ -135,20 +135,6 @@ static bool set_opt(const char* name, int value) {
   return false;
 }
 
-// option chain = 0 (GCGCN_CHAIN=0) runs every per-(doc, head) product as its own batched launch instead of inside the chain
-// kernels (A/B testing of chain.hip).
-static bool use_chain() { return option("chain", 1) != 0; }
-
-// Graphs of more than 64 entities have no LDS-resident chain kernel: the generic chain kernels hand every product's tiles through
-// L2 inside one workgroup per (document, head) pair, and at that size each product is a full launch of its own anyway (cfg 5:
-// 4096 tiles).  Measured at cfg 5 (same session, profiles/r04_ab_chain_big.txt): per-product launches 7.67-7.74 ms, chain
-// kernels 7.86-7.90 ms per step; the one chain launch that pays is a FORWARD one with an edge mean riding in it (the chain hides
-// under the HBM-bound passenger: 698 us against 705 + 64).  Option chain_big = 1 restores the chain kernels everywhere (A/B, tests).
-static bool use_chain_for(int N, bool fwd_with_ride) {
-  if (!use_chain()) return false;
-  return N <= 64 || fwd_with_ride || option("chain_big", 0) != 0;
-}
-
 // option mha_core = 0 (GCGCN_MHA_CORE=0) sends small graphs through the generic batched-GEMM + row-softmax attention path as
 // well (A/B testing of mha_core.hip).
 static bool use_mha_core() { return option("mha_core", 1) != 0; }
@@ -171,6 +157,24 @@ static void use_rows(GemmArgs& g, const int* rowblk, int mode, int zero_dead = 0
   if (!rowblk) return;
   g.rb = rowblk + ROWBLK_HDR, g.rb_n = rowblk;
   g.rb_mode = mode, g.rb_zero = zero_dead;
+}
+
+// The row-block list of a call, or NULL where the call does not walk the live row blocks (dense batch, or a graph size whose
+// documents are not whole 16-row blocks)
+static const int* live_rows(const int32_t* rowblk, int N, bool ragged) {
+  return (rowblk && ragged && N % 16 == 0 && N >= 32) ? rowblk : nullptr;
+}
+
+// What chain_plan_fwd / _bwd (chain.hip) decide on, apart from the direction's own operands (set by the caller)
+static ChainQuery make_query(int B, int N, int D, int L, int H, const GcnLayout& y, const float* flat, bool ragged, bool scratch,
+                             bool hook, const EdgeRide& ride, const void* A, const void* Pn, const void* Y) {
+  ChainQuery q = ChainQuery();
+  q.B = B, q.N = N, q.D = D, q.L = L, q.H = H, q.gh = y.gh;
+  q.HD = (long)H * D, q.oWd = y.oWd, q.wd_head = y.wd_head, q.oWlin = y.oWlin;
+  q.flat = flat, q.ragged = ragged, q.scratch = scratch, q.hook = hook, q.ride = ride;
+  q.A = A, q.Pn = Pn, q.Y = Y;
+  q.chain = option("chain", 1), q.chain_big = option("chain_big", 0), q.chain_t = option("chain_t", 1);
+  return q;
 }
 
 static GcnCtx make_ctx(int B, int N, int D, int L, int H, const GcnLayout& y, const float* X, const float* A,
@@ -381,7 +385,7 @@ int gcgcn_mha_fwd(int B, int N, int D, int H, const float* X, const int32_t* n_v
     g.C = Q, g.ldc = D;
     g.M = (int)M, g.N = D, g.K = D;
     g.bias = flat + (long)D * D;
-    use_rows(g, (n_valid && N % 16 == 0 && N >= 32) ? rowblk : nullptr, 1, 1);
+    use_rows(g, live_rows(rowblk, N, n_valid != nullptr), 1, 1);
     GC_TRY(gemm(g, st));
   }
   const float alpha = 1.f / sqrtf((float)dh);
@@ -445,7 +449,8 @@ int gcgcn_mha_bwd(int B, int N, int D, int H, const float* X, const float* flat,
     gs[1].B = X, gs[1].ldb = D, gs[1].b_kc = 0;
     gs[1].C = dflat, gs[1].ldc = D;
     gs[1].M = D, gs[1].N = D, gs[1].K = (int)M;
-    if (N % 16 == 0 && N >= 32) use_rows(gs[0], rowblk, 1, 1), use_rows(gs[1], rowblk, 2);   // ragged batch: the rows that exist
+    const int* rows = live_rows(rowblk, N, true);   // (a list is only handed in for a ragged batch): the rows that exist
+    use_rows(gs[0], rows, 1, 1), use_rows(gs[1], rows, 2);
     const int ng = gemm_defer((DeferQueue*)defer_queue, gs[1]) ? 1 : 2;  // dWq parked (see gcgcn_gcn_bwd)
     if (scratch) {  // dbq = column sums of dQ ride in the same two launches
       ColRide cr;
@@ -524,13 +529,13 @@ int gcgcn_gcn_fwd(int B, int N, int D, int L, int H, const float* X, const float
   // The per-(doc, head) context, with the passenger that will actually ride attached.  Ragged batch with a row-block list:
   // the products around the chain run on the rows that exist; what they leave on the dead row blocks is ZERO (rb_zero), so the
   // chain kernels -- whichever serves the shape -- see exactly what the dense products would have left there.
-  const bool chain = use_chain_for(N, er.kind && chain_can_carry(er));
-  EdgeRide er_chain = er;
-  if (er.kind && !(chain && chain_can_carry(er))) er_chain.kind = 0;
+  ChainQuery q = make_query(B, N, D, L, H, y, flat, n_valid != nullptr, scratch != nullptr, mha != nullptr, er, A, Pn, Y);
+  q.G = G, q.HO = HO, q.X = X;
+  const ChainPlan plan = chain_plan_fwd(q);
   GcnCtx c = make_ctx(B, N, D, L, H, y, X, A, flat, n_valid, drop);
   c.G = G, c.Pn = Pn, c.Y = Y, c.HO = HO, c.rinv = rinv;
-  c.ride = er_chain;
-  const int* rows = (rowblk && n_valid && N % 16 == 0 && N >= 32) ? rowblk : nullptr;
+  if (plan.ride) c.ride = er;
+  const int* rows = live_rows(rowblk, N, n_valid != nullptr);
 
   {  // one launch: Pn = X WnX (node term of every (head, sub-layer), X part of the dense input)
      //             G  = Ebar We (edge term, mean commuted with the projection, glove:40-41)
@@ -560,23 +565,23 @@ int gcgcn_gcn_fwd(int B, int N, int D, int L, int H, const float* X, const float
     GC_TRY(gemm_group(g3, mha ? 3 : 2, st, hs.X ? &hs : nullptr));
   }
   {  // the dependent per-(doc, head) sequence: normaliser, then per sub-layer dense connection + aggregation
-    if (er.kind && !er_chain.kind) {  // the riding pass as its own launch
+    if (er.kind && !plan.ride) {  // the riding pass as its own launch
       GC_TRY(edge_fwd(er.in, nullptr, er.n_valid, er.out, nullptr, nullptr, nullptr, Drop(), er.B, er.N, er.D, st));
       er.kind = 0;
     }
     if (mha) {  // the attention core: scores in LDS, P / A out (glove:137-140) -- in the chain workgroups' prologue where the
-                // shape's chain kernel can do that (chain.hip), as a launch of its own otherwise
+                // shape's chain kernel can do that (plan.attention), as a launch of its own otherwise
       const Drop adrop = make_drop(mha->rng_snap, GCGCN_SALT_MHA, mha->p);
       GC_REQUIRE(!adrop.snap || mha->A, "gcn_fwd: attention dropout on but A is NULL");
       const float alpha = 1.f / sqrtf((float)(D / H));
-      if (chain && chain_fwd_computes_attention(c))
+      if (plan.attention)
         c.mha.Q = mha->Q, c.mha.P = mha->P, c.mha.A = mha->A, c.mha.alpha = alpha, c.mha.drop = adrop, c.mha.dh = D / H,
         c.mha.kchunk = mha_chunk(D / H);
       else
         GC_TRY(mha_core_fwd(mha->Q, n_valid, mha->P, mha->A, B, N, D, H, alpha, adrop, st));
     }
-    if (chain) {
-      GC_TRY(gcn_chain_fwd(c, st));
+    if (plan.kind != ChainPlan::NONE) {
+      GC_TRY(gcn_chain_fwd(c, plan, st));
     } else {
       GC_TRY(rowsum_inv(A, rinv, (long)B * H * N, N, st));  // glove:47-49
       for (int l = 0; l < L; ++l) {
@@ -644,21 +649,18 @@ int gcgcn_gcn_bwd(int B, int N, int D, int L, int H, const float* X, const float
   float* dM = W2;   // gradient of M_l = G_l + A_h Pn_l  (== dG)
   float* dP = W3;   // gradient of Pn_l
 
-  // The chain kernel of the default shape computes dHO = dout Wlin and dXres = sum_h dHO_h itself (chain.hip): no launch for
-  // that product, no head-sum / dropout kernel, dHO never in HBM.  Decided on the same context the chain will get.
+  // Where the plan says fuse, the chain kernel computes dHO = dout Wlin and dXres = sum_h dHO_h itself (chain.hip): no launch for
+  // that product, no head-sum / dropout kernel, dHO never in HBM.
+  ChainQuery q = make_query(B, N, D, L, H, y, flat, n_valid != nullptr, scratch != nullptr, false, er, A, Pn, Y);
+  q.dYa = dYa, q.dM = dM, q.dP = dP, q.dA = dA, q.dout = dout, q.dXres = dXres, q.dout_m = dout_m;
+  const ChainPlan plan = chain_plan_bwd(q);
+  const bool fuse = plan.fuse;
   GcnCtx c = make_ctx(B, N, D, L, H, y, X, A, flat, n_valid, drop);
   c.Pn = const_cast<float*>(Pn), c.Y = const_cast<float*>(Y), c.rinv = const_cast<float*>(rinv);
   c.dYa = dYa, c.dM = dM, c.dP = dP, c.dA = dA, c.drow = drow, c.oWlin = y.oWlin;
   // ragged batch with a row-block list: the products around the chain run on the rows that exist (see gcgcn_gcn_fwd)
-  const bool chain = use_chain_for(N, false);
-  {
-    EdgeRide er_chain = er;
-    if (er.kind && !(chain && chain_can_carry(er))) er_chain.kind = 0;
-    c.ride = er_chain;
-  }
-  const int* rows = (rowblk && n_valid && N % 16 == 0 && N >= 32) ? rowblk : nullptr;
-  const bool fuse = chain && scratch && chain_bwd_fusable(c) && (((uintptr_t)dXres) & 15) == 0 &&
-                    (((uintptr_t)dout) & 15) == 0 && (((uintptr_t)dout_m) & 15) == 0 && (long)M * HD >= (long)D * D;
+  if (plan.ride) c.ride = er;
+  const int* rows = live_rows(rowblk, N, n_valid != nullptr);
   // sum_h Wlin_h: from the forward call if it left one, else summed here into dYa's buffer (free when the chain computes dHO)
   const float* wsum = (fuse && H > 1) ? (wsum_fwd ? wsum_fwd : dYa) : nullptr;
   const float* dout_raw = dout;
@@ -738,8 +740,8 @@ int gcgcn_gcn_bwd(int B, int N, int D, int L, int H, const float* X, const float
       GC_TRY(edge_bcast(er.in, er.n_valid, er.out, er.B, er.N, er.D, st));
       er.kind = 0;
     }
-    if (chain) {
-      GC_TRY(gcn_chain_bwd(c, st, dq));  // + parked weight gradients of earlier blocks where the chain leaves room
+    if (plan.kind != ChainPlan::NONE) {
+      GC_TRY(gcn_chain_bwd(c, plan, st, dq));  // + parked weight gradients of earlier blocks where the chain leaves room
     } else {
       for (int l = L - 1; l >= 0; --l) {
         GC_TRY(relu_norm_bwd(dYa, Y, rinv, dM, drow, M, N, H, L, gh, l, l == L - 1, st));
@@ -933,6 +935,26 @@ int gcgcn_debug_spread(int64_t n_tiles, int64_t n_others, int64_t cohort, int64_
     kind[x] = spread_pick((int)x, sp, idx) ? 1 : 0;
     ordinal[x] = idx;
   }
+  return 0;
+}
+
+// The chain kernel a convolution call of this shape gets, by the very plan function gcgcn_gcn_fwd / _bwd call (chain.hip), on
+// made-up operand addresses: misalign bit 0 puts the per-(document, head) tensors off a 16-byte boundary, bit 1 the output
+// projection's dout / dXres / dout_m, bit 2 the ride's in / out, bit 3 the parameter block.  out[0..5] = kind (0 none, 1 generic,
+// 2 s, 3 t), aligned, full, fuse, attention, ride.  Exposed for tests (no GPU needed).
+int gcgcn_debug_chain_plan(int bwd, int B, int N, int D, int L, int H, int ragged, int ride, int hook, int scratch, int misalign,
+                           int32_t* out) {
+  GC_TRY(check_dims("debug_chain_plan", B, N, D, L, H));
+  GC_REQUIRE(out, "debug_chain_plan: null pointer");
+  int slot = 0;
+  auto at = [&](int bit) { return (const float*)(uintptr_t)(0x100000ul * ++slot + ((misalign & bit) ? 4 : 0)); };
+  EdgeRide er = EdgeRide();
+  if (ride) er.kind = bwd ? 2 : 1, er.B = B, er.N = N, er.D = D, er.in = at(4), er.out = const_cast<float*>(at(4));
+  ChainQuery q = make_query(B, N, D, L, H, gcn_layout(D, L, H), at(8), ragged != 0, scratch != 0, hook != 0, er, at(1), at(1), at(1));
+  q.G = at(1), q.HO = at(1), q.X = at(1), q.dYa = at(1), q.dM = at(1), q.dP = at(1), q.dA = at(1);
+  q.dout = at(2), q.dXres = at(2), q.dout_m = at(2);
+  const ChainPlan p = bwd ? chain_plan_bwd(q) : chain_plan_fwd(q);
+  out[0] = p.kind, out[1] = p.aligned, out[2] = p.full, out[3] = p.fuse, out[4] = p.attention, out[5] = p.ride;
   return 0;
 }
 

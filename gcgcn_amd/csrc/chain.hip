@@ -9,6 +9,10 @@
 // workgroup share the CU's vector L1, so no cache maintenance is needed at workgroup scope.
 // Pairs never touch each other's slices, so there is no inter-workgroup synchronisation at all
 // and every wave reaches the end of the phase list (no spin, no flag).
+//
+// At the end of the file: what each kernel generation serves, and chain_plan_fwd / _bwd, the ONE place
+// that decides which of them (or none: one launch per product) a convolution call gets.  The launchers
+// gcn_chain_fwd / _bwd run what that plan says.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -802,83 +806,96 @@ __global__ __launch_bounds__(64 * CW) void gcn_chain_s_bwd_kernel(const GcnCtx c
   TS(55);
 }
 
-// the shape the LDS-resident kernels are written for
-static bool chain_small_ok(const GcnCtx& c, bool bwd) {
-  return c.N == 64 && c.L == 2 && c.gh == S_GH && c.D == 2 * S_GH && (c.flat + c.oWd) && c.wd_head % 4 == 0 &&
-         (c.wd_off(1) % 4) == 0;
-}
-
-static bool chain_aligned(const GcnCtx& c, bool bwd);
-// the dispatch rule of gcn_chain_fwd / _bwd: the column-strip kernels (chain_t.hpp) take the shape instead of the default shape's own kernels
-// (option chain_t: 0 never; 1 (default) wherever the default shape's own kernels do not apply, and at that shape too for RAGGED
-// batches -- the column-strip kernels skip 16-row blocks per document, gcn_chain_s_* own 32 rows per wave and do not: cfg 2
-// ragged 71.2 k -> 72.5 k docs/s at B = 32; dense batches stay on gcn_chain_s_* (0.522 vs 0.542 ms); 2: everywhere)
-static bool chain_s_preferred(const GcnCtx& c, bool s_ok) {
-  const int mode = option("chain_t", 1);
-  return s_ok && (mode < 2) && !(mode == 1 && c.n_valid != nullptr);
-}
-static bool chain_t_takes(const GcnCtx& c, bool bwd) {
-  const bool s_ok = chain_aligned(c, bwd) && chain_small_ok(c, bwd);
-  return chain_t_ok(c, bwd) && !chain_s_preferred(c, s_ok);
-}
-bool chain_bwd_fusable(const GcnCtx& c) {   // asked before c.dout is set
-  auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  if (chain_t_takes(c, true)) return chain_t_bwd_fusable(c);
-  return chain_small_ok(c, true) && c.N == 64 && (c.H == 1 || c.H == 8) && al(c.A) && al(c.Pn) && al(c.Y) && al(c.dM) &&
-         al(c.dP) && al(c.dA) && al(c.flat + c.oWd) && al(c.flat + c.oWlin) && c.HD % 4 == 0;
-}
-
-static bool chain_aligned(const GcnCtx& c, bool bwd) {
-  auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  bool ok = c.N % 64 == 0 && c.gh % 64 == 0 && al(c.A) && al(c.flat + c.oWd) && al(c.Pn) && al(c.Y);
-  if (bwd) ok = ok && (c.dout ? al(c.dout) && al(c.dXres) : al(c.dYa)) && al(c.dM) && al(c.dP) && al(c.dA);
-  else ok = ok && al(c.G) && al(c.HO) && al(c.X);
+// ---- what each generation of this file serves (asked by the plan functions below only) --------------------------------------
+// the generic kernels run anything; their <ALIGNED> instantiation wants whole 64-tiles and 16-byte operands
+bool chain_g_aligned(const ChainQuery& q, bool bwd) {
+  bool ok = q.N % 64 == 0 && q.gh % 64 == 0 && al16(q.A) && al16(q.flat + q.oWd) && al16(q.Pn) && al16(q.Y);
+  if (bwd) ok = ok && al16(q.dYa) && al16(q.dM) && al16(q.dP) && al16(q.dA);
+  else ok = ok && al16(q.G) && al16(q.HO) && al16(q.X);
   return ok;
 }
-
-bool chain_fwd_computes_attention(const GcnCtx& c) {   // before c.mha is set: a question about the shape and the options
-  if (chain_t_takes(c, false)) return chain_t_fwd_att_ok(c);
-  return chain_aligned(c, false) && chain_small_ok(c, false) && mha_lds_bytes(c.D / c.H) <= sizeof(float) * 64 * S_LP &&
-         (c.D / c.H) % 4 == 0;
+// the LDS-resident kernels are written for one shape
+bool chain_s_serves(const ChainQuery& q, bool bwd) {
+  return chain_g_aligned(q, bwd) && q.N == 64 && q.L == 2 && q.gh == S_GH && q.D == 2 * S_GH && q.wd_head % 4 == 0 && q.oWd % 4 == 0;
 }
-
+bool chain_s_fuses(const ChainQuery& q) {   // gcn_chain_s_bwd_kernel<true>
+  return (q.H == 1 || q.H == 8) && al16(q.flat + q.oWlin) && q.HD % 4 == 0 && al16(q.dout) && al16(q.dXres) && al16(q.dout_m);
+}
+bool chain_s_attends(const ChainQuery& q) {
+  return mha_lds_bytes(q.D / q.H) <= sizeof(float) * 64 * S_LP && (q.D / q.H) % 4 == 0;
+}
 // The riding pass uses the 16-byte row bodies and the chain kernel's static LDS for its per-wave column sums.
 bool chain_can_carry(const EdgeRide& r) {
-  auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  return r.kind != 0 && r.D % 4 == 0 && al(r.in) && al(r.out) && (long)CW * r.D <= CHAIN_LDS &&
+  return r.kind != 0 && r.D % 4 == 0 && al16(r.in) && al16(r.out) && (long)CW * r.D <= CHAIN_LDS &&
          (long)r.B * r.N <= 0x3fffffffL;
+}
+
+// ---- THE dispatch rule: which kernel a convolution call gets, and what rides in it --------------------------------------------
+// Between the two LDS-resident generations: the column-strip kernels (chain_t.hpp) take a shape unless the default shape's own
+// kernels serve it and are preferred there (option chain_t: 0 never; 1 (default) wherever gcn_chain_s_* do not apply, and at
+// that shape too for RAGGED batches -- the column-strip kernels skip 16-row blocks per document, gcn_chain_s_* own 32 rows per
+// wave and do not: cfg 2 ragged 71.2 k -> 72.5 k docs/s at B = 32; dense batches stay on gcn_chain_s_* (0.522 vs 0.542 ms);
+// 2: everywhere).  What neither serves runs the generic kernels.
+static ChainPlan chain_pick(const ChainQuery& q, bool bwd, bool ride) {
+  ChainPlan p;
+  p.ride = ride;
+  const bool s = chain_s_serves(q, bwd), t = q.chain_t != 0 && chain_t_serves(q, bwd, ride);
+  const bool s_preferred = s && q.chain_t < 2 && !(q.chain_t == 1 && q.ragged);
+  p.kind = (t && !s_preferred) ? ChainPlan::T : s ? ChainPlan::S : ChainPlan::GENERIC;
+  p.aligned = p.kind == ChainPlan::GENERIC && chain_g_aligned(q, bwd);
+  p.full = p.kind == ChainPlan::T && q.N == 64 && !q.ragged;
+  return p;
+}
+// Graphs of more than 64 entities have no LDS-resident chain kernel: the generic chain kernels hand every product's tiles through
+// L2 inside one workgroup per (document, head) pair, and at that size each product is a full launch of its own anyway (cfg 5:
+// 4096 tiles).  Measured at cfg 5 (same session, profiles/r04_ab_chain_big.txt): per-product launches 7.67-7.74 ms, chain
+// kernels 7.86-7.90 ms per step; the one chain launch that pays is a FORWARD one with an edge mean riding in it (the chain hides
+// under the HBM-bound passenger: 698 us against 705 + 64).  Option chain_big = 1 restores the chain kernels everywhere (A/B,
+// tests); option chain = 0 runs every product as its own batched launch at every size (A/B testing of this file).
+ChainPlan chain_plan_fwd(const ChainQuery& q) {
+  const bool ride = chain_can_carry(q.ride);
+  if (!q.chain || !(q.N <= 64 || ride || q.chain_big)) return ChainPlan();
+  ChainPlan p = chain_pick(q, false, ride);
+  // the attention core in the chain workgroups' prologue: the LDS-resident kernels only, where its scratch fits
+  p.attention = q.hook && (p.kind == ChainPlan::T ? chain_t_attends(q) : p.kind == ChainPlan::S && chain_s_attends(q));
+  return p;
+}
+ChainPlan chain_plan_bwd(const ChainQuery& q) {
+  if (!q.chain || !(q.N <= 64 || q.chain_big)) return ChainPlan();
+  ChainPlan p = chain_pick(q, true, chain_can_carry(q.ride));
+  // dHO = dout Wlin and dXres = sum_h dHO_h inside the chain: where the kernel can, the call has workspace for the bias
+  // gradient's column sums, and the product is not smaller than the weight it reads
+  p.fuse = q.scratch && (long)q.B * q.N * q.HD >= (long)q.D * q.D &&
+           (p.kind == ChainPlan::T ? chain_t_fuses(q) : p.kind == ChainPlan::S && chain_s_fuses(q));
+  return p;
 }
 
 static unsigned chain_grid(const GcnCtx& c, int kind) {
   return (unsigned)(c.B * c.H) + (c.ride.kind == kind ? (unsigned)(c.ride.B * c.ride.N) : 0u);
 }
 
-int gcn_chain_fwd(const GcnCtx& c, hipStream_t st) {
+int gcn_chain_fwd(const GcnCtx& c, const ChainPlan& p, hipStream_t st) {
+  GC_REQUIRE(p.kind != ChainPlan::NONE, "gcn_chain_fwd: the plan names no chain kernel");
   GC_REQUIRE((long)c.B * c.H <= 0x3fffffffL, "gcn_chain_fwd: too many (doc, head) pairs");
   GC_REQUIRE(c.ride.kind == 0 || (c.ride.kind == 1 && chain_can_carry(c.ride)), "gcn_chain_fwd: bad passenger");
   dim3 grid(chain_grid(c, 1)), block(64 * CW);
   double fl = 0;
   for (int l = 0; l < c.L; ++l) fl += 2.0 * c.N * c.gh * (c.N + (double)l * c.gh);
-  // (which kernel generation serves the shape: chain_s_preferred above)
-  const bool s_ok = chain_aligned(c, false) && chain_small_ok(c, false);
-  if (chain_t_ok(c, false) && !chain_s_preferred(c, s_ok)) return gcn_chain_t_fwd(c, grid, fl * c.B * c.H, st);
-  // only the LDS-resident kernels run the attention core in their prologue: a caller that left it to the chain (c.mha) and ends
-  // up here would get a convolution over adjacencies nobody computed
-  GC_REQUIRE(!c.mha.Q || s_ok, "gcn_chain_fwd: the attention core was left to a chain kernel that does not run it");
-  if (s_ok)
+  if (p.kind == ChainPlan::T) return gcn_chain_t_fwd(c, p, grid, fl * c.B * c.H, st);
+  if (p.kind == ChainPlan::S)
     GC_LAUNCH_TIMED("gcn_chain_fwd", fl * c.B * c.H, gcn_chain_s_fwd_kernel, grid, block, 0, st, c);
-  else if (chain_aligned(c, false)) GC_LAUNCH_TIMED("gcn_chain_fwd", fl * c.B * c.H, gcn_chain_fwd_kernel<true>, grid, block, 0, st, c);
+  else if (p.aligned) GC_LAUNCH_TIMED("gcn_chain_fwd", fl * c.B * c.H, gcn_chain_fwd_kernel<true>, grid, block, 0, st, c);
   else GC_LAUNCH_TIMED("gcn_chain_fwd", fl * c.B * c.H, gcn_chain_fwd_kernel<false>, grid, block, 0, st, c);
   return check_launch("gcn_chain_fwd");
 }
 
-static int chain_bwd_launch(const GcnCtx& c, const GemmGroup4& cg, dim3 grid, dim3 block, double fl, hipStream_t st);
-
-int gcn_chain_bwd(const GcnCtx& c, hipStream_t st, DeferQueue* carry) {
+int gcn_chain_bwd(const GcnCtx& c, const ChainPlan& p, hipStream_t st, DeferQueue* carry) {
+  GC_REQUIRE(p.kind != ChainPlan::NONE, "gcn_chain_bwd: the plan names no chain kernel");
   GC_REQUIRE(c.ride.kind == 0 || (c.ride.kind == 2 && chain_can_carry(c.ride)), "gcn_chain_bwd: bad passenger");
   double fl = 0;
   for (int l = 0; l < c.L; ++l) fl += 4.0 * c.N * c.gh * c.N + 2.0 * c.N * c.gh * (double)l * c.gh;
   fl *= (double)c.B * c.H;
+  if (p.kind == ChainPlan::T) return gcn_chain_t_bwd(c, p, fl, st, carry);
   GemmGroup4 cg;
   cg.nprob = 0, cg.tile_begin[0] = 0;
   // Parked products ride only where the chain leaves the chip mostly empty (few (doc, head) pairs): a passenger workgroup
@@ -886,9 +903,6 @@ int gcn_chain_bwd(const GcnCtx& c, hipStream_t st, DeferQueue* carry) {
   // of the tile -- and occupies its compute unit alone (register footprint of this kernel).  As many tiles ride as fit
   // beside the chain's own duration (~8 us per dependent product and tile pass, measured at cfg 2 / cfg 3); a problem is
   // split at the budget, the rest of its tiles rides in GATAttention's edge pass.  K % 64 == 0 for equal halves.
-  const bool s_ok = chain_aligned(c, true) && chain_small_ok(c, true);
-  const bool use_t = chain_t_ok(c, true) && !chain_s_preferred(c, s_ok);
-  if (use_t) return gcn_chain_t_bwd(c, fl, st, carry);
   int ng = 0;
   if (carry && carry->n > 0 && (long)c.B * c.H <= 64 && ((long)c.B * c.N) % 64 == 0) {
     const int passes = (((c.N + 63) / 64) * ((c.gh + 63) / 64) + 1) / 2;
@@ -905,7 +919,14 @@ int gcn_chain_bwd(const GcnCtx& c, hipStream_t st, DeferQueue* carry) {
   dim3 grid(chain_grid(c, 2) + (unsigned)ng), block(64 * CW);
   GcnCtx cc = c;
   cc.carry = chain_carry_spread(c, ng);
-  return chain_bwd_launch(cc, cg, grid, block, fl, st);
+  if (p.kind == ChainPlan::S && p.fuse) {
+    fl += 2.0 * c.B * c.N * c.D * c.D * (c.H + (c.H > 1 ? 1 : 0));
+    GC_LAUNCH_TIMED("gcn_chain_bwd", fl, gcn_chain_s_bwd_kernel<true>, grid, block, 0, st, cc, cg);
+  } else if (p.kind == ChainPlan::S)
+    GC_LAUNCH_TIMED("gcn_chain_bwd", fl, gcn_chain_s_bwd_kernel<false>, grid, block, 0, st, cc, cg);
+  else if (p.aligned) GC_LAUNCH_TIMED("gcn_chain_bwd", fl, gcn_chain_bwd_kernel<true>, grid, block, 0, st, cc, cg);
+  else GC_LAUNCH_TIMED("gcn_chain_bwd", fl, gcn_chain_bwd_kernel<false>, grid, block, 0, st, cc, cg);
+  return check_launch("gcn_chain_bwd");
 }
 
 Spread chain_carry_spread(const GcnCtx& c, int ng) {
@@ -916,18 +937,6 @@ Spread chain_carry_spread(const GcnCtx& c, int ng) {
   const long rows = c.ride.kind == 2 ? (long)c.ride.B * c.ride.N : 0;
   const bool on = rows > 0 && ng >= spread_min;
   return make_spread(ng, rows, cohort, on ? spread_pct : 0);
-}
-
-static int chain_bwd_launch(const GcnCtx& c, const GemmGroup4& cg, dim3 grid, dim3 block, double fl, hipStream_t st) {
-  if (c.dout) {  // the caller asked for the fused output-projection gradient (after chain_bwd_fusable said yes)
-    GC_REQUIRE(chain_aligned(c, true) && chain_bwd_fusable(c) && c.dXres && (c.H == 1 || c.Wsum), "gcn_chain_bwd: fused backward not available");
-    fl += 2.0 * c.B * c.N * c.D * c.D * (c.H + (c.H > 1 ? 1 : 0));
-    GC_LAUNCH_TIMED("gcn_chain_bwd", fl, gcn_chain_s_bwd_kernel<true>, grid, block, 0, st, c, cg);
-  } else if (chain_aligned(c, true) && chain_small_ok(c, true))
-    GC_LAUNCH_TIMED("gcn_chain_bwd", fl, gcn_chain_s_bwd_kernel<false>, grid, block, 0, st, c, cg);
-  else if (chain_aligned(c, true)) GC_LAUNCH_TIMED("gcn_chain_bwd", fl, gcn_chain_bwd_kernel<true>, grid, block, 0, st, c, cg);
-  else GC_LAUNCH_TIMED("gcn_chain_bwd", fl, gcn_chain_bwd_kernel<false>, grid, block, 0, st, c, cg);
-  return check_launch("gcn_chain_bwd");
 }
 
 }  // namespace gc

@@ -1,81 +1,61 @@
-// Host side of the column-strip chain kernels: which shapes they serve, how many parked weight-gradient tiles a backward
-// launch takes along, and the dispatch to the translation unit that holds a shape's instantiations (chain_t.hpp explains the
+// Host side of the column-strip chain kernels: which inputs they serve (asked by chain_plan_fwd / _bwd, chain.hip, and by
+// nobody else: the launchers below run what the ChainPlan says), how many parked weight-gradient tiles a backward launch takes along, and the dispatch to the translation unit that holds a shape's instantiations (chain_t.hpp explains the
 // kernels; chain_t_u0 .. u3.hip instantiate them, four units so that the build compiles them side by side).
+#include "chain_t_shapes.hpp"
 #include "gcn_plan.hpp"
 #include "gemm_body.hpp"
 #include "rowops.hpp"
 
 namespace gc {
 
-constexpr int T_LA = 68;   // (chain_t.hpp) row pitch of the adjacency image: part of the forward kernel's LDS size below
-
-// (gh, L) pairs with an instantiation -- the same list as GC_CHAIN_T_SHAPES in chain_t.hpp
-#define GC_CHAIN_T_HOST_SHAPES(X) X(32, 2) X(32, 4) X(64, 1) X(64, 2) X(64, 3) X(64, 4) X(128, 1) X(128, 2) X(128, 3) X(128, 4) X(192, 2) X(192, 4) X(256, 1) X(256, 2)
-
 #define GC_T_UNITS(X) X(0) X(1) X(2) X(3)
 #define X(u) \
-  int chain_t_fwd_unit##u(const GcnCtx& c, dim3 grid, double fl, hipStream_t st, int* rc); \
-  int chain_t_bwd_unit##u(const GcnCtx& c, const GemmGroup4& cg, int npw, dim3 grid, double fl, hipStream_t st, int* rc);
+  int chain_t_fwd_unit##u(const GcnCtx& c, const ChainPlan& p, dim3 grid, double fl, hipStream_t st, int* rc); \
+  int chain_t_bwd_unit##u(const GcnCtx& c, const ChainPlan& p, const GemmGroup4& cg, int npw, dim3 grid, double fl, hipStream_t st, int* rc);
 GC_T_UNITS(X)
 #undef X
 
 static int chain_t_waves(int gh) { return gh / 16; }
 
-// 0 = not served by these kernels (the generic chain kernels take it)
-bool chain_t_ok(const GcnCtx& c, bool bwd) {
-  const int mode = option("chain_t", 1);
-  if (!mode || c.N > 64 || c.N < 1) return false;
-  bool shape = false;
-#define X(gh_, l_) shape = shape || (c.gh == gh_ && c.L == l_);
-  GC_CHAIN_T_HOST_SHAPES(X)
-#undef X
-  if (!shape) return false;
-  auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  bool ok = al(c.A) && al(c.flat + c.oWd) && c.wd_head % 4 == 0 && c.HD % 4 == 0 && al(c.Pn) && al(c.Y);
-  if (bwd) ok = ok && (c.dout ? chain_t_bwd_fusable(c) && al(c.dout) && al(c.dXres) && (!c.dout_m || al(c.dout_m)) : al(c.dYa)) && al(c.dM) && al(c.dP);
-  else ok = ok && al(c.G) && al(c.HO) && al(c.X);
-  if (c.ride.kind) {   // the passenger bodies use 16-byte accesses and (forward) waves x D floats of the kernel's LDS
-    const int lds_fwd = 64 * T_LA + 64 * (c.gh + 4) + 2 * (c.L - 1) * 16 * (c.gh + 4) + 64;
-    ok = ok && c.ride.D % 4 == 0 && al(c.ride.in) && al(c.ride.out) && (bwd || (long)chain_t_waves(c.gh) * c.ride.D <= lds_fwd);
-  }
+// The column-strip kernels serve this input: an instantiated shape, 16-byte operands (the unfused backward reads dYa)
+bool chain_t_serves(const ChainQuery& q, bool bwd, bool ride) {
+  if (q.N > 64 || q.N < 1 || !t_instantiated(q.gh, q.L)) return false;
+  bool ok = al16(q.A) && al16(q.flat + q.oWd) && q.wd_head % 4 == 0 && q.HD % 4 == 0 && al16(q.Pn) && al16(q.Y);
+  if (bwd) ok = ok && al16(q.dYa) && al16(q.dM) && al16(q.dP);
+  else ok = ok && al16(q.G) && al16(q.HO) && al16(q.X);
+  if (ride)   // the passenger bodies use 16-byte accesses and (forward) waves x D floats of the kernel's LDS
+    ok = ok && q.ride.D % 4 == 0 && al16(q.ride.in) && al16(q.ride.out) && (bwd || (long)chain_t_waves(q.gh) * q.ride.D <= t_fwd_lds(q.gh, q.L));
   return ok;
 }
 
 // The backward kernel can compute the output projection's input gradient itself (chain_t.hpp FUSE): blocks of at most 256
 // features whose residual-gradient share divides over the waves (one head: no such product)
-bool chain_t_bwd_fusable(const GcnCtx& c) {
-  if (c.N > 64 || c.D != c.L * c.gh || c.D > 256 || c.D % 32 != 0 || c.gh > 128 || 16 % c.L != 0) return false;
-  bool shape = false;
-#define X(gh_, l_) shape = shape || (c.gh == gh_ && c.L == l_);
-  GC_CHAIN_T_HOST_SHAPES(X)
-#undef X
-  if (!shape) return false;
-  auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-  if (!al(c.flat + c.oWlin) || c.HD % 4 != 0) return false;
-  if (c.H == 1) return true;
-  const int W = c.gh / 16;
-  if (c.D % c.H != 0) return false;
-  const int DH = c.D / c.H;
+bool chain_t_fuses(const ChainQuery& q) {
+  if (!t_fuse_shape(q.gh, q.L) || q.D != q.L * q.gh || q.D % 32 != 0) return false;
+  if (!al16(q.flat + q.oWlin) || q.HD % 4 != 0 || !al16(q.dout) || !al16(q.dXres) || !al16(q.dout_m)) return false;
+  if (q.H == 1) return true;
+  const int W = q.gh / 16;
+  if (q.D % q.H != 0) return false;
+  const int DH = q.D / q.H;
   if (DH % 16 != 0) return false;
   const int ncg = DH / 16;
   if (ncg > W || W % ncg != 0) return false;
   const int kw = W / ncg;
-  return c.D % kw == 0 && (c.D / kw) % 16 == 0;
+  return q.D % kw == 0 && (q.D / kw) % 16 == 0;
 }
 
 // the forward kernel can run the attention core in its prologue: the core's scratch (score tile + one Q chunk) fits the Y image
 // and the weight stages
-bool chain_t_fwd_att_ok(const GcnCtx& c) {
-  const int dh = c.D / c.H;
-  const long room = 64L * (c.gh + 4) + 2L * (c.L - 1) * 16 * (c.gh + 4);
+bool chain_t_attends(const ChainQuery& q) {
+  const int dh = q.D / q.H;
   // (the core's body runs on the first four waves of the workgroup: widths of at least 64)
-  return c.N <= 64 && c.gh >= 64 && dh % 4 == 0 && (long)(mha_lds_bytes(dh) / sizeof(float)) <= room;
+  return q.gh >= 64 && dh % 4 == 0 && (long)(mha_lds_bytes(dh) / sizeof(float)) <= t_fwd_room(q.gh, q.L);
 }
 
-int gcn_chain_t_fwd(const GcnCtx& c, dim3 grid, double fl, hipStream_t st) {
+int gcn_chain_t_fwd(const GcnCtx& c, const ChainPlan& p, dim3 grid, double fl, hipStream_t st) {
   int rc = 0;
 #define X(u) \
-  if (chain_t_fwd_unit##u(c, grid, fl, st, &rc)) return rc;
+  if (chain_t_fwd_unit##u(c, p, grid, fl, st, &rc)) return rc;
   GC_T_UNITS(X)
 #undef X
   set_error("gcn_chain_t_fwd: shape gh=%d L=%d not instantiated", c.gh, c.L);
@@ -84,7 +64,7 @@ int gcn_chain_t_fwd(const GcnCtx& c, dim3 grid, double fl, hipStream_t st) {
 
 // carry: parked weight-gradient products; as many of their tiles ride as fit on the compute units this launch leaves idle
 // in one round (a tile's whole K takes about as long as the chain itself), half of them when the dE broadcast rides as well
-int gcn_chain_t_bwd(const GcnCtx& c, double fl, hipStream_t st, DeferQueue* carry) {
+int gcn_chain_t_bwd(const GcnCtx& c, const ChainPlan& p, double fl, hipStream_t st, DeferQueue* carry) {
   GemmGroup4 cg;
   cg.nprob = 0, cg.tile_begin[0] = 0;
   const int nteam = c.gh / 64;
@@ -95,7 +75,7 @@ int gcn_chain_t_bwd(const GcnCtx& c, double fl, hipStream_t st, DeferQueue* carr
     int kmax = 0;
     for (int i = 0; i < carry->n; ++i) {
       ok = ok && carry->p[i].K % BK == 0 && carry->p[i].splits <= 1;
-      ok = ok && !(carry->p[i].rb && (chain_t_full(c) || carry->p[i].rb_mode != 2));   // row-block products: the ragged instantiations only
+      ok = ok && !(carry->p[i].rb && (p.full || carry->p[i].rb_mode != 2));   // row-block products: the ragged instantiations only
       // (a row-block product walks the live blocks only -- 43 % of K at DocRED's entity counts; the host never reads n_valid and
       // prices it at half its K.  At full price no tile fitted beside cfg 2's ragged CAGGC chain, whose 224 idle compute units then
       // waited out the launch while the last edge pass ran all 740 tiles: chain 43.6 -> 51.2 us with 304 of them aboard, edge pass
@@ -122,7 +102,7 @@ int gcn_chain_t_bwd(const GcnCtx& c, double fl, hipStream_t st, DeferQueue* carr
   cc.carry = chain_carry_spread(c, npw);
   int rc = 0;
 #define X(u) \
-  if (chain_t_bwd_unit##u(cc, cg, npw, grid, fl, st, &rc)) return rc;
+  if (chain_t_bwd_unit##u(cc, p, cg, npw, grid, fl, st, &rc)) return rc;
   GC_T_UNITS(X)
 #undef X
   set_error("gcn_chain_t_bwd: shape gh=%d L=%d not instantiated", c.gh, c.L);

@@ -38,6 +38,7 @@
 #pragma once
 #include <type_traits>
 
+#include "chain_t_shapes.hpp"
 #include "edge_body.hpp"
 #include "gcn_plan.hpp"
 #include "gemm_body.hpp"
@@ -57,8 +58,6 @@ static __device__ long long gc_trace_t[256];   // (one copy per translation unit
 #endif
 
 typedef float t4 __attribute__((ext_vector_type(4)));
-
-constexpr int T_LA = 68;  // row pitch of the 64 x 64 adjacency image (16-byte rows, conflict-free 16-byte reads)
 
 __device__ __forceinline__ void t_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ t4 mfma16(float a, float b, t4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
@@ -95,21 +94,6 @@ __device__ __forceinline__ void t_st4(t_desc d, unsigned voff, unsigned soff, t4
 // "this value exists now": an empty volatile statement that reads and writes an accumulator, so that the instructions producing
 // it can be neither sunk past this point nor hoisted above it
 __device__ __forceinline__ void t_pin(t4& acc) { asm volatile("" : "+v"(acc)); }
-
-template <int GH, int L>
-constexpr int t_fwd_lds() { return 64 * T_LA + 64 * (GH + 4) + 2 * (L - 1) * 16 * (GH + 4) + 64; }
-template <int GH>
-constexpr int t_bwd_lds() { return 64 * T_LA + 2 * 64 * (GH + 4) + (GH / 16) * 64 + 128; }
-// FUSE (the output projection's input gradient computed by the backward kernel itself): the dout image [64][D + 4] and two
-// 16-deep stages of Wlin's slice lie over the dM / Pn images (used only afterwards); behind the row-sum areas the K slices of
-// the residual gradient meet
-constexpr int t_max(int a, int b) { return a > b ? a : b; }
-template <int GH, int L>
-constexpr int t_bwd_region() { return t_max(2 * 64 * (GH + 4), 96 * (L * GH + 4)); }
-template <int GH, int L>
-constexpr int t_bwd_fuse_lds() { return 64 * T_LA + t_bwd_region<GH, L>() + (GH / 16) * 64 + 128 + (GH / 16) * 1024; }
-template <int GH, int L>
-constexpr bool t_fuse_shape() { return L * GH <= 256 && GH <= 128 && 16 % L == 0; }   // wider blocks: the images do not fit (and the product is a launch's worth); L = 3: the image pieces do not divide over the threads
 
 // ---------------------------------------------------------------------------------------------------------------------
 // forward:  rinv = 1 / rowsum(A_h);  for l:  Y_l = relu((G_l + A_h Pn_l) rinv),  HO_l = dropout(Y_l) + X_l,
@@ -320,7 +304,7 @@ __device__ __forceinline__ void chain_t_fwd_body(const GcnCtx& c, float* __restr
 template <int GH, int L, bool FULL>
 __global__ __launch_bounds__(4 * GH) void gcn_chain_t_fwd_kernel(const GcnCtx c) {
   constexpr int W = GH / 16;
-  __shared__ __attribute__((aligned(16))) float lds[t_fwd_lds<GH, L>()];
+  __shared__ __attribute__((aligned(16))) float lds[t_fwd_lds(GH, L)];
   if (blockIdx.x >= c.B * c.H) {  // passenger workgroup: one entity row of the riding edge mean
     const EdgeRide& r = c.ride;
     edge_fwd_row<4, false, W>(r.in, nullptr, r.n_valid, r.out, nullptr, nullptr, nullptr, Drop(), r.N, r.D,
@@ -393,7 +377,7 @@ __device__ __forceinline__ void t_parked_tiles(const GemmGroup4& cg, int pb, flo
 // head-sum / dropout kernel (glove:74-78 / 111-118): five launches of a ragged cfg-2 step's 27, four of cfg 1's 24.
 template <int GH, int L, int NRB, bool FUSE>
 __device__ __forceinline__ void chain_t_bwd_body(const GcnCtx& c, float* __restrict__ lds, const int z, const int b, const int h, const int nv) {
-  constexpr int REG = FUSE ? t_bwd_region<GH, L>() : 2 * 64 * (GH + 4);       // floats of the image region
+  constexpr int REG = FUSE ? t_bwd_region(GH, L) : 2 * 64 * (GH + 4);       // floats of the image region
   constexpr int W = GH / 16, NT = 4 * GH, P = GH + 4, NC = GH / 16, SP = 20;   // SP: row pitch of a [gh][16 k] weight stage
   static_assert(2 * GH * SP <= 64 * P, "weight stages live in the Pn image");
   static_assert(W <= 4 || (W / 4 - 1) * 4096 <= 64 * P, "dA exchange lives in the dM image");
@@ -683,7 +667,7 @@ __device__ __forceinline__ void chain_t_bwd_body(const GcnCtx& c, float* __restr
       }
     }
     // this head's D / H columns of dXres_b = dout_b Wsum (H > 1): DH / 16 column groups, each K-split over W / (DH / 16) waves
-    // (the host only fuses shapes where these divide: chain_t_bwd_fusable); the slices meet in Es behind the product's barriers
+    // (the host only fuses shapes where these divide: chain_t_fuses); the slices meet in Es behind the product's barriers
     const int DH = D / c.H, ncg = max(DH >> 4, 1), kw = max(W / ncg, 1), cgi = w % ncg, ksl = w / ncg, klen = D / kw;
     t4 xa[4];
 #pragma unroll
@@ -822,7 +806,7 @@ __device__ __forceinline__ void chain_t_bwd_body(const GcnCtx& c, float* __restr
 template <int GH, int L, bool FULL, bool FUSE>
 __global__ __launch_bounds__(4 * GH) void gcn_chain_t_bwd_kernel(const GcnCtx c, const GemmGroup4 cg, const int npw) {
   constexpr int W = GH / 16;
-  constexpr int LDSF = FUSE ? t_bwd_fuse_lds<GH, L>() : t_bwd_lds<GH>();
+  constexpr int LDSF = FUSE ? t_bwd_fuse_lds(GH, L) : t_bwd_lds(GH);
   static_assert(LDSF * sizeof(float) <= 160 * 1024, "LDS of one compute unit");
   __shared__ __attribute__((aligned(16))) float lds[LDSF];
   static_assert((GH / 64) * T_TEAM_LDS <= LDSF, "parked tiles use the chain kernel's LDS");
@@ -853,42 +837,34 @@ __global__ __launch_bounds__(4 * GH) void gcn_chain_t_bwd_kernel(const GcnCtx c,
   }
 }
 
+// the launchers run the instantiation the ChainPlan names (p.full, p.fuse) and decide nothing themselves
 template <int GH, int L>
-static int chain_t_run_fwd(const GcnCtx& c, dim3 grid, double fl, hipStream_t st) {
-  if (chain_t_full(c)) GC_LAUNCH_TIMED("gcn_chain_fwd", fl, (gcn_chain_t_fwd_kernel<GH, L, true>), grid, dim3(4 * GH), 0, st, c);
+static int chain_t_run_fwd(const GcnCtx& c, const ChainPlan& p, dim3 grid, double fl, hipStream_t st) {
+  if (p.full) GC_LAUNCH_TIMED("gcn_chain_fwd", fl, (gcn_chain_t_fwd_kernel<GH, L, true>), grid, dim3(4 * GH), 0, st, c);
   else GC_LAUNCH_TIMED("gcn_chain_fwd", fl, (gcn_chain_t_fwd_kernel<GH, L, false>), grid, dim3(4 * GH), 0, st, c);
   return check_launch("gcn_chain_t_fwd");
 }
 template <int GH, int L>
-static int chain_t_run_bwd(const GcnCtx& c, const GemmGroup4& cg, int npw, dim3 grid, double fl, hipStream_t st) {
-  if constexpr (t_fuse_shape<GH, L>()) {
-    if (c.dout) {   // the fused output-projection gradient (chain_t_bwd_fusable said yes)
-      if (chain_t_full(c)) GC_LAUNCH_TIMED("gcn_chain_bwd", fl, (gcn_chain_t_bwd_kernel<GH, L, true, true>), grid, dim3(4 * GH), 0, st, c, cg, npw);
+static int chain_t_run_bwd(const GcnCtx& c, const ChainPlan& p, const GemmGroup4& cg, int npw, dim3 grid, double fl, hipStream_t st) {
+  if constexpr (t_fuse_shape(GH, L)) {
+    if (p.fuse) {
+      if (p.full) GC_LAUNCH_TIMED("gcn_chain_bwd", fl, (gcn_chain_t_bwd_kernel<GH, L, true, true>), grid, dim3(4 * GH), 0, st, c, cg, npw);
       else GC_LAUNCH_TIMED("gcn_chain_bwd", fl, (gcn_chain_t_bwd_kernel<GH, L, false, true>), grid, dim3(4 * GH), 0, st, c, cg, npw);
       return check_launch("gcn_chain_t_bwd");
     }
   }
-  if (chain_t_full(c)) GC_LAUNCH_TIMED("gcn_chain_bwd", fl, (gcn_chain_t_bwd_kernel<GH, L, true, false>), grid, dim3(4 * GH), 0, st, c, cg, npw);
+  if (p.full) GC_LAUNCH_TIMED("gcn_chain_bwd", fl, (gcn_chain_t_bwd_kernel<GH, L, true, false>), grid, dim3(4 * GH), 0, st, c, cg, npw);
   else GC_LAUNCH_TIMED("gcn_chain_bwd", fl, (gcn_chain_t_bwd_kernel<GH, L, false, false>), grid, dim3(4 * GH), 0, st, c, cg, npw);
   return check_launch("gcn_chain_t_bwd");
 }
 
-// (gh, L) pairs the templates are instantiated for: the reference's model (64, 2), cfg 2's width (128, 2), cfg 3 (192, 4),
-// and the neighbours a user is most likely to configure.  Four translation units (chain_t_{a,b,c,d}.hip) share them so that
-// the build runs them side by side; X(gh, L, unit)
-#define GC_CHAIN_T_SHAPES(X) \
-  X(32, 2, 0) X(32, 4, 0) X(64, 1, 0) X(64, 2, 0) X(64, 3, 0) X(64, 4, 0) \
-  X(128, 1, 1) X(128, 2, 1) X(128, 3, 1) X(128, 4, 1) \
-  X(192, 2, 2) X(192, 4, 2) \
-  X(256, 1, 3) X(256, 2, 3)
-
 // chain_t_u<U>.hip:  GC_CHAIN_T_UNIT(U)  defines the two entry points of unit U (1 = launched, *rc set; 0 = not its shape)
 template <int U>
-static int chain_t_unit_fwd(const GcnCtx& c, dim3 grid, double fl, hipStream_t st, int* rc) {
+static int chain_t_unit_fwd(const GcnCtx& c, const ChainPlan& p, dim3 grid, double fl, hipStream_t st, int* rc) {
 #define X(gh_, l_, u_)                                    \
   if constexpr (u_ == U) {                                \
     if (c.gh == gh_ && c.L == l_) {                       \
-      *rc = chain_t_run_fwd<gh_, l_>(c, grid, fl, st);    \
+      *rc = chain_t_run_fwd<gh_, l_>(c, p, grid, fl, st); \
       return 1;                                           \
     }                                                     \
   }
@@ -897,11 +873,11 @@ static int chain_t_unit_fwd(const GcnCtx& c, dim3 grid, double fl, hipStream_t s
   return 0;
 }
 template <int U>
-static int chain_t_unit_bwd(const GcnCtx& c, const GemmGroup4& cg, int npw, dim3 grid, double fl, hipStream_t st, int* rc) {
+static int chain_t_unit_bwd(const GcnCtx& c, const ChainPlan& p, const GemmGroup4& cg, int npw, dim3 grid, double fl, hipStream_t st, int* rc) {
 #define X(gh_, l_, u_)                                             \
   if constexpr (u_ == U) {                                         \
     if (c.gh == gh_ && c.L == l_) {                                \
-      *rc = chain_t_run_bwd<gh_, l_>(c, cg, npw, grid, fl, st);    \
+      *rc = chain_t_run_bwd<gh_, l_>(c, p, cg, npw, grid, fl, st); \
       return 1;                                                    \
     }                                                              \
   }
@@ -917,9 +893,9 @@ static int chain_t_unit_bwd(const GcnCtx& c, const GemmGroup4& cg, int npw, dim3
 #endif
 #define GC_CHAIN_T_UNIT(U)                                                                                                          \
   namespace gc {                                                                                                                    \
-  int chain_t_fwd_unit##U(const GcnCtx& c, dim3 grid, double fl, hipStream_t st, int* rc) { return chain_t_unit_fwd<U>(c, grid, fl, st, rc); } \
-  int chain_t_bwd_unit##U(const GcnCtx& c, const GemmGroup4& cg, int npw, dim3 grid, double fl, hipStream_t st, int* rc) {          \
-    return chain_t_unit_bwd<U>(c, cg, npw, grid, fl, st, rc);                                                                       \
+  int chain_t_fwd_unit##U(const GcnCtx& c, const ChainPlan& p, dim3 grid, double fl, hipStream_t st, int* rc) { return chain_t_unit_fwd<U>(c, p, grid, fl, st, rc); } \
+  int chain_t_bwd_unit##U(const GcnCtx& c, const ChainPlan& p, const GemmGroup4& cg, int npw, dim3 grid, double fl, hipStream_t st, int* rc) {          \
+    return chain_t_unit_bwd<U>(c, p, cg, npw, grid, fl, st, rc);                                                                       \
   }                                                                                                                                 \
   }                                                                                                                                 \
   GC_CHAIN_T_TRACE_EXPORT(U)

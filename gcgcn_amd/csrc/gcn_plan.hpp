@@ -1,6 +1,7 @@
 // The per-(document, head) products of the densely connected GraphConv stack, described once and
-// used twice: by the host (one batched launch per product: gcgcn_gcn_fwd/_bwd with option chain = 0)
-// and by the chain kernels (chain.hip: one persistent workgroup per (b, h) runs them back to back).
+// used twice: by the host (one batched launch per product: ChainPlan::NONE) and by the chain kernels
+// (chain.hip: one persistent workgroup per (b, h) runs them back to back).  Below them: ChainQuery /
+// ChainPlan, the one decision which of the two, and which chain kernel, a convolution call gets.
 //
 // Tensors are [B*N, H, L, gh] row-major (row stride HD = H*D, D = L*gh); A is [B, H, N, N];
 // z1 = document, z2 = head.  Reference: GraphConv.forward glove:36-50 inside the dense loops of
@@ -146,22 +147,56 @@ __host__ __device__ inline GemmArgs plan_bwd_dY(const GcnCtx& c, int l) {
   return g;
 }
 
+// ---- which chain kernel serves a convolution call -------------------------------------------------------------------------
+// Decided ONCE per gcgcn_gcn_fwd / _bwd call, by chain_plan_fwd / _bwd (chain.hip), from a ChainQuery that holds everything the
+// decision may depend on; the ChainPlan travels BESIDE the GcnCtx (a kernel argument, whose layout it must not move) to
+// gcn_chain_fwd / _bwd and on to the column-strip launchers, which select the kernel from it and ask nothing again.
+struct ChainQuery {
+  int B, N, D, L, H, gh;
+  long HD, oWd, wd_head, oWlin;
+  const float* flat;
+  bool ragged;    // n_valid given
+  bool scratch;   // the call has workspace (the fused backward parks its column sums there)
+  bool hook;      // forward: the attention core is left to this call (gcgcn_mha_hook)
+  EdgeRide ride;  // the passenger the caller offers (kind 0: none)
+  const void *A, *Pn, *Y;               // operands whose alignment matters: both directions,
+  const void *G, *HO, *X;               // forward,
+  const void *dYa, *dM, *dP, *dA;       // backward,
+  const void *dout, *dXres, *dout_m;    // the fused output projection's (dout_m: NULL or the masked gradient's workspace)
+  int chain, chain_big, chain_t;        // the options of the same names
+};
+struct ChainPlan {
+  enum Kind { NONE, GENERIC, S, T };   // one launch per product | gcn_chain_fwd/bwd_kernel | gcn_chain_s_* | gcn_chain_t_*
+  int kind = NONE;
+  bool aligned = false;     // GENERIC: the <ALIGNED> instantiation
+  bool full = false;        // T: the FULL instantiation (every document fills all four 16-row blocks: N == 64, no n_valid)
+  bool fuse = false;        // backward, S / T: the chain computes dHO = dout Wlin and dXres itself (c.dout, c.dXres, c.Wsum)
+  bool attention = false;   // forward, S / T: the chain runs the attention core in its prologue (c.mha)
+  bool ride = false;        // the offered edge pass is a passenger of the chain launch (c.ride)
+};
+inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+ChainPlan chain_plan_fwd(const ChainQuery& q);
+ChainPlan chain_plan_bwd(const ChainQuery& q);
+
+// Each kernel generation answers for itself only, next to its kernels: "I serve this input" (shape + alignment), and for the
+// LDS-resident ones whether the backward can fuse the output projection's gradient / the forward can run the attention core.
+// Called from chain_plan_fwd / _bwd and from nowhere else; the preference between generations lives there.
+bool chain_g_aligned(const ChainQuery& q, bool bwd);                       // chain.hip: generic kernels, <ALIGNED> or not
+bool chain_s_serves(const ChainQuery& q, bool bwd);                        // chain.hip: gcn_chain_s_*
+bool chain_s_fuses(const ChainQuery& q);
+bool chain_s_attends(const ChainQuery& q);
+bool chain_t_serves(const ChainQuery& q, bool bwd, bool ride);            // chain_t.hip: gcn_chain_t_* (ride: q.ride comes along)
+bool chain_t_fuses(const ChainQuery& q);
+bool chain_t_attends(const ChainQuery& q);
+bool chain_can_carry(const EdgeRide& r);                                   // chain.hip: a passenger every chain kernel can take
+
 // chain_t.hip (host side) + chain_t.hpp / chain_t_u0..3.hip (kernels): LDS-resident chain kernels for N <= 64 and the instantiated (gh, L) pairs
-bool chain_t_ok(const GcnCtx& c, bool bwd);
-bool chain_t_bwd_fusable(const GcnCtx& c);   // the column-strip backward computes dHO / dXres itself (c.dout) at this shape
-bool chain_t_fwd_att_ok(const GcnCtx& c);
-int gcn_chain_t_fwd(const GcnCtx& c, dim3 grid, double flops, hipStream_t st);
-int gcn_chain_t_bwd(const GcnCtx& c, double flops, hipStream_t st, DeferQueue* carry);
-// the full-size instantiation: every document fills all four 16-row blocks exactly (N == 64, no n_valid) -- one body, no
-// switch, no bounds test; everything else runs the instantiation that picks a body per document (chain_t.hpp)
-inline bool chain_t_full(const GcnCtx& c) { return c.N == 64 && !c.n_valid; }
+int gcn_chain_t_fwd(const GcnCtx& c, const ChainPlan& p, dim3 grid, double flops, hipStream_t st);
+int gcn_chain_t_bwd(const GcnCtx& c, const ChainPlan& p, double flops, hipStream_t st, DeferQueue* carry);
 
 // chain.hip
-bool chain_fwd_computes_attention(const GcnCtx& c);   // the forward chain kernel of this shape takes c.mha
-bool chain_can_carry(const EdgeRide& r);
 Spread chain_carry_spread(const GcnCtx& c, int n_tile_workgroups);
-int gcn_chain_fwd(const GcnCtx& c, hipStream_t st);
-int gcn_chain_bwd(const GcnCtx& c, hipStream_t st, DeferQueue* carry = nullptr);
-bool chain_bwd_fusable(const GcnCtx& c);   // c.dout / c.dXres / c.Wsum may be used instead of c.dYa
+int gcn_chain_fwd(const GcnCtx& c, const ChainPlan& p, hipStream_t st);
+int gcn_chain_bwd(const GcnCtx& c, const ChainPlan& p, hipStream_t st, DeferQueue* carry = nullptr);
 
 }  // namespace gc

@@ -360,6 +360,16 @@ int gcgcn_tensorise(int B, int N, int S, int T, int R, int dis_plus, int n_slots
  * kind[x] / ordinal[x] for every workgroup index x < n_tiles + n_others: 1 / tile number or 0 / row number.  Host-only. */
 int gcgcn_debug_spread(int64_t n_tiles, int64_t n_others, int64_t cohort, int64_t pct, int32_t* kind, int32_t* ordinal);
 
+/* ---- test hook: which chain kernel a gcgcn_gcn_fwd (bwd = 0) / gcgcn_gcn_bwd (bwd = 1) call of this shape gets -------
+ * Evaluates the plan function the two entry points call (csrc/chain.hip chain_plan_fwd / _bwd) under the current options.
+ * ragged: n_valid given; ride / hook / scratch: those arguments given; misalign: bit 0 the per-(document, head) tensors,
+ * bit 1 dout / dXres / dout_m, bit 2 the ride's in / out, bit 3 flat are NOT 16-byte aligned.
+ * out[6] = kind (0 one launch per product, 1 generic chain kernels, 2 gcn_chain_s_*, 3 gcn_chain_t_*), aligned (kind 1),
+ * full (kind 3), fuse (backward computes dHO / dXres), attention (forward runs the core), ride (the edge pass is a
+ * passenger of the chain launch).  Host-only. */
+int gcgcn_debug_chain_plan(int bwd, int B, int N, int D, int L, int H, int ragged, int ride, int hook, int scratch,
+                           int misalign, int32_t* out);
+
 /* ---- raw batched GEMM (exposed for unit tests and benchmarks of the MFMA kernel) ----------- */
 /* C[z] = alpha * opA(A[z]) opB(B[z]);  a_kc: A stored [M][K] else [K][M];  b_kc: B stored [N][K]
  * else [K][N];  z < batch with element strides sA, sB, sC;  tile: 0 or 1 = 64x64 block tiles (the only body; other values are refused);

@@ -300,3 +300,202 @@ def test_tile_passengers_and_rows_each_get_exactly_one_workgroup(tiles, others, 
         assert np.array_equal(run, np.arange(run[0], run[0] + len(run)))
         if cohort % 8 == 0:
             assert run[0] % 8 == 0
+
+
+# (label, B, N, D, L, H): the bench shapes, the golden-fixture shapes, and graph sizes either side of the kernels' limits
+CHAIN_PLAN_SHAPES = [("c1", 8, 16, 128, 2, 8), ("c2", 32, 64, 256, 2, 8), ("c2/H1", 32, 64, 256, 2, 1), ("c3", 32, 64, 768, 4, 4),
+                     ("c5", 32, 256, 512, 2, 8), ("g7", 2, 7, 12, 4, 4), ("g16a", 2, 16, 64, 4, 4), ("g16b", 2, 16, 128, 2, 8),
+                     ("g5", 2, 5, 8, 2, 2), ("n48", 32, 48, 256, 2, 8), ("n128", 32, 128, 256, 2, 8)]
+# (label, option to set or None, value, misalign bits, scratch given)
+CHAIN_PLAN_VARIANTS = [("default", None, 0, 0, 1), ("misalign=tensors", None, 0, 1, 1), ("misalign=dout", None, 0, 2, 1),
+                       ("misalign=ride", None, 0, 4, 1), ("misalign=flat", None, 0, 8, 1), ("misalign=all", None, 0, 15, 1),
+                       ("no scratch", None, 0, 0, 0), ("chain=0", "chain", 0, 0, 1), ("chain_big=1", "chain_big", 1, 0, 1),
+                       ("chain_t=0", "chain_t", 0, 0, 1), ("chain_t=1", "chain_t", 1, 0, 1), ("chain_t=2", "chain_t", 2, 0, 1)]
+
+
+def chain_plan_table(plan, set_option, hook_allowed):
+    """One line per (shape, variant): the plan of forward (dense / ragged) x (no ride / ride) x (no hook / hook), then of backward
+    (dense / ragged) x (no ride / ride), each as the kind's letter (n one launch per product, g generic, s, t) followed by the
+    letters of the bits that are set: a aligned, F full, u fuse, x attention, r ride; '-' where the attention hook may not be
+    given.  plan(bwd, B, N, D, L, H, ragged, ride, hook, scratch, misalign) -> six ints."""
+    lines = []
+    for label, B, N, D, L, H in CHAIN_PLAN_SHAPES:
+        for vlabel, opt, value, misalign, scratch in CHAIN_PLAN_VARIANTS:
+            codes = []
+            try:
+                if opt:
+                    set_option(opt, value)
+                for bwd in (0, 1):
+                    for ragged in (0, 1):
+                        for ride in (0, 1):
+                            for hook in ((0,) if bwd else (0, 1)):
+                                if hook and not hook_allowed(N, D, H):
+                                    codes.append("-")
+                                    continue
+                                out = plan(bwd, B, N, D, L, H, ragged, ride, hook, scratch, misalign)
+                                codes.append("ngst"[out[0]] + "".join(c for c, bit in zip("aFuxr", out[1:]) if bit))
+            finally:
+                if opt:
+                    set_option(opt, OPTION_DEFAULTS[opt])
+            lines.append(f"{label:6s}{vlabel:17s}: " + " ".join(codes))
+    return lines
+
+
+# Recorded from the PARENT of the commit that introduced chain_plan_fwd / _bwd, not from the code under test: in a scratch copy of
+# the parent a throw-away function evaluated the parent's own predicates (use_chain_for, chain_can_carry, chain_bwd_fusable + the
+# alignment tests of dXres / dout / dout_m, chain_fwd_computes_attention, then chain_aligned, chain_small_ok, chain_t_ok,
+# chain_s_preferred, chain_t_full and the FUSE choice of chain_t_run_bwd) in the order gcgcn_gcn_fwd / _bwd and gcn_chain_fwd /
+# _bwd evaluated them, on the operand addresses gcgcn_debug_chain_plan makes up, and chain_plan_table printed this.
+CHAIN_PLAN_EXPECTED = """
+c1    default          : t tx tr txr t tx tr txr tu tur tu tur
+c1    misalign=tensors : g g gr gr g g gr gr g gr g gr
+c1    misalign=dout    : t tx tr txr t tx tr txr t tr t tr
+c1    misalign=ride    : t tx t tx t tx t tx tu tu tu tu
+c1    misalign=flat    : g g gr gr g g gr gr g gr g gr
+c1    misalign=all     : g g g g g g g g g g g g
+c1    no scratch       : t tx tr txr t tx tr txr t tr t tr
+c1    chain=0          : n n n n n n n n n n n n
+c1    chain_big=1      : t tx tr txr t tx tr txr tu tur tu tur
+c1    chain_t=0        : g g gr gr g g gr gr g gr g gr
+c1    chain_t=1        : t tx tr txr t tx tr txr tu tur tu tur
+c1    chain_t=2        : t tx tr txr t tx tr txr tu tur tu tur
+c2    default          : s sx sr sxr t tx tr txr su sur tu tur
+c2    misalign=tensors : g g gr gr g g gr gr g gr g gr
+c2    misalign=dout    : s sx sr sxr t tx tr txr s sr t tr
+c2    misalign=ride    : s sx s sx t tx t tx su su tu tu
+c2    misalign=flat    : g g gr gr g g gr gr g gr g gr
+c2    misalign=all     : g g g g g g g g g g g g
+c2    no scratch       : s sx sr sxr t tx tr txr s sr t tr
+c2    chain=0          : n n n n n n n n n n n n
+c2    chain_big=1      : s sx sr sxr t tx tr txr su sur tu tur
+c2    chain_t=0        : s sx sr sxr s sx sr sxr su sur su sur
+c2    chain_t=1        : s sx sr sxr t tx tr txr su sur tu tur
+c2    chain_t=2        : tF tFx tFr tFxr t tx tr txr tFu tFur tu tur
+c2/H1 default          : s s sr sr t tx tr txr su sur tu tur
+c2/H1 misalign=tensors : g g gr gr g g gr gr g gr g gr
+c2/H1 misalign=dout    : s s sr sr t tx tr txr s sr t tr
+c2/H1 misalign=ride    : s s s s t tx t tx su su tu tu
+c2/H1 misalign=flat    : g g gr gr g g gr gr g gr g gr
+c2/H1 misalign=all     : g g g g g g g g g g g g
+c2/H1 no scratch       : s s sr sr t tx tr txr s sr t tr
+c2/H1 chain=0          : n n n n n n n n n n n n
+c2/H1 chain_big=1      : s s sr sr t tx tr txr su sur tu tur
+c2/H1 chain_t=0        : s s sr sr s s sr sr su sur su sur
+c2/H1 chain_t=1        : s s sr sr t tx tr txr su sur tu tur
+c2/H1 chain_t=2        : tF tFx tFr tFxr t tx tr txr tFu tFur tu tur
+c3    default          : tF tFx tFr tFxr t tx tr txr tF tFr t tr
+c3    misalign=tensors : g g gr gr g g gr gr g gr g gr
+c3    misalign=dout    : tF tFx tFr tFxr t tx tr txr tF tFr t tr
+c3    misalign=ride    : tF tFx tF tFx t tx t tx tF tF t t
+c3    misalign=flat    : g g gr gr g g gr gr g gr g gr
+c3    misalign=all     : g g g g g g g g g g g g
+c3    no scratch       : tF tFx tFr tFxr t tx tr txr tF tFr t tr
+c3    chain=0          : n n n n n n n n n n n n
+c3    chain_big=1      : tF tFx tFr tFxr t tx tr txr tF tFr t tr
+c3    chain_t=0        : ga ga gar gar ga ga gar gar ga gar ga gar
+c3    chain_t=1        : tF tFx tFr tFxr t tx tr txr tF tFr t tr
+c3    chain_t=2        : tF tFx tFr tFxr t tx tr txr tF tFr t tr
+c5    default          : n - gar - n - gar - n n n n
+c5    misalign=tensors : n - gr - n - gr - n n n n
+c5    misalign=dout    : n - gar - n - gar - n n n n
+c5    misalign=ride    : n - n - n - n - n n n n
+c5    misalign=flat    : n - gr - n - gr - n n n n
+c5    misalign=all     : n - n - n - n - n n n n
+c5    no scratch       : n - gar - n - gar - n n n n
+c5    chain=0          : n - n - n - n - n n n n
+c5    chain_big=1      : ga - gar - ga - gar - ga gar ga gar
+c5    chain_t=0        : n - gar - n - gar - n n n n
+c5    chain_t=1        : n - gar - n - gar - n n n n
+c5    chain_t=2        : n - gar - n - gar - n n n n
+g7    default          : g - gr - g - gr - g gr g gr
+g7    misalign=tensors : g - gr - g - gr - g gr g gr
+g7    misalign=dout    : g - gr - g - gr - g gr g gr
+g7    misalign=ride    : g - g - g - g - g g g g
+g7    misalign=flat    : g - gr - g - gr - g gr g gr
+g7    misalign=all     : g - g - g - g - g g g g
+g7    no scratch       : g - gr - g - gr - g gr g gr
+g7    chain=0          : n - n - n - n - n n n n
+g7    chain_big=1      : g - gr - g - gr - g gr g gr
+g7    chain_t=0        : g - gr - g - gr - g gr g gr
+g7    chain_t=1        : g - gr - g - gr - g gr g gr
+g7    chain_t=2        : g - gr - g - gr - g gr g gr
+g16a  default          : g g gr gr g g gr gr g gr g gr
+g16a  misalign=tensors : g g gr gr g g gr gr g gr g gr
+g16a  misalign=dout    : g g gr gr g g gr gr g gr g gr
+g16a  misalign=ride    : g g g g g g g g g g g g
+g16a  misalign=flat    : g g gr gr g g gr gr g gr g gr
+g16a  misalign=all     : g g g g g g g g g g g g
+g16a  no scratch       : g g gr gr g g gr gr g gr g gr
+g16a  chain=0          : n n n n n n n n n n n n
+g16a  chain_big=1      : g g gr gr g g gr gr g gr g gr
+g16a  chain_t=0        : g g gr gr g g gr gr g gr g gr
+g16a  chain_t=1        : g g gr gr g g gr gr g gr g gr
+g16a  chain_t=2        : g g gr gr g g gr gr g gr g gr
+g16b  default          : t tx tr txr t tx tr txr tu tur tu tur
+g16b  misalign=tensors : g g gr gr g g gr gr g gr g gr
+g16b  misalign=dout    : t tx tr txr t tx tr txr t tr t tr
+g16b  misalign=ride    : t tx t tx t tx t tx tu tu tu tu
+g16b  misalign=flat    : g g gr gr g g gr gr g gr g gr
+g16b  misalign=all     : g g g g g g g g g g g g
+g16b  no scratch       : t tx tr txr t tx tr txr t tr t tr
+g16b  chain=0          : n n n n n n n n n n n n
+g16b  chain_big=1      : t tx tr txr t tx tr txr tu tur tu tur
+g16b  chain_t=0        : g g gr gr g g gr gr g gr g gr
+g16b  chain_t=1        : t tx tr txr t tx tr txr tu tur tu tur
+g16b  chain_t=2        : t tx tr txr t tx tr txr tu tur tu tur
+g5    default          : g g gr gr g g gr gr g gr g gr
+g5    misalign=tensors : g g gr gr g g gr gr g gr g gr
+g5    misalign=dout    : g g gr gr g g gr gr g gr g gr
+g5    misalign=ride    : g g g g g g g g g g g g
+g5    misalign=flat    : g g gr gr g g gr gr g gr g gr
+g5    misalign=all     : g g g g g g g g g g g g
+g5    no scratch       : g g gr gr g g gr gr g gr g gr
+g5    chain=0          : n n n n n n n n n n n n
+g5    chain_big=1      : g g gr gr g g gr gr g gr g gr
+g5    chain_t=0        : g g gr gr g g gr gr g gr g gr
+g5    chain_t=1        : g g gr gr g g gr gr g gr g gr
+g5    chain_t=2        : g g gr gr g g gr gr g gr g gr
+n48   default          : t tx tr txr t tx tr txr tu tur tu tur
+n48   misalign=tensors : g g gr gr g g gr gr g gr g gr
+n48   misalign=dout    : t tx tr txr t tx tr txr t tr t tr
+n48   misalign=ride    : t tx t tx t tx t tx tu tu tu tu
+n48   misalign=flat    : g g gr gr g g gr gr g gr g gr
+n48   misalign=all     : g g g g g g g g g g g g
+n48   no scratch       : t tx tr txr t tx tr txr t tr t tr
+n48   chain=0          : n n n n n n n n n n n n
+n48   chain_big=1      : t tx tr txr t tx tr txr tu tur tu tur
+n48   chain_t=0        : g g gr gr g g gr gr g gr g gr
+n48   chain_t=1        : t tx tr txr t tx tr txr tu tur tu tur
+n48   chain_t=2        : t tx tr txr t tx tr txr tu tur tu tur
+n128  default          : n - gar - n - gar - n n n n
+n128  misalign=tensors : n - gr - n - gr - n n n n
+n128  misalign=dout    : n - gar - n - gar - n n n n
+n128  misalign=ride    : n - n - n - n - n n n n
+n128  misalign=flat    : n - gr - n - gr - n n n n
+n128  misalign=all     : n - n - n - n - n n n n
+n128  no scratch       : n - gar - n - gar - n n n n
+n128  chain=0          : n - n - n - n - n n n n
+n128  chain_big=1      : ga - gar - ga - gar - ga gar ga gar
+n128  chain_t=0        : n - gar - n - gar - n n n n
+n128  chain_t=1        : n - gar - n - gar - n n n n
+n128  chain_t=2        : n - gar - n - gar - n n n n
+"""
+
+
+def test_chain_plan_is_the_decision_the_scattered_predicates_made():
+    """gcgcn_debug_chain_plan (the plan function gcgcn_gcn_fwd / _bwd call) gives, for every row, the kernel and the dependent
+    bits the code before it chose.  No tolerance, no row left out."""
+    import ctypes
+    import numpy as np
+
+    def plan(*args):
+        out = np.full(6, -1, np.int32)
+        _lib.call("gcgcn_debug_chain_plan", *args, out.ctypes.data_as(ctypes.c_void_p))
+        return [int(v) for v in out]
+
+    got = chain_plan_table(plan, lambda name, v: _lib.call("gcgcn_set_option", name.encode(), v),
+                           lambda N, D, H: bool(_lib.lib().gcgcn_maggc_fusable(N, D, H)))
+    want = CHAIN_PLAN_EXPECTED.strip("\n").split("\n")
+    assert len(got) == len(want) == len(CHAIN_PLAN_SHAPES) * len(CHAIN_PLAN_VARIANTS)
+    wrong = [f"want {w}\n got {g}" for g, w in zip(got, want) if g != w]
+    assert not wrong, "\n".join(wrong)
