@@ -378,12 +378,7 @@ int gcgcn_mha_fwd(int B, int N, int D, int H, const float* X, const int32_t* n_v
   const long M = (long)B * N;
   const int dh = D / H;
   {  // Q = X Wq^T + bq      (glove:136, all heads at once)
-    GemmArgs g;
-    g.ws = scratch, g.ws_elems = wse;
-    g.A = X, g.lda = D, g.a_kc = 1;
-    g.B = flat, g.ldb = D, g.b_kc = 1;
-    g.C = Q, g.ldc = D;
-    g.M = (int)M, g.N = D, g.K = D;
+    GemmArgs g = gemm_nt(X, D, flat, D, Q, D, (int)M, D, D).split_ws(scratch, wse);
     g.bias = flat + (long)D * D;
     use_rows(g, live_rows(rowblk, N, n_valid != nullptr), 1, 1);
     GC_TRY(gemm(g, st));
@@ -392,13 +387,8 @@ int gcgcn_mha_fwd(int B, int N, int D, int H, const float* X, const int32_t* n_v
   if (use_mha_core() && mha_core_ok(N, D, H, Q, nullptr))  // small graph: scores stay in LDS
     return mha_core_fwd(Q, n_valid, P, A, B, N, D, H, alpha, drop, st);
   {  // S[b,h] = Q_h Q_h^T / sqrt(dh)   (glove:137-138: keys use the query projection)
-    GemmArgs g;
-    g.ws = scratch, g.ws_elems = wse;
-    g.A = Q, g.lda = D, g.a_kc = 1, g.sA1 = (long)N * D, g.sA2 = dh;
-    g.B = Q, g.ldb = D, g.b_kc = 1, g.sB1 = (long)N * D, g.sB2 = dh;
-    g.C = P, g.ldc = N, g.sC1 = (long)H * N * N, g.sC2 = (long)N * N;
-    g.M = N, g.N = N, g.K = dh;
-    g.batch1 = B, g.batch2 = H;
+    GemmArgs g = gemm_nt(Q, D, Q, D, P, N, N, N, dh).split_ws(scratch, wse);
+    g.batch_z1(B, (long)N * D, (long)N * D, (long)H * N * N).batch_z2(H, dh, dh, (long)N * N);
     g.alpha = alpha;
     GC_TRY(gemm(g, st));
   }
@@ -424,31 +414,18 @@ int gcgcn_mha_bwd(int B, int N, int D, int H, const float* X, const float* flat,
     GC_TRY(mha_core_bwd(Q, P, dA, dQ, B, N, D, H, alpha, drop, st));
   } else {
     GC_TRY(softmax_bwd(P, dA, dS, M * H, N, drop, st));
-    for (int pass = 0; pass < 2; ++pass) {  // dQ_h = alpha (dS + dS^T) Q_h
-      GemmArgs g;
-      g.ws = scratch, g.ws_elems = wse;
-      g.A = dS, g.lda = N, g.a_kc = (pass == 0), g.sA1 = (long)H * N * N, g.sA2 = (long)N * N;
-      g.B = Q, g.ldb = D, g.b_kc = 0, g.sB1 = (long)N * D, g.sB2 = dh;
-      g.C = dQ, g.ldc = D, g.sC1 = (long)N * D, g.sC2 = dh;
-      g.M = N, g.N = dh, g.K = N;
-      g.batch1 = B, g.batch2 = H;
+    for (int pass = 0; pass < 2; ++pass) {  // dQ_h = alpha (dS + dS^T) Q_h: dS Q_h, then += dS^T Q_h
+      GemmArgs g = (pass == 0 ? gemm_nn : gemm_tn)(dS, N, Q, D, dQ, D, N, dh, N).split_ws(scratch, wse);
+      g.batch_z1(B, (long)H * N * N, (long)N * D, (long)N * D).batch_z2(H, (long)N * N, dh, dh);
       g.alpha = alpha;
       g.accumulate = pass;
       GC_TRY(gemm(g, st));
     }
   }
   {  // one launch: dX = dQ Wq  and  dWq = dQ^T X
-    GemmArgs gs[2];
-    gs[0].ws = gs[1].ws = scratch, gs[0].ws_elems = gs[1].ws_elems = wse;
-    gs[0].A = dQ, gs[0].lda = D, gs[0].a_kc = 1;
-    gs[0].B = flat, gs[0].ldb = D, gs[0].b_kc = 0;
-    gs[0].C = dX, gs[0].ldc = D;
-    gs[0].M = (int)M, gs[0].N = D, gs[0].K = D;
+    GemmArgs gs[2] = {gemm_nn(dQ, D, flat, D, dX, D, (int)M, D, D).split_ws(scratch, wse),
+                      gemm_tn(dQ, D, X, D, dflat, D, D, D, (int)M).split_ws(scratch, wse)};
     gs[0].add = dX_in, gs[0].ldadd = D;  // + the gradient X already collected downstream (NULL = none)
-    gs[1].A = dQ, gs[1].lda = D, gs[1].a_kc = 0;
-    gs[1].B = X, gs[1].ldb = D, gs[1].b_kc = 0;
-    gs[1].C = dflat, gs[1].ldc = D;
-    gs[1].M = D, gs[1].N = D, gs[1].K = (int)M;
     const int* rows = live_rows(rowblk, N, true);   // (a list is only handed in for a ragged batch): the rows that exist
     use_rows(gs[0], rows, 1, 1), use_rows(gs[1], rows, 2);
     const int ng = gemm_defer((DeferQueue*)defer_queue, gs[1]) ? 1 : 2;  // dWq parked (see gcgcn_gcn_bwd)
@@ -539,30 +516,17 @@ int gcgcn_gcn_fwd(int B, int N, int D, int L, int H, const float* X, const float
 
   {  // one launch: Pn = X WnX (node term of every (head, sub-layer), X part of the dense input)
      //             G  = Ebar We (edge term, mean commuted with the projection, glove:40-41)
-    GemmArgs gs[2];
-    for (int q = 0; q < 2; ++q) {
-      GemmArgs& g = gs[q];
-      g.ws = scratch, g.ws_elems = wse;
-      g.A = q ? Ebar : X, g.lda = D, g.a_kc = 1;
-      g.B = flat + (q ? y.oWe : y.oWnX), g.ldb = HD, g.b_kc = 0;
-      g.C = q ? G : Pn, g.ldc = HD;
-      g.M = (int)M, g.N = (int)HD, g.K = D;
-      use_rows(g, rows, 1, 1);
+    GemmArgs g3[3] = {gemm_nn(X, D, flat + y.oWnX, HD, Pn, HD, (int)M, (int)HD, D).split_ws(scratch, wse),
+                      gemm_nn(Ebar, D, flat + y.oWe, HD, G, HD, (int)M, (int)HD, D).split_ws(scratch, wse), GemmArgs()};
+    const int ng = mha ? 3 : 2;
+    if (mha) {  // Q = X Wq^T + bq (glove:136, all heads at once): one more problem of this launch
+      g3[2] = gemm_nt(X, D, mha->flat_q, D, mha->Q, D, (int)M, D, D).split_ws(scratch, wse);
+      g3[2].bias = mha->flat_q + (long)D * D;
     }
+    for (int q = 0; q < ng; ++q) use_rows(g3[q], rows, 1, 1);   // (the attention core stages all N rows of Q: zeros past the live blocks)
     ColRide hs;  // wsum = sum_h Wlin[:, h, :] (a by-product for gcgcn_gcn_bwd) in trailing workgroups of this launch
     if (wsum && H > 1) hs.X = flat + y.oWlin, hs.out = wsum, hs.R = H, hs.ld = D, hs.C = D * D, hs.ready_slices = -1;
-    GemmArgs g3[3] = {gs[0], gs[1], GemmArgs()};
-    if (mha) {  // Q = X Wq^T + bq (glove:136, all heads at once): one more problem of this launch
-      GemmArgs& g = g3[2];
-      g.ws = scratch, g.ws_elems = wse;
-      g.A = X, g.lda = D, g.a_kc = 1;
-      g.B = mha->flat_q, g.ldb = D, g.b_kc = 1;
-      g.C = mha->Q, g.ldc = D;
-      g.M = (int)M, g.N = D, g.K = D;
-      g.bias = mha->flat_q + (long)D * D;
-      use_rows(g, rows, 1, 1);   // (the attention core stages all N rows of Q: zeros past the live blocks)
-    }
-    GC_TRY(gemm_group(g3, mha ? 3 : 2, st, hs.X ? &hs : nullptr));
+    GC_TRY(gemm_group(g3, ng, st, hs.X ? &hs : nullptr));
   }
   {  // the dependent per-(doc, head) sequence: normaliser, then per sub-layer dense connection + aggregation
     if (er.kind && !plan.ride) {  // the riding pass as its own launch
@@ -591,12 +555,7 @@ int gcgcn_gcn_fwd(int B, int N, int D, int L, int H, const float* X, const float
     }
   }
   {  // out = HO Wlin^T + blin   (glove:78 / 118)
-    GemmArgs g;
-    g.ws = scratch, g.ws_elems = wse;
-    g.A = HO, g.lda = HD, g.a_kc = 1;
-    g.B = flat + y.oWlin, g.ldb = HD, g.b_kc = 1;
-    g.C = out, g.ldc = D;
-    g.M = (int)M, g.N = D, g.K = (int)HD;
+    GemmArgs g = gemm_nt(HO, HD, flat + y.oWlin, HD, out, D, (int)M, D, (int)HD).split_ws(scratch, wse);
     g.bias = flat + y.oblin;
     g.n_valid = n_valid, g.nv_rows = N, g.nv_zdoc = 0;
     use_rows(g, rows, 1, 1);   // the block's output: its padding rows are zero
@@ -626,7 +585,7 @@ int gcgcn_gcn_bwd(int B, int N, int D, int L, int H, const float* X, const float
     GC_REQUIRE(gcgcn_maggc_fusable(N, D, H) && mha->Q && mha->P && mha->dQ && mha_core_ok(N, D, H, mha->Q, mha->dQ),
                "gcn_bwd: attention hook on a shape it does not serve");
     mp.Q = mha->Q, mp.P = mha->P, mp.dA = dA, mp.dQ = mha->dQ;
-    mp.N = N, mp.D = D, mp.H = H, mp.dh = D / H, mp.kchunk = (D / H < 128) ? (D / H + 31) / 32 * 32 : 128, mp.count = B * H;
+    mp.N = N, mp.D = D, mp.H = H, mp.dh = D / H, mp.kchunk = mha_chunk(D / H), mp.count = B * H;
     mp.alpha = 1.f / sqrtf((float)(D / H));
     mp.drop = make_drop(mha->rng_snap, GCGCN_SALT_MHA, mha->p);
   }
@@ -671,12 +630,18 @@ int gcgcn_gcn_bwd(int B, int N, int D, int L, int H, const float* X, const float
     GC_TRY(mask_rows(dout, dout_m, M, D, N, n_valid, odrop, st));
     dout = dout_m;
   }
+  // dWlin = dout^T HO: a weight gradient nobody needs before the end of backward.  It is parked for a later launch with idle
+  // matrix pipes, or runs in the launch in front of the chain -- where the chain computes dHO (fuse), in the one behind it
+  GemmArgs dWlin = gemm_tn(dout, D, HO, HD, dflat + y.oWlin, HD, D, (int)HD, (int)M).split_ws(scratch, wse);
+  use_rows(dWlin, rows, 2);
+  // dblin = column sums of dout: they ride in a launch of this call where it has workspace (`scratch`; unused otherwise)
   ColRide cr;
+  cr.X = dout, cr.out = dflat + y.oblin, cr.part = scratch + wse, cr.R = M, cr.ld = D, cr.C = D;
   bool col_later = false, col_pending = false;
-  if (fuse) {  // dWlin = dout^T HO is parked or joins the launch after the chain; dblin's column sums ride there too
+  if (fuse) {  // the sums ride in the launch after the chain
     c.dout = dout_raw, c.dXres = dXres, c.Wsum = wsum, c.oWlin = y.oWlin;
     if (dout != dout_raw) c.dout_m = dout_m, c.odrop = odrop;   // c.n_valid is set
-    cr.X = dout, cr.out = dflat + y.oblin, cr.part = scratch + wse, cr.R = M, cr.ld = D, cr.C = D, col_pending = true;
+    col_pending = true;
     if (2 * B <= COL_RIDE_SLICES) c.colpart = cr.part, cr.ready_slices = 2 * B;  // stage 1 inside the chain (it holds dout_b in LDS)
   } else {
     // Small blocks (launch-bound: cfg 1, the reference's own model) fold the head-sum / dropout-backward kernel into this
@@ -686,41 +651,19 @@ int gcgcn_gcn_bwd(int B, int N, int D, int L, int H, const float* X, const float
     constexpr long fold_max = 2L << 20;   // elements of dHO up to which the fold pays
     const bool fold_hs = scratch && (H == 1 || wsum_fwd) && (long)M * HD <= fold_max && (((uintptr_t)dXres) & 15) == 0;
     {  // one launch: dHO = dout Wlin  and  dWlin = dout^T HO
-      GemmArgs gs[3];
-      gs[0].ws = gs[1].ws = gs[2].ws = scratch, gs[0].ws_elems = gs[1].ws_elems = gs[2].ws_elems = wse;
-      gs[0].A = dout, gs[0].lda = D, gs[0].a_kc = 1;
-      gs[0].B = flat + y.oWlin, gs[0].ldb = HD, gs[0].b_kc = 0;
-      gs[0].C = dYa, gs[0].ldc = HD;
-      gs[0].M = (int)M, gs[0].N = (int)HD, gs[0].K = D;
-      gs[1].A = dout, gs[1].lda = D, gs[1].a_kc = 0;
-      gs[1].B = HO, gs[1].ldb = HD, gs[1].b_kc = 0;
-      gs[1].C = dflat + y.oWlin, gs[1].ldc = HD;
-      gs[1].M = D, gs[1].N = (int)HD, gs[1].K = (int)M;
-      use_rows(gs[0], rows, 1, 1), use_rows(gs[1], rows, 2);
-      int np1 = 2;
-      if (fold_hs) {
-        if (H == 1) {
-          gs[0].C = dXres, gs[0].ldc = D;                                  // HD == D: the head sum is dHO
-          gs[0].C2 = dYa, gs[0].ldc2 = HD, gs[0].drop = drop, gs[0].drop_base = 0;
-        } else {
-          if (drop.snap) gs[0].C2 = dYa, gs[0].ldc2 = HD, gs[0].drop = drop, gs[0].drop_base = 0;   // over C: the dropped value stays
-          gs[2].A = dout, gs[2].lda = D, gs[2].a_kc = 1;
-          gs[2].B = wsum_fwd, gs[2].ldb = D, gs[2].b_kc = 0;
-          gs[2].C = dXres, gs[2].ldc = D;
-          gs[2].M = (int)M, gs[2].N = D, gs[2].K = D;
-          use_rows(gs[2], rows, 1, 1);
-          np1 = 3;
-        }
-      }
-      // a weight gradient nobody needs before the end of backward: parked for a later launch with idle matrix pipes
-      const bool parked = gemm_defer(dq, gs[1]);
       GemmArgs run[3];
-      int nr = 0;
-      run[nr++] = gs[0];
-      if (!parked) run[nr++] = gs[1];
-      if (np1 == 3) run[nr++] = gs[2];
-      if (scratch) {  // dblin = column sums of dout ride in this launch (stage 1) and in its reduce or the next kernel (stage 2)
-        cr.X = dout, cr.out = dflat + y.oblin, cr.part = scratch + wse, cr.R = M, cr.ld = D, cr.C = D;
+      int nr = 1;
+      GemmArgs& dHO = run[0];
+      dHO = gemm_nn(dout, D, flat + y.oWlin, HD, dYa, HD, (int)M, (int)HD, D).split_ws(scratch, wse);
+      use_rows(dHO, rows, 1, 1);
+      if (fold_hs && H == 1) dHO.C = dXres, dHO.ldc = D;                                   // HD == D: the head sum is dHO
+      if (fold_hs && (H == 1 || drop.snap)) dHO.C2 = dYa, dHO.ldc2 = HD, dHO.drop = drop, dHO.drop_base = 0;   // H > 1: over C, the dropped value stays
+      if (!gemm_defer(dq, dWlin)) run[nr++] = dWlin;
+      if (fold_hs && H > 1) {  // dXres = dout (sum_h Wlin_h)
+        run[nr] = gemm_nn(dout, D, wsum_fwd, D, dXres, D, (int)M, D, D).split_ws(scratch, wse);
+        use_rows(run[nr++], rows, 1, 1);
+      }
+      if (scratch) {  // dblin's sums ride in this launch (stage 1) and in its reduce or the next kernel (stage 2)
         GC_TRY(gemm_group(run, nr, st, &cr, &col_later));
       } else {
         GC_TRY(gemm_group(run, nr, st));
@@ -757,72 +700,27 @@ int gcgcn_gcn_bwd(int B, int N, int D, int L, int H, const float* X, const float
     constexpr int GMAX = 16;
     GemmArgs gs[GMAX];
     int n = 0;
-    auto next = [&]() -> GemmArgs& {
-      GemmArgs& g = gs[n++];
-      g = GemmArgs();
-      g.ws = scratch, g.ws_elems = wse;
-      return g;
+    auto weight_grad = [&](GemmArgs g) {  // over the rows that exist; parked if asked to (and possible)
+      use_rows(g.split_ws(scratch, wse), rows, 2);
+      if (!gemm_defer(dq, g)) gs[n++] = g;
     };
-    auto park = [&]() {  // the problem just described is a weight gradient: park it if asked to (and possible)
-      if (gemm_defer(dq, gs[n - 1])) --n;
+    auto data_grad = [&](GemmArgs g) -> GemmArgs& {  // the gradients that leave the block: zero on padding rows
+      use_rows(g.split_ws(scratch, wse), rows, 1, 1);
+      return gs[n++] = g;
     };
-    if (fuse) {  // dWlin = dout^T HO
-      GemmArgs& g = next();
-      g.A = dout, g.lda = D, g.a_kc = 0;
-      g.B = HO, g.ldb = HD, g.b_kc = 0;
-      g.C = dflat + y.oWlin, g.ldc = HD;
-      g.M = D, g.N = (int)HD, g.K = (int)M;
-      use_rows(g, rows, 2);
-      park();
-    }
-    {
-      GemmArgs& g = next();
-      g.A = X, g.lda = D, g.a_kc = 0;
-      g.B = dP, g.ldb = HD, g.b_kc = 0;
-      g.C = dflat + y.oWnX, g.ldc = HD;
-      g.M = D, g.N = (int)HD, g.K = (int)M;
-      use_rows(g, rows, 2);
-      park();
-    }
-    {
-      GemmArgs& g = next();
-      g.A = Ebar, g.lda = D, g.a_kc = 0;
-      g.B = dM, g.ldb = HD, g.b_kc = 0;
-      g.C = dflat + y.oWe, g.ldc = HD;
-      g.M = D, g.N = (int)HD, g.K = (int)M;
-      use_rows(g, rows, 2);
-      park();
-    }
-    {
-      GemmArgs& g = next();
-      g.A = dP, g.lda = HD, g.a_kc = 1;
-      g.B = flat + y.oWnX, g.ldb = HD, g.b_kc = 1;
-      g.C = dX, g.ldc = D;
-      g.M = (int)M, g.N = D, g.K = (int)HD;
-      g.add = dXres, g.ldadd = D;
-      use_rows(g, rows, 1, 1);   // the gradients that leave the block: zero on padding rows
-    }
-    {
-      GemmArgs& g = next();
-      g.A = dM, g.lda = HD, g.a_kc = 1;
-      g.B = flat + y.oWe, g.ldb = HD, g.b_kc = 1;
-      g.C = dEbar, g.ldc = D;
-      g.M = (int)M, g.N = D, g.K = (int)HD;
-      use_rows(g, rows, 1, 1);
-    }
+    if (fuse) weight_grad(dWlin);
+    weight_grad(gemm_tn(X, D, dP, HD, dflat + y.oWnX, HD, D, (int)HD, (int)M));
+    weight_grad(gemm_tn(Ebar, D, dM, HD, dflat + y.oWe, HD, D, (int)HD, (int)M));
+    GemmArgs& gx = data_grad(gemm_nt(dP, HD, flat + y.oWnX, HD, dX, D, (int)M, D, (int)HD));
+    gx.add = dXres, gx.ldadd = D;
+    data_grad(gemm_nt(dM, HD, flat + y.oWe, HD, dEbar, D, (int)M, D, (int)HD));
     for (int l = 1; l < L; ++l) {
       if (n == GMAX) {  // many sub-layers and nothing parked: launch what has been described so far
         GC_TRY(gemm_group(gs, n, st));
         n = 0;
       }
-      GemmArgs& g = next();
-      g.A = Y, g.lda = HD, g.a_kc = 0, g.sA2 = (long)L * gh;
-      g.B = dP + (long)l * gh, g.ldb = HD, g.b_kc = 0, g.sB2 = (long)L * gh;
-      g.C = dflat + y.wd_off(0, l), g.ldc = gh, g.sC2 = y.wd_head;
-      g.M = l * gh, g.N = gh, g.K = (int)M;
-      g.batch2 = H;
-      use_rows(g, rows, 2);
-      park();
+      weight_grad(gemm_tn(Y, HD, dP + (long)l * gh, HD, dflat + y.wd_off(0, l), gh, l * gh, gh, (int)M)
+                      .batch_z2(H, (long)L * gh, (long)L * gh, y.wd_head));
     }
     // + the attention core's backward: as passenger workgroups of this launch where a (document, head) pair's scratch fits
     // the tile kernel's LDS (head width <= 32), as a launch of its own in front of it otherwise
@@ -856,20 +754,12 @@ int gcgcn_graphconv_fwd(int B, int N, int Din, int De, int Dout, const float* X,
   const long wse = scratch ? scratch_elems(B, N, Dout > Din ? Dout : Din, 1) : 0;
   GC_TRY(rowsum_inv(A, rinv, M, N, st));
   {  // one launch: out <- Ebar We (edge term),  T <- X Wn
-    GemmArgs gs[2];
-    gs[0].ws = gs[1].ws = scratch, gs[0].ws_elems = gs[1].ws_elems = wse;
-    gs[0].A = Ebar, gs[0].lda = De, gs[0].a_kc = 1, gs[0].B = We, gs[0].ldb = Dout, gs[0].b_kc = 0;
-    gs[0].C = out, gs[0].ldc = Dout, gs[0].M = (int)M, gs[0].N = Dout, gs[0].K = De;
-    gs[1].A = X, gs[1].lda = Din, gs[1].a_kc = 1, gs[1].B = Wn, gs[1].ldb = Dout, gs[1].b_kc = 0;
-    gs[1].C = T, gs[1].ldc = Dout, gs[1].M = (int)M, gs[1].N = Dout, gs[1].K = Din;
+    GemmArgs gs[2] = {gemm_nn(Ebar, De, We, Dout, out, Dout, (int)M, Dout, De).split_ws(scratch, wse),
+                      gemm_nn(X, Din, Wn, Dout, T, Dout, (int)M, Dout, Din).split_ws(scratch, wse)};
     GC_TRY(gemm_group(gs, 2, st));
   }
   {  // out = (out + A T + bias) * rinv        (glove:42-50; the bias joins before the division, glove:45-46)
-    GemmArgs g;
-    g.A = A, g.lda = N, g.a_kc = 1, g.sA1 = (long)N * N;
-    g.B = T, g.ldb = Dout, g.b_kc = 0, g.sB1 = (long)N * Dout;
-    g.C = out, g.ldc = Dout, g.sC1 = (long)N * Dout;
-    g.M = N, g.N = Dout, g.K = N, g.batch1 = B;
+    GemmArgs g = gemm_nn(A, N, T, Dout, out, Dout, N, Dout, N).batch_z1(B, (long)N * N, (long)N * Dout, (long)N * Dout);
     g.add = out, g.ldadd = Dout, g.sAdd1 = (long)N * Dout;
     g.bias = bias;
     g.rowscale = rinv, g.sRs1 = N;
@@ -893,33 +783,17 @@ int gcgcn_graphconv_bwd(int B, int N, int Din, int De, int Dout, const float* X,
   GC_TRY(relu_norm_bwd(dout, out, rinv, dS, drow, M, N, 1, 1, Dout, 0, 1, st, 0));
   if (dbias) GC_TRY(colsum(dS, nullptr, dbias, M, Dout, Dout, 1, 0, 0, 0, 0, scratch, st));
   {  // dT = A^T dS
-    GemmArgs g;
-    g.A = A, g.lda = N, g.a_kc = 0, g.sA1 = (long)N * N;
-    g.B = dS, g.ldb = Dout, g.b_kc = 0, g.sB1 = (long)N * Dout;
-    g.C = dT, g.ldc = Dout, g.sC1 = (long)N * Dout;
-    g.M = N, g.N = Dout, g.K = N, g.batch1 = B;
+    GemmArgs g = gemm_tn(A, N, dS, Dout, dT, Dout, N, Dout, N).batch_z1(B, (long)N * N, (long)N * Dout, (long)N * Dout);
     GC_TRY(gemm(g, st, 0, 1));
   }
-  GemmArgs gs[5];
-  for (auto& g : gs) g.ws = scratch, g.ws_elems = wse;
-  // dA = dS T^T + drow (broadcast along j)
-  gs[0].A = dS, gs[0].lda = Dout, gs[0].a_kc = 1, gs[0].sA1 = (long)N * Dout;
-  gs[0].B = T, gs[0].ldb = Dout, gs[0].b_kc = 1, gs[0].sB1 = (long)N * Dout;
-  gs[0].C = dA, gs[0].ldc = N, gs[0].sC1 = (long)N * N;
-  gs[0].M = N, gs[0].N = N, gs[0].K = Dout, gs[0].batch1 = B;
-  gs[0].rowadd = drow, gs[0].sRa1 = N;
-  // dWe = Ebar^T dS
-  gs[1].A = Ebar, gs[1].lda = De, gs[1].a_kc = 0, gs[1].B = dS, gs[1].ldb = Dout, gs[1].b_kc = 0;
-  gs[1].C = dWe, gs[1].ldc = Dout, gs[1].M = De, gs[1].N = Dout, gs[1].K = (int)M;
-  // dEbar = dS We^T
-  gs[2].A = dS, gs[2].lda = Dout, gs[2].a_kc = 1, gs[2].B = We, gs[2].ldb = Dout, gs[2].b_kc = 1;
-  gs[2].C = dEbar, gs[2].ldc = De, gs[2].M = (int)M, gs[2].N = De, gs[2].K = Dout;
-  // dWn = X^T dT
-  gs[3].A = X, gs[3].lda = Din, gs[3].a_kc = 0, gs[3].B = dT, gs[3].ldb = Dout, gs[3].b_kc = 0;
-  gs[3].C = dWn, gs[3].ldc = Dout, gs[3].M = Din, gs[3].N = Dout, gs[3].K = (int)M;
-  // dX = dT Wn^T
-  gs[4].A = dT, gs[4].lda = Dout, gs[4].a_kc = 1, gs[4].B = Wn, gs[4].ldb = Dout, gs[4].b_kc = 1;
-  gs[4].C = dX, gs[4].ldc = Din, gs[4].M = (int)M, gs[4].N = Din, gs[4].K = Dout;
+  GemmArgs gs[5] = {
+      gemm_nt(dS, Dout, T, Dout, dA, N, N, N, Dout).batch_z1(B, (long)N * Dout, (long)N * Dout, (long)N * N),  // dA = dS T^T + drow
+      gemm_tn(Ebar, De, dS, Dout, dWe, Dout, De, Dout, (int)M),                                                // dWe = Ebar^T dS
+      gemm_nt(dS, Dout, We, Dout, dEbar, De, (int)M, De, Dout),                                                // dEbar = dS We^T
+      gemm_tn(X, Din, dT, Dout, dWn, Dout, Din, Dout, (int)M),                                                 // dWn = X^T dT
+      gemm_nt(dT, Dout, Wn, Dout, dX, Din, (int)M, Din, Dout)};                                                // dX = dT Wn^T
+  for (auto& g : gs) g.split_ws(scratch, wse);
+  gs[0].rowadd = drow, gs[0].sRa1 = N;   // (broadcast along j)
   GC_TRY(gemm_group(gs, 5, st));
   return 0;
 }
@@ -961,15 +835,8 @@ int gcgcn_debug_chain_plan(int bwd, int B, int N, int D, int L, int H, int ragge
 int gcgcn_gemm(int M, int N, int K, const float* A, int64_t lda, int a_kc, const float* B, int64_t ldb, int b_kc,
                float* C, int64_t ldc, int batch, int64_t sA, int64_t sB, int64_t sC, float alpha, const float* bias,
                int relu, int accumulate, int tile, int splits, float* ws, int64_t ws_elems, void* stream) {
-  GemmArgs g;
-  g.A = A, g.lda = lda, g.a_kc = a_kc;
-  g.B = B, g.ldb = ldb, g.b_kc = b_kc;
-  g.C = C, g.ldc = ldc;
-  g.M = M, g.N = N, g.K = K;
-  g.batch1 = 1, g.batch2 = batch;
-  g.sA2 = sA, g.sB2 = sB, g.sC2 = sC;
+  GemmArgs g = gemm_stored(a_kc, b_kc, A, lda, B, ldb, C, ldc, M, N, K).batch_z2(batch, sA, sB, sC).split_ws(ws, ws_elems);
   g.alpha = alpha, g.bias = bias, g.relu = relu, g.accumulate = accumulate;
-  g.ws = ws, g.ws_elems = ws_elems;
   return gemm(g, (hipStream_t)stream, tile, splits);
 }
 
@@ -977,13 +844,8 @@ int gcgcn_gemm(int M, int N, int K, const float* A, int64_t lda, int a_kc, const
 int gcgcn_gemm_dyn(int M, int N, int K, const float* A, int64_t lda, int a_kc, const float* B, int64_t ldb, int b_kc, float* C,
                    int64_t ldc, const float* bias, int accumulate, const int32_t* count, int dyn, int64_t cap, float* ws,
                    int64_t ws_elems, void* stream) {
-  GemmArgs g;
-  g.A = A, g.lda = lda, g.a_kc = a_kc;
-  g.B = B, g.ldb = ldb, g.b_kc = b_kc;
-  g.C = C, g.ldc = ldc;
-  g.M = M, g.N = N, g.K = K;
+  GemmArgs g = gemm_stored(a_kc, b_kc, A, lda, B, ldb, C, ldc, M, N, K).split_ws(ws, ws_elems);
   g.bias = bias, g.accumulate = accumulate;
-  g.ws = ws, g.ws_elems = ws_elems;
   return gemm_dyn(g, count, dyn, cap, (hipStream_t)stream);
 }
 

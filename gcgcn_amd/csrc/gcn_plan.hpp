@@ -68,19 +68,12 @@ struct GcnCtx {
   __host__ __device__ long wd_off(int l) const { return oWd + (long)gh * gh * l * (l - 1) / 2; }
 };
 
-__host__ __device__ inline void plan_common(const GcnCtx& c, GemmArgs& g) {
-  g.batch1 = c.B, g.batch2 = c.H;
-  g.splits = 1;
-}
-
 // Pn_l += [Y_0 .. Y_{l-1}] Wd_l          (dense connection, glove:73 / 110), l >= 1
 __host__ __device__ inline GemmArgs plan_fwd_dense(const GcnCtx& c, int l) {
-  GemmArgs g;
-  plan_common(c, g);
-  g.A = c.Y, g.lda = c.HD, g.a_kc = 1, g.sA1 = (long)c.N * c.HD, g.sA2 = (long)c.L * c.gh;
-  g.B = c.flat + c.wd_off(l), g.ldb = c.gh, g.b_kc = 0, g.sB1 = 0, g.sB2 = c.wd_head;
-  g.C = c.Pn + (long)l * c.gh, g.ldc = c.HD, g.sC1 = (long)c.N * c.HD, g.sC2 = (long)c.L * c.gh;
-  g.M = c.N, g.N = c.gh, g.K = l * c.gh;
+  const long sb = (long)c.N * c.HD, sh = (long)c.L * c.gh;
+  GemmArgs g = gemm_nn(c.Y, c.HD, c.flat + c.wd_off(l), c.gh, c.Pn + (long)l * c.gh, c.HD, c.N, c.gh, l * c.gh);
+  g.batch_z1(c.B, sb, 0, sb).batch_z2(c.H, sh, c.wd_head, sh);
+  g.splits = 1;
   g.accumulate = 1;
   g.tag = "gemm_dense";
   return g;
@@ -88,13 +81,10 @@ __host__ __device__ inline GemmArgs plan_fwd_dense(const GcnCtx& c, int l) {
 
 // Y_l = relu((G_l + A_h Pn_l) * rinv);  HO_l = dropout(Y_l) + X_l      (glove:42-50, 71-76)
 __host__ __device__ inline GemmArgs plan_fwd_agg(const GcnCtx& c, int l) {
-  GemmArgs g;
-  plan_common(c, g);
   const long off = (long)l * c.gh, sb = (long)c.N * c.HD, sh = (long)c.L * c.gh;
-  g.A = c.A, g.lda = c.N, g.a_kc = 1, g.sA1 = (long)c.H * c.N * c.N, g.sA2 = (long)c.N * c.N;
-  g.B = c.Pn + off, g.ldb = c.HD, g.b_kc = 0, g.sB1 = sb, g.sB2 = sh;
-  g.C = c.Y + off, g.ldc = c.HD, g.sC1 = sb, g.sC2 = sh;
-  g.M = c.N, g.N = c.gh, g.K = c.N;
+  GemmArgs g = gemm_nn(c.A, c.N, c.Pn + off, c.HD, c.Y + off, c.HD, c.N, c.gh, c.N);
+  g.batch_z1(c.B, (long)c.H * c.N * c.N, sb, sb).batch_z2(c.H, (long)c.N * c.N, sh, sh);
+  g.splits = 1;
   g.add = c.G + off, g.ldadd = c.HD, g.sAdd1 = sb, g.sAdd2 = sh;
   g.rowscale = c.rinv, g.sRs1 = (long)c.H * c.N, g.sRs2 = c.N;
   g.relu = 1;
@@ -107,26 +97,20 @@ __host__ __device__ inline GemmArgs plan_fwd_agg(const GcnCtx& c, int l) {
 
 // dPn_l = A_h^T dM_l
 __host__ __device__ inline GemmArgs plan_bwd_dP(const GcnCtx& c, int l) {
-  GemmArgs g;
-  plan_common(c, g);
   const long off = (long)l * c.gh, sb = (long)c.N * c.HD, sh = (long)c.L * c.gh;
-  g.A = c.A, g.lda = c.N, g.a_kc = 0, g.sA1 = (long)c.H * c.N * c.N, g.sA2 = (long)c.N * c.N;
-  g.B = c.dM + off, g.ldb = c.HD, g.b_kc = 0, g.sB1 = sb, g.sB2 = sh;
-  g.C = c.dP + off, g.ldc = c.HD, g.sC1 = sb, g.sC2 = sh;
-  g.M = c.N, g.N = c.gh, g.K = c.N;
+  GemmArgs g = gemm_tn(c.A, c.N, c.dM + off, c.HD, c.dP + off, c.HD, c.N, c.gh, c.N);
+  g.batch_z1(c.B, (long)c.H * c.N * c.N, sb, sb).batch_z2(c.H, (long)c.N * c.N, sh, sh);
+  g.splits = 1;
   g.tag = "gemm_dP";
   return g;
 }
 
 // dA_h (+)= dM_l Pn_l^T ; the normaliser's gradient drow[i] is added to every column on the last pass (l == 0)
 __host__ __device__ inline GemmArgs plan_bwd_dA(const GcnCtx& c, int l) {
-  GemmArgs g;
-  plan_common(c, g);
   const long off = (long)l * c.gh, sb = (long)c.N * c.HD, sh = (long)c.L * c.gh;
-  g.A = c.dM + off, g.lda = c.HD, g.a_kc = 1, g.sA1 = sb, g.sA2 = sh;
-  g.B = c.Pn + off, g.ldb = c.HD, g.b_kc = 1, g.sB1 = sb, g.sB2 = sh;
-  g.C = c.dA, g.ldc = c.N, g.sC1 = (long)c.H * c.N * c.N, g.sC2 = (long)c.N * c.N;
-  g.M = c.N, g.N = c.N, g.K = c.gh;
+  GemmArgs g = gemm_nt(c.dM + off, c.HD, c.Pn + off, c.HD, c.dA, c.N, c.N, c.N, c.gh);
+  g.batch_z1(c.B, sb, sb, (long)c.H * c.N * c.N).batch_z2(c.H, sh, sh, (long)c.N * c.N);
+  g.splits = 1;
   g.accumulate = (l != c.L - 1);
   if (l == 0) g.rowadd = c.drow, g.sRa1 = (long)c.H * c.N, g.sRa2 = c.N;
   g.tag = "gemm_dA";
@@ -135,13 +119,10 @@ __host__ __device__ inline GemmArgs plan_bwd_dA(const GcnCtx& c, int l) {
 
 // dY_{0..l-1} += dPn_l Wd_l^T, l >= 1
 __host__ __device__ inline GemmArgs plan_bwd_dY(const GcnCtx& c, int l) {
-  GemmArgs g;
-  plan_common(c, g);
   const long sb = (long)c.N * c.HD, sh = (long)c.L * c.gh;
-  g.A = c.dP + (long)l * c.gh, g.lda = c.HD, g.a_kc = 1, g.sA1 = sb, g.sA2 = sh;
-  g.B = c.flat + c.wd_off(l), g.ldb = c.gh, g.b_kc = 1, g.sB1 = 0, g.sB2 = c.wd_head;
-  g.C = c.dYa, g.ldc = c.HD, g.sC1 = sb, g.sC2 = sh;
-  g.M = c.N, g.N = l * c.gh, g.K = c.gh;
+  GemmArgs g = gemm_nt(c.dP + (long)l * c.gh, c.HD, c.flat + c.wd_off(l), c.gh, c.dYa, c.HD, c.N, l * c.gh, c.gh);
+  g.batch_z1(c.B, sb, 0, sb).batch_z2(c.H, sh, c.wd_head, sh);
+  g.splits = 1;
   g.accumulate = 1;
   g.tag = "gemm_dY";
   return g;

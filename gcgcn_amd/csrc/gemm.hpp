@@ -6,8 +6,14 @@
 namespace gc {
 
 // C[z] = epilogue( alpha * opA(A[z]) * opB(B[z]) )          z = z1 * batch2 + z2
-//   a_kc : A is stored [M][K] (k contiguous, "N" form);  else A is stored [K][M] ("T" form)
-//   b_kc : B is stored [N][K] (k contiguous, "T" form);  else B is stored [K][N] ("N" form)
+// A problem is described by one of three constructors, named after how the operands are STORED (gemm_nn / gemm_nt / gemm_tn
+// below the struct; they launch nothing), then whatever recurs is attached (split_ws, batch_z1 / batch_z2, tagged) and the
+// epilogue fields are assigned:
+//   NN : A[M][K], B[K][N]   C = A B      activations times a [K][N] weight; every data gradient dX = dY W
+//   NT : A[M][K], B[N][K]   C = A B^T    Y = X W^T with a Linear's [out][in] weight; Q_h Q_h^T; dM We^T
+//   TN : A[K][M], B[K][N]   C = A^T B    K = the row dimension of both operands: every weight gradient dW = dY^T X
+//   a_kc : A is stored [M][K] (k contiguous: NN, NT);  else A is stored [K][M] (TN)        -- set by the constructors,
+//   b_kc : B is stored [N][K] (k contiguous: NT);      else B is stored [K][N] (NN, TN)    -- by nobody else
 // epilogue, in this order (every pointer optional):
 //   v  = alpha * acc
 //   v += add[row * ldadd + col]            (batch strided)
@@ -71,7 +77,35 @@ struct GemmArgs {
   int splits = 1, ksplit = 0;
   int widen = 1;   // rb_mode 1, splits > 1: a launch of a ragged batch may cut K up to `widen` times finer ON THE DEVICE, with the tile
                    // workgroups its dead rows leave idle (split_width, gemm_body.hpp); the workspace holds splits * widen slabs
+
+  // What recurs beside the product itself; each returns *this, so a description reads gemm_tn(...).split_ws(...).tagged(...)
+  __host__ __device__ GemmArgs& split_ws(float* w, long elems) { return ws = w, ws_elems = elems, *this; }
+  __host__ __device__ GemmArgs& tagged(const char* t) { return tag = t, *this; }
+  // the two batch levels (z = z1 * batch2 + z2) with the strides of A, B and C; epilogue operands keep their own stride fields
+  __host__ __device__ GemmArgs& batch_z1(int n, long sA, long sB, long sC) { return batch1 = n, sA1 = sA, sB1 = sB, sC1 = sC, *this; }
+  __host__ __device__ GemmArgs& batch_z2(int n, long sA, long sB, long sC) { return batch2 = n, sA2 = sA, sB2 = sB, sC2 = sC, *this; }
 };
+
+// The storage forms (see the top of this file).  gemm_stored takes the two flags as data: for the C ABI's gcgcn_gemm /
+// gcgcn_gemm_dyn, whose callers hand them in, and for nobody else.
+__host__ __device__ inline GemmArgs gemm_stored(int a_kc, int b_kc, const float* A, long lda, const float* B, long ldb, float* C, long ldc,
+                                                int M, int N, int K) {
+  GemmArgs g;
+  g.A = A, g.lda = lda, g.a_kc = a_kc;
+  g.B = B, g.ldb = ldb, g.b_kc = b_kc;
+  g.C = C, g.ldc = ldc;
+  g.M = M, g.N = N, g.K = K;
+  return g;
+}
+__host__ __device__ inline GemmArgs gemm_nn(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K) {
+  return gemm_stored(1, 0, A, lda, B, ldb, C, ldc, M, N, K);
+}
+__host__ __device__ inline GemmArgs gemm_nt(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K) {
+  return gemm_stored(1, 1, A, lda, B, ldb, C, ldc, M, N, K);
+}
+__host__ __device__ inline GemmArgs gemm_tn(const float* A, long lda, const float* B, long ldb, float* C, long ldc, int M, int N, int K) {
+  return gemm_stored(0, 0, A, lda, B, ldb, C, ldc, M, N, K);
+}
 
 // Enqueue on `stream`.  tile: 0 or 1 = the 64x64 block body (the only one; the two 128x128 bodies of earlier rounds lost every
 // A/B on this path's products and are gone).

@@ -1013,15 +1013,6 @@ static bool head_compacts(const int* n_valid, int R) {
   return n_valid && option("head_compact", 1) != 0 && R > 64 && R <= 97;
 }
 
-static int small_gemm(const float* A, long lda, int a_kc, const float* B, long ldb, int b_kc, float* C, long ldc, int M, int N, int K,
-                      const float* bias, int accumulate, float* ws, long wse, hipStream_t st) {
-  GemmArgs g;
-  g.A = A, g.lda = lda, g.a_kc = a_kc, g.B = B, g.ldb = ldb, g.b_kc = b_kc, g.C = C, g.ldc = ldc;
-  g.M = M, g.N = N, g.K = K, g.bias = bias, g.accumulate = accumulate, g.ws = ws, g.ws_elems = wse;
-  g.tag = "head_gemm";
-  return gemm(g, st);
-}
-
 int head_fwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int dis_plus, const float* const* feats, const long long* type,
              const long long* rel, const float* ner_emb, const float* dis_table, const int* n_valid, const float* flat, HeadBufs w,
              float* logits, hipStream_t st) {
@@ -1030,9 +1021,11 @@ int head_fwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int di
   GC_REQUIRE(pairs < (1L << 31) / 2 && R >= 1 && R <= HW, "head: %ld pairs / %d relations out of range", pairs, R);
   const bool compact = head_compacts(n_valid, R);
   GC_REQUIRE(!compact || w.idx, "head_fwd: n_valid given without the index workspace");
-  for (int k = 0; k < nf; ++k)  // U = sum_k feats_k W_k^T + b           (glove:354-355, the entity part of the dense layer)
-    GC_TRY(small_gemm(feats[k], Hd, 1, flat + y.Wd + (long)k * Hd, y.Fin, 1, w.U, HW, (int)BN, HW, Hd, k == 0 ? flat + y.bd : nullptr,
-                      k > 0, nullptr, 0, st));
+  for (int k = 0; k < nf; ++k) {  // U = sum_k feats_k W_k^T + b           (glove:354-355, the entity part of the dense layer)
+    GemmArgs g = gemm_nt(feats[k], Hd, flat + y.Wd + (long)k * Hd, y.Fin, w.U, HW, (int)BN, HW, Hd).tagged("head_gemm");
+    g.bias = k == 0 ? flat + y.bd : nullptr, g.accumulate = k > 0;
+    GC_TRY(gemm(g, st));
+  }
   {
     ProfScope ps("head_gemm", st);
     hipLaunchKernelGGL(head_tables_fwd_kernel, dim3(cdiv((long)(ND > 7 ? ND : 7) * HW, 256), 2), dim3(256), 0, st, ner_emb, dis_table,
@@ -1090,16 +1083,15 @@ int head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int di
     hipLaunchKernelGGL(head_pad_kernel, dim3(cdiv(prows * HW, 256)), dim3(256), 0, st, dlogits, n_valid, w.doutp, prows, N, R, cnt, prow);
     GC_TRY(check_launch("head_pad"));
   }
-  // (products over the pair rows: M or K = the device-side count on the compacted path)
-  auto rows_gemm = [&](const float* A, long lda, int a_kc, const float* Bm, long ldb, int b_kc, float* C, long ldc, int M, int Nn, int K,
-                       int accumulate, int dyn) -> int {
-    if (!compact) return small_gemm(A, lda, a_kc, Bm, ldb, b_kc, C, ldc, M, Nn, K, nullptr, accumulate, dyn == 2 ? ws : nullptr, dyn == 2 ? wse : 0, st);
-    GemmArgs g;
-    g.A = A, g.lda = lda, g.a_kc = a_kc, g.B = Bm, g.ldb = ldb, g.b_kc = b_kc, g.C = C, g.ldc = ldc;
-    g.M = M, g.N = Nn, g.K = K, g.accumulate = accumulate, g.ws = ws, g.ws_elems = wse;
-    g.tag = "head_gemm";
-    return gemm_dyn(g, cnt, dyn, pairs, st);
-  };
+  // The W_c products over the pair rows, side q = 0: eh, 1: et.  Compacted, the row count is on the device: the two sides share
+  // one gemm_dyn_pair launch; dense, each is a launch of its own (the data gradients then need no workspace).
+  GemmArgs dE_c[2], dW_c[2];
+  for (int q = 0; q < 2; ++q) {
+    dE_c[q] = gemm_nn(w.doutp, HW, flat + y.Wc + q * HW, 2 * HW, q ? w.dET : w.dEH, HW, (int)pairs, HW, HW).tagged("head_gemm");
+    dE_c[q].accumulate = 1;   // d e += dout W_c[:, q * 128 ...]
+    if (compact) dE_c[q].split_ws(ws, wse);
+    dW_c[q] = gemm_tn(w.doutp, HW, q ? w.ET : w.EH, HW, w.dW + q * HW, 2 * HW, HW, HW, (int)pairs).split_ws(ws, wse).tagged("head_gemm");
+  }
   // bias gradients: both biases see the column sums of dlogits
   GC_TRY(colsum(w.doutp, nullptr, dflat + y.bb, pairs, R, HW, 1, 0, 0, 0, 0, ws, st));
   GC_REQUIRE(hipMemcpyAsync(dflat + y.bc, dflat + y.bb, sizeof(float) * R, hipMemcpyDeviceToDevice, st) == hipSuccess, "head: copy failed");
@@ -1113,7 +1105,7 @@ int head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int di
     if (compact || !head_v1(pairs))
       GC_TRY(head_bil2(2, w.doutp, w.ET, flat + y.Wb, nullptr, nullptr, w.dEH, pairs, R, HW, HW, st, cnt, nullptr, compact ? w.partB : nullptr, w.part_rows));
     else GC_TRY(head_gemm(2, g, o, st));
-    if (!compact) GC_TRY(rows_gemm(w.doutp, HW, 1, flat + y.Wc, 2 * HW, 0, w.dEH, HW, (int)pairs, HW, HW, 1, 1));   // (compacted: with d et's, below)
+    if (!compact) GC_TRY(gemm(dE_c[0], st));   // (compacted: with d et's, below)
   }
   {  // d et = sum_(r,a) dout[p,r] eh[p,a] W_b[r,a,b]  + dout W_c[:, 128:]
     GemmArgs g;
@@ -1122,19 +1114,8 @@ int head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int di
     if (compact || !head_v1(pairs))
       GC_TRY(head_bil2(3, w.doutp, w.EH, flat + y.Wb, nullptr, nullptr, w.dET, pairs, R, HW, HW, st, cnt, nullptr, compact ? w.partB : nullptr, w.part_rows));
     else GC_TRY(head_gemm(3, g, o, st));
-    if (compact) {   // + dout W_c on both sides, over the device-side pair count: one launch for the two halves
-      GemmArgs gh[2];
-      for (int q = 0; q < 2; ++q) {
-        GemmArgs& g2 = gh[q];
-        g2.A = w.doutp, g2.lda = HW, g2.a_kc = 1, g2.B = flat + y.Wc + q * HW, g2.ldb = 2 * HW, g2.b_kc = 0;
-        g2.C = q ? w.dET : w.dEH, g2.ldc = HW, g2.M = (int)pairs, g2.N = HW, g2.K = HW, g2.accumulate = 1;
-        g2.ws = ws, g2.ws_elems = wse;
-        g2.tag = "head_gemm";
-      }
-      GC_TRY(gemm_dyn_pair_xx(gh[0], gh[1], cnt, pairs, st));
-    } else {
-      GC_TRY(rows_gemm(w.doutp, HW, 1, flat + y.Wc + HW, 2 * HW, 0, w.dET, HW, (int)pairs, HW, HW, 1, 1));
-    }
+    if (compact) GC_TRY(gemm_dyn_pair_xx(dE_c[0], dE_c[1], cnt, pairs, st));   // + dout W_c on both sides: one launch for the two halves
+    else GC_TRY(gemm(dE_c[1], st));
   }
   {  // d W_b[r, (a, b)] = sum_p dout[p, r] eh[p, a] et[p, b]
     GemmArgs g;
@@ -1162,18 +1143,10 @@ int head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int di
   }
   // d W_c = dout^T [eh | et]    (computed 128 rows deep into a workspace, the R real rows copied out)
   if (compact) {   // the two halves over the same device-side pair count: one launch, one reduce
-    GemmArgs gh[2];
-    for (int q = 0; q < 2; ++q) {
-      GemmArgs& g = gh[q];
-      g.A = w.doutp, g.lda = HW, g.a_kc = 0, g.B = q ? w.ET : w.EH, g.ldb = HW, g.b_kc = 0;
-      g.C = w.dW + q * HW, g.ldc = 2 * HW, g.M = HW, g.N = HW, g.K = (int)pairs;
-      g.ws = ws, g.ws_elems = wse;
-      g.tag = "head_gemm";
-    }
-    GC_TRY(gemm_dyn_pair_ww(gh[0], gh[1], cnt, pairs, st));
+    GC_TRY(gemm_dyn_pair_ww(dW_c[0], dW_c[1], cnt, pairs, st));
   } else {
-    GC_TRY(rows_gemm(w.doutp, HW, 0, w.EH, HW, 0, w.dW, 2 * HW, HW, HW, (int)pairs, 0, 2));
-    GC_TRY(rows_gemm(w.doutp, HW, 0, w.ET, HW, 0, w.dW + HW, 2 * HW, HW, HW, (int)pairs, 0, 2));
+    GC_TRY(gemm(dW_c[0], st));
+    GC_TRY(gemm(dW_c[1], st));
   }
   GC_REQUIRE(hipMemcpyAsync(dflat + y.Wc, w.dW, sizeof(float) * R * 2 * HW, hipMemcpyDeviceToDevice, st) == hipSuccess, "head: copy failed");
   {
@@ -1197,28 +1170,23 @@ int head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int di
   // dense layer: entity part, type part, relative-position part.  The entity part's 2 nf products (data and weight gradient of
   // every feature group) are independent of each other: ONE group launch (+ one reduce for the split weight gradients) with
   // the bias gradient's column sums riding in both, where round 4 issued 3 nf + 2 launches of 5-8 us each.
+  auto dfeat = [&](int k, long wsn) {  // d feats_k = dUT W_k
+    return gemm_nn(w.dUT, HW, flat + y.Wd + (long)k * Hd, y.Fin, dfeats[k], Hd, (int)BN, Hd, HW).split_ws(ws, wsn).tagged("head_gemm");
+  };
+  auto dWk = [&](int k, long wsn) {  // d W_k = dUT^T feats_k
+    return gemm_tn(w.dUT, HW, feats[k], Hd, dflat + y.Wd + (long)k * Hd, y.Fin, HW, Hd, (int)BN).split_ws(ws, wsn).tagged("head_gemm");
+  };
   if (nf >= 1 && 2 * nf <= 8 && ws && wse > (long)COL_RIDE_SLICES * HW + 4) {
     GemmArgs gs[8];
     const long col_elems = ((long)COL_RIDE_SLICES * HW + 3) & ~3L;    // the riding column sum's partials: the workspace's tail
-    for (int k = 0; k < nf; ++k) {
-      GemmArgs& gx = gs[2 * k];
-      gx = GemmArgs();
-      gx.A = w.dUT, gx.lda = HW, gx.a_kc = 1, gx.B = flat + y.Wd + (long)k * Hd, gx.ldb = y.Fin, gx.b_kc = 0;
-      gx.C = dfeats[k], gx.ldc = Hd, gx.M = (int)BN, gx.N = Hd, gx.K = HW;
-      GemmArgs& gw = gs[2 * k + 1];
-      gw = GemmArgs();
-      gw.A = w.dUT, gw.lda = HW, gw.a_kc = 0, gw.B = feats[k], gw.ldb = Hd, gw.b_kc = 0;
-      gw.C = dflat + y.Wd + (long)k * Hd, gw.ldc = y.Fin, gw.M = HW, gw.N = Hd, gw.K = (int)BN;
-      gx.ws = gw.ws = ws, gx.ws_elems = gw.ws_elems = wse - col_elems;
-      gx.tag = gw.tag = "head_gemm";
-    }
+    for (int k = 0; k < nf; ++k) gs[2 * k] = dfeat(k, wse - col_elems), gs[2 * k + 1] = dWk(k, wse - col_elems);
     ColRide cr;
     cr.X = w.dUT, cr.out = dflat + y.bd, cr.part = ws + (wse - col_elems), cr.R = BN, cr.ld = HW, cr.C = HW;
     GC_TRY(gemm_group(gs, 2 * nf, st, &cr));
   } else {
     for (int k = 0; k < nf; ++k) {
-      GC_TRY(small_gemm(w.dUT, HW, 1, flat + y.Wd + (long)k * Hd, y.Fin, 0, dfeats[k], Hd, (int)BN, Hd, HW, nullptr, 0, ws, wse, st));
-      GC_TRY(small_gemm(w.dUT, HW, 0, feats[k], Hd, 0, dflat + y.Wd + (long)k * Hd, y.Fin, HW, Hd, (int)BN, nullptr, 0, ws, wse, st));
+      GC_TRY(gemm(dfeat(k, wse), st));
+      GC_TRY(gemm(dWk(k, wse), st));
     }
     GC_TRY(colsum(w.dUT, nullptr, dflat + y.bd, BN, HW, HW, 1, 0, 0, 0, 0, ws, st));
   }

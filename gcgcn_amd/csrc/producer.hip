@@ -918,54 +918,32 @@ int prod_index(const unsigned char* sen, const int* n_valid, ProdIdx ix, int B, 
   return check_launch("prod_index_b");
 }
 
-static int linear_fwd(const float* X, long M, int K, const float* W, const float* bias, int Nout, float* Y, float* ws, long wse,
-                      hipStream_t st, const int* cnt = nullptr, long cap = 0) {  // Y = X W^T + b, W stored [Nout, K]
-  GemmArgs g;
-  g.A = X, g.lda = K, g.a_kc = 1;
-  g.B = W, g.ldb = K, g.b_kc = 1;
-  g.C = Y, g.ldc = Nout;
-  g.M = (int)M, g.N = Nout, g.K = K;
+// The three products of one Linear layer over `rows` rows, W stored [Nout, K] -- described here, launched by their callers.
+// rows = 0 where the count lives on the device (gemm_dyn*).
+static GemmArgs linear_y(const float* X, long rows, int K, const float* W, const float* bias, int Nout, float* Y, float* ws, long wse) {
+  GemmArgs g = gemm_nt(X, K, W, K, Y, Nout, (int)rows, Nout, K).split_ws(ws, wse).tagged("prod_gemm");   // Y = X W^T + b
   g.bias = bias;
-  g.ws = ws, g.ws_elems = wse;
-  g.tag = "prod_gemm";
-  return cnt ? gemm_dyn(g, cnt, 1, cap, st) : gemm(g, st);
+  return g;
 }
-// dX (+)= dY W          (W stored [Nout, K]: the "N" form with k = Nout)
-static int linear_bwd_x(const float* dY, long M, int Nout, const float* W, int K, float* dX, int accumulate, float* ws, long wse,
-                        hipStream_t st, const int* cnt = nullptr, long cap = 0) {
-  GemmArgs g;
-  g.A = dY, g.lda = Nout, g.a_kc = 1;
-  g.B = W, g.ldb = K, g.b_kc = 0;
-  g.C = dX, g.ldc = K;
-  g.M = (int)M, g.N = K, g.K = Nout;
+static GemmArgs linear_dx(const float* dY, long rows, int Nout, const float* W, int K, float* dX, int accumulate, float* ws, long wse) {
+  GemmArgs g = gemm_nn(dY, Nout, W, K, dX, K, (int)rows, K, Nout).split_ws(ws, wse).tagged("prod_gemm");   // dX (+)= dY W
   g.accumulate = accumulate;
-  g.ws = ws, g.ws_elems = wse;
-  g.tag = "prod_gemm";
-  return cnt ? gemm_dyn(g, cnt, 1, cap, st) : gemm(g, st);
+  return g;
 }
-// dW[Nout, K] = dY^T X   (rows = the reduction dimension)
-static int linear_bwd_w(const float* dY, const float* X, long M, int Nout, int K, float* dW, float* ws, long wse, hipStream_t st,
-                        const int* cnt = nullptr, long cap = 0) {
-  GemmArgs g;
-  g.A = dY, g.lda = Nout, g.a_kc = 0;
-  g.B = X, g.ldb = K, g.b_kc = 0;
-  g.C = dW, g.ldc = K;
-  g.M = Nout, g.N = K, g.K = (int)M;
-  g.ws = ws, g.ws_elems = wse;
-  g.tag = "prod_gemm";
-  return cnt ? gemm_dyn(g, cnt, 2, cap, st) : gemm(g, st);
+static GemmArgs linear_dw(const float* dY, const float* X, long rows, int Nout, int K, float* dW, float* ws, long wse) {
+  return gemm_tn(dY, Nout, X, K, dW, K, Nout, K, (int)rows).split_ws(ws, wse).tagged("prod_gemm");   // dW = dY^T X
+}
+
+static int linear_fwd(const float* X, long M, int K, const float* W, const float* bias, int Nout, float* Y, float* ws, long wse,
+                      hipStream_t st, const int* cnt = nullptr, long cap = 0) {
+  const GemmArgs g = linear_y(X, M, K, W, bias, Nout, Y, ws, wse);
+  return cnt ? gemm_dyn(g, cnt, 1, cap, st) : gemm(g, st);
 }
 
 // dW = dY^T X and dX (+)= dY W of one Linear layer whose row count lives on the device: one launch (+ dW's reduce), gemm_dyn_pair
 static int linear_bwd_wx_dyn(const float* dY, const float* X, int Nout, int K, const float* W, float* dW, float* dX, int accumulate_x,
                              float* ws, long wse, hipStream_t st, const int* cnt, long cap) {
-  GemmArgs gw, gx;
-  gw.A = dY, gw.lda = Nout, gw.a_kc = 0, gw.B = X, gw.ldb = K, gw.b_kc = 0, gw.C = dW, gw.ldc = K, gw.M = Nout, gw.N = K, gw.K = 0;
-  gx.A = dY, gx.lda = Nout, gx.a_kc = 1, gx.B = W, gx.ldb = K, gx.b_kc = 0, gx.C = dX, gx.ldc = K, gx.M = 0, gx.N = K, gx.K = Nout;
-  gx.accumulate = accumulate_x;
-  gw.ws = gx.ws = ws, gw.ws_elems = gx.ws_elems = wse;
-  gw.tag = gx.tag = "prod_gemm";
-  return gemm_dyn_pair(gw, gx, cnt, cap, st);
+  return gemm_dyn_pair(linear_dw(dY, X, 0, Nout, K, dW, ws, wse), linear_dx(dY, 0, Nout, W, K, dX, accumulate_x, ws, wse), cnt, cap, st);
 }
 
 // The three gradients of one Linear layer on a static row count -- dW = dY^T X, db = column sums of dY, dX (+)= dY W -- in ONE
@@ -975,17 +953,12 @@ static int linear_bwd_all(const float* dY, const float* X, long M, int Nout, int
                           int accumulate_x, float* ws, long wse, hipStream_t st) {
   const long col_elems = ((long)COL_RIDE_SLICES * Nout + 3) & ~3L;
   if (!ws || wse <= col_elems + 4) {
-    GC_TRY(linear_bwd_w(dY, X, M, Nout, K, dW, ws, wse, st));
+    GC_TRY(gemm(linear_dw(dY, X, M, Nout, K, dW, ws, wse), st));
     GC_TRY(colsum(dY, nullptr, db, M, Nout, Nout, 1, 0, 0, 0, 0, ws, st));
-    return linear_bwd_x(dY, M, Nout, W, K, dX, accumulate_x, ws, wse, st);
+    return gemm(linear_dx(dY, M, Nout, W, K, dX, accumulate_x, ws, wse), st);
   }
-  GemmArgs gs[2];
-  gs[0].A = dY, gs[0].lda = Nout, gs[0].a_kc = 0, gs[0].B = X, gs[0].ldb = K, gs[0].b_kc = 0;
-  gs[0].C = dW, gs[0].ldc = K, gs[0].M = Nout, gs[0].N = K, gs[0].K = (int)M;
-  gs[1].A = dY, gs[1].lda = Nout, gs[1].a_kc = 1, gs[1].B = W, gs[1].ldb = K, gs[1].b_kc = 0;
-  gs[1].C = dX, gs[1].ldc = K, gs[1].M = (int)M, gs[1].N = K, gs[1].K = Nout, gs[1].accumulate = accumulate_x;
-  gs[0].ws = gs[1].ws = ws, gs[0].ws_elems = gs[1].ws_elems = wse - col_elems;
-  gs[0].tag = gs[1].tag = "prod_gemm";
+  const GemmArgs gs[2] = {linear_dw(dY, X, M, Nout, K, dW, ws, wse - col_elems),   // (the workspace's tail: the column sums' partials)
+                          linear_dx(dY, M, Nout, W, K, dX, accumulate_x, ws, wse - col_elems)};
   ColRide cr;
   cr.X = dY, cr.out = db, cr.part = ws + (wse - col_elems), cr.R = M, cr.ld = Nout, cr.C = Nout;
   return gemm_group(gs, 2, st, &cr);
@@ -1005,17 +978,8 @@ int prod_fwd(int B, int N, int S, int T, int Hd, int P, int ND, const float* ctx
   const long BT = (long)B * T;
   {  // two Linear layers on static inputs in one launch: the token states (glove:178) and the per-entity term of the sentence
      // attention (glove:202), which nothing needs before prod_sent_fwd below
-    GemmArgs gs[2];
-    for (int q = 0; q < 2; ++q) {
-      GemmArgs& g = gs[q];
-      g.A = q ? node : ctx, g.lda = Hd, g.a_kc = 1;
-      g.B = flat + (q ? y.Wsp : y.Ws), g.ldb = Hd, g.b_kc = 1;
-      g.C = q ? w.nterm : w.sentF, g.ldc = Hd;
-      g.M = q ? (int)((long)B * N) : (int)BT, g.N = Hd, g.K = Hd;
-      g.bias = flat + (q ? y.bsp : y.bs);
-      g.ws = ws, g.ws_elems = wse;
-      g.tag = "prod_gemm";
-    }
+    const GemmArgs gs[2] = {linear_y(ctx, BT, Hd, flat + y.Ws, flat + y.bs, Hd, w.sentF, ws, wse),
+                            linear_y(node, (long)B * N, Hd, flat + y.Wsp, flat + y.bsp, Hd, w.nterm, ws, wse)};
     GC_TRY(gemm_group(gs, 2, st));
   }
   GC_TRY(linear_fwd(dis_table, ND, P, flat + y.Wp, flat + y.bp, Hd, w.disF, ws, wse, st));      // glove:179 on the 21 ids
@@ -1144,9 +1108,9 @@ int prod_bwd(int B, int N, int S, int T, int Hd, int P, int ND, const float* ctx
                "producer: copy failed");
   // word_attention.attention_sent / attention_pos
   GC_TRY(linear_bwd_all(g.dsentF, ctx, BT, Hd, Hd, flat + y.Ws, dflat + y.Ws, dflat + y.bs, dctx, 1, ws, wse, st));   // dctx += dsentF W_s
-  GC_TRY(linear_bwd_w(g.ddisF, dis_table, ND, Hd, P, dflat + y.Wp, ws, wse, st));
+  GC_TRY(gemm(linear_dw(g.ddisF, dis_table, ND, Hd, P, dflat + y.Wp, ws, wse), st));
   GC_TRY(colsum(g.ddisF, nullptr, dflat + y.bp, ND, Hd, Hd, 1, 0, 0, 0, 0, ws, st));
-  GC_TRY(linear_bwd_x(g.ddisF, ND, Hd, flat + y.Wp, P, ddis_table, 0, ws, wse, st));
+  GC_TRY(gemm(linear_dx(g.ddisF, ND, Hd, flat + y.Wp, P, ddis_table, 0, ws, wse), st));
   return 0;
 }
 
