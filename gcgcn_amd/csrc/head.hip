@@ -558,19 +558,6 @@ __global__ __launch_bounds__(256, 3) void head_dw_kernel(const HeadDw a) {
   if (a.R > 96 && lh == 0) o[96L * (HW * HW)] = a96;
 }
 
-// Which generation runs the outer-product passes.  The register-generated one (head_bil2 / head_bil3: 128-pair tiles, two
-// workgroups per compute unit) wins once there is a tile per compute unit (B = 32: N = 64 15.8 vs 19.2 ms per step, N = 42 8.1 vs
-// 8.3); below that the first one's finer tiles (64 x 64, four per compute unit) fill the chip better.  GCGCN_HEAD_V1=1 / =0 (or
-// gcgcn_set_option("head_v1", 1 / 0; -1 = by size) forces one of them (A/B runs and the test suite, which runs both).
-static bool head_v1(long pairs) {
-  const int v = option("head_v1", -1);
-  if (v >= 0) return v != 0;
-  return cdiv(pairs, 128) < 256;
-}
-
-// the forward pass's 128-pair tile with column 96 on the vector ALU (GCGCN_HEAD_BIL3=0 / set_option("head_bil3", 0): A/B knob)
-static bool head_bil3_ok(int ncol) { return option("head_bil3", 1) != 0 && ncol > 64 && ncol <= 97; }
-
 // out[row, col] = sum_y part[y][row][col] + bias[col] for the K-split passes above (y in order: deterministic), row < *rows_dev,
 // scattered through crow where the output is the padded logits tensor.
 __global__ __launch_bounds__(256) void head_bil_combine_kernel(const float* __restrict__ part, int part_rows, const int* __restrict__ rows_dev,
@@ -595,64 +582,70 @@ __global__ __launch_bounds__(256) void head_bil_combine_kernel(const float* __re
     if (c4 + u < ncol) o[c4 + u] = vs[u] + (bias ? bias[c4 + u] : 0.f);
 }
 
-constexpr int HEAD_TILE128_MIN_ROWS = 32768;   // one 128-pair tile per compute unit (the rule head_v1 applies to host-side counts)
-static int head_bil2(int mode, const float* P, const float* Q, const float* W, const float* W2, const float* bias, float* C, long rows,
-                     int nA, int ncol, int ldc, hipStream_t st, const int* rows_dev = nullptr, const int* crow = nullptr,
-                     float* part = nullptr, long part_rows = 0) {
-  Bil2 a;
-  a.P = P, a.Q = Q, a.W = W, a.W2 = W2, a.bias = bias, a.C = C, a.rows = (int)rows, a.nA = nA, a.ncol = ncol, a.ldc = ldc, a.accumulate_unused = 0;
-  a.rows_dev = rows_dev, a.crow = crow;   // (rows = the capacity the grid is sized for)
-  a.sel_lo = 0, a.sel_hi = 0x7fffffff;
-  a.part = nullptr, a.part_rows = 0;
-  const dim3 grid((unsigned)cdiv(rows, 64)), grid128((unsigned)cdiv(rows, 128)), block(256);
-  const double flops = 2.0 * rows * ncol * (double)(nA * HW + (mode == 1 ? 2 * HW : 0));
-  const bool wide = option("head_bil3_bwd", 1) != 0;
-  const bool tile128 = (mode == 1 && head_bil3_ok(ncol)) || (mode != 1 && wide && ncol == 128);
-  auto launch128 = [&](const Bil2& b, const double flops) {   // 128 pairs per workgroup: 3 MFMA column blocks + column 96 on the vector ALU (mode 1), four accumulators (2 / 3)
-    if (mode == 1) GC_LAUNCH_TIMED("head_bilinear", flops, head_bil3_kernel<1>, grid128, block, 0, st, b);
-    else if (mode == 2) GC_LAUNCH_TIMED("head_bilinear", flops, head_bil3_kernel<2>, grid128, block, 0, st, b);
-    else GC_LAUNCH_TIMED("head_bilinear", flops, head_bil3_kernel<3>, grid128, block, 0, st, b);
-  };
-  auto launch64 = [&](const Bil2& b, const double flops) {
-    if (mode == 1) GC_LAUNCH_TIMED("head_bilinear", flops, (head_bil2_kernel<1>), grid, block, 0, st, b);
-    else if (mode == 2) GC_LAUNCH_TIMED("head_bilinear", flops, (head_bil2_kernel<2>), grid, block, 0, st, b);
-    else GC_LAUNCH_TIMED("head_bilinear", flops, (head_bil2_kernel<3>), grid, block, 0, st, b);
-  };
-  if (rows_dev && tile128) {
-    // The count is on the device and the better launch shape depends on it; the host launches both, the one whose range does
-    // not hold the count leaves at once (a few microseconds of a millisecond-sized pass).  One 128-pair tile per compute unit
-    // and more (>= 32 768 pairs): the plain tiles.  Fewer (a DocRED batch of 32 documents: 14 k real pairs = 109 tiles on 256
-    // compute units, each streaming the whole 6.4 MB weight through its LDS): every tile split four ways over the b-chunks of
-    // the k sequence -- four times the workgroups, a quarter of the weight each -- plus a combine pass; without a partial-sum
-    // workspace, 64-pair tiles (4.14 -> 3.39 ms per step; the split: see DESIGN.md section 9).
-    Bil2 big = a, small = a;
-    big.sel_lo = HEAD_TILE128_MIN_ROWS, small.sel_hi = HEAD_TILE128_MIN_ROWS;
-    launch128(big, 0.5 * flops);    // (the host-side work counter: one of the two runs, the timer sees both)
-    if (int e = check_launch("head_bil3")) return e;
-    if (part && part_rows > 0) {
-      small.part = part, small.part_rows = (int)part_rows;
-      const long prow = rows < part_rows ? rows : part_rows;     // (counts below the threshold never exceed the slab)
-      const dim3 grid4((unsigned)cdiv(prow, 128), 4);
-      if (mode == 1) GC_LAUNCH_TIMED("head_bilinear", 0.5 * flops, head_bil3_kernel<1>, grid4, block, 0, st, small);
-      else if (mode == 2) GC_LAUNCH_TIMED("head_bilinear", 0.5 * flops, head_bil3_kernel<2>, grid4, block, 0, st, small);
-      else GC_LAUNCH_TIMED("head_bilinear", 0.5 * flops, head_bil3_kernel<3>, grid4, block, 0, st, small);
-      if (int e = check_launch("head_bil3 split")) return e;
-      hipLaunchKernelGGL(head_bil_combine_kernel, dim3((unsigned)cdiv(prow * 32, 256)), dim3(256), 0, st, part, (int)part_rows, rows_dev,
-                         small.sel_lo, small.sel_hi, bias, crow, C, ncol, ldc);
-      return check_launch("head_bil_combine");
-    }
-    launch64(small, 0.5 * flops);
-    return check_launch("head_bil2");
-  }
-  if (tile128) {
-    launch128(a, flops);
-    return check_launch("head_bil3");
-  }
-  launch64(a, flops);
-  return check_launch("head_bil2");
+// ---- which kernel serves which pass: decided once per call, here and nowhere else (gcgcn_debug_head_plan shows the result) ----
+constexpr int HEAD_TILE128_MIN_ROWS = 32768;   // one 128-pair tile per compute unit (the rule head_plan applies to host-side counts)
+struct HeadPlan {
+  enum Pass { GEMM, TILE64, TILE128 };   // head_gemm_kernel<mode> | head_bil2_kernel<mode> | head_bil3_kernel<mode>
+  enum Dw { DW_GEMM, DW_ROWS };          // head_gemm_kernel<4> | head_dw_kernel
+  bool compact;      // the pair passes run on the pairs that exist (compacted rows); their count is on the device
+  Pass fwd, bwd_e;   // the forward pass (mode 1); the d eh / d et passes (modes 2 and 3)
+  Dw dw;             // d W_b
+  bool by_count(Pass p) const { return compact && p == TILE128; }   // both launch shapes, the device-side count selects one (head_pass)
+};
+static HeadPlan head_plan(long pairs, int R, bool ragged) {
+  // Which generation runs the outer-product passes.  The register-generated one (head_bil2 / head_bil3: 128-pair tiles, two
+  // workgroups per compute unit) wins once there is a tile per compute unit (B = 32: N = 64 15.8 vs 19.2 ms per step, N = 42 8.1
+  // vs 8.3); below that the first one's finer tiles (64 x 64, four per compute unit) fill the chip better.  GCGCN_HEAD_V1=1 / =0
+  // (or gcgcn_set_option("head_v1", 1 / 0; -1 = by size) forces one of them (A/B runs and the test suite, which runs both).
+  const int force = option("head_v1", -1);
+  const bool gen1 = force >= 0 ? force != 0 : cdiv(pairs, 128) < 256;
+  const bool past96 = R > 64 && R <= 97;   // the relation count just past 96 (the reference's 97): row / column 96 on the vector ALU
+  // the forward pass's 128-pair tile with column 96 on the vector ALU (GCGCN_HEAD_BIL3=0 / set_option("head_bil3", 0): A/B knob)
+  const bool fwd128 = option("head_bil3", 1) != 0 && past96;
+  const bool bwd128 = option("head_bil3_bwd", 1) != 0;   // d eh / d et: four accumulators per wave (their 128 columns are exact)
+  HeadPlan p;
+  // option head_compact (default 1): ragged batches run the pair passes on the pairs that exist.  Served by the register-generated
+  // kernels with the relation count just past 96 (head_bil3 / head_dw); anything else keeps the dense path, which computes every
+  // pair slot of the padded batch.  Compacted rows override the generation rule in every pass.
+  p.compact = ragged && option("head_compact", 1) != 0 && past96;
+  // forward: the 128-pair tile wherever it applies, with generation 1 forced too (looks like an accident -- the backward passes
+  // honour head_v1 = 1 -- and is left for a measured change)
+  p.fwd = fwd128 ? HeadPlan::TILE128 : (p.compact || !gen1) ? HeadPlan::TILE64 : HeadPlan::GEMM;
+  p.bwd_e = (p.compact || !gen1) ? (bwd128 ? HeadPlan::TILE128 : HeadPlan::TILE64) : HeadPlan::GEMM;
+  // d W_b: all R rows per workgroup, row 96 on the vector ALU (head_dw_kernel); the GEMM form pads R to 128 rows
+  p.dw = (p.compact || (option("head_dw3", 1) != 0 && past96 && !gen1)) ? HeadPlan::DW_ROWS : HeadPlan::DW_GEMM;
+  return p;
 }
 
-static int head_gemm(int mode, GemmArgs g, const HeadOps& o, hipStream_t st) {
+// One outer-product pass (the MODE table above struct Bil2): the factors, the bilinear weight, the output.  The caller adds
+// W2 / bias (mode 1) and, for compacted rows, rows_dev / crow / the slab of the four-way split (part, part_rows).
+static Bil2 bil_pass(int mode, const float* P, const float* Q, const float* W, float* C, long rows, int R) {
+  Bil2 a;
+  a.P = P, a.Q = Q, a.W = W, a.W2 = nullptr, a.bias = nullptr, a.C = C, a.rows = (int)rows, a.accumulate_unused = 0;
+  a.nA = mode == 1 ? HW : R, a.ncol = a.ldc = mode == 1 ? R : HW;
+  a.rows_dev = nullptr, a.crow = nullptr, a.sel_lo = 0, a.sel_hi = 0x7fffffff, a.part = nullptr, a.part_rows = 0;
+  return a;
+}
+using BilKernel = void (*)(Bil2);   // the register-generated kernels by tile and mode: the one mode -> template switch
+static const BilKernel bil_kernels[2][3] = {{head_bil3_kernel<1>, head_bil3_kernel<2>, head_bil3_kernel<3>},    // 128 pairs per workgroup
+                                            {head_bil2_kernel<1>, head_bil2_kernel<2>, head_bil2_kernel<3>}};   // 64
+// The same pass as the first generation sees it (MODE 1..3 above struct HeadOperands); head_gemm fills the launch fields.
+struct Gen1 { GemmArgs g; HeadOps o; };
+static HeadOps head_ops(const float* P, const float* Q, int KB, long rows, int R) {
+  HeadOps o = {};
+  o.P = P, o.Q = Q, o.ldp = o.ldq = HW, o.KB = KB, o.nmax = R, o.rows = (int)rows;
+  return o;
+}
+static Gen1 gen1_pass(int mode, const Bil2& a) {
+  Gen1 p;
+  const int KB = a.nA * HW;
+  p.g.A = a.P, p.g.B = a.W, p.g.C = a.C, p.g.ldc = a.ldc, p.g.M = a.rows, p.g.N = a.ncol, p.g.K = KB + (mode == 1 ? 2 * HW : 0), p.g.bias = a.bias;
+  p.o = head_ops(a.P, a.Q, KB, a.rows, mode == 1 ? a.ncol : a.nA);
+  p.o.W2 = a.W2, p.o.ldw2 = mode == 1 ? 2 * HW : 0;
+  return p;
+}
+static int head_gemm(int mode, const Gen1& p, hipStream_t st) {
+  GemmArgs g = p.g;
   const long tiles = (long)cdiv(g.M, 64) * cdiv(g.N, 64);
   int splits = 1;
   if (g.ws && tiles < 2048) {  // long-K weight gradient with few output tiles
@@ -666,13 +659,46 @@ static int head_gemm(int mode, GemmArgs g, const HeadOps& o, hipStream_t st) {
   const dim3 grid((unsigned)(tiles * splits)), block(256);
   const double flops = 2.0 * g.M * g.N * g.K;
   switch (mode) {
-    case 1: GC_LAUNCH_TIMED("head_bilinear", flops, (head_gemm_kernel<1, true, true>), grid, block, 0, st, g, o); break;
-    case 2: GC_LAUNCH_TIMED("head_bilinear", flops, (head_gemm_kernel<2, true, true>), grid, block, 0, st, g, o); break;
-    case 3: GC_LAUNCH_TIMED("head_bilinear", flops, (head_gemm_kernel<3, true, false>), grid, block, 0, st, g, o); break;
-    default: GC_LAUNCH_TIMED("head_bilinear", flops, (head_gemm_kernel<4, false, false>), grid, block, 0, st, g, o); break;
+    case 1: GC_LAUNCH_TIMED("head_bilinear", flops, (head_gemm_kernel<1, true, true>), grid, block, 0, st, g, p.o); break;
+    case 2: GC_LAUNCH_TIMED("head_bilinear", flops, (head_gemm_kernel<2, true, true>), grid, block, 0, st, g, p.o); break;
+    case 3: GC_LAUNCH_TIMED("head_bilinear", flops, (head_gemm_kernel<3, true, false>), grid, block, 0, st, g, p.o); break;
+    default: GC_LAUNCH_TIMED("head_bilinear", flops, (head_gemm_kernel<4, false, false>), grid, block, 0, st, g, p.o); break;
   }
   if (int e = check_launch("head_gemm")) return e;
   return splits > 1 ? splitk_reduce(g, st) : 0;
+}
+// Runs one pass with the kernel the plan names.
+static int head_pass(int mode, const Bil2& pass, const HeadPlan& plan, hipStream_t st) {
+  const HeadPlan::Pass tile = mode == 1 ? plan.fwd : plan.bwd_e;
+  if (tile == HeadPlan::GEMM) return head_gemm(mode, gen1_pass(mode, pass), st);
+  const long rows = pass.rows;
+  const double flops = 2.0 * rows * pass.ncol * (double)(pass.nA * HW + (mode == 1 ? 2 * HW : 0));
+  // 128 pairs per workgroup: 3 MFMA column blocks + column 96 on the vector ALU (mode 1), four accumulators (2 / 3); ysplit = 4:
+  // every tile split over the four b-chunks of the k sequence
+  auto launch = [&](HeadPlan::Pass t, const Bil2& b, long nrows, int ysplit, double work) {
+    const bool t128 = t == HeadPlan::TILE128;
+    GC_LAUNCH_TIMED("head_bilinear", work, bil_kernels[!t128][mode - 1], dim3((unsigned)cdiv(nrows, t128 ? 128 : 64), ysplit), dim3(256), 0, st, b);
+    return check_launch(!t128 ? "head_bil2" : ysplit > 1 ? "head_bil3 split" : "head_bil3");
+  };
+  Bil2 a = pass;   // unsplit: the slab is for the split launch alone
+  a.part = nullptr, a.part_rows = 0;
+  if (!plan.by_count(tile)) return launch(tile, a, rows, 1, flops);
+  // The count is on the device and the better launch shape depends on it; the host launches both, the one whose range does
+  // not hold the count leaves at once (a few microseconds of a millisecond-sized pass).  One 128-pair tile per compute unit
+  // and more (>= 32 768 pairs): the plain tiles.  Fewer (a DocRED batch of 32 documents: 14 k real pairs = 109 tiles on 256
+  // compute units, each streaming the whole 6.4 MB weight through its LDS): every tile split four ways over the b-chunks of
+  // the k sequence -- four times the workgroups, a quarter of the weight each -- plus a combine pass; without a partial-sum
+  // workspace, 64-pair tiles (4.14 -> 3.39 ms per step; the split: see DESIGN.md section 9).
+  Bil2 big = a, small = a;
+  big.sel_lo = HEAD_TILE128_MIN_ROWS, small.sel_hi = HEAD_TILE128_MIN_ROWS;
+  GC_TRY(launch(HeadPlan::TILE128, big, rows, 1, 0.5 * flops));   // (the host-side work counter: one of the two runs, the timer sees both)
+  if (!pass.part || pass.part_rows <= 0) return launch(HeadPlan::TILE64, small, rows, 1, 0.5 * flops);
+  small.part = pass.part, small.part_rows = pass.part_rows;
+  const long prow = rows < pass.part_rows ? rows : pass.part_rows;     // (counts below the threshold never exceed the slab)
+  GC_TRY(launch(HeadPlan::TILE128, small, prow, 4, 0.5 * flops));
+  hipLaunchKernelGGL(head_bil_combine_kernel, dim3((unsigned)cdiv(prow * 32, 256)), dim3(256), 0, st, small.part, small.part_rows, small.rows_dev,
+                     small.sel_lo, small.sel_hi, small.bias, small.crow, small.C, small.ncol, small.ldc);
+  return check_launch("head_bil_combine");
 }
 
 // ---- per-entity term + type table:  UT[b, n, :] = U[b, n, :] + Tt[type[b, n], :];  bsum = b_bilinear + b_linear -------
@@ -1006,20 +1032,13 @@ static const int* idx_cnt(const HeadBufs& w) { return w.idx; }
 static const int* idx_off(const HeadBufs& w) { return w.idx ? w.idx + 2 : nullptr; }
 static int* idx_prow(const HeadBufs& w, int B) { return w.idx ? w.idx + ((2 + (long)B + 1 + 3) & ~3L) : nullptr; }
 
-// option head_compact (default 1): ragged batches run the pair passes on the pairs that exist (compacted rows).  Served by the
-// register-generated kernels with the relation count just past 96 (the reference's 97; head_bil3 / head_dw); anything else keeps
-// the dense path, which computes every pair slot of the padded batch.
-static bool head_compacts(const int* n_valid, int R) {
-  return n_valid && option("head_compact", 1) != 0 && R > 64 && R <= 97;
-}
-
 int head_fwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int dis_plus, const float* const* feats, const long long* type,
              const long long* rel, const float* ner_emb, const float* dis_table, const int* n_valid, const float* flat, HeadBufs w,
-             float* logits, hipStream_t st) {
+             float* logits, const HeadPlan& plan, hipStream_t st) {
   const HeadLayout y = head_layout(Hd, nf, Pt, Pr, R);
   const long BN = (long)B * N, pairs = BN * N;
   GC_REQUIRE(pairs < (1L << 31) / 2 && R >= 1 && R <= HW, "head: %ld pairs / %d relations out of range", pairs, R);
-  const bool compact = head_compacts(n_valid, R);
+  const bool compact = plan.compact;
   GC_REQUIRE(!compact || w.idx, "head_fwd: n_valid given without the index workspace");
   for (int k = 0; k < nf; ++k) {  // U = sum_k feats_k W_k^T + b           (glove:354-355, the entity part of the dense layer)
     GemmArgs g = gemm_nt(feats[k], Hd, flat + y.Wd + (long)k * Hd, y.Fin, w.U, HW, (int)BN, HW, Hd).tagged("head_gemm");
@@ -1048,32 +1067,27 @@ int head_fwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int di
                        compact ? idx_cnt(w) : nullptr, compact ? idx_prow(w, B) : nullptr);
     GC_TRY(check_launch("head_feat_fwd"));
   }
+  // logits = [eh (x) et | eh | et] [W_b ; W_c]^T + (b_b + b_c)                                   (glove:358)
+  Bil2 a = bil_pass(1, w.EH, w.ET, flat + y.Wb, logits, pairs, R);
+  a.W2 = flat + y.Wc, a.bias = w.bsum;
   if (compact) {   // the pairs that exist, scattered into the padded tensor; every other slot is zero
     GC_REQUIRE(hipMemsetAsync(logits, 0, sizeof(float) * pairs * R, st) == hipSuccess, "head: memset failed");
-    return head_bil2(1, w.EH, w.ET, flat + y.Wb, flat + y.Wc, w.bsum, logits, pairs, HW, R, R, st, idx_cnt(w), idx_prow(w, B), w.partF,
-                     w.part_rows);
+    a.rows_dev = idx_cnt(w), a.crow = idx_prow(w, B), a.part = w.partF, a.part_rows = (int)w.part_rows;
   }
-  GemmArgs g;   // logits = [eh (x) et | eh | et] [W_b ; W_c]^T + (b_b + b_c)                     (glove:358)
-  g.A = w.EH, g.B = flat + y.Wb, g.C = logits, g.ldc = R;
-  g.M = (int)pairs, g.N = R, g.K = HW * HW + 2 * HW;
-  g.bias = w.bsum;
-  HeadOps o;
-  memset(&o, 0, sizeof(o));
-  o.P = w.EH, o.Q = w.ET, o.ldp = o.ldq = HW, o.KB = HW * HW, o.W2 = flat + y.Wc, o.ldw2 = 2 * HW, o.nmax = R, o.rows = (int)pairs;
-  if (head_bil3_ok(R) || !head_v1(pairs)) return head_bil2(1, w.EH, w.ET, flat + y.Wb, flat + y.Wc, w.bsum, logits, pairs, HW, R, R, st);
-  return head_gemm(1, g, o, st);
+  return head_pass(1, a, plan, st);
 }
 
 int head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int dis_plus, const float* const* feats, const long long* type,
              const long long* rel, const float* ner_emb, const float* dis_table, const int* n_valid, const float* flat, HeadBufs w,
-             const float* dlogits, float* const* dfeats, float* dner_emb, float* ddis_table, float* dflat, hipStream_t st) {
+             const float* dlogits, float* const* dfeats, float* dner_emb, float* ddis_table, float* dflat, const HeadPlan& plan,
+             hipStream_t st) {
   const HeadLayout y = head_layout(Hd, nf, Pt, Pr, R);
   const long BN = (long)B * N, pairs = BN * N;
   float* ws = w.scratch;
   const long wse = w.scratch_elems;
   // ragged batch: the rows of EH / ET (written by head_fwd), dout, dEH, dET are the pairs that exist, compacted (head_fwd built
   // the index); their count is on the device
-  const bool compact = head_compacts(n_valid, R);
+  const bool compact = plan.compact;
   GC_REQUIRE(!compact || w.idx, "head_bwd: n_valid given without the index workspace");
   const int* cnt = compact ? idx_cnt(w) : nullptr;
   const int* prow = compact ? idx_prow(w, B) : nullptr;
@@ -1095,35 +1109,21 @@ int head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int di
   // bias gradients: both biases see the column sums of dlogits
   GC_TRY(colsum(w.doutp, nullptr, dflat + y.bb, pairs, R, HW, 1, 0, 0, 0, 0, ws, st));
   GC_REQUIRE(hipMemcpyAsync(dflat + y.bc, dflat + y.bb, sizeof(float) * R, hipMemcpyDeviceToDevice, st) == hipSuccess, "head: copy failed");
-  HeadOps o;
-  memset(&o, 0, sizeof(o));
-  o.ldp = o.ldq = HW, o.KB = R * HW, o.nmax = R, o.rows = (int)pairs;
-  {  // d eh = sum_(r,b) dout[p,r] et[p,b] W_b[r,a,b]  + dout W_c[:, :128]
-    GemmArgs g;
-    g.A = w.doutp, g.B = flat + y.Wb, g.C = w.dEH, g.ldc = HW, g.M = (int)pairs, g.N = HW, g.K = R * HW;
-    o.P = w.doutp, o.Q = w.ET;
-    if (compact || !head_v1(pairs))
-      GC_TRY(head_bil2(2, w.doutp, w.ET, flat + y.Wb, nullptr, nullptr, w.dEH, pairs, R, HW, HW, st, cnt, nullptr, compact ? w.partB : nullptr, w.part_rows));
-    else GC_TRY(head_gemm(2, g, o, st));
-    if (!compact) GC_TRY(gemm(dE_c[0], st));   // (compacted: with d et's, below)
-  }
-  {  // d et = sum_(r,a) dout[p,r] eh[p,a] W_b[r,a,b]  + dout W_c[:, 128:]
-    GemmArgs g;
-    g.A = w.doutp, g.B = flat + y.Wb, g.C = w.dET, g.ldc = HW, g.M = (int)pairs, g.N = HW, g.K = R * HW;
-    o.P = w.doutp, o.Q = w.EH;
-    if (compact || !head_v1(pairs))
-      GC_TRY(head_bil2(3, w.doutp, w.EH, flat + y.Wb, nullptr, nullptr, w.dET, pairs, R, HW, HW, st, cnt, nullptr, compact ? w.partB : nullptr, w.part_rows));
-    else GC_TRY(head_gemm(3, g, o, st));
-    if (compact) GC_TRY(gemm_dyn_pair_xx(dE_c[0], dE_c[1], cnt, pairs, st));   // + dout W_c on both sides: one launch for the two halves
-    else GC_TRY(gemm(dE_c[1], st));
-  }
-  {  // d W_b[r, (a, b)] = sum_p dout[p, r] eh[p, a] et[p, b]
-    GemmArgs g;
-    g.A = w.doutp, g.lda = HW, g.B = w.EH, g.C = dflat + y.Wb, g.ldc = HW * HW, g.M = R, g.N = HW * HW, g.K = (int)pairs;
-    g.ws = ws, g.ws_elems = wse;
-    o.P = w.EH, o.Q = w.ET, o.KB = 0;
-    const bool dw3 = option("head_dw3", 1) != 0;
-    if (compact || (dw3 && R > 64 && R <= 97 && !head_v1(pairs))) {  // all R rows per workgroup, row 96 on the vector ALU (head_dw_kernel)
+  auto d_e = [&](int mode, const float* Q, float* C) {   // the bilinear part of d eh (mode 2, Q = et) / d et (mode 3, Q = eh)
+    Bil2 a = bil_pass(mode, w.doutp, Q, flat + y.Wb, C, pairs, R);
+    if (compact) a.rows_dev = cnt, a.part = w.partB, a.part_rows = (int)w.part_rows;   // (dEH / dET rows are compacted like the operands)
+    return head_pass(mode, a, plan, st);
+  };
+  // d eh = sum_(r,b) dout[p,r] et[p,b] W_b[r,a,b]  + dout W_c[:, :128]
+  GC_TRY(d_e(2, w.ET, w.dEH));
+  if (!compact) GC_TRY(gemm(dE_c[0], st));   // (compacted: with d et's, below)
+  // d et = sum_(r,a) dout[p,r] eh[p,a] W_b[r,a,b]  + dout W_c[:, 128:]
+  GC_TRY(d_e(3, w.EH, w.dET));
+  if (compact) GC_TRY(gemm_dyn_pair_xx(dE_c[0], dE_c[1], cnt, pairs, st));   // + dout W_c on both sides: one launch for the two halves
+  else GC_TRY(gemm(dE_c[1], st));
+  {  // d W_b[r, (a, b)] = sum_p dout[p, r] eh[p, a] et[p, b]: dout^T against the generated [pairs, 16384] operand
+    GemmArgs g = gemm_tn(w.doutp, HW, w.EH, HW, dflat + y.Wb, HW * HW, R, HW * HW, (int)pairs).split_ws(ws, wse);
+    if (plan.dw == HeadPlan::DW_ROWS) {
       const long ksteps = cdiv(pairs, 32);
       int splits = 1;
       while (splits < 16 && (long)HW * splits < 2048 && ksteps / (splits * 2) >= 64 && (long)(splits * 2) * R * HW * HW <= wse) splits *= 2;
@@ -1138,7 +1138,7 @@ int head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int di
         GC_TRY(splitk_reduce(g, st));
       }
     } else {
-      GC_TRY(head_gemm(4, g, o, st));
+      GC_TRY(head_gemm(4, {g, head_ops(w.EH, w.ET, 0, pairs, R)}, st));
     }
   }
   // d W_c = dout^T [eh | et]    (computed 128 rows deep into a workspace, the R real rows copied out)
@@ -1249,6 +1249,17 @@ int gcgcn_head_sizes(int B, int N, int R, int ND, int64_t* out3) {
   return 0;
 }
 
+// The kernels a head call of this shape gets under the current options, by the very plan function gcgcn_head_fwd / _bwd call:
+// out[0..5] = compact, forward pass, d eh / d et passes (0 first-generation GEMM, 1 64-pair tile, 2 128-pair tile), d W_b (0 GEMM,
+// 1 all rows per workgroup), then whether the forward / the d e passes launch both shapes for the device-side count.  Exposed for
+// tests (no GPU needed).
+int gcgcn_debug_head_plan(int B, int N, int R, int ragged, int32_t* out) {
+  GC_REQUIRE(B > 0 && N > 0 && (long)B * N * N < (1L << 31) / 2 && R >= 1 && R <= HW && out, "debug_head_plan: bad arguments");
+  const HeadPlan p = head_plan((long)B * N * N, R, ragged != 0);
+  out[0] = p.compact, out[1] = p.fwd, out[2] = p.bwd_e, out[3] = p.dw, out[4] = p.by_count(p.fwd), out[5] = p.by_count(p.bwd_e);
+  return 0;
+}
+
 int gcgcn_head_fwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int dis_plus, const float* const* feats,
                    const int64_t* node_type, const int64_t* node_relative_pos, const float* ner_emb, const float* dis_table,
                    const int32_t* n_valid, const float* flat, float* fbuf, int32_t* ibuf, float* logits, void* stream) {
@@ -1259,7 +1270,7 @@ int gcgcn_head_fwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, 
   HeadBufs w = head_bind(fbuf, nullptr, B, N, R, ND, nullptr, nullptr);
   w.idx = ibuf;
   return head_fwd(B, N, Hd, nf, Pt, Pr, R, ND, dis_plus, feats, (const long long*)node_type, (const long long*)node_relative_pos, ner_emb,
-                  dis_table, n_valid, flat, w, logits, (hipStream_t)stream);
+                  dis_table, n_valid, flat, w, logits, head_plan((long)B * N * N, R, n_valid != nullptr), (hipStream_t)stream);
 }
 
 int gcgcn_head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int dis_plus, const float* const* feats,
@@ -1274,7 +1285,8 @@ int gcgcn_head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, 
   HeadBufs w = head_bind(fbuf, bbuf, B, N, R, ND, nullptr, nullptr);
   w.idx = ibuf;
   return head_bwd(B, N, Hd, nf, Pt, Pr, R, ND, dis_plus, feats, (const long long*)node_type, (const long long*)node_relative_pos, ner_emb,
-                  dis_table, n_valid, flat, w, dlogits, dfeats, dner_emb, ddis_table, dflat, (hipStream_t)stream);
+                  dis_table, n_valid, flat, w, dlogits, dfeats, dner_emb, ddis_table, dflat, head_plan((long)B * N * N, R, n_valid != nullptr),
+                  (hipStream_t)stream);
 }
 
 }  // extern "C"

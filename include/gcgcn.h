@@ -39,7 +39,8 @@ const char* gcgcn_last_error(void); /* message of the last failing call on this 
  * chain kernels, 0 = one batched launch per product.  "mha_core": 1 (default) = graphs of N <= 64 entities take the
  * one-workgroup-per-(doc, head) attention kernels, 0 = batched GEMM + row softmax for every N.  Results are identical
  * up to fp32 summation order.  "head_v1" (-1 = by problem size), "head_bil3", "head_bil3_bwd", "head_dw3",
- * "head_compact", "chain_t", "chain_big" and "split_widen" select kernel generations; "group_dump" (0 = off) prints what
+ * "head_compact", "chain_t", "chain_big" and "split_widen" select kernel generations (the five head options take effect in
+ * csrc/head.hip head_plan and nowhere else: gcgcn_debug_head_plan shows the result); "group_dump" (0 = off) prints what
  * every GEMM launch is made of on stderr.  Each name also reads the environment variable GCGCN_<NAME> once when nobody set
  * it (GCGCN_CHAIN=0, GCGCN_HEAD_V1=1, ...: DESIGN.md section 6 lists them).  Any other name fails. */
 int gcgcn_set_option(const char* name, int value);
@@ -369,6 +370,14 @@ int gcgcn_debug_spread(int64_t n_tiles, int64_t n_others, int64_t cohort, int64_
  * passenger of the chain launch).  Host-only. */
 int gcgcn_debug_chain_plan(int bwd, int B, int N, int D, int L, int H, int ragged, int ride, int hook, int scratch,
                            int misalign, int32_t* out);
+
+/* ---- test hook: which kernels a gcgcn_head_fwd / gcgcn_head_bwd call of this shape gets ------------------------------
+ * Evaluates the plan function the two entry points call (csrc/head.hip head_plan) under the current options.  ragged: n_valid
+ * given.  out[6] = compact (the pair passes run on the pairs that exist), the forward pass and the d eh / d et passes (0
+ * head_gemm_kernel, 1 head_bil2_kernel: 64-pair tiles, 2 head_bil3_kernel: 128-pair tiles), d W_b (0 head_gemm_kernel<4>, 1
+ * head_dw_kernel), then for the forward and the d eh / d et passes whether both launch shapes are issued and the device-side
+ * pair count selects one.  Host-only. */
+int gcgcn_debug_head_plan(int B, int N, int R, int ragged, int32_t* out);
 
 /* ---- raw batched GEMM (exposed for unit tests and benchmarks of the MFMA kernel) ----------- */
 /* C[z] = alpha * opA(A[z]) opB(B[z]);  a_kc: A stored [M][K] else [K][M];  b_kc: B stored [N][K]

@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture(params=["by_size", "gen1", "gen2"])
 def head_generation(request):
-    """The outer-product passes exist in two generations chosen by problem size (head.hip head_v1: the second one only from
+    """The outer-product passes exist in two generations chosen by problem size (head.hip head_plan: the second one only from
     32 641 pairs up).  Every parity test runs under the size rule AND with each generation forced, so the kernels the
     benchmarks time (head_bil3_kernel<1..3>, head_dw_kernel, head_bil2_kernel) are the kernels the fixtures check."""
     _lib.call("gcgcn_set_option", b"head_v1", {"by_size": -1, "gen1": 1, "gen2": 0}[request.param])

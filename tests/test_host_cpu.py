@@ -499,3 +499,124 @@ def test_chain_plan_is_the_decision_the_scattered_predicates_made():
     assert len(got) == len(want) == len(CHAIN_PLAN_SHAPES) * len(CHAIN_PLAN_VARIANTS)
     wrong = [f"want {w}\n got {g}" for g, w in zip(got, want) if g != w]
     assert not wrong, "\n".join(wrong)
+
+
+# (B, N) of 1 000 pairs, and of 32 640 / 32 641: either side of the size rule (a 128-pair tile per compute unit: 256 tiles)
+HEAD_PLAN_SHAPES = [(10, 10), (510, 8), (32641, 1)]
+HEAD_PLAN_R = [5, 64, 65, 97, 98, 128]
+HEAD_PLAN_OPTIONS = ["head_v1", "head_bil3", "head_bil3_bwd", "head_dw3", "head_compact"]
+# a plan as four characters: compacted rows (c) or not (.); the forward pass, then the d eh / d et passes: g first-generation GEMM,
+# s 64-pair tiles, b 128-pair tiles, B 128-pair tiles in both launch shapes (the device-side pair count selects one); d W_b: g GEMM,
+# r all rows per workgroup
+HEAD_PLAN_LEGEND = {"a": ".bbg", "b": ".bbr", "c": ".bgg", "d": ".bsg", "e": ".bsr", "f": ".ggg", "g": ".sbg", "h": ".sbr", "i": ".ssg",
+                    "j": ".ssr", "k": "cBBr", "l": "cBsr", "m": "csBr", "n": "cssr"}
+
+
+def head_plan_table(plan, set_option):
+    """One line per setting of the five head options (head_v1 in -1, 0, 1; the others 0, 1): a group per shape, in it one plan per
+    R and dense / ragged (ragged varying fastest), as the four characters HEAD_PLAN_LEGEND explains.
+    plan(B, N, R, ragged) -> six ints."""
+    import itertools
+    lines = []
+    try:
+        for values in itertools.product((-1, 0, 1), (0, 1), (0, 1), (0, 1), (0, 1)):
+            for name, v in zip(HEAD_PLAN_OPTIONS, values):
+                set_option(name, v)
+            groups = []
+            for B, N in HEAD_PLAN_SHAPES:
+                codes = []
+                for R in HEAD_PLAN_R:
+                    for ragged in (0, 1):
+                        compact, fwd, bwd_e, dw, by_f, by_b = plan(B, N, R, ragged)
+                        codes.append(".c"[compact] + ("GSB" if by_f else "gsb")[fwd] + ("GSB" if by_b else "gsb")[bwd_e] + "gr"[dw])
+                groups.append(codes)
+            lines.append((values, groups))
+    finally:
+        for name in HEAD_PLAN_OPTIONS:
+            set_option(name, OPTION_DEFAULTS[name])
+    return lines
+
+
+# Recorded from the PARENT of the commit that introduced head_plan, not from the code under test: in a scratch copy of the parent a
+# throw-away function evaluated the parent's own predicates (head_compacts, head_bil3_ok, head_v1, the tile choice and the
+# both-shapes test of head_bil2, the head_dw3 condition) in the order head_fwd, head_bwd and head_bil2 evaluated them, and
+# head_plan_table printed this with each distinct plan given a letter (HEAD_PLAN_LEGEND).  1 728 plans: a line per option setting
+# (head_v1, head_bil3, head_bil3_bwd, head_dw3, head_compact), a group per shape (1 000, 32 640, 32 641 pairs).
+HEAD_PLAN_EXPECTED = """
+-1  0  0  0  0 : ffffffffffff ffffffffffff iiiiiiiiiiii
+-1  0  0  0  1 : fffffnfnffff fffffnfnffff iiiiininiiii
+-1  0  0  1  0 : ffffffffffff ffffffffffff iiiijjjjiiii
+-1  0  0  1  1 : fffffnfnffff fffffnfnffff iiiijnjniiii
+-1  0  1  0  0 : ffffffffffff ffffffffffff gggggggggggg
+-1  0  1  0  1 : fffffmfmffff fffffmfmffff gggggmgmgggg
+-1  0  1  1  0 : ffffffffffff ffffffffffff gggghhhhgggg
+-1  0  1  1  1 : fffffmfmffff fffffmfmffff gggghmhmgggg
+-1  1  0  0  0 : ffffccccffff ffffccccffff iiiiddddiiii
+-1  1  0  0  1 : ffffclclffff ffffclclffff iiiidldliiii
+-1  1  0  1  0 : ffffccccffff ffffccccffff iiiieeeeiiii
+-1  1  0  1  1 : ffffclclffff ffffclclffff iiiieleliiii
+-1  1  1  0  0 : ffffccccffff ffffccccffff ggggaaaagggg
+-1  1  1  0  1 : ffffckckffff ffffckckffff ggggakakgggg
+-1  1  1  1  0 : ffffccccffff ffffccccffff ggggbbbbgggg
+-1  1  1  1  1 : ffffckckffff ffffckckffff ggggbkbkgggg
+ 0  0  0  0  0 : iiiiiiiiiiii iiiiiiiiiiii iiiiiiiiiiii
+ 0  0  0  0  1 : iiiiininiiii iiiiininiiii iiiiininiiii
+ 0  0  0  1  0 : iiiijjjjiiii iiiijjjjiiii iiiijjjjiiii
+ 0  0  0  1  1 : iiiijnjniiii iiiijnjniiii iiiijnjniiii
+ 0  0  1  0  0 : gggggggggggg gggggggggggg gggggggggggg
+ 0  0  1  0  1 : gggggmgmgggg gggggmgmgggg gggggmgmgggg
+ 0  0  1  1  0 : gggghhhhgggg gggghhhhgggg gggghhhhgggg
+ 0  0  1  1  1 : gggghmhmgggg gggghmhmgggg gggghmhmgggg
+ 0  1  0  0  0 : iiiiddddiiii iiiiddddiiii iiiiddddiiii
+ 0  1  0  0  1 : iiiidldliiii iiiidldliiii iiiidldliiii
+ 0  1  0  1  0 : iiiieeeeiiii iiiieeeeiiii iiiieeeeiiii
+ 0  1  0  1  1 : iiiieleliiii iiiieleliiii iiiieleliiii
+ 0  1  1  0  0 : ggggaaaagggg ggggaaaagggg ggggaaaagggg
+ 0  1  1  0  1 : ggggakakgggg ggggakakgggg ggggakakgggg
+ 0  1  1  1  0 : ggggbbbbgggg ggggbbbbgggg ggggbbbbgggg
+ 0  1  1  1  1 : ggggbkbkgggg ggggbkbkgggg ggggbkbkgggg
+ 1  0  0  0  0 : ffffffffffff ffffffffffff ffffffffffff
+ 1  0  0  0  1 : fffffnfnffff fffffnfnffff fffffnfnffff
+ 1  0  0  1  0 : ffffffffffff ffffffffffff ffffffffffff
+ 1  0  0  1  1 : fffffnfnffff fffffnfnffff fffffnfnffff
+ 1  0  1  0  0 : ffffffffffff ffffffffffff ffffffffffff
+ 1  0  1  0  1 : fffffmfmffff fffffmfmffff fffffmfmffff
+ 1  0  1  1  0 : ffffffffffff ffffffffffff ffffffffffff
+ 1  0  1  1  1 : fffffmfmffff fffffmfmffff fffffmfmffff
+ 1  1  0  0  0 : ffffccccffff ffffccccffff ffffccccffff
+ 1  1  0  0  1 : ffffclclffff ffffclclffff ffffclclffff
+ 1  1  0  1  0 : ffffccccffff ffffccccffff ffffccccffff
+ 1  1  0  1  1 : ffffclclffff ffffclclffff ffffclclffff
+ 1  1  1  0  0 : ffffccccffff ffffccccffff ffffccccffff
+ 1  1  1  0  1 : ffffckckffff ffffckckffff ffffckckffff
+ 1  1  1  1  0 : ffffccccffff ffffccccffff ffffccccffff
+ 1  1  1  1  1 : ffffckckffff ffffckckffff ffffckckffff
+"""
+
+
+def test_head_plan_is_the_decision_the_scattered_predicates_made():
+    """gcgcn_debug_head_plan (the plan function gcgcn_head_fwd / _bwd call) gives, for every shape and every setting of the five head
+    options, the kernels the code before it chose.  No tolerance, no row left out."""
+    import ctypes
+    import numpy as np
+
+    def plan(*args):
+        out = np.full(6, -1, np.int32)
+        _lib.call("gcgcn_debug_head_plan", *args, out.ctypes.data_as(ctypes.c_void_p))
+        return [int(v) for v in out]
+
+    got = head_plan_table(plan, lambda name, v: _lib.call("gcgcn_set_option", name.encode(), v))
+    want = HEAD_PLAN_EXPECTED.strip("\n").split("\n")
+    assert len(got) == len(want) == 48
+    rows, wrong = 0, []
+    for (values, groups), line in zip(got, want):
+        label, letters = line.split(" : ")
+        assert [int(v) for v in label.split()] == list(values)
+        for (B, N), codes, group in zip(HEAD_PLAN_SHAPES, groups, letters.split(" ")):
+            assert len(codes) == len(group) == 2 * len(HEAD_PLAN_R)
+            for k, (code, letter) in enumerate(zip(codes, group)):
+                rows += 1
+                if code != HEAD_PLAN_LEGEND[letter]:
+                    wrong.append(f"options {values} B {B} N {N} R {HEAD_PLAN_R[k // 2]} ragged {k % 2}: want {HEAD_PLAN_LEGEND[letter]} got {code}")
+    assert rows == 1728
+    assert not wrong, "\n".join(wrong[:40])
