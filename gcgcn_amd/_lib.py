@@ -76,6 +76,10 @@ SIGNATURES = {
     "gcgcn_graphconv_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "gcgcn_pair_bce_fwd": (I, [I, I, I, P, P, P, P, P, P]),
     "gcgcn_pair_bce_bwd": (I, [I, I, I, P, P, P, P, P, P]),
+    "gcgcn_eval_ws_bytes": (L, [L, L]),
+    "gcgcn_eval_scan": (I, [I, I, I, P, P, P, P, P, P, L, P, P]),
+    "gcgcn_eval_rank": (I, [P, L, P, L, P, P]),
+    "gcgcn_eval_curve": (I, [P, L, L, P, ctypes.c_double, P, P, P, P, P, L, P]),
     "gcgcn_producer_layout": (I, [I, I, P]),
     "gcgcn_producer_count": (I, [I, I, I, I, P, P, P, P]),
     "gcgcn_producer_sizes": (I, [I, I, I, I, I, I, I, L, L, P]),

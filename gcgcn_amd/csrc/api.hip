@@ -832,6 +832,42 @@ int gcgcn_debug_chain_plan(int bwd, int B, int N, int D, int L, int H, int ragge
   return 0;
 }
 
+// ---- trainer evaluation (eval.hip) ------------------------------------------------------------------------------------
+static const int64_t kEvalMaxRecords = 0xffffffffLL;  // a record's ordinal has 32 bits
+
+int64_t gcgcn_eval_ws_bytes(int64_t n_records, int64_t n_keep) {
+  if (n_records < 0 || n_keep < 0 || n_records > kEvalMaxRecords) {
+    set_error("eval: %lld records do not fit the 32-bit ordinal of a record (at most %lld)", (long long)n_records,
+              (long long)kEvalMaxRecords);
+    return -1;
+  }
+  return eval_ws_bytes(n_records, n_keep < n_records ? n_keep : n_records);
+}
+
+int gcgcn_eval_scan(int B, int N, int R, const float* logits, const float* labels, const uint8_t* in_train, const int32_t* n_valid,
+                    const int64_t* doc_base, uint64_t* records, int64_t capacity, int64_t* counters, void* stream) {
+  GC_REQUIRE(B > 0 && N > 0 && R > 1 && (long)B * N <= 0x7fffffffL && (long)N * R <= 0x7fffffffL,
+             "eval_scan: bad shape B=%d N=%d R=%d", B, N, R);
+  GC_REQUIRE(logits && labels && doc_base && records && counters, "eval_scan: null pointer");
+  GC_REQUIRE(capacity > 0 && capacity <= kEvalMaxRecords, "eval_scan: capacity %lld outside (0, %lld]: a record's ordinal has 32 bits",
+             (long long)capacity, (long long)kEvalMaxRecords);
+  return eval_scan(logits, labels, in_train, n_valid, doc_base, records, capacity, counters, B, N, R, (hipStream_t)stream);
+}
+
+int gcgcn_eval_rank(const uint64_t* records, int64_t n, void* ws, int64_t ws_bytes, int64_t* sorted_off, void* stream) {
+  GC_REQUIRE(n > 0 && n <= kEvalMaxRecords, "eval_rank: %lld records outside (0, %lld]", (long long)n, (long long)kEvalMaxRecords);
+  GC_REQUIRE(records && ws && sorted_off, "eval_rank: null pointer");
+  return eval_rank(records, n, ws, ws_bytes, sorted_off, (hipStream_t)stream);
+}
+
+int gcgcn_eval_curve(const uint64_t* ranked, int64_t m, int64_t n_records, const int64_t* counters, double input_theta,
+                     float* pr_x, float* pr_y, float* ign_pr_y, double* result, void* ws, int64_t ws_bytes, void* stream) {
+  GC_REQUIRE(m > 0 && m <= n_records && n_records <= kEvalMaxRecords, "eval_curve: bad sizes m=%lld n_records=%lld", (long long)m,
+             (long long)n_records);
+  GC_REQUIRE(ranked && counters && pr_x && pr_y && result && ws, "eval_curve: null pointer");
+  return eval_curve(ranked, m, counters, input_theta, pr_x, pr_y, ign_pr_y, result, ws, ws_bytes, n_records, (hipStream_t)stream);
+}
+
 int gcgcn_gemm(int M, int N, int K, const float* A, int64_t lda, int a_kc, const float* B, int64_t ldb, int b_kc,
                float* C, int64_t ldc, int batch, int64_t sA, int64_t sB, int64_t sC, float alpha, const float* bias,
                int relu, int accumulate, int tile, int splits, float* ws, int64_t ws_elems, void* stream) {

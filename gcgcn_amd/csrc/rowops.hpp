@@ -64,4 +64,12 @@ int pair_bce_fwd(const float* logits, const float* labels, const int* n_valid, f
 int pair_bce_bwd(const float* logits, const float* labels, const int* n_valid, const float* dloss, float* dlogits, int B, int N,
                  int R, hipStream_t st);
 
+// eval.hip: the trainer's evaluation (Config.test): record scan, stable radix ranking, PR curve / F1 / AUC
+int64_t eval_ws_bytes(int64_t n_records, int64_t n_keep);
+int eval_scan(const float* logits, const float* labels, const uint8_t* in_train, const int* n_valid, const int64_t* doc_base,
+              uint64_t* rec, int64_t capacity, int64_t* counters, int B, int N, int R, hipStream_t st);
+int eval_rank(const uint64_t* rec, int64_t n, void* ws, int64_t ws_bytes, int64_t* sorted_off, hipStream_t st);
+int eval_curve(const uint64_t* keys, int64_t m, const int64_t* counters, double input_theta, float* pr_x, float* pr_y,
+               float* ign_pr_y, double* res, void* ws, int64_t ws_bytes, int64_t n_records, hipStream_t st);
+
 }  // namespace gc

@@ -251,6 +251,41 @@ int gcgcn_pair_bce_fwd(int B, int N, int R, const float* logits, const float* la
 int gcgcn_pair_bce_bwd(int B, int N, int R, const float* logits, const float* labels, const int32_t* n_valid,
                        const float* dloss, float* dlogits, void* stream);
 
+/* ---- trainer evaluation  config/Config.py:432-561 (test), config/Config_bert.py:488-656 (ignore-train-facts curve) ---------
+ * The reference copies every document's probabilities to the host, appends one Python tuple per (head, tail, relation != NA),
+ * sorts the list by score, and walks it for the precision/recall curve, F1, theta and AUC.  Here that is three device stages
+ * over 64-bit records; a record's ORDINAL is its position in the reference's append order.
+ *   record = (0x3fffffff - bits(p)) << 34 | ordinal << 2 | (label != 0) << 1 | flag      (ascending = the ranking)
+ * with p = 1 / (1 + expf(-logit)) in fp32 and flag the pair's sticky in-train flag: the OR over 1 <= k' <= k of
+ * label[k'] && in_train[k'] (Config_bert.py:545-562).
+ *
+ * Workspace bytes of the rank and curve stages for n_records records of which n_keep are kept.  An ordinal has 32 bits: more
+ * than 2^32 - 1 records (or a negative count) returns -1 with a message in the last-error buffer; nothing ever wraps. */
+int64_t gcgcn_eval_ws_bytes(int64_t n_records, int64_t n_keep);
+/* One workgroup per (document, head entity) row of logits / labels [B,N,N,R] (fp32; in_train uint8 [B,N,N,R] or NULL).
+ * Only the first n_valid[b] (NULL: N) entities form pairs.  Pair (i, j != i) of document b writes its R - 1 records at
+ * doc_base[b] + ((i (n - 1) + j') (R - 1)) + (k - 1), j' = j with the diagonal skipped; doc_base (device int64[B]) is the
+ * caller's running exclusive prefix of n (n - 1) (R - 1).  records has room for `capacity` (<= 2^32 - 1) records.
+ * counters (device int64[8], ADDED to): top1_acc, na_recall, na_correct, total_recall, total_correct, have_label as
+ * Config.py:487-505 (argmax = first maximum of the probabilities), then the number of pairs holding a NaN probability and the
+ * number of pairs with a record at or past `capacity` (such records are not written). */
+int gcgcn_eval_scan(int B, int N, int R, const float* logits, const float* labels, const uint8_t* in_train, const int32_t* n_valid,
+                    const int64_t* doc_base, uint64_t* records, int64_t capacity, int64_t* counters, void* stream);
+/* Stable least-significant-digit radix sort of records[0, n) (which must be in ordinal order, as the scan leaves them) by
+ * score, in this library's own kernels; digits that all records share are skipped.  records is not modified; the ranked copy
+ * is left in ws at byte offset *sorted_off (host).  Reads one 4 KiB histogram back: SYNCHRONISES the stream. */
+int gcgcn_eval_rank(const uint64_t* records, int64_t n, void* ws, int64_t ws_bytes, int64_t* sorted_off, void* stream);
+/* Curve over ranked[0, m), m <= n_records, with total_recall = counters[3] (1 when 0):
+ *   pr_y[i] = fp32(correct_i / (i + 1)), pr_x[i] = fp32(correct_i / total_recall)    (fp64 quotients),
+ *   ign_pr_y[i] (NULL: not stored) = 0 if correct_in_train_i == correct_i, else
+ *                 fp32((correct_i - correct_in_train_i) / (i + 1 - correct_in_train_i)),
+ *   f1_arr = 2 pr_x pr_y / (pr_x + pr_y + 1e-20) in fp32; trapezoids in fp64, summed in index order.
+ * result (device double[16]): f1, f1_pos (first argmax), theta = score at f1_pos, p = pr_x[f1_pos], r = pr_y[f1_pos] (named
+ * as the reference names them), w (f1_pos when input_theta == -1, else the last i with score_i > input_theta, else 0),
+ * f1_arr[w], auc, ign_f1, ign_auc, total_recall as used.  ws / ws_bytes / n_records as given to the rank stage. */
+int gcgcn_eval_curve(const uint64_t* ranked, int64_t m, int64_t n_records, const int64_t* counters, double input_theta,
+                     float* pr_x, float* pr_y, float* ign_pr_y, double* result, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- edge-feature producer  GCGCN_glove.py:171-214 and the call sequence :300-330 ------------ */
 /* Builds E = context_sent_att[B,N,N,Hd] -- the edge tensor the blocks above consume -- from the token states:
  * WordAttention (glove:171-190) on the head- and tail-side distance embeddings, Linear(2Hd, Hd) (linear_word_att),
