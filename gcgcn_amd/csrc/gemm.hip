@@ -222,47 +222,18 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmArgs g) {
   reduce4(g, blockIdx.y, (long)blockIdx.x * 256 + threadIdx.x);
 }
 
-int splitk_reduce(const GemmArgs& g, hipStream_t st) {
+int splitk_reduce(const GemmArgs& g, hipStream_t st, const char* what) {
   ProfScope ps("gemm_splitk_reduce", st);
   dim3 rgrid(cdiv((long)g.M * g.N / 4, 256), g.batch1 * g.batch2);
   hipLaunchKernelGGL(splitk_reduce_kernel, rgrid, dim3(256), 0, st, g);
-  return check_launch("gemm_splitk_reduce");
+  return check_launch(what);
 }
 
 static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-
-template <int TM, int TN, bool ALIGNED>
-static int launch(const GemmArgs& g, hipStream_t stream) {
-  dim3 grid(cdiv(g.N, 64 * TN), cdiv(g.M, 64 * TM), g.batch1 * g.batch2 * g.splits), block(256);
-  const double flops = 2.0 * g.M * g.N * g.K * g.batch1 * g.batch2;
-  if constexpr (ALIGNED) {
-    if (g.rb) {  // ragged batch: the instantiation with the row-block paths (prepare() kept rb only where they apply)
-      if (g.a_kc && !g.b_kc) GC_LAUNCH_TIMED(g.tag, flops, (gemm_kernel<TM, TN, true, false, true, true>), grid, block, 0, stream, g);
-      else if (g.a_kc && g.b_kc) GC_LAUNCH_TIMED(g.tag, flops, (gemm_kernel<TM, TN, true, true, true, true>), grid, block, 0, stream, g);
-      else GC_LAUNCH_TIMED(g.tag, flops, (gemm_kernel<TM, TN, false, false, true, true>), grid, block, 0, stream, g);
-      if (int e = check_launch("gemm")) return e;
-      if (g.splits > 1) {
-        ProfScope ps("gemm_splitk_reduce", stream);
-        dim3 rgrid(cdiv((long)g.M * g.N / 4, 256), g.batch1 * g.batch2);
-        hipLaunchKernelGGL(splitk_reduce_kernel, rgrid, dim3(256), 0, stream, g);
-        return check_launch("gemm_splitk_reduce");
-      }
-      return 0;
-    }
-  }
-  if (g.a_kc && !g.b_kc) GC_LAUNCH_TIMED(g.tag, flops, (gemm_kernel<TM, TN, true, false, ALIGNED>), grid, block, 0, stream, g);
-  else if (g.a_kc && g.b_kc) GC_LAUNCH_TIMED(g.tag, flops, (gemm_kernel<TM, TN, true, true, ALIGNED>), grid, block, 0, stream, g);
-  else if (!g.a_kc && !g.b_kc) GC_LAUNCH_TIMED(g.tag, flops, (gemm_kernel<TM, TN, false, false, ALIGNED>), grid, block, 0, stream, g);
-  else GC_LAUNCH_TIMED(g.tag, flops, (gemm_kernel<TM, TN, false, true, ALIGNED>), grid, block, 0, stream, g);
-  if (int e = check_launch("gemm")) return e;
-  if (g.splits > 1) {
-    ProfScope ps("gemm_splitk_reduce", stream);
-    dim3 rgrid(cdiv((long)g.M * g.N / 4, 256), g.batch1 * g.batch2);
-    hipLaunchKernelGGL(splitk_reduce_kernel, rgrid, dim3(256), 0, stream, g);
-    return check_launch("gemm_splitk_reduce");
-  }
-  return 0;
-}
+// 64 x 64 output tiles (batches included, splits not), tile-k-steps and flops of a problem
+static long tiles_of(const GemmArgs& g) { return (long)cdiv(g.M, 64) * cdiv(g.N, 64) * g.batch1 * g.batch2; }
+static long work_of(const GemmArgs& g) { return tiles_of(g) * cdiv(g.K, BK); }
+static double flops_of(const GemmArgs& g) { return 2.0 * g.M * g.N * g.K * g.batch1 * g.batch2; }
 
 // Split factor of a problem inside a launch whose 64x64 tiles carry `work` tile-k-steps in total: no
 // workgroup should run much longer than the average load of one of the 256 x 4 resident slots
@@ -277,67 +248,152 @@ static int pick_splits(int K, long work) {
   while (iters / splits > thr && splits < 16 && K % (splits * 2 * BK) == 0) splits *= 2;
   return splits;
 }
+// Split factor of a weight gradient whose K is a device-side count of at most `cap`: enough K slices to fill the chip with its few
+// output tiles; each slice >= 8 k-steps
+static int dyn_splits(long tiles, long cap) {
+  long want = (1024 + tiles - 1) / tiles, most = cap / (8 * BK);
+  if (most < 1) most = 1;
+  const long splits = want < most ? want : most;
+  return (int)(splits > 64 ? 64 : splits);
+}
+// the workspace takes `slabs` partial [M x N] images for the reduce's 16-byte loads
+static bool ws_holds(const GemmArgs& g, long slabs) { return g.ws && slabs * g.M * g.N <= g.ws_elems && g.N % 4 == 0 && aligned16(g.ws); }
 
-// Fill the launcher-owned fields (vec flags, tile, split factor).  Returns the chosen tile (1 or 2) or -1.
-static int prepare(GemmArgs& g, int tile, int splits, long group_work) {
-  if (!(g.A && g.B && g.C)) { set_error("gemm: null operand"); return -1; }
-  if (!(g.M >= 0 && g.N >= 0 && g.K >= 1 && g.batch1 >= 1 && g.batch2 >= 1)) { set_error("gemm: bad shape"); return -1; }
+// ---- what the launcher decides for one problem: here and nowhere else (gcgcn_debug_gemm_plan shows the result) ----------------
+enum GemmForm {    // who asks
+  GEMM_SINGLE,     // gemm(): the caller's split request, the problem's own work
+  GEMM_MEMBER,     // a problem of a gemm_group launch: split by the whole launch's work
+  GEMM_PARK,       // gemm_defer: unsplit
+  GEMM_DYN_M,      // gemm_dyn and the pairs: M, or K, is a device-side count of at most `cap`
+  GEMM_DYN_K
+};
+struct GemmPlan {
+  bool ok;         // false: the problem is refused (set_error has the reason)
+  bool interior;   // the unguarded tile body: 16-byte loads, whole tiles, whole k-steps
+  int splits, ksplit, widen;   // as written to GemmArgs
+  int rb_mode;     // the row-block list is kept (1 / 2), or the problem runs dense (0)
+  long tiles;      // tiles_of
+  bool reduce;     // a split-K reduce launch follows
+  bool zero_fill;  // device-side K, unsplit: gemm_dyn_zero_kernel defines C for a count of zero
+  int grid;        // device-side forms: the persistent workgroups that walk the tile list
+};
+// Checks the problem, fills the launcher-owned fields of g (vecA, vecB, splits, ksplit, widen; a device-side form's capped dimension)
+// and drops the row-block list where the problem runs dense.  `splits` counts for GEMM_SINGLE, `group_work` for GEMM_MEMBER, `cap` for
+// the device-side forms.
+static GemmPlan gemm_plan(GemmArgs& g, GemmForm form, int splits, long group_work, long cap) {
+  GemmPlan p = {};
+  const bool dyn = form == GEMM_DYN_M || form == GEMM_DYN_K;
+  const long nb = (long)g.batch1 * g.batch2;
+  if (dyn && nb != 1) { set_error("gemm_dyn: batched problems are not supported"); return p; }
+  if (dyn && cap == 0) cap = 1;
+  // the count's bound, rounded up to whole tiles, stands in for the dimension: what may run unguarded reads that far (gemm.hpp)
+  if (dyn) (form == GEMM_DYN_M ? g.M : g.K) = (int)((cap + 63) & ~63L);
+  if (!(g.A && g.B && g.C)) { set_error("gemm: null operand"); return p; }
+  if (!(g.M >= 0 && g.N >= 0 && g.K >= 1 && g.batch1 >= 1 && g.batch2 >= 1)) { set_error("gemm: bad shape"); return p; }
   {  // the epilogue addresses one (batch entry's) [M x ld] slice with 32-bit offsets
     long ldmax = g.ldc;
     if (g.add && g.ldadd > ldmax) ldmax = g.ldadd;
     if (g.C2 && g.ldc2 > ldmax) ldmax = g.ldc2;
     if (g.add2 && g.ldadd2 > ldmax) ldmax = g.ldadd2;
-    if ((long)g.M * ldmax >= (1L << 32)) { set_error("gemm: M * ld = %ld exceeds 32-bit epilogue offsets", (long)g.M * ldmax); return -1; }
+    if ((long)g.M * ldmax >= (1L << 32)) { set_error("gemm: M * ld = %ld exceeds 32-bit epilogue offsets", (long)g.M * ldmax); return p; }
   }
-  const long nb = (long)g.batch1 * g.batch2;
+  const bool widen_on = option("split_widen", 1) != 0;
   g.vecA = aligned16(g.A) && g.lda % 4 == 0 && g.sA1 % 4 == 0 && g.sA2 % 4 == 0;
   g.vecB = aligned16(g.B) && g.ldb % 4 == 0 && g.sB1 % 4 == 0 && g.sB2 % 4 == 0;
-  const long t64 = (long)cdiv(g.M, 64) * cdiv(g.N, 64) * nb;
-  (void)t64;
-  tile = 1;  // measured: 64x64 tiles beat both 128x128 bodies on every product of this path (dropped experiments)
+  p.tiles = tiles_of(g);
+  if (form != GEMM_SINGLE) splits = form == GEMM_MEMBER ? 0 : 1;   // parked tiles run their whole K in one workgroup; a device-side K is cut below
   if (splits == 0) {
-    splits = pick_splits(g.K, group_work > 0 ? group_work : t64 * cdiv(g.K, BK));
+    splits = pick_splits(g.K, form == GEMM_MEMBER ? group_work : work_of(g));
     // The host never reads n_valid: a long-K problem on the row blocks of a ragged batch that "fills the chip" by its dense tile
     // count (cfg 3's K = 3072 data gradients: 768 tiles, three per compute unit, unsplit) runs with fewer than half of them live,
     // one to a compute unit, at a lone workgroup's pace (336 live tiles of 96 k-tiles: 109 us).  Split it once here; what the launch
     // really finds is dealt with on the device (split_width cuts finer with the workgroups of the dead rows).  Counting every
     // row-block problem at half its dense work instead split the short ones too: cfg 2 ragged 78.0k -> 71.9k docs/s.
-    if (splits == 1 && g.rb && g.rb_mode == 1 && cdiv(g.K, BK) >= 48 && t64 <= 1024 && g.K % (2 * BK) == 0 && option("split_widen", 1)) splits = 2;
+    // (Applied before the row-block rule below has had its say: a problem that then runs dense -- a batched one, a small one -- stays
+    // split.  Looks like an accident and is left for a measured change.)
+    if (splits == 1 && g.rb && g.rb_mode == 1 && cdiv(g.K, BK) >= 48 && p.tiles <= 1024 && g.K % (2 * BK) == 0 && widen_on) splits = 2;
   }
-  if (splits > 1 && (!g.ws || (long)splits * nb * g.M * g.N > g.ws_elems || g.K % (splits * BK) != 0 || g.N % 4 != 0 ||
-                     (((uintptr_t)g.ws) & 15) != 0))
-    splits = 1;
+  if (splits > 1 && !(ws_holds(g, splits * nb) && g.K % (splits * BK) == 0)) splits = 1;
   g.splits = splits;
   g.ksplit = (splits > 1) ? g.K / splits : g.K;
+  // One predicate for every form: ksplit is K for an unsplit problem and a divisor of K whose multiple of BK divides K for a split
+  // one, and a device-side form's capped dimension is a multiple of 64 by now.
+  p.interior = g.vecA && g.vecB && g.M % 64 == 0 && g.N % 64 == 0 && g.ksplit % BK == 0;
   if (g.rb) {  // row blocks of a ragged batch: only what the gathering tile body serves, anything else runs dense (equally correct)
-    const bool interior = g.vecA && g.vecB && g.M % 64 == 0 && g.N % 64 == 0 && g.K % BK == 0 && g.ksplit % BK == 0 && g.rb_n;
-    const bool ok = interior && ((g.rb_mode == 1 && g.a_kc && nb == 1) || (g.rb_mode == 2 && !g.a_kc && !g.b_kc && g.K % 64 == 0 && g.K / 16 <= ROWBLK_LIST_MAX));
+    const bool served = p.interior && g.rb_n && ((g.rb_mode == 1 && g.a_kc && nb == 1) ||
+                                                  (g.rb_mode == 2 && !g.a_kc && !g.b_kc && g.K % 64 == 0 && g.K / 16 <= ROWBLK_LIST_MAX));
     // M-side: a launch that does not fill the chip anyway gains nothing from skipping tiles and pays the list's lookups in
     // its latency-bound prologue (128-tile output projection: 21 vs 16 us measured) -- dense below one tile per compute unit
-    // and slot (a problem inside a group launch shares the launch: group_work > 0 keeps it)
-    const bool small = g.rb_mode == 1 && group_work <= 0 && (long)cdiv(g.M, 64) * cdiv(g.N, 64) * splits <= 256;
-    if (!ok || small) g.rb = nullptr, g.rb_n = nullptr, g.rb_mode = 0, g.rb_zero = 0;
+    // and slot (a problem inside a group launch shares the launch and keeps the list)
+    const bool small = g.rb_mode == 1 && form != GEMM_MEMBER && (long)cdiv(g.M, 64) * cdiv(g.N, 64) * splits <= 256;
+    if (!served || small) g.rb = nullptr, g.rb_n = nullptr, g.rb_mode = 0, g.rb_zero = 0;
   }
   // a split row-block problem may cut K finer on the device (split_width): as far as the workspace holds the slabs
   g.widen = 1;
-  if (g.rb && g.rb_mode == 1 && g.splits > 1 && option("split_widen", 1))
+  if (g.rb && g.rb_mode == 1 && g.splits > 1 && widen_on)
     while (g.widen < 4 && (long)g.splits * 2 * g.widen * nb * g.M * g.N <= g.ws_elems) g.widen *= 2;
-  return tile;
+  if (form == GEMM_DYN_K) {  // the device cuts K by the count it finds (gemm_dyn_walk): any factor the workspace holds, ksplit stays K here
+    g.splits = dyn_splits(p.tiles, cap);
+    if (g.splits > 1 && !ws_holds(g, g.splits)) g.splits = 1;
+    p.zero_fill = g.splits == 1;
+  }
+  if (dyn) {  // at most one workgroup per resident slot
+    const long walk = form == GEMM_DYN_M ? (long)cdiv(cap, 64) * cdiv(g.N, 64) : p.tiles * g.splits;
+    p.grid = (int)(walk < 1024 ? (walk > 0 ? walk : 1) : 1024);
+  }
+  p.ok = true;
+  p.splits = g.splits, p.ksplit = g.ksplit, p.widen = g.widen;
+  p.rb_mode = g.rb ? g.rb_mode : 0;
+  p.reduce = g.splits > 1;
+  return p;
+}
+// The members of a group launch share one workspace, each split one taking the next slice: fewer device-side slabs where the widened
+// ones do not fit, unsplit where none do.  Returns whether the member stays split.
+static bool gemm_plan_slice(GemmArgs& g, long& ws_used) {
+  if (g.splits <= 1) return false;
+  const long slab = (long)g.splits * g.batch1 * g.batch2 * g.M * g.N;
+  while (g.widen > 1 && ws_used + slab * g.widen > g.ws_elems) g.widen /= 2;
+  if (ws_used + slab * g.widen > g.ws_elems) {  // no room left: this problem goes unsplit
+    g.splits = 1, g.ksplit = g.K, g.widen = 1;
+    return false;
+  }
+  g.ws = g.ws + ws_used;
+  ws_used += slab * g.widen;
+  return true;
+}
+
+// gemm_kernel by [dense][guarded][A stored K x M][b_kc], in the order the code object has always held them.  The row-block paths
+// exist for what gemm_plan keeps the list for: interior problems with A stored [M][K] (mode 1) or both operands stored [K][.] (mode 2).
+using GemmKernel = void (*)(const GemmArgs);
+static const GemmKernel gemm_kernels[2][2][2][2] = {
+    {{{gemm_kernel<1, 1, true, false, true, true>, gemm_kernel<1, 1, true, true, true, true>}, {gemm_kernel<1, 1, false, false, true, true>, nullptr}},
+     {{nullptr, nullptr}, {nullptr, nullptr}}},
+    {{{gemm_kernel<1, 1, true, false, true>, gemm_kernel<1, 1, true, true, true>}, {gemm_kernel<1, 1, false, false, true>, gemm_kernel<1, 1, false, true, true>}},
+     {{gemm_kernel<1, 1, true, false, false>, gemm_kernel<1, 1, true, true, false>}, {gemm_kernel<1, 1, false, false, false>, gemm_kernel<1, 1, false, true, false>}}}};
+
+static int launch(const GemmArgs& g, const GemmPlan& p, hipStream_t stream) {
+  const GemmKernel kernel = gemm_kernels[p.rb_mode == 0][!p.interior][!g.a_kc][g.b_kc != 0];
+  GC_REQUIRE(kernel && (p.rb_mode == 0 || (p.rb_mode == 1) == (g.a_kc != 0)), "gemm: no kernel for a_kc %d b_kc %d row-block mode %d %s", g.a_kc,
+             g.b_kc, p.rb_mode, p.interior ? "interior" : "guarded");
+  dim3 grid(cdiv(g.N, 64), cdiv(g.M, 64), g.batch1 * g.batch2 * g.splits), block(256);
+  GC_LAUNCH_TIMED(g.tag, flops_of(g), kernel, grid, block, 0, stream, g);
+  if (int e = check_launch("gemm")) return e;
+  return p.reduce ? splitk_reduce(g, stream) : 0;
 }
 
 int gemm(const GemmArgs& g_in, hipStream_t stream, int tile, int splits) {
   GemmArgs g = g_in;
   if (g.M == 0 || g.N == 0) return 0;
   GC_REQUIRE(tile == 0 || tile == 1, "gemm: tile %d (64 x 64 tiles are the only body; 128 x 128 bodies lost every A/B on this path)", tile);
-  if (prepare(g, 1, splits, 0) < 0) return 1;
+  const GemmPlan p = gemm_plan(g, GEMM_SINGLE, splits, 0, 0);
+  if (!p.ok) return 1;
   const long nb = (long)g.batch1 * g.batch2;
   GC_REQUIRE(nb * g.splits <= 65535, "gemm: batch %ld x splits %d exceeds grid.z", nb, g.splits);
   GC_REQUIRE(cdiv(g.M, 64) <= 65535, "gemm: M %d exceeds grid.y", g.M);
-  const bool al = g.vecA && g.vecB && g.M % 64 == 0 && g.N % 64 == 0 && g.ksplit % BK == 0;
   if (option("group_dump", 0))   // diagnosis (with the group launches' dump)
     fprintf(stderr, "gemm: %-12s M %5d N %5d K %5d batch %3ld splits %2d a_kc %d b_kc %d rb_mode %d %s\n", g.tag, g.M, g.N, g.K, nb, g.splits,
-            g.a_kc, g.b_kc, g.rb ? g.rb_mode : 0, al ? "interior" : "guarded");
-  return al ? launch<1, 1, true>(g, stream) : launch<1, 1, false>(g, stream);
+            g.a_kc, g.b_kc, p.rb_mode, p.interior ? "interior" : "guarded");
+  return launch(g, p, stream);
 }
 
 // Independent problems in one launch (plus at most one reduce launch).  Problems that are not interior
@@ -353,13 +409,32 @@ int gemm_group_mha_chunk(int dh) {
 }
 bool gemm_group_can_carry_mha(int dh) { return gemm_group_mha_chunk(dh) > 0; }
 
+// What rides in the trailing workgroups of a group launch (the host's reading of a ColRide; the kernels read ready_slices themselves)
+enum RideKind {
+  RIDE_NONE,
+  RIDE_COLSUM,   // stage 1 of a column sum here, stage 2 in the reduce launch (or with the caller: col_later)
+  RIDE_STAGE2,   // ready_slices > 0: the partials of an earlier launch are summed here
+  RIDE_HEADS     // ready_slices < 0: the sum over heads -- no partials, no second stage
+};
+static RideKind ride_kind(const ColRide* col) {
+  if (!col || col->C <= 0) return RIDE_NONE;
+  if (col->ready_slices != 0) return col->ready_slices < 0 ? RIDE_HEADS : RIDE_STAGE2;
+  return col->X && col->R > 0 ? RIDE_COLSUM : RIDE_NONE;
+}
+// the instantiation with the row-block paths if any problem of the launch walks row blocks
+template <class Kernel>
+static Kernel by_row_blocks(const GemmGroup& gg, Kernel with, Kernel without) {
+  for (int i = 0; i < gg.nprob; ++i)
+    if (gg.p[i].rb) return with;
+  return without;
+}
+
 int gemm_group(const GemmArgs* probs, int n, hipStream_t stream, const ColRide* col, bool* col_later, const MhaPass* mha) {
   if (col_later) *col_later = false;
   GemmGroup gg;
   gg.nprob = 0;
   long work = 0;  // tile-k-steps of the whole launch
-  for (int i = 0; i < n; ++i)
-    work += (long)cdiv(probs[i].M, 64) * cdiv(probs[i].N, 64) * probs[i].batch1 * probs[i].batch2 * cdiv(probs[i].K, BK);
+  for (int i = 0; i < n; ++i) work += work_of(probs[i]);
   int tiles = 0, reds = 0;
   double flops = 0;
   bool any_split = false;
@@ -383,9 +458,9 @@ int gemm_group(const GemmArgs* probs, int n, hipStream_t stream, const ColRide* 
     g = probs[order[oi]];
     groupable[oi] = false;
     if (g.M == 0 || g.N == 0) continue;
-    if (prepare(g, 1, 0, work) < 0) return 1;
-    const bool al = g.vecA && g.vecB && g.M % 64 == 0 && g.N % 64 == 0 && g.ksplit % BK == 0;
-    groupable[oi] = al && ng < GemmGroup::MAXP;
+    const GemmPlan p = gemm_plan(g, GEMM_MEMBER, 0, work, 0);
+    if (!p.ok) return 1;
+    groupable[oi] = p.interior && ng < GemmGroup::MAXP;
     if (groupable[oi]) ++ng;
   }
   // (Until round 5 a launch that overflowed the 1024 resident slots by <= 128 workgroups had its smallest problem peeled into a
@@ -401,27 +476,16 @@ int gemm_group(const GemmArgs* probs, int n, hipStream_t stream, const ColRide* 
   for (int oi = 0; oi < n; ++oi) {
     if (!groupable[oi]) continue;
     GemmArgs g = prep[oi];
-    const long nb = (long)g.batch1 * g.batch2;
-    const long own = (long)cdiv(g.M, 64) * cdiv(g.N, 64) * nb;
-    // the group shares one workspace: give each split problem its own slice
-    if (g.splits > 1) {
-      while (g.widen > 1 && ws_used + (long)g.splits * g.widen * nb * g.M * g.N > g.ws_elems) g.widen /= 2;
-      const long need = (long)g.splits * g.widen * nb * g.M * g.N;
-      if (ws_used + need > g.ws_elems) {  // no room left: this problem goes unsplit
-        g.splits = 1, g.ksplit = g.K, g.widen = 1;
-      } else {
-        g.ws = g.ws + ws_used;
-        ws_used += need, any_split = true;
-      }
-    }
+    if (gemm_plan_slice(g, ws_used)) any_split = true;
+    const int own = (int)(tiles_of(g) * g.splits);
     tiles = (tiles + 7) & ~7;
     gg.tile_begin[gg.nprob] = tiles;
-    gg.tile_count[gg.nprob] = (int)(own * g.splits);
-    gg.tile_first[gg.nprob] = 0, gg.tile_take[gg.nprob] = (int)(own * g.splits);
+    gg.tile_count[gg.nprob] = own;
+    gg.tile_first[gg.nprob] = 0, gg.tile_take[gg.nprob] = own;
     gg.red_begin[gg.nprob] = reds;
-    tiles += (int)(own * g.splits);
-    if (g.splits > 1) reds += (int)(nb * cdiv((long)g.M * g.N / 4, 256));
-    flops += 2.0 * g.M * g.N * g.K * nb;
+    tiles += own;
+    if (g.splits > 1) reds += g.batch1 * g.batch2 * cdiv((long)g.M * g.N / 4, 256);
+    flops += flops_of(g);
     gg.p[gg.nprob++] = g;
   }
   if (option("group_dump", 0)) {   // diagnosis: what each group launch is made of
@@ -432,44 +496,35 @@ int gemm_group(const GemmArgs* probs, int n, hipStream_t stream, const ColRide* 
               g.batch1 * g.batch2, g.splits, g.widen, g.a_kc, g.b_kc, g.rb ? g.rb_mode : 0, gg.tile_count[i]);
     }
   }
-  const bool ride3 = col && col->ready_slices < 0 && col->C > 0;   // head sum: no partials, no second stage
-  const bool ride2 = col && col->ready_slices > 0 && col->C > 0;
-  const bool ride = !ride2 && !ride3 && col && col->X && col->C > 0 && col->R > 0;
-  if (ride || ride2) GC_REQUIRE(col->out && col->part, "gemm_group: column ride without out / part");
-  if (ride3) GC_REQUIRE(col->X && col->out && col->R > 0 && col->ld > 0 && col->C == col->ld * col->ld, "gemm_group: bad head sum");
+  const RideKind ride = ride_kind(col);
+  if (ride == RIDE_COLSUM || ride == RIDE_STAGE2) GC_REQUIRE(col->out && col->part, "gemm_group: column ride without out / part");
+  if (ride == RIDE_HEADS) GC_REQUIRE(col->X && col->out && col->R > 0 && col->ld > 0 && col->C == col->ld * col->ld, "gemm_group: bad head sum");
   static_assert(sizeof(GemmGroup) + sizeof(MhaPass) + 32 <= 4096, "gemm_group_pass_kernel: kernel arguments exceed 4 KB");
   if (gg.nprob == 0 && mha && mha->count > 0)   // nothing to ride on: the pairs get their launch
     if (int e = mha_core_bwd(mha->Q, mha->P, mha->dA, mha->dQ, mha->count / mha->H, mha->N, mha->D, mha->H, mha->alpha, mha->drop, stream)) return e;
   if (gg.nprob == 0) {  // nothing to ride on
-    if (ride3) return mask_rows(nullptr, nullptr, 0, (int)col->ld, 1, nullptr, make_drop(nullptr, 0, 0.f), stream, col->X, col->out, (int)col->R);
-    if (ride2) return colsum(col->part, nullptr, col->out, col->ready_slices, col->C, col->C, 1, 0, 0, 0, 0, nullptr, stream);
-    return ride ? colsum(col->X, nullptr, col->out, col->R, col->C, col->ld, 1, 0, 0, 0, 0, col->part, stream) : 0;
+    if (ride == RIDE_HEADS) return mask_rows(nullptr, nullptr, 0, (int)col->ld, 1, nullptr, make_drop(nullptr, 0, 0.f), stream, col->X, col->out, (int)col->R);
+    if (ride == RIDE_STAGE2) return colsum(col->part, nullptr, col->out, col->ready_slices, col->C, col->C, 1, 0, 0, 0, 0, nullptr, stream);
+    return ride == RIDE_COLSUM ? colsum(col->X, nullptr, col->out, col->R, col->C, col->ld, 1, 0, 0, 0, 0, col->part, stream) : 0;
   }
   gg.tile_begin[gg.nprob] = tiles;
   gg.red_begin[gg.nprob] = reds;
-  int col1 = 0, col2 = 0;
-  if (ride) {
-    gg.col = *col;
-    col1 = cdiv(col->C, 64) * COL_RIDE_SLICES, col2 = cdiv(col->C, 256);
-  } else if (ride2 || ride3) {
-    gg.col = *col;
-    col1 = cdiv(col->C, 256);
-  }
-  bool any_rb = false;
-  for (int i = 0; i < gg.nprob; ++i) any_rb = any_rb || gg.p[i].rb != nullptr;
-  if (mha && mha->count > 0) {
-    if (any_rb) GC_LAUNCH_TIMED("gemm_group", flops, gemm_group_pass_kernel<true>, dim3(tiles + mha->count + col1), dim3(256), 0, stream, gg, *mha);
-    else GC_LAUNCH_TIMED("gemm_group", flops, gemm_group_pass_kernel<false>, dim3(tiles + mha->count + col1), dim3(256), 0, stream, gg, *mha);
-  } else {
-    if (any_rb) GC_LAUNCH_TIMED("gemm_group", flops, gemm_group_kernel<true>, dim3(tiles + col1), dim3(256), 0, stream, gg);
-    else GC_LAUNCH_TIMED("gemm_group", flops, gemm_group_kernel<false>, dim3(tiles + col1), dim3(256), 0, stream, gg);
-  }
+  int col1 = 0, col2 = 0;   // trailing workgroups of the launch and of its reduce
+  if (ride != RIDE_NONE) gg.col = *col;
+  if (ride == RIDE_COLSUM) col1 = cdiv(col->C, 64) * COL_RIDE_SLICES, col2 = cdiv(col->C, 256);
+  else if (ride != RIDE_NONE) col1 = cdiv(col->C, 256);
+  if (mha && mha->count > 0)
+    GC_LAUNCH_TIMED("gemm_group", flops, by_row_blocks(gg, gemm_group_pass_kernel<true>, gemm_group_pass_kernel<false>),
+                    dim3(tiles + mha->count + col1), dim3(256), 0, stream, gg, *mha);
+  else
+    GC_LAUNCH_TIMED("gemm_group", flops, by_row_blocks(gg, gemm_group_kernel<true>, gemm_group_kernel<false>), dim3(tiles + col1), dim3(256), 0,
+                    stream, gg);
   if (int e = check_launch("gemm_group")) return e;
-  if (ride && !any_split && col_later) {  // nothing to reduce: the caller folds stage 2 into a kernel of its own
+  if (ride == RIDE_COLSUM && !any_split && col_later) {  // nothing to reduce: the caller folds stage 2 into a kernel of its own
     *col_later = true;
     return 0;
   }
-  if (any_split || ride) {
+  if (any_split || ride == RIDE_COLSUM) {
     ProfScope ps("gemm_splitk_reduce", stream);
     hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3(reds + col2), dim3(256), 0, stream, gg);
     return check_launch("gemm_group_reduce");
@@ -552,144 +607,85 @@ __global__ __launch_bounds__(256) void gemm_dyn_zero_kernel(GemmArgs g, const in
   if (!g.accumulate) g.C[(long)row * g.ldc + col] = 0.f;
 }
 
+using DynKernel = void (*)(GemmArgs, const int*, int, int);   // gemm_dyn_kernel by [guarded][A stored K x M][b_kc] (same order)
+static const DynKernel dyn_kernels[2][2][2] = {
+    {{gemm_dyn_kernel<true, false, true>, gemm_dyn_kernel<true, true, true>}, {gemm_dyn_kernel<false, false, true>, gemm_dyn_kernel<false, true, true>}},
+    {{gemm_dyn_kernel<true, false, false>, gemm_dyn_kernel<true, true, false>}, {gemm_dyn_kernel<false, false, false>, gemm_dyn_kernel<false, true, false>}}};
+
 int gemm_dyn(const GemmArgs& g_in, const int* cnt, int dyn, long cap, hipStream_t st) {
   GemmArgs g = g_in;
   GC_REQUIRE(cnt && (dyn == 1 || dyn == 2) && cap >= 0, "gemm_dyn: bad arguments");
-  GC_REQUIRE(g.batch1 == 1 && g.batch2 == 1, "gemm_dyn: batched problems are not supported");
-  if (cap == 0) cap = 1;
-  if (dyn == 1) g.M = (int)((cap + 63) & ~63L); else g.K = (int)((cap + 63) & ~63L);
-  if (prepare(g, 1, 1, 0) < 0) return 1;
-  const bool al = g.vecA && g.vecB && g.N % 64 == 0 && (dyn == 1 ? g.K % BK == 0 : g.M % 64 == 0);
-  int splits = 1;
-  if (dyn == 2) {
-    // enough K slices to fill the chip with the few output tiles of a weight gradient; each slice >= 8 k-steps
-    const long tiles = (long)cdiv(g.M, 64) * cdiv(g.N, 64);
-    long want = (1024 + tiles - 1) / tiles, most = cap / (8 * BK);
-    if (most < 1) most = 1;
-    splits = (int)(want < most ? want : most);
-    if (splits > 64) splits = 64;
-    if (splits > 1 && (!g.ws || (long)splits * g.M * g.N > g.ws_elems || g.N % 4 != 0 || (((uintptr_t)g.ws) & 15) != 0)) splits = 1;
-    if (splits == 1) {
-      dim3 zg(cdiv((long)g.M * g.N, 256));
-      hipLaunchKernelGGL(gemm_dyn_zero_kernel, zg, dim3(256), 0, st, g, cnt);
-    }
-  }
-  g.splits = splits;
-  const long tiles_cap = dyn == 1 ? (long)cdiv(cap, 64) * cdiv(g.N, 64) : (long)cdiv(g.M, 64) * cdiv(g.N, 64) * splits;
-  const unsigned grid = (unsigned)(tiles_cap < 1024 ? (tiles_cap > 0 ? tiles_cap : 1) : 1024);
-  const double flops = 0.0;  // data-dependent: not counted by the host-side timer
-#define GC_DYN(AK, BKc, AL) GC_LAUNCH_TIMED("gemm_dyn", flops, (gemm_dyn_kernel<AK, BKc, AL>), dim3(grid), dim3(256), 0, st, g, cnt, dyn, splits)
-  if (al) {
-    if (g.a_kc && !g.b_kc) GC_DYN(true, false, true);
-    else if (g.a_kc && g.b_kc) GC_DYN(true, true, true);
-    else if (!g.a_kc && !g.b_kc) GC_DYN(false, false, true);
-    else GC_DYN(false, true, true);
-  } else {
-    if (g.a_kc && !g.b_kc) GC_DYN(true, false, false);
-    else if (g.a_kc && g.b_kc) GC_DYN(true, true, false);
-    else if (!g.a_kc && !g.b_kc) GC_DYN(false, false, false);
-    else GC_DYN(false, true, false);
-  }
-#undef GC_DYN
+  const GemmPlan p = gemm_plan(g, dyn == 1 ? GEMM_DYN_M : GEMM_DYN_K, 1, 0, cap);
+  if (!p.ok) return 1;
+  if (p.zero_fill) hipLaunchKernelGGL(gemm_dyn_zero_kernel, dim3(cdiv((long)g.M * g.N, 256)), dim3(256), 0, st, g, cnt);
+  // (flops are data-dependent: not counted by the host-side timer)
+  GC_LAUNCH_TIMED("gemm_dyn", 0.0, dyn_kernels[!p.interior][!g.a_kc][g.b_kc != 0], dim3(p.grid), dim3(256), 0, st, g, cnt, dyn, p.splits);
   if (int e = check_launch("gemm_dyn")) return e;
-  if (splits > 1) {  // sums `splits` partial slabs (empty slices wrote zeros) and runs the epilogue
-    ProfScope ps("gemm_splitk_reduce", st);
-    dim3 rgrid(cdiv((long)g.M * g.N / 4, 256), 1);
-    hipLaunchKernelGGL(splitk_reduce_kernel, rgrid, dim3(256), 0, st, g);
-    return check_launch("gemm_dyn_reduce");
+  // sums `splits` partial slabs (empty slices wrote zeros) and runs the epilogue
+  return p.reduce ? splitk_reduce(g, st, "gemm_dyn_reduce") : 0;
+}
+
+// Two products on the same device-side row count in ONE launch of gemm_dyn_pair_kernel<kind>: dyn[i] says which dimension of
+// problem i is the count (gemm_dyn's numbering: 1 = M, 2 = K).  The kernel instantiates one walk per dimension: A [M][K] times
+// B [K][N] for a count in M, both operands [K][.] for a count in K, interior shapes only.  A count in K runs split, its partials
+// reduced by splitk_reduce, or for two such problems (same shape, one split factor, one gridW) by splitk_reduce_pair_kernel.
+struct DynPairForm {
+  const char* name;
+  int kind;
+  int dyn[2];
+};
+struct DynPairPlan {
+  bool fused;   // false: two gemm_dyn calls (guarded tiles, another storage form, an unsplittable weight gradient)
+  GemmPlan p[2];
+  int gridW;    // the first problem's workgroups; the second problem's follow
+};
+static DynPairPlan dyn_pair_plan(const DynPairForm& f, GemmArgs (&g)[2], long cap) {
+  DynPairPlan pp = {};
+  const bool both_k = f.dyn[0] == 2 && f.dyn[1] == 2;
+  bool ok = !both_k || (g[0].M == g[1].M && g[0].N == g[1].N);
+  for (int i = 0; i < 2; ++i) ok = ok && !g[i].b_kc && (g[i].a_kc != 0) == (f.dyn[i] == 1);
+  for (int i = 0; i < 2 && ok; ++i) {
+    if (i == 1 && both_k) {  // the first problem's workspace holds both problems' partials, one behind the other
+      const long slab = (long)pp.p[0].splits * g[0].M * g[0].N;
+      g[1].split_ws(g[0].ws + slab, g[0].ws_elems - slab);
+    }
+    pp.p[i] = gemm_plan(g[i], f.dyn[i] == 1 ? GEMM_DYN_M : GEMM_DYN_K, 1, 0, cap);
+    ok = pp.p[i].ok && pp.p[i].interior && (f.dyn[i] == 1 || pp.p[i].reduce);
   }
-  return 0;
+  pp.fused = ok;
+  pp.gridW = pp.p[0].grid;
+  return pp;
+}
+using DynPairKernel = void (*)(GemmArgs, GemmArgs, const int*, int, int);
+static const DynPairKernel dyn_pair_kernels[3] = {gemm_dyn_pair_kernel<0>, gemm_dyn_pair_kernel<1>, gemm_dyn_pair_kernel<2>};
+
+static int dyn_pair(const DynPairForm& f, const GemmArgs& a_in, const GemmArgs& b_in, const int* cnt, long cap, hipStream_t st) {
+  GC_REQUIRE(cnt && cap >= 0, "%s: bad arguments", f.name);
+  GemmArgs g[2] = {a_in, b_in};
+  const DynPairPlan pp = dyn_pair_plan(f, g, cap);
+  if (!pp.fused) {
+    if (int e = gemm_dyn(a_in, cnt, f.dyn[0], cap, st)) return e;
+    return gemm_dyn(b_in, cnt, f.dyn[1], cap, st);
+  }
+  GC_LAUNCH_TIMED("gemm_dyn", 0.0, dyn_pair_kernels[f.kind], dim3(pp.gridW + pp.p[1].grid), dim3(256), 0, st, g[0], g[1], cnt, pp.p[0].splits, pp.gridW);
+  if (int e = check_launch(f.name)) return e;
+  if (!pp.p[1].reduce) return pp.p[0].reduce ? splitk_reduce(g[0], st, "gemm_dyn_reduce") : 0;
+  ProfScope ps("gemm_splitk_reduce", st);
+  dim3 rgrid(cdiv((long)g[0].M * g[0].N / 4, 256), 2);
+  hipLaunchKernelGGL(splitk_reduce_pair_kernel, rgrid, dim3(256), 0, st, g[0], g[1]);
+  return check_launch("gemm_dyn_reduce");
 }
 
 // dW = dY^T X (dyn = 2) and dX (+)= dY W (dyn = 1) of one Linear layer whose row count lives on the device: one launch + the
-// weight gradient's reduce instead of two launches + the reduce.  Falls back to two gemm_dyn calls for shapes the pair kernel
-// does not serve (guarded tiles, an unsplittable weight gradient).
-int gemm_dyn_pair(const GemmArgs& gw_in, const GemmArgs& gx_in, const int* cnt, long cap, hipStream_t st) {
-  GemmArgs gw = gw_in, gx = gx_in;
-  GC_REQUIRE(cnt && cap >= 0, "gemm_dyn_pair: bad arguments");
-  if (cap == 0) cap = 1;
-  gw.K = (int)((cap + 63) & ~63L), gx.M = (int)((cap + 63) & ~63L);
-  bool ok = gw.batch1 == 1 && gw.batch2 == 1 && gx.batch1 == 1 && gx.batch2 == 1 && !gw.a_kc && !gw.b_kc && gx.a_kc && !gx.b_kc;
-  ok = ok && prepare(gw, 1, 1, 0) >= 0 && prepare(gx, 1, 1, 0) >= 0;
-  ok = ok && gw.vecA && gw.vecB && gw.N % 64 == 0 && gw.M % 64 == 0 && gx.vecA && gx.vecB && gx.N % 64 == 0 && gx.K % BK == 0;
-  int splits = 1;
-  if (ok) {   // the split factor of gemm_dyn (dyn = 2)
-    const long tiles = (long)cdiv(gw.M, 64) * cdiv(gw.N, 64);
-    long want = (1024 + tiles - 1) / tiles, most = cap / (8 * BK);
-    if (most < 1) most = 1;
-    splits = (int)(want < most ? want : most);
-    if (splits > 64) splits = 64;
-    ok = splits > 1 && gw.ws && (long)splits * gw.M * gw.N <= gw.ws_elems && gw.N % 4 == 0 && (((uintptr_t)gw.ws) & 15) == 0;
-  }
-  if (!ok) {
-    if (int e = gemm_dyn(gw_in, cnt, 2, cap, st)) return e;
-    return gemm_dyn(gx_in, cnt, 1, cap, st);
-  }
-  gw.splits = splits;
-  const long tw = (long)cdiv(gw.M, 64) * cdiv(gw.N, 64) * splits, tx = (long)cdiv(cap, 64) * cdiv(gx.N, 64);
-  const int gridW = (int)(tw < 1024 ? tw : 1024), gridX = (int)(tx < 1024 ? (tx > 0 ? tx : 1) : 1024);
-  GC_LAUNCH_TIMED("gemm_dyn", 0.0, gemm_dyn_pair_kernel<0>, dim3(gridW + gridX), dim3(256), 0, st, gw, gx, cnt, splits, gridW);
-  if (int e = check_launch("gemm_dyn_pair")) return e;
-  ProfScope ps("gemm_splitk_reduce", st);
-  dim3 rgrid(cdiv((long)gw.M * gw.N / 4, 256), 1);
-  hipLaunchKernelGGL(splitk_reduce_kernel, rgrid, dim3(256), 0, st, gw);
-  return check_launch("gemm_dyn_reduce");
-}
-
+// weight gradient's reduce instead of two launches + the reduce.
+static const DynPairForm pair_wx = {"gemm_dyn_pair", 0, {2, 1}};
+int gemm_dyn_pair(const GemmArgs& gw, const GemmArgs& gx, const int* cnt, long cap, hipStream_t st) { return dyn_pair(pair_wx, gw, gx, cnt, cap, st); }
 // Two weight gradients over the same device-side row count and of the same shape (dyn = 2 both): one launch + one reduce launch.
-int gemm_dyn_pair_ww(const GemmArgs& ga_in, const GemmArgs& gb_in, const int* cnt, long cap, hipStream_t st) {
-  GemmArgs ga = ga_in, gb = gb_in;
-  GC_REQUIRE(cnt && cap >= 0, "gemm_dyn_pair_ww: bad arguments");
-  if (cap == 0) cap = 1;
-  ga.K = gb.K = (int)((cap + 63) & ~63L);
-  bool ok = ga.batch1 == 1 && ga.batch2 == 1 && gb.batch1 == 1 && gb.batch2 == 1 && !ga.a_kc && !ga.b_kc && !gb.a_kc && !gb.b_kc &&
-            ga.M == gb.M && ga.N == gb.N;
-  ok = ok && prepare(ga, 1, 1, 0) >= 0 && prepare(gb, 1, 1, 0) >= 0;
-  ok = ok && ga.vecA && ga.vecB && gb.vecA && gb.vecB && ga.N % 64 == 0 && ga.M % 64 == 0;
-  int splits = 1;
-  if (ok) {
-    const long tiles = (long)cdiv(ga.M, 64) * cdiv(ga.N, 64);
-    long want = (1024 + tiles - 1) / tiles, most = cap / (8 * BK);
-    if (most < 1) most = 1;
-    splits = (int)(want < most ? want : most);
-    if (splits > 64) splits = 64;
-    const long slab = (long)splits * ga.M * ga.N;   // each problem's partials: the workspace holds both, one behind the other
-    ok = splits > 1 && ga.ws && 2 * slab <= ga.ws_elems && ga.N % 4 == 0 && (((uintptr_t)ga.ws) & 15) == 0 && slab % 4 == 0;
-    if (ok) gb.ws = ga.ws + slab;
-  }
-  if (!ok) {
-    if (int e = gemm_dyn(ga_in, cnt, 2, cap, st)) return e;
-    return gemm_dyn(gb_in, cnt, 2, cap, st);
-  }
-  ga.splits = gb.splits = splits;
-  const long tw = (long)cdiv(ga.M, 64) * cdiv(ga.N, 64) * splits;
-  const int gridW = (int)(tw < 1024 ? tw : 1024);
-  GC_LAUNCH_TIMED("gemm_dyn", 0.0, gemm_dyn_pair_kernel<1>, dim3(2 * gridW), dim3(256), 0, st, ga, gb, cnt, splits, gridW);
-  if (int e = check_launch("gemm_dyn_pair_ww")) return e;
-  ProfScope ps("gemm_splitk_reduce", st);
-  dim3 rgrid(cdiv((long)ga.M * ga.N / 4, 256), 2);
-  hipLaunchKernelGGL(splitk_reduce_pair_kernel, rgrid, dim3(256), 0, st, ga, gb);
-  return check_launch("gemm_dyn_reduce");
-}
-
+static const DynPairForm pair_ww = {"gemm_dyn_pair_ww", 1, {2, 2}};
+int gemm_dyn_pair_ww(const GemmArgs& ga, const GemmArgs& gb, const int* cnt, long cap, hipStream_t st) { return dyn_pair(pair_ww, ga, gb, cnt, cap, st); }
 // Two products whose M is the same device-side row count (dyn = 1 both, A [M][K] row-major, B [K][N]): one launch.
-int gemm_dyn_pair_xx(const GemmArgs& ga_in, const GemmArgs& gb_in, const int* cnt, long cap, hipStream_t st) {
-  GemmArgs ga = ga_in, gb = gb_in;
-  GC_REQUIRE(cnt && cap >= 0, "gemm_dyn_pair_xx: bad arguments");
-  if (cap == 0) cap = 1;
-  ga.M = gb.M = (int)((cap + 63) & ~63L);
-  bool ok = ga.batch1 == 1 && ga.batch2 == 1 && gb.batch1 == 1 && gb.batch2 == 1 && ga.a_kc && !ga.b_kc && gb.a_kc && !gb.b_kc;
-  ok = ok && prepare(ga, 1, 1, 0) >= 0 && prepare(gb, 1, 1, 0) >= 0;
-  ok = ok && ga.vecA && ga.vecB && gb.vecA && gb.vecB && ga.N % 64 == 0 && gb.N % 64 == 0 && ga.K % BK == 0 && gb.K % BK == 0;
-  if (!ok) {
-    if (int e = gemm_dyn(ga_in, cnt, 1, cap, st)) return e;
-    return gemm_dyn(gb_in, cnt, 1, cap, st);
-  }
-  const long ta = (long)cdiv(cap, 64) * cdiv(ga.N, 64), tb = (long)cdiv(cap, 64) * cdiv(gb.N, 64);
-  const int gridA = (int)(ta < 1024 ? (ta > 0 ? ta : 1) : 1024), gridB = (int)(tb < 1024 ? (tb > 0 ? tb : 1) : 1024);
-  GC_LAUNCH_TIMED("gemm_dyn", 0.0, gemm_dyn_pair_kernel<2>, dim3(gridA + gridB), dim3(256), 0, st, ga, gb, cnt, 1, gridA);
-  return check_launch("gemm_dyn_pair_xx");
-}
+static const DynPairForm pair_xx = {"gemm_dyn_pair_xx", 2, {1, 1}};
+int gemm_dyn_pair_xx(const GemmArgs& ga, const GemmArgs& gb, const int* cnt, long cap, hipStream_t st) { return dyn_pair(pair_xx, ga, gb, cnt, cap, st); }
 
 // ---- deferred problems ------------------------------------------------------------------------------------------
 // One DeferQueue per backward pass (owned by the host side, gcgcn_defer_create / _destroy): no process-wide state, so
@@ -699,8 +695,8 @@ bool gemm_defer(DeferQueue* q, const GemmArgs& g_in) {
   if (!q) return false;
   GemmArgs g = g_in;
   if (q->n >= DeferQueue::CAP || g.M == 0 || g.N == 0) return false;
-  if (prepare(g, 1, 1, 0) < 0) return false;
-  if (!(g.vecA && g.vecB && g.M % 64 == 0 && g.N % 64 == 0 && g.K % BK == 0)) return false;
+  const GemmPlan p = gemm_plan(g, GEMM_PARK, 1, 0, 0);
+  if (!(p.ok && p.interior)) return false;
   g.ws = nullptr, g.ws_elems = 0;  // unsplit: the whole K inside one workgroup
   q->done[q->n] = 0;
   q->p[q->n++] = g;
@@ -718,7 +714,6 @@ bool gemm_take_deferred_col2(DeferQueue* q, ColRide& out) {
   return true;
 }
 
-static int tiles_of(const GemmArgs& g);
 // longest K first (they run the longest: start them first); small_first: among equal K the problems with the fewest tiles
 // lead -- a carrier with a tile budget then completes whole small problems instead of a slice of a big one, which keeps the
 // NUMBER of parked problems within what the last carrier's argument block holds (GemmGroup::MAXP)
@@ -736,9 +731,6 @@ static void sort_parked(DeferQueue* q, bool small_first = false) {
     }
 }
 
-static double flops_of(const GemmArgs& g) { return 2.0 * g.M * g.N * g.K * g.batch1 * g.batch2; }
-static int tiles_of(const GemmArgs& g) { return (g.M >> 6) * (g.N >> 6) * g.batch1 * g.batch2; }
-
 // Move parked work into gg: up to G::MAXP problems, at most max_tiles tiles in all; a problem is split when the budget
 // ends inside it (its remaining tiles stay parked).  Returns the number of workgroups (one per tile, ranges 8-aligned).
 template <class G>
@@ -750,7 +742,7 @@ static int take_parked(DeferQueue* q, G& gg, double* flops, long max_tiles, bool
   int wgs = 0, np = 0, keep = 0;
   for (int i = 0; i < q->n; ++i) {
     const GemmArgs& g = q->p[i];
-    const int total = tiles_of(g), avail = total - q->done[i];
+    const int total = (int)tiles_of(g), avail = total - q->done[i];
     const long take = (np < G::MAXP && max_tiles > 0) ? (avail < max_tiles ? avail : max_tiles) : 0;
     if (take > 0) {
       wgs = (wgs + 7) & ~7;
@@ -794,10 +786,7 @@ int gemm_flush_deferred(DeferQueue* q, hipStream_t stream) {
       double fl = 0;
       const int wgs = gemm_take_deferred(q, gg, &fl);
       if (wgs > 0) {
-        bool any_rb = false;
-        for (int i = 0; i < gg.nprob; ++i) any_rb = any_rb || gg.p[i].rb != nullptr;
-        if (any_rb) GC_LAUNCH_TIMED("gemm_group", fl, gemm_parked_kernel<true>, dim3(wgs), dim3(256), 0, stream, gg);
-        else GC_LAUNCH_TIMED("gemm_group", fl, gemm_parked_kernel<false>, dim3(wgs), dim3(256), 0, stream, gg);
+        GC_LAUNCH_TIMED("gemm_group", fl, by_row_blocks(gg, gemm_parked_kernel<true>, gemm_parked_kernel<false>), dim3(wgs), dim3(256), 0, stream, gg);
         if (int e = check_launch("gemm_parked")) return e;
       }
       continue;
@@ -815,3 +804,54 @@ int gemm_flush_deferred(DeferQueue* q, hipStream_t stream) {
 }
 
 }  // namespace gc
+
+#include "../../include/gcgcn.h"
+
+extern "C" {
+
+// The launcher's decision for one problem (form 0..4: the GemmForm values) or for a pair on a device-side count (5 gemm_dyn_pair,
+// 6 _ww, 7 _xx), by the very functions the launchers call, on made-up operand addresses.  A problem is 13 integers: M, N, K, a_kc,
+// b_kc, lda, ldb, ldc, batch1, batch2, row-block mode, workspace elements (0: no workspace) and a misalign mask (bit 0 A, bit 1 B,
+// bit 2 the workspace off a 16-byte boundary).  out[0..11] and, for a pair, out[12..23]: ok, interior, splits, ksplit, widen, kept
+// row-block mode, vecA, vecB, tiles, reduce, zero fill, grid (a pair that is not fused: of the two gemm_dyn calls that run instead);
+// out[24], out[25]: fused, gridW.  Fields that do not apply are -1.  Exposed for tests (no GPU needed).
+int gcgcn_debug_gemm_plan(int form, const int64_t* prob_a, const int64_t* prob_b, int splits, int64_t group_work, int64_t cap, int32_t* out) {
+  using namespace gc;
+  GC_REQUIRE(form >= 0 && form <= 7 && prob_a && (form < 5 || prob_b) && cap >= 0 && out, "debug_gemm_plan: bad arguments");
+  GC_REQUIRE(prob_a[0] > 0 && prob_a[1] > 0 && (form < 5 || (prob_b[0] > 0 && prob_b[1] > 0)), "debug_gemm_plan: empty problem");
+  for (int i = 0; i < 26; ++i) out[i] = -1;
+  int slot = 0;
+  auto at = [&](bool off) { return (float*)(uintptr_t)(0x10000000ul * ++slot + (off ? 4 : 0)); };
+  static const int live_blocks = 0;   // only its address is used: a row-block list is present
+  auto problem = [&](const int64_t* d) {
+    GemmArgs g = gemm_stored((int)d[3], (int)d[4], at(d[12] & 1), d[5], at(d[12] & 2), d[6], at(false), d[7], (int)d[0], (int)d[1], (int)d[2]);
+    g.batch_z1((int)d[8], d[0] * d[2], d[1] * d[2], d[0] * d[1]).batch_z2((int)d[9], d[8] * d[0] * d[2], d[8] * d[1] * d[2], d[8] * d[0] * d[1]);
+    float* ws = at(d[12] & 4);
+    if (d[11] > 0) g.split_ws(ws, d[11]);
+    if (d[10]) g.rb = g.rb_n = &live_blocks, g.rb_mode = (int)d[10];
+    return g;
+  };
+  auto show = [&](const GemmArgs& g, const GemmPlan& p, int32_t* o) {
+    o[0] = p.ok;
+    if (!p.ok) return;
+    o[1] = p.interior, o[2] = p.splits, o[3] = p.ksplit, o[4] = p.widen, o[5] = p.rb_mode, o[6] = g.vecA, o[7] = g.vecB, o[8] = (int32_t)p.tiles;
+    o[9] = p.reduce, o[10] = p.zero_fill, o[11] = p.grid;
+  };
+  if (form < 5) {
+    GemmArgs g = problem(prob_a);
+    show(g, gemm_plan(g, (GemmForm)form, splits, group_work, cap), out);
+    return 0;
+  }
+  const DynPairForm& f = form == 5 ? pair_wx : form == 6 ? pair_ww : pair_xx;
+  const GemmArgs in[2] = {problem(prob_a), problem(prob_b)};
+  GemmArgs g[2] = {in[0], in[1]};
+  DynPairPlan pp = dyn_pair_plan(f, g, cap);
+  for (int i = 0; i < 2; ++i) {
+    if (!pp.fused) g[i] = in[i], pp.p[i] = gemm_plan(g[i], f.dyn[i] == 1 ? GEMM_DYN_M : GEMM_DYN_K, 1, 0, cap);
+    show(g[i], pp.p[i], out + 12 * i);
+  }
+  out[24] = pp.fused, out[25] = pp.fused ? pp.gridW : -1;
+  return 0;
+}
+
+}  // extern "C"

@@ -40,7 +40,8 @@ const char* gcgcn_last_error(void); /* message of the last failing call on this 
  * one-workgroup-per-(doc, head) attention kernels, 0 = batched GEMM + row softmax for every N.  Results are identical
  * up to fp32 summation order.  "head_v1" (-1 = by problem size), "head_bil3", "head_bil3_bwd", "head_dw3",
  * "head_compact", "chain_t", "chain_big" and "split_widen" select kernel generations (the five head options take effect in
- * csrc/head.hip head_plan and nowhere else: gcgcn_debug_head_plan shows the result); "group_dump" (0 = off) prints what
+ * csrc/head.hip head_plan and nowhere else: gcgcn_debug_head_plan shows the result; "split_widen" in csrc/gemm.hip gemm_plan and
+ * nowhere else: gcgcn_debug_gemm_plan); "group_dump" (0 = off) prints what
  * every GEMM launch is made of on stderr.  Each name also reads the environment variable GCGCN_<NAME> once when nobody set
  * it (GCGCN_CHAIN=0, GCGCN_HEAD_V1=1, ...: DESIGN.md section 6 lists them).  Any other name fails. */
 int gcgcn_set_option(const char* name, int value);
@@ -413,6 +414,18 @@ int gcgcn_debug_chain_plan(int bwd, int B, int N, int D, int L, int H, int ragge
  * head_dw_kernel), then for the forward and the d eh / d et passes whether both launch shapes are issued and the device-side
  * pair count selects one.  Host-only. */
 int gcgcn_debug_head_plan(int B, int N, int R, int ragged, int32_t* out);
+
+/* ---- test hook: what the GEMM launcher decides for a problem ----------------------------------------------------------
+ * Evaluates the plan function every launcher of csrc/gemm.hip calls (gemm_plan) under the current options, on made-up operand
+ * addresses.  form: 0 a single launch (splits: the caller's request), 1 a member of a group launch of group_work tile-k-steps,
+ * 2 parking, 3 / 4 M / K is a device-side count of at most cap; 5, 6, 7: the pairs gemm_dyn_pair, _ww, _xx over prob_a and prob_b.
+ * A problem is int64[13]: M, N, K, a_kc, b_kc, lda, ldb, ldc, batch1, batch2, row-block mode, workspace elements (0: none),
+ * misalign (bit 0 A, bit 1 B, bit 2 the workspace are NOT 16-byte aligned).
+ * out[26]: for prob_a in out[0..11], for a pair's prob_b in out[12..23]: ok, interior, splits, ksplit, widen, kept row-block mode,
+ * vecA, vecB, tiles, reduce launch, zero-fill launch, grid of a device-side form (a pair that is not fused: the plans of the two
+ * gemm_dyn calls that run instead); out[24] = the pair runs fused, out[25] = its gridW.  -1: does not apply.  Host-only. */
+int gcgcn_debug_gemm_plan(int form, const int64_t* prob_a, const int64_t* prob_b, int splits, int64_t group_work, int64_t cap,
+                          int32_t* out);
 
 /* ---- raw batched GEMM (exposed for unit tests and benchmarks of the MFMA kernel) ----------- */
 /* C[z] = alpha * opA(A[z]) opB(B[z]);  a_kc: A stored [M][K] else [K][M];  b_kc: B stored [N][K]

@@ -620,3 +620,376 @@ def test_head_plan_is_the_decision_the_scattered_predicates_made():
                     wrong.append(f"options {values} B {B} N {N} R {HEAD_PLAN_R[k // 2]} ragged {k % 2}: want {HEAD_PLAN_LEGEND[letter]} got {code}")
     assert rows == 1728
     assert not wrong, "\n".join(wrong[:40])
+
+
+# ---- the GEMM launcher's plan ---------------------------------------------------------------------------------------------------
+GEMM_WS = 16 << 20   # workspace elements that hold every split of these shapes
+
+
+def gemm_problem(form, M, N, K, rb=0, batch=1, ws=GEMM_WS, mis=0, lda_off=0):
+    """The 13 integers of a problem for gcgcn_debug_gemm_plan: form nn / nt / tn with its natural leading dimensions."""
+    a_kc, b_kc = {"nn": (1, 0), "nt": (1, 1), "tn": (0, 0), "tt": (0, 1)}[form]
+    return [M, N, K, a_kc, b_kc, (K if a_kc else M) + lda_off, K if b_kc else N, N, batch, 1, rb, ws, mis]
+
+
+# name -> problem.  The three products of the path in their natural storage forms; the forced split of a long-K row-block problem
+# (768 x 768 x 3072: 144 tiles, 96 k-steps) and the same batched (the list is dropped: nb != 1); the smallest interior problem; a mode 2
+# list longer than ROWBLK_LIST_MAX; K % 64 != 0 under mode 2; a guarded shape; N % 4 != 0; a 128-tile mode 1 problem (the `small`
+# rule) next to a 1024-tile one; mode 2 / mode 1 with the storage form they serve and with one they do not; then workspace absent, too
+# small for the chosen split (4 x 256 x 2048 floats), misaligned; the forced split's workspace at exactly 2, 4 and 7 slabs (widen 1,
+# 2, 2); A / B misaligned; a leading dimension that is no multiple of 4; a guarded problem with a row-block list; the two refusals.
+GEMM_PLAN_CASES = {
+    "nt2048x2048x256": gemm_problem("nt", 2048, 2048, 256),
+    "nn2048x256x2048": gemm_problem("nn", 2048, 256, 2048),
+    "tn256x2048x2048": gemm_problem("tn", 256, 2048, 2048),
+    "longK rb1": gemm_problem("nn", 768, 768, 3072, rb=1),
+    "longK rb1 batch8": gemm_problem("nn", 768, 768, 3072, rb=1, batch=8),
+    "nn64x64x32": gemm_problem("nn", 64, 64, 32),
+    "tn64x64x16384 rb2": gemm_problem("tn", 64, 64, 16384, rb=2),
+    "tn128x128x96 rb2": gemm_problem("tn", 128, 128, 96, rb=2),
+    "nn100x40x50": gemm_problem("nn", 100, 40, 50),
+    "nn128x130x64": gemm_problem("nn", 128, 130, 64),
+    "128 tiles rb1": gemm_problem("nn", 512, 1024, 256, rb=1),
+    "1024 tiles rb1": gemm_problem("nn", 2048, 2048, 256, rb=1),
+    "tn rb2": gemm_problem("tn", 256, 2048, 2048, rb=2),
+    "nt rb2": gemm_problem("nt", 2048, 2048, 256, rb=2),
+    "tn rb1": gemm_problem("tn", 256, 2048, 2048, rb=1),
+    "tn no ws": gemm_problem("tn", 256, 2048, 2048, ws=0),
+    "tn ws small": gemm_problem("tn", 256, 2048, 2048, ws=1 << 20),
+    "tn ws misaligned": gemm_problem("tn", 256, 2048, 2048, mis=4),
+    "longK rb1 no ws": gemm_problem("nn", 768, 768, 3072, rb=1, ws=0),
+    "longK rb1 ws 2 slabs": gemm_problem("nn", 768, 768, 3072, rb=1, ws=2 * 768 * 768),
+    "longK rb1 ws 4 slabs": gemm_problem("nn", 768, 768, 3072, rb=1, ws=4 * 768 * 768),
+    "longK rb1 ws 7 slabs": gemm_problem("nn", 768, 768, 3072, rb=1, ws=7 * 768 * 768),
+    "nt A misaligned": gemm_problem("nt", 2048, 2048, 256, mis=1),
+    "nt B misaligned": gemm_problem("nt", 2048, 2048, 256, mis=2),
+    "nn lda + 2": gemm_problem("nn", 2048, 256, 2048, lda_off=2),
+    "guarded rb1": gemm_problem("nn", 2048, 2040, 256, rb=1),
+    "K = 0": gemm_problem("nn", 64, 64, 0),
+    "M * ld = 2^32": gemm_problem("nn", 1 << 21, 2048, 64),
+}
+GEMM_PLAN_CAPS = [0, 1, 63, 64, 65, 4096, 100000]
+GEMM_GROUP_WORK = 1 << 20
+# (pair form 5 gemm_dyn_pair / 6 _ww / 7 _xx, problem a, problem b); the count replaces K of a weight gradient (tn), M of the others
+GEMM_PAIR_CASES = {
+    "wx": (5, gemm_problem("tn", 256, 512, 1), gemm_problem("nn", 1, 256, 512)),
+    "wx no ws": (5, gemm_problem("tn", 256, 512, 1, ws=0), gemm_problem("nn", 1, 256, 512)),
+    "wx ws misaligned": (5, gemm_problem("tn", 256, 512, 1, mis=4), gemm_problem("nn", 1, 256, 512)),
+    "wx x guarded": (5, gemm_problem("tn", 256, 512, 1), gemm_problem("nn", 1, 256, 50)),
+    "wx w guarded": (5, gemm_problem("tn", 250, 512, 1), gemm_problem("nn", 1, 256, 512)),
+    "wx w stored nt": (5, gemm_problem("nt", 256, 512, 1), gemm_problem("nn", 1, 256, 512)),
+    "wx x stored nt": (5, gemm_problem("tn", 256, 512, 1), gemm_problem("nt", 1, 256, 512)),
+    "wx w batched": (5, gemm_problem("tn", 256, 512, 1, batch=2), gemm_problem("nn", 1, 256, 512)),
+    "wx x B misaligned": (5, gemm_problem("tn", 256, 512, 1), gemm_problem("nn", 1, 256, 512, mis=2)),
+    "ww": (6, gemm_problem("tn", 256, 512, 1), gemm_problem("tn", 256, 512, 1)),
+    "ww ws 3M": (6, gemm_problem("tn", 256, 512, 1, ws=3 << 20), gemm_problem("tn", 256, 512, 1)),
+    "ww shapes differ": (6, gemm_problem("tn", 256, 512, 1), gemm_problem("tn", 256, 256, 1)),
+    "ww ws misaligned": (6, gemm_problem("tn", 256, 512, 1, mis=4), gemm_problem("tn", 256, 512, 1)),
+    "ww b A misaligned": (6, gemm_problem("tn", 256, 512, 1), gemm_problem("tn", 256, 512, 1, mis=1)),
+    "ww b stored nn": (6, gemm_problem("tn", 256, 512, 1), gemm_problem("nn", 256, 512, 1)),
+    "ww guarded": (6, gemm_problem("tn", 256, 500, 1), gemm_problem("tn", 256, 500, 1)),
+    "xx": (7, gemm_problem("nn", 1, 256, 512), gemm_problem("nn", 1, 128, 96)),
+    "xx b guarded": (7, gemm_problem("nn", 1, 256, 512), gemm_problem("nn", 1, 100, 96)),
+    "xx a K guarded": (7, gemm_problem("nn", 1, 256, 50), gemm_problem("nn", 1, 128, 96)),
+    "xx a A misaligned": (7, gemm_problem("nn", 1, 256, 512, mis=1), gemm_problem("nn", 1, 128, 96)),
+    "xx b stored tn": (7, gemm_problem("nn", 1, 256, 512), gemm_problem("tn", 1, 128, 96)),
+    "xx b batched": (7, gemm_problem("nn", 1, 256, 512), gemm_problem("nn", 1, 128, 96, batch=2)),
+}
+
+
+def gemm_plan_code(o):
+    """Twelve integers of a plan as I|G (interior | guarded) splits / ksplit, then what differs from the usual: w widen (1), r kept
+    row-block mode (0), v vecA vecB (11); t tiles, R (a reduce launch follows), Z (the zero-fill launch), g grid (0); x: refused."""
+    if o[0] != 1:
+        return "x"
+    return (f"{'GI'[o[1]]}{o[2]}/{o[3]}" + (f"w{o[4]}" if o[4] != 1 else "") + (f"r{o[5]}" if o[5] else "") +
+            (f"v{o[6]}{o[7]}" if (o[6], o[7]) != (1, 1) else "") + f"t{o[8]}" + ("R" if o[9] else "") + ("Z" if o[10] else "") +
+            (f"g{o[11]}" if o[11] else ""))
+
+
+def gemm_plan_table(plan, set_option):
+    """plan(form, prob_a, prob_b, splits, group_work, cap) -> 26 ints.  Per case and split_widen setting three lines: the host-side
+    forms (single launch with requested splits 0, 1, 4; member of a group launch of GEMM_GROUP_WORK tile-k-steps; parking), device-side
+    M per cap, device-side K per cap.  Then per pair case and setting one line: per cap F gridW (fused) or 2 (two gemm_dyn calls) and
+    the two problems' plans."""
+    lines, plans = [], 0
+    try:
+        for name, prob in GEMM_PLAN_CASES.items():
+            for sw in (0, 1):
+                set_option("split_widen", sw)
+                host = [plan(0, prob, None, s, 0, 0) for s in (0, 1, 4)] + [plan(1, prob, None, 0, GEMM_GROUP_WORK, 0), plan(2, prob, None, 0, 0, 0)]
+                lines.append(f"{name} sw{sw} host: " + " ".join(gemm_plan_code(o) for o in host))
+                for form, label in ((3, "dynM"), (4, "dynK")):
+                    lines.append(f"{name} sw{sw} {label}: " + " ".join(gemm_plan_code(plan(form, prob, None, 0, 0, cap)) for cap in GEMM_PLAN_CAPS))
+                plans += 5 + 2 * len(GEMM_PLAN_CAPS)
+        for name, (form, a, b) in GEMM_PAIR_CASES.items():
+            for sw in (0, 1):
+                set_option("split_widen", sw)
+                codes = []
+                for cap in GEMM_PLAN_CAPS:
+                    o = plan(form, a, b, 0, 0, cap)
+                    codes.append((f"F{o[25]}" if o[24] else "2") + "," + gemm_plan_code(o[:12]) + "," + gemm_plan_code(o[12:24]))
+                    plans += 1
+                lines.append(f"pair {name} sw{sw}: " + " ".join(codes))
+    finally:
+        set_option("split_widen", OPTION_DEFAULTS["split_widen"])
+    return lines, plans
+
+
+# Recorded from the PARENT of the commit that introduced gemm_plan, not from the code under test: in a scratch copy of the parent a
+# throw-away function called the parent's own prepare() and evaluated, in the order each caller did, the `al` expressions of gemm,
+# gemm_group and gemm_defer, gemm_dyn's `al`, split factor, workspace test and grid, and the three pair functions' `ok` chains, split
+# factors, workspace tests and grids (a pair that falls back: gemm_dyn's on the two original problems), on the operand addresses
+# gcgcn_debug_gemm_plan makes up, and gemm_plan_table printed this.  Rows that take / do not take each branch:
+#   prepare() refuses: "K = 0", "M * ld = 2^32" / every other case;  splits == 0 picks: host column 1 / columns 2, 3 (requested 1, 4)
+#   the forced split of a long-K row-block problem: "longK rb1 sw1" host column 4 (2/1536) / sw0 (split_widen), "1024 tiles rb1" (K
+#     short), "longK rb1 batch8" (1152 tiles); applied before the list is dropped: "tn rb1 sw1" column 4 stays split, list gone
+#   the workspace rule unsplits: "tn no ws", "tn ws small", "tn ws misaligned", "nn128x130x64" (N % 4), "tn128x128x96 rb2" column 3
+#     (K % (4 BK)) / "tn256x2048x2048"
+#   the list is kept: "1024 tiles rb1" (mode 1), "tn rb2" (mode 2) / dropped: "guarded rb1" (not interior), "longK rb1 batch8" (nb),
+#     "tn rb1", "nt rb2" (storage form), "tn128x128x96 rb2" (K % 64), "tn64x64x16384 rb2" (list too long; its dynK caps <= 4096 keep it)
+#   small: "128 tiles rb1" columns 1, 5 (single launch, parking: dense) / column 4 (member: kept), "longK rb1" column 1 (288 workgroups)
+#   widen: "longK rb1 ws 2 / 4 / 7 slabs sw1" column 4 (1, 2, 2), "longK rb1 sw1" (4) / the same under sw0
+#   gemm_dyn: interior I / guarded G; the split factor is want ("nn2048x256x2048" cap 4096: 8), most ("nn64x64x32" cap 4096: 16), 1
+#     (caps < 256) or the limit of 64 (cap 100000); its workspace test fails: "tn no ws" dynK (Z: the zero-fill launch) /
+#     "tn256x2048x2048"; batched: "longK rb1 batch8" refused
+#   the pairs' ok chains: batch ("wx w batched", "xx b batched"), storage forms ("wx w stored nt", "wx x stored nt", "ww b stored nn",
+#     "xx b stored tn"), equal shapes ("ww shapes differ"), interior ("wx x guarded", "wx w guarded", "wx x B misaligned", "ww b A
+#     misaligned", "ww guarded", "xx b guarded", "xx a K guarded", "xx a A misaligned"), splits > 1 (caps < 512), the workspace ("wx no
+#     ws", "wx ws misaligned", "ww ws 3M": holds one problem's slabs, not both, "ww ws misaligned") / "wx", "ww", "xx" at caps >= 4096
+GEMM_PLAN_EXPECTED = """
+nt2048x2048x256 sw0 host: I1/256t1024 I1/256t1024 I4/64t1024R I1/256t1024 I1/256t1024
+nt2048x2048x256 sw0 dynM: I1/256t32g32 I1/256t32g32 I1/256t32g32 I1/256t32g32 I1/256t64g64 I1/256t2048g1024 I1/256t50016g1024
+nt2048x2048x256 sw0 dynK: I1/64t1024Zg1024 I1/64t1024Zg1024 I1/64t1024Zg1024 I1/64t1024Zg1024 I1/128t1024Zg1024 I1/4096t1024Zg1024 I1/100032t1024Zg1024
+nt2048x2048x256 sw1 host: I1/256t1024 I1/256t1024 I4/64t1024R I1/256t1024 I1/256t1024
+nt2048x2048x256 sw1 dynM: I1/256t32g32 I1/256t32g32 I1/256t32g32 I1/256t32g32 I1/256t64g64 I1/256t2048g1024 I1/256t50016g1024
+nt2048x2048x256 sw1 dynK: I1/64t1024Zg1024 I1/64t1024Zg1024 I1/64t1024Zg1024 I1/64t1024Zg1024 I1/128t1024Zg1024 I1/4096t1024Zg1024 I1/100032t1024Zg1024
+nn2048x256x2048 sw0 host: I4/512t128R I1/2048t128 I4/512t128R I1/2048t128 I1/2048t128
+nn2048x256x2048 sw0 dynM: I1/2048t4g4 I1/2048t4g4 I1/2048t4g4 I1/2048t4g4 I1/2048t8g8 I1/2048t256g256 I1/2048t6252g1024
+nn2048x256x2048 sw0 dynK: I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/128t128Zg128 I8/4096t128Rg1024 I8/100032t128Rg1024
+nn2048x256x2048 sw1 host: I4/512t128R I1/2048t128 I4/512t128R I1/2048t128 I1/2048t128
+nn2048x256x2048 sw1 dynM: I1/2048t4g4 I1/2048t4g4 I1/2048t4g4 I1/2048t4g4 I1/2048t8g8 I1/2048t256g256 I1/2048t6252g1024
+nn2048x256x2048 sw1 dynK: I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/128t128Zg128 I8/4096t128Rg1024 I8/100032t128Rg1024
+tn256x2048x2048 sw0 host: I4/512t128R I1/2048t128 I4/512t128R I1/2048t128 I1/2048t128
+tn256x2048x2048 sw0 dynM: I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t64g64 I1/2048t2048g1024 I1/2048t50016g1024
+tn256x2048x2048 sw0 dynK: I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/128t128Zg128 I8/4096t128Rg1024 I8/100032t128Rg1024
+tn256x2048x2048 sw1 host: I4/512t128R I1/2048t128 I4/512t128R I1/2048t128 I1/2048t128
+tn256x2048x2048 sw1 dynM: I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t64g64 I1/2048t2048g1024 I1/2048t50016g1024
+tn256x2048x2048 sw1 dynK: I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/128t128Zg128 I8/4096t128Rg1024 I8/100032t128Rg1024
+longK rb1 sw0 host: I4/768r1t144R I1/3072t144 I4/768r1t144R I1/3072r1t144 I1/3072t144
+longK rb1 sw0 dynM: I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t24g24 I1/3072r1t768g768 I1/3072r1t18756g1024
+longK rb1 sw0 dynK: I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/128t144Zg144 I8/4096t144Rg1024 I8/100032t144Rg1024
+longK rb1 sw1 host: I4/768w4r1t144R I1/3072t144 I4/768w4r1t144R I2/1536w4r1t144R I1/3072t144
+longK rb1 sw1 dynM: I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t24g24 I1/3072r1t768g768 I1/3072r1t18756g1024
+longK rb1 sw1 dynK: I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/128t144Zg144 I8/4096t144Rg1024 I8/100032t144Rg1024
+longK rb1 batch8 sw0 host: I1/3072t1152 I1/3072t1152 I1/3072t1152 I1/3072t1152 I1/3072t1152
+longK rb1 batch8 sw0 dynM: x x x x x x x
+longK rb1 batch8 sw0 dynK: x x x x x x x
+longK rb1 batch8 sw1 host: I1/3072t1152 I1/3072t1152 I1/3072t1152 I1/3072t1152 I1/3072t1152
+longK rb1 batch8 sw1 dynM: x x x x x x x
+longK rb1 batch8 sw1 dynK: x x x x x x x
+nn64x64x32 sw0 host: I1/32t1 I1/32t1 I1/32t1 I1/32t1 I1/32t1
+nn64x64x32 sw0 dynM: I1/32t1g1 I1/32t1g1 I1/32t1g1 I1/32t1g1 I1/32t2g2 I1/32t64g64 I1/32t1563g1024
+nn64x64x32 sw0 dynK: I1/64t1Zg1 I1/64t1Zg1 I1/64t1Zg1 I1/64t1Zg1 I1/128t1Zg1 I16/4096t1Rg16 I64/100032t1Rg64
+nn64x64x32 sw1 host: I1/32t1 I1/32t1 I1/32t1 I1/32t1 I1/32t1
+nn64x64x32 sw1 dynM: I1/32t1g1 I1/32t1g1 I1/32t1g1 I1/32t1g1 I1/32t2g2 I1/32t64g64 I1/32t1563g1024
+nn64x64x32 sw1 dynK: I1/64t1Zg1 I1/64t1Zg1 I1/64t1Zg1 I1/64t1Zg1 I1/128t1Zg1 I16/4096t1Rg16 I64/100032t1Rg64
+tn64x64x16384 rb2 sw0 host: I16/1024t1R I1/16384t1 I4/4096t1R I1/16384t1 I1/16384t1
+tn64x64x16384 rb2 sw0 dynM: I1/16384t1g1 I1/16384t1g1 I1/16384t1g1 I1/16384t1g1 I1/16384t2g2 I1/16384t64g64 I1/16384t1563g1024
+tn64x64x16384 rb2 sw0 dynK: I1/64r2t1Zg1 I1/64r2t1Zg1 I1/64r2t1Zg1 I1/64r2t1Zg1 I1/128r2t1Zg1 I16/4096r2t1Rg16 I64/100032t1Rg64
+tn64x64x16384 rb2 sw1 host: I16/1024t1R I1/16384t1 I4/4096t1R I1/16384t1 I1/16384t1
+tn64x64x16384 rb2 sw1 dynM: I1/16384t1g1 I1/16384t1g1 I1/16384t1g1 I1/16384t1g1 I1/16384t2g2 I1/16384t64g64 I1/16384t1563g1024
+tn64x64x16384 rb2 sw1 dynK: I1/64r2t1Zg1 I1/64r2t1Zg1 I1/64r2t1Zg1 I1/64r2t1Zg1 I1/128r2t1Zg1 I16/4096r2t1Rg16 I64/100032t1Rg64
+tn128x128x96 rb2 sw0 host: I1/96t4 I1/96t4 I1/96t4 I1/96t4 I1/96t4
+tn128x128x96 rb2 sw0 dynM: I1/96t2g2 I1/96t2g2 I1/96t2g2 I1/96t2g2 I1/96t4g4 I1/96t128g128 I1/96t3126g1024
+tn128x128x96 rb2 sw0 dynK: I1/64r2t4Zg4 I1/64r2t4Zg4 I1/64r2t4Zg4 I1/64r2t4Zg4 I1/128r2t4Zg4 I16/4096r2t4Rg64 I64/100032t4Rg256
+tn128x128x96 rb2 sw1 host: I1/96t4 I1/96t4 I1/96t4 I1/96t4 I1/96t4
+tn128x128x96 rb2 sw1 dynM: I1/96t2g2 I1/96t2g2 I1/96t2g2 I1/96t2g2 I1/96t4g4 I1/96t128g128 I1/96t3126g1024
+tn128x128x96 rb2 sw1 dynK: I1/64r2t4Zg4 I1/64r2t4Zg4 I1/64r2t4Zg4 I1/64r2t4Zg4 I1/128r2t4Zg4 I16/4096r2t4Rg64 I64/100032t4Rg256
+nn100x40x50 sw0 host: G1/50v01t2 G1/50v01t2 G1/50v01t2 G1/50v01t2 G1/50v01t2
+nn100x40x50 sw0 dynM: G1/50v01t1g1 G1/50v01t1g1 G1/50v01t1g1 G1/50v01t1g1 G1/50v01t2g2 G1/50v01t64g64 G1/50v01t1563g1024
+nn100x40x50 sw0 dynK: G1/64v01t2Zg2 G1/64v01t2Zg2 G1/64v01t2Zg2 G1/64v01t2Zg2 G1/128v01t2Zg2 G16/4096v01t2Rg32 G64/100032v01t2Rg128
+nn100x40x50 sw1 host: G1/50v01t2 G1/50v01t2 G1/50v01t2 G1/50v01t2 G1/50v01t2
+nn100x40x50 sw1 dynM: G1/50v01t1g1 G1/50v01t1g1 G1/50v01t1g1 G1/50v01t1g1 G1/50v01t2g2 G1/50v01t64g64 G1/50v01t1563g1024
+nn100x40x50 sw1 dynK: G1/64v01t2Zg2 G1/64v01t2Zg2 G1/64v01t2Zg2 G1/64v01t2Zg2 G1/128v01t2Zg2 G16/4096v01t2Rg32 G64/100032v01t2Rg128
+nn128x130x64 sw0 host: G1/64v10t6 G1/64v10t6 G1/64v10t6 G1/64v10t6 G1/64v10t6
+nn128x130x64 sw0 dynM: G1/64v10t3g3 G1/64v10t3g3 G1/64v10t3g3 G1/64v10t3g3 G1/64v10t6g6 G1/64v10t192g192 G1/64v10t4689g1024
+nn128x130x64 sw0 dynK: G1/64v10t6Zg6 G1/64v10t6Zg6 G1/64v10t6Zg6 G1/64v10t6Zg6 G1/128v10t6Zg6 G1/4096v10t6Zg6 G1/100032v10t6Zg6
+nn128x130x64 sw1 host: G1/64v10t6 G1/64v10t6 G1/64v10t6 G1/64v10t6 G1/64v10t6
+nn128x130x64 sw1 dynM: G1/64v10t3g3 G1/64v10t3g3 G1/64v10t3g3 G1/64v10t3g3 G1/64v10t6g6 G1/64v10t192g192 G1/64v10t4689g1024
+nn128x130x64 sw1 dynK: G1/64v10t6Zg6 G1/64v10t6Zg6 G1/64v10t6Zg6 G1/64v10t6Zg6 G1/128v10t6Zg6 G1/4096v10t6Zg6 G1/100032v10t6Zg6
+128 tiles rb1 sw0 host: I1/256t128 I1/256t128 I4/64r1t128R I1/256r1t128 I1/256t128
+128 tiles rb1 sw0 dynM: I1/256t16g16 I1/256t16g16 I1/256t16g16 I1/256t16g16 I1/256t32g32 I1/256r1t1024g1024 I1/256r1t25008g1024
+128 tiles rb1 sw0 dynK: I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/128t128Zg128 I8/4096t128Rg1024 I8/100032t128Rg1024
+128 tiles rb1 sw1 host: I1/256t128 I1/256t128 I4/64w4r1t128R I1/256r1t128 I1/256t128
+128 tiles rb1 sw1 dynM: I1/256t16g16 I1/256t16g16 I1/256t16g16 I1/256t16g16 I1/256t32g32 I1/256r1t1024g1024 I1/256r1t25008g1024
+128 tiles rb1 sw1 dynK: I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/128t128Zg128 I8/4096t128Rg1024 I8/100032t128Rg1024
+1024 tiles rb1 sw0 host: I1/256r1t1024 I1/256r1t1024 I4/64r1t1024R I1/256r1t1024 I1/256r1t1024
+1024 tiles rb1 sw0 dynM: I1/256t32g32 I1/256t32g32 I1/256t32g32 I1/256t32g32 I1/256t64g64 I1/256r1t2048g1024 I1/256r1t50016g1024
+1024 tiles rb1 sw0 dynK: I1/64r1t1024Zg1024 I1/64r1t1024Zg1024 I1/64r1t1024Zg1024 I1/64r1t1024Zg1024 I1/128r1t1024Zg1024 I1/4096r1t1024Zg1024 I1/100032r1t1024Zg1024
+1024 tiles rb1 sw1 host: I1/256r1t1024 I1/256r1t1024 I4/64r1t1024R I1/256r1t1024 I1/256r1t1024
+1024 tiles rb1 sw1 dynM: I1/256t32g32 I1/256t32g32 I1/256t32g32 I1/256t32g32 I1/256t64g64 I1/256r1t2048g1024 I1/256r1t50016g1024
+1024 tiles rb1 sw1 dynK: I1/64r1t1024Zg1024 I1/64r1t1024Zg1024 I1/64r1t1024Zg1024 I1/64r1t1024Zg1024 I1/128r1t1024Zg1024 I1/4096r1t1024Zg1024 I1/100032r1t1024Zg1024
+tn rb2 sw0 host: I4/512r2t128R I1/2048r2t128 I4/512r2t128R I1/2048r2t128 I1/2048r2t128
+tn rb2 sw0 dynM: I1/2048r2t32g32 I1/2048r2t32g32 I1/2048r2t32g32 I1/2048r2t32g32 I1/2048r2t64g64 I1/2048r2t2048g1024 I1/2048r2t50016g1024
+tn rb2 sw0 dynK: I1/64r2t128Zg128 I1/64r2t128Zg128 I1/64r2t128Zg128 I1/64r2t128Zg128 I1/128r2t128Zg128 I8/4096r2t128Rg1024 I8/100032t128Rg1024
+tn rb2 sw1 host: I4/512r2t128R I1/2048r2t128 I4/512r2t128R I1/2048r2t128 I1/2048r2t128
+tn rb2 sw1 dynM: I1/2048r2t32g32 I1/2048r2t32g32 I1/2048r2t32g32 I1/2048r2t32g32 I1/2048r2t64g64 I1/2048r2t2048g1024 I1/2048r2t50016g1024
+tn rb2 sw1 dynK: I1/64r2t128Zg128 I1/64r2t128Zg128 I1/64r2t128Zg128 I1/64r2t128Zg128 I1/128r2t128Zg128 I8/4096r2t128Rg1024 I8/100032t128Rg1024
+nt rb2 sw0 host: I1/256t1024 I1/256t1024 I4/64t1024R I1/256t1024 I1/256t1024
+nt rb2 sw0 dynM: I1/256t32g32 I1/256t32g32 I1/256t32g32 I1/256t32g32 I1/256t64g64 I1/256t2048g1024 I1/256t50016g1024
+nt rb2 sw0 dynK: I1/64t1024Zg1024 I1/64t1024Zg1024 I1/64t1024Zg1024 I1/64t1024Zg1024 I1/128t1024Zg1024 I1/4096t1024Zg1024 I1/100032t1024Zg1024
+nt rb2 sw1 host: I1/256t1024 I1/256t1024 I4/64t1024R I1/256t1024 I1/256t1024
+nt rb2 sw1 dynM: I1/256t32g32 I1/256t32g32 I1/256t32g32 I1/256t32g32 I1/256t64g64 I1/256t2048g1024 I1/256t50016g1024
+nt rb2 sw1 dynK: I1/64t1024Zg1024 I1/64t1024Zg1024 I1/64t1024Zg1024 I1/64t1024Zg1024 I1/128t1024Zg1024 I1/4096t1024Zg1024 I1/100032t1024Zg1024
+tn rb1 sw0 host: I4/512t128R I1/2048t128 I4/512t128R I1/2048t128 I1/2048t128
+tn rb1 sw0 dynM: I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t64g64 I1/2048t2048g1024 I1/2048t50016g1024
+tn rb1 sw0 dynK: I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/128t128Zg128 I8/4096t128Rg1024 I8/100032t128Rg1024
+tn rb1 sw1 host: I4/512t128R I1/2048t128 I4/512t128R I2/1024t128R I1/2048t128
+tn rb1 sw1 dynM: I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t64g64 I1/2048t2048g1024 I1/2048t50016g1024
+tn rb1 sw1 dynK: I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/128t128Zg128 I8/4096t128Rg1024 I8/100032t128Rg1024
+tn no ws sw0 host: I1/2048t128 I1/2048t128 I1/2048t128 I1/2048t128 I1/2048t128
+tn no ws sw0 dynM: I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t64g64 I1/2048t2048g1024 I1/2048t50016g1024
+tn no ws sw0 dynK: I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/128t128Zg128 I1/4096t128Zg128 I1/100032t128Zg128
+tn no ws sw1 host: I1/2048t128 I1/2048t128 I1/2048t128 I1/2048t128 I1/2048t128
+tn no ws sw1 dynM: I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t64g64 I1/2048t2048g1024 I1/2048t50016g1024
+tn no ws sw1 dynK: I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/128t128Zg128 I1/4096t128Zg128 I1/100032t128Zg128
+tn ws small sw0 host: I1/2048t128 I1/2048t128 I1/2048t128 I1/2048t128 I1/2048t128
+tn ws small sw0 dynM: I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t64g64 I1/2048t2048g1024 I1/2048t50016g1024
+tn ws small sw0 dynK: I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/128t128Zg128 I1/4096t128Zg128 I1/100032t128Zg128
+tn ws small sw1 host: I1/2048t128 I1/2048t128 I1/2048t128 I1/2048t128 I1/2048t128
+tn ws small sw1 dynM: I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t64g64 I1/2048t2048g1024 I1/2048t50016g1024
+tn ws small sw1 dynK: I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/128t128Zg128 I1/4096t128Zg128 I1/100032t128Zg128
+tn ws misaligned sw0 host: I1/2048t128 I1/2048t128 I1/2048t128 I1/2048t128 I1/2048t128
+tn ws misaligned sw0 dynM: I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t64g64 I1/2048t2048g1024 I1/2048t50016g1024
+tn ws misaligned sw0 dynK: I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/128t128Zg128 I1/4096t128Zg128 I1/100032t128Zg128
+tn ws misaligned sw1 host: I1/2048t128 I1/2048t128 I1/2048t128 I1/2048t128 I1/2048t128
+tn ws misaligned sw1 dynM: I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t32g32 I1/2048t64g64 I1/2048t2048g1024 I1/2048t50016g1024
+tn ws misaligned sw1 dynK: I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/64t128Zg128 I1/128t128Zg128 I1/4096t128Zg128 I1/100032t128Zg128
+longK rb1 no ws sw0 host: I1/3072t144 I1/3072t144 I1/3072t144 I1/3072r1t144 I1/3072t144
+longK rb1 no ws sw0 dynM: I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t24g24 I1/3072r1t768g768 I1/3072r1t18756g1024
+longK rb1 no ws sw0 dynK: I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/128t144Zg144 I1/4096t144Zg144 I1/100032t144Zg144
+longK rb1 no ws sw1 host: I1/3072t144 I1/3072t144 I1/3072t144 I1/3072r1t144 I1/3072t144
+longK rb1 no ws sw1 dynM: I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t24g24 I1/3072r1t768g768 I1/3072r1t18756g1024
+longK rb1 no ws sw1 dynK: I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/128t144Zg144 I1/4096t144Zg144 I1/100032t144Zg144
+longK rb1 ws 2 slabs sw0 host: I1/3072t144 I1/3072t144 I1/3072t144 I1/3072r1t144 I1/3072t144
+longK rb1 ws 2 slabs sw0 dynM: I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t24g24 I1/3072r1t768g768 I1/3072r1t18756g1024
+longK rb1 ws 2 slabs sw0 dynK: I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/128t144Zg144 I1/4096t144Zg144 I1/100032t144Zg144
+longK rb1 ws 2 slabs sw1 host: I1/3072t144 I1/3072t144 I1/3072t144 I2/1536r1t144R I1/3072t144
+longK rb1 ws 2 slabs sw1 dynM: I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t24g24 I1/3072r1t768g768 I1/3072r1t18756g1024
+longK rb1 ws 2 slabs sw1 dynK: I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/128t144Zg144 I1/4096t144Zg144 I1/100032t144Zg144
+longK rb1 ws 4 slabs sw0 host: I4/768r1t144R I1/3072t144 I4/768r1t144R I1/3072r1t144 I1/3072t144
+longK rb1 ws 4 slabs sw0 dynM: I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t24g24 I1/3072r1t768g768 I1/3072r1t18756g1024
+longK rb1 ws 4 slabs sw0 dynK: I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/128t144Zg144 I1/4096t144Zg144 I1/100032t144Zg144
+longK rb1 ws 4 slabs sw1 host: I4/768r1t144R I1/3072t144 I4/768r1t144R I2/1536w2r1t144R I1/3072t144
+longK rb1 ws 4 slabs sw1 dynM: I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t24g24 I1/3072r1t768g768 I1/3072r1t18756g1024
+longK rb1 ws 4 slabs sw1 dynK: I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/128t144Zg144 I1/4096t144Zg144 I1/100032t144Zg144
+longK rb1 ws 7 slabs sw0 host: I4/768r1t144R I1/3072t144 I4/768r1t144R I1/3072r1t144 I1/3072t144
+longK rb1 ws 7 slabs sw0 dynM: I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t24g24 I1/3072r1t768g768 I1/3072r1t18756g1024
+longK rb1 ws 7 slabs sw0 dynK: I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/128t144Zg144 I1/4096t144Zg144 I1/100032t144Zg144
+longK rb1 ws 7 slabs sw1 host: I4/768r1t144R I1/3072t144 I4/768r1t144R I2/1536w2r1t144R I1/3072t144
+longK rb1 ws 7 slabs sw1 dynM: I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t12g12 I1/3072t24g24 I1/3072r1t768g768 I1/3072r1t18756g1024
+longK rb1 ws 7 slabs sw1 dynK: I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/64t144Zg144 I1/128t144Zg144 I1/4096t144Zg144 I1/100032t144Zg144
+nt A misaligned sw0 host: G1/256v01t1024 G1/256v01t1024 G4/64v01t1024R G1/256v01t1024 G1/256v01t1024
+nt A misaligned sw0 dynM: G1/256v01t32g32 G1/256v01t32g32 G1/256v01t32g32 G1/256v01t32g32 G1/256v01t64g64 G1/256v01t2048g1024 G1/256v01t50016g1024
+nt A misaligned sw0 dynK: G1/64v01t1024Zg1024 G1/64v01t1024Zg1024 G1/64v01t1024Zg1024 G1/64v01t1024Zg1024 G1/128v01t1024Zg1024 G1/4096v01t1024Zg1024 G1/100032v01t1024Zg1024
+nt A misaligned sw1 host: G1/256v01t1024 G1/256v01t1024 G4/64v01t1024R G1/256v01t1024 G1/256v01t1024
+nt A misaligned sw1 dynM: G1/256v01t32g32 G1/256v01t32g32 G1/256v01t32g32 G1/256v01t32g32 G1/256v01t64g64 G1/256v01t2048g1024 G1/256v01t50016g1024
+nt A misaligned sw1 dynK: G1/64v01t1024Zg1024 G1/64v01t1024Zg1024 G1/64v01t1024Zg1024 G1/64v01t1024Zg1024 G1/128v01t1024Zg1024 G1/4096v01t1024Zg1024 G1/100032v01t1024Zg1024
+nt B misaligned sw0 host: G1/256v10t1024 G1/256v10t1024 G4/64v10t1024R G1/256v10t1024 G1/256v10t1024
+nt B misaligned sw0 dynM: G1/256v10t32g32 G1/256v10t32g32 G1/256v10t32g32 G1/256v10t32g32 G1/256v10t64g64 G1/256v10t2048g1024 G1/256v10t50016g1024
+nt B misaligned sw0 dynK: G1/64v10t1024Zg1024 G1/64v10t1024Zg1024 G1/64v10t1024Zg1024 G1/64v10t1024Zg1024 G1/128v10t1024Zg1024 G1/4096v10t1024Zg1024 G1/100032v10t1024Zg1024
+nt B misaligned sw1 host: G1/256v10t1024 G1/256v10t1024 G4/64v10t1024R G1/256v10t1024 G1/256v10t1024
+nt B misaligned sw1 dynM: G1/256v10t32g32 G1/256v10t32g32 G1/256v10t32g32 G1/256v10t32g32 G1/256v10t64g64 G1/256v10t2048g1024 G1/256v10t50016g1024
+nt B misaligned sw1 dynK: G1/64v10t1024Zg1024 G1/64v10t1024Zg1024 G1/64v10t1024Zg1024 G1/64v10t1024Zg1024 G1/128v10t1024Zg1024 G1/4096v10t1024Zg1024 G1/100032v10t1024Zg1024
+nn lda + 2 sw0 host: G4/512v01t128R G1/2048v01t128 G4/512v01t128R G1/2048v01t128 G1/2048v01t128
+nn lda + 2 sw0 dynM: G1/2048v01t4g4 G1/2048v01t4g4 G1/2048v01t4g4 G1/2048v01t4g4 G1/2048v01t8g8 G1/2048v01t256g256 G1/2048v01t6252g1024
+nn lda + 2 sw0 dynK: G1/64v01t128Zg128 G1/64v01t128Zg128 G1/64v01t128Zg128 G1/64v01t128Zg128 G1/128v01t128Zg128 G8/4096v01t128Rg1024 G8/100032v01t128Rg1024
+nn lda + 2 sw1 host: G4/512v01t128R G1/2048v01t128 G4/512v01t128R G1/2048v01t128 G1/2048v01t128
+nn lda + 2 sw1 dynM: G1/2048v01t4g4 G1/2048v01t4g4 G1/2048v01t4g4 G1/2048v01t4g4 G1/2048v01t8g8 G1/2048v01t256g256 G1/2048v01t6252g1024
+nn lda + 2 sw1 dynK: G1/64v01t128Zg128 G1/64v01t128Zg128 G1/64v01t128Zg128 G1/64v01t128Zg128 G1/128v01t128Zg128 G8/4096v01t128Rg1024 G8/100032v01t128Rg1024
+guarded rb1 sw0 host: G1/256t1024 G1/256t1024 G4/64t1024R G1/256t1024 G1/256t1024
+guarded rb1 sw0 dynM: G1/256t32g32 G1/256t32g32 G1/256t32g32 G1/256t32g32 G1/256t64g64 G1/256t2048g1024 G1/256t50016g1024
+guarded rb1 sw0 dynK: G1/64t1024Zg1024 G1/64t1024Zg1024 G1/64t1024Zg1024 G1/64t1024Zg1024 G1/128t1024Zg1024 G1/4096t1024Zg1024 G1/100032t1024Zg1024
+guarded rb1 sw1 host: G1/256t1024 G1/256t1024 G4/64t1024R G1/256t1024 G1/256t1024
+guarded rb1 sw1 dynM: G1/256t32g32 G1/256t32g32 G1/256t32g32 G1/256t32g32 G1/256t64g64 G1/256t2048g1024 G1/256t50016g1024
+guarded rb1 sw1 dynK: G1/64t1024Zg1024 G1/64t1024Zg1024 G1/64t1024Zg1024 G1/64t1024Zg1024 G1/128t1024Zg1024 G1/4096t1024Zg1024 G1/100032t1024Zg1024
+K = 0 sw0 host: x x x x x
+K = 0 sw0 dynM: x x x x x x x
+K = 0 sw0 dynK: I1/64t1Zg1 I1/64t1Zg1 I1/64t1Zg1 I1/64t1Zg1 I1/128t1Zg1 I16/4096t1Rg16 I64/100032t1Rg64
+K = 0 sw1 host: x x x x x
+K = 0 sw1 dynM: x x x x x x x
+K = 0 sw1 dynK: I1/64t1Zg1 I1/64t1Zg1 I1/64t1Zg1 I1/64t1Zg1 I1/128t1Zg1 I16/4096t1Rg16 I64/100032t1Rg64
+M * ld = 2^32 sw0 host: x x x x x
+M * ld = 2^32 sw0 dynM: I1/64t32g32 I1/64t32g32 I1/64t32g32 I1/64t32g32 I1/64t64g64 I1/64t2048g1024 I1/64t50016g1024
+M * ld = 2^32 sw0 dynK: x x x x x x x
+M * ld = 2^32 sw1 host: x x x x x
+M * ld = 2^32 sw1 dynM: I1/64t32g32 I1/64t32g32 I1/64t32g32 I1/64t32g32 I1/64t64g64 I1/64t2048g1024 I1/64t50016g1024
+M * ld = 2^32 sw1 dynK: x x x x x x x
+pair wx sw0: 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/128t32Zg32,I1/512t8g8 F512,I16/4096t32Rg512,I1/512t256g256 F1024,I32/100032t32Rg1024,I1/512t6252g1024
+pair wx sw1: 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/128t32Zg32,I1/512t8g8 F512,I16/4096t32Rg512,I1/512t256g256 F1024,I32/100032t32Rg1024,I1/512t6252g1024
+pair wx no ws sw0: 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/128t32Zg32,I1/512t8g8 2,I1/4096t32Zg32,I1/512t256g256 2,I1/100032t32Zg32,I1/512t6252g1024
+pair wx no ws sw1: 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/128t32Zg32,I1/512t8g8 2,I1/4096t32Zg32,I1/512t256g256 2,I1/100032t32Zg32,I1/512t6252g1024
+pair wx ws misaligned sw0: 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/128t32Zg32,I1/512t8g8 2,I1/4096t32Zg32,I1/512t256g256 2,I1/100032t32Zg32,I1/512t6252g1024
+pair wx ws misaligned sw1: 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/128t32Zg32,I1/512t8g8 2,I1/4096t32Zg32,I1/512t256g256 2,I1/100032t32Zg32,I1/512t6252g1024
+pair wx x guarded sw0: 2,I1/64t32Zg32,G1/50v01t4g4 2,I1/64t32Zg32,G1/50v01t4g4 2,I1/64t32Zg32,G1/50v01t4g4 2,I1/64t32Zg32,G1/50v01t4g4 2,I1/128t32Zg32,G1/50v01t8g8 2,I16/4096t32Rg512,G1/50v01t256g256 2,I32/100032t32Rg1024,G1/50v01t6252g1024
+pair wx x guarded sw1: 2,I1/64t32Zg32,G1/50v01t4g4 2,I1/64t32Zg32,G1/50v01t4g4 2,I1/64t32Zg32,G1/50v01t4g4 2,I1/64t32Zg32,G1/50v01t4g4 2,I1/128t32Zg32,G1/50v01t8g8 2,I16/4096t32Rg512,G1/50v01t256g256 2,I32/100032t32Rg1024,G1/50v01t6252g1024
+pair wx w guarded sw0: 2,G1/64v01t32Zg32,I1/512t4g4 2,G1/64v01t32Zg32,I1/512t4g4 2,G1/64v01t32Zg32,I1/512t4g4 2,G1/64v01t32Zg32,I1/512t4g4 2,G1/128v01t32Zg32,I1/512t8g8 2,G16/4096v01t32Rg512,I1/512t256g256 2,G32/100032v01t32Rg1024,I1/512t6252g1024
+pair wx w guarded sw1: 2,G1/64v01t32Zg32,I1/512t4g4 2,G1/64v01t32Zg32,I1/512t4g4 2,G1/64v01t32Zg32,I1/512t4g4 2,G1/64v01t32Zg32,I1/512t4g4 2,G1/128v01t32Zg32,I1/512t8g8 2,G16/4096v01t32Rg512,I1/512t256g256 2,G32/100032v01t32Rg1024,I1/512t6252g1024
+pair wx w stored nt sw0: 2,G1/64v00t32Zg32,I1/512t4g4 2,G1/64v00t32Zg32,I1/512t4g4 2,G1/64v00t32Zg32,I1/512t4g4 2,G1/64v00t32Zg32,I1/512t4g4 2,G1/128v00t32Zg32,I1/512t8g8 2,G16/4096v00t32Rg512,I1/512t256g256 2,G32/100032v00t32Rg1024,I1/512t6252g1024
+pair wx w stored nt sw1: 2,G1/64v00t32Zg32,I1/512t4g4 2,G1/64v00t32Zg32,I1/512t4g4 2,G1/64v00t32Zg32,I1/512t4g4 2,G1/64v00t32Zg32,I1/512t4g4 2,G1/128v00t32Zg32,I1/512t8g8 2,G16/4096v00t32Rg512,I1/512t256g256 2,G32/100032v00t32Rg1024,I1/512t6252g1024
+pair wx x stored nt sw0: 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/128t32Zg32,I1/512t8g8 2,I16/4096t32Rg512,I1/512t256g256 2,I32/100032t32Rg1024,I1/512t6252g1024
+pair wx x stored nt sw1: 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/64t32Zg32,I1/512t4g4 2,I1/128t32Zg32,I1/512t8g8 2,I16/4096t32Rg512,I1/512t256g256 2,I32/100032t32Rg1024,I1/512t6252g1024
+pair wx w batched sw0: 2,x,I1/512t4g4 2,x,I1/512t4g4 2,x,I1/512t4g4 2,x,I1/512t4g4 2,x,I1/512t8g8 2,x,I1/512t256g256 2,x,I1/512t6252g1024
+pair wx w batched sw1: 2,x,I1/512t4g4 2,x,I1/512t4g4 2,x,I1/512t4g4 2,x,I1/512t4g4 2,x,I1/512t8g8 2,x,I1/512t256g256 2,x,I1/512t6252g1024
+pair wx x B misaligned sw0: 2,I1/64t32Zg32,G1/512v10t4g4 2,I1/64t32Zg32,G1/512v10t4g4 2,I1/64t32Zg32,G1/512v10t4g4 2,I1/64t32Zg32,G1/512v10t4g4 2,I1/128t32Zg32,G1/512v10t8g8 2,I16/4096t32Rg512,G1/512v10t256g256 2,I32/100032t32Rg1024,G1/512v10t6252g1024
+pair wx x B misaligned sw1: 2,I1/64t32Zg32,G1/512v10t4g4 2,I1/64t32Zg32,G1/512v10t4g4 2,I1/64t32Zg32,G1/512v10t4g4 2,I1/64t32Zg32,G1/512v10t4g4 2,I1/128t32Zg32,G1/512v10t8g8 2,I16/4096t32Rg512,G1/512v10t256g256 2,I32/100032t32Rg1024,G1/512v10t6252g1024
+pair ww sw0: 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/128t32Zg32,I1/128t32Zg32 F512,I16/4096t32Rg512,I16/4096t32Rg512 F1024,I32/100032t32Rg1024,I32/100032t32Rg1024
+pair ww sw1: 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/128t32Zg32,I1/128t32Zg32 F512,I16/4096t32Rg512,I16/4096t32Rg512 F1024,I32/100032t32Rg1024,I32/100032t32Rg1024
+pair ww ws 3M sw0: 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/128t32Zg32,I1/128t32Zg32 2,I16/4096t32Rg512,I16/4096t32Rg512 2,I1/100032t32Zg32,I32/100032t32Rg1024
+pair ww ws 3M sw1: 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/128t32Zg32,I1/128t32Zg32 2,I16/4096t32Rg512,I16/4096t32Rg512 2,I1/100032t32Zg32,I32/100032t32Rg1024
+pair ww shapes differ sw0: 2,I1/64t32Zg32,I1/64t16Zg16 2,I1/64t32Zg32,I1/64t16Zg16 2,I1/64t32Zg32,I1/64t16Zg16 2,I1/64t32Zg32,I1/64t16Zg16 2,I1/128t32Zg32,I1/128t16Zg16 2,I16/4096t32Rg512,I16/4096t16Rg256 2,I32/100032t32Rg1024,I64/100032t16Rg1024
+pair ww shapes differ sw1: 2,I1/64t32Zg32,I1/64t16Zg16 2,I1/64t32Zg32,I1/64t16Zg16 2,I1/64t32Zg32,I1/64t16Zg16 2,I1/64t32Zg32,I1/64t16Zg16 2,I1/128t32Zg32,I1/128t16Zg16 2,I16/4096t32Rg512,I16/4096t16Rg256 2,I32/100032t32Rg1024,I64/100032t16Rg1024
+pair ww ws misaligned sw0: 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/128t32Zg32,I1/128t32Zg32 2,I1/4096t32Zg32,I16/4096t32Rg512 2,I1/100032t32Zg32,I32/100032t32Rg1024
+pair ww ws misaligned sw1: 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/64t32Zg32,I1/64t32Zg32 2,I1/128t32Zg32,I1/128t32Zg32 2,I1/4096t32Zg32,I16/4096t32Rg512 2,I1/100032t32Zg32,I32/100032t32Rg1024
+pair ww b A misaligned sw0: 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/128t32Zg32,G1/128v01t32Zg32 2,I16/4096t32Rg512,G16/4096v01t32Rg512 2,I32/100032t32Rg1024,G32/100032v01t32Rg1024
+pair ww b A misaligned sw1: 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/128t32Zg32,G1/128v01t32Zg32 2,I16/4096t32Rg512,G16/4096v01t32Rg512 2,I32/100032t32Rg1024,G32/100032v01t32Rg1024
+pair ww b stored nn sw0: 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/128t32Zg32,G1/128v01t32Zg32 2,I16/4096t32Rg512,G16/4096v01t32Rg512 2,I32/100032t32Rg1024,G32/100032v01t32Rg1024
+pair ww b stored nn sw1: 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/64t32Zg32,G1/64v01t32Zg32 2,I1/128t32Zg32,G1/128v01t32Zg32 2,I16/4096t32Rg512,G16/4096v01t32Rg512 2,I32/100032t32Rg1024,G32/100032v01t32Rg1024
+pair ww guarded sw0: 2,G1/64t32Zg32,G1/64t32Zg32 2,G1/64t32Zg32,G1/64t32Zg32 2,G1/64t32Zg32,G1/64t32Zg32 2,G1/64t32Zg32,G1/64t32Zg32 2,G1/128t32Zg32,G1/128t32Zg32 2,G16/4096t32Rg512,G16/4096t32Rg512 2,G32/100032t32Rg1024,G32/100032t32Rg1024
+pair ww guarded sw1: 2,G1/64t32Zg32,G1/64t32Zg32 2,G1/64t32Zg32,G1/64t32Zg32 2,G1/64t32Zg32,G1/64t32Zg32 2,G1/64t32Zg32,G1/64t32Zg32 2,G1/128t32Zg32,G1/128t32Zg32 2,G16/4096t32Rg512,G16/4096t32Rg512 2,G32/100032t32Rg1024,G32/100032t32Rg1024
+pair xx sw0: F4,I1/512t4g4,I1/96t2g2 F4,I1/512t4g4,I1/96t2g2 F4,I1/512t4g4,I1/96t2g2 F4,I1/512t4g4,I1/96t2g2 F8,I1/512t8g8,I1/96t4g4 F256,I1/512t256g256,I1/96t128g128 F1024,I1/512t6252g1024,I1/96t3126g1024
+pair xx sw1: F4,I1/512t4g4,I1/96t2g2 F4,I1/512t4g4,I1/96t2g2 F4,I1/512t4g4,I1/96t2g2 F4,I1/512t4g4,I1/96t2g2 F8,I1/512t8g8,I1/96t4g4 F256,I1/512t256g256,I1/96t128g128 F1024,I1/512t6252g1024,I1/96t3126g1024
+pair xx b guarded sw0: 2,I1/512t4g4,G1/96t2g2 2,I1/512t4g4,G1/96t2g2 2,I1/512t4g4,G1/96t2g2 2,I1/512t4g4,G1/96t2g2 2,I1/512t8g8,G1/96t4g4 2,I1/512t256g256,G1/96t128g128 2,I1/512t6252g1024,G1/96t3126g1024
+pair xx b guarded sw1: 2,I1/512t4g4,G1/96t2g2 2,I1/512t4g4,G1/96t2g2 2,I1/512t4g4,G1/96t2g2 2,I1/512t4g4,G1/96t2g2 2,I1/512t8g8,G1/96t4g4 2,I1/512t256g256,G1/96t128g128 2,I1/512t6252g1024,G1/96t3126g1024
+pair xx a K guarded sw0: 2,G1/50v01t4g4,I1/96t2g2 2,G1/50v01t4g4,I1/96t2g2 2,G1/50v01t4g4,I1/96t2g2 2,G1/50v01t4g4,I1/96t2g2 2,G1/50v01t8g8,I1/96t4g4 2,G1/50v01t256g256,I1/96t128g128 2,G1/50v01t6252g1024,I1/96t3126g1024
+pair xx a K guarded sw1: 2,G1/50v01t4g4,I1/96t2g2 2,G1/50v01t4g4,I1/96t2g2 2,G1/50v01t4g4,I1/96t2g2 2,G1/50v01t4g4,I1/96t2g2 2,G1/50v01t8g8,I1/96t4g4 2,G1/50v01t256g256,I1/96t128g128 2,G1/50v01t6252g1024,I1/96t3126g1024
+pair xx a A misaligned sw0: 2,G1/512v01t4g4,I1/96t2g2 2,G1/512v01t4g4,I1/96t2g2 2,G1/512v01t4g4,I1/96t2g2 2,G1/512v01t4g4,I1/96t2g2 2,G1/512v01t8g8,I1/96t4g4 2,G1/512v01t256g256,I1/96t128g128 2,G1/512v01t6252g1024,I1/96t3126g1024
+pair xx a A misaligned sw1: 2,G1/512v01t4g4,I1/96t2g2 2,G1/512v01t4g4,I1/96t2g2 2,G1/512v01t4g4,I1/96t2g2 2,G1/512v01t4g4,I1/96t2g2 2,G1/512v01t8g8,I1/96t4g4 2,G1/512v01t256g256,I1/96t128g128 2,G1/512v01t6252g1024,I1/96t3126g1024
+pair xx b stored tn sw0: 2,I1/512t4g4,G1/96v01t2g2 2,I1/512t4g4,G1/96v01t2g2 2,I1/512t4g4,G1/96v01t2g2 2,I1/512t4g4,G1/96v01t2g2 2,I1/512t8g8,G1/96v01t4g4 2,I1/512t256g256,G1/96v01t128g128 2,I1/512t6252g1024,G1/96v01t3126g1024
+pair xx b stored tn sw1: 2,I1/512t4g4,G1/96v01t2g2 2,I1/512t4g4,G1/96v01t2g2 2,I1/512t4g4,G1/96v01t2g2 2,I1/512t4g4,G1/96v01t2g2 2,I1/512t8g8,G1/96v01t4g4 2,I1/512t256g256,G1/96v01t128g128 2,I1/512t6252g1024,G1/96v01t3126g1024
+pair xx b batched sw0: 2,I1/512t4g4,x 2,I1/512t4g4,x 2,I1/512t4g4,x 2,I1/512t4g4,x 2,I1/512t8g8,x 2,I1/512t256g256,x 2,I1/512t6252g1024,x
+pair xx b batched sw1: 2,I1/512t4g4,x 2,I1/512t4g4,x 2,I1/512t4g4,x 2,I1/512t4g4,x 2,I1/512t8g8,x 2,I1/512t256g256,x 2,I1/512t6252g1024,x
+"""
+
+
+def test_gemm_plan_is_the_decision_the_scattered_predicates_made():
+    """gcgcn_debug_gemm_plan (the plan function every launcher of gemm.hip calls) gives, for every row, the launch the code before it
+    chose: interior or guarded, split factor, ksplit, widen, kept row-block mode, vector flags, tiles, reduce and zero-fill launches,
+    grid, and for a pair fused or not and gridW.  No tolerance, no row left out."""
+    import ctypes
+    import numpy as np
+
+    def plan(form, a, b, splits, group_work, cap):
+        out = np.full(26, -7, np.int32)
+        pa = (ctypes.c_int64 * 13)(*a)
+        pb = (ctypes.c_int64 * 13)(*b) if b is not None else None
+        _lib.call("gcgcn_debug_gemm_plan", form, pa, pb, splits, group_work, cap, out.ctypes.data_as(ctypes.c_void_p))
+        return [int(v) for v in out]
+
+    got, plans = gemm_plan_table(plan, lambda name, v: _lib.call("gcgcn_set_option", name.encode(), v))
+    want = GEMM_PLAN_EXPECTED.strip("\n").split("\n")
+    assert len(got) == len(want) == 2 * (3 * len(GEMM_PLAN_CASES) + len(GEMM_PAIR_CASES)) == 212
+    assert plans == 2 * ((5 + 2 * len(GEMM_PLAN_CAPS)) * len(GEMM_PLAN_CASES) + len(GEMM_PLAN_CAPS) * len(GEMM_PAIR_CASES)) == 1372
+    wrong = [f"want {w}\n got {g}" for g, w in zip(got, want) if g != w]
+    assert not wrong, "\n".join(wrong[:20])
