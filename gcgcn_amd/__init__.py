@@ -9,8 +9,8 @@ from .modules import (ClassifierHead, EdgeFeatureProducer, GraphModelTail, GATAt
 from .functional import manual_seed, pair_bce_loss  # noqa: F401
 from . import evaluation, functional, models, optim, params  # noqa: F401
 from .evaluation import EvalResult, RelationEvaluator, evaluate  # noqa: F401
-from .optim import FusedAdam  # noqa: F401
+from .optim import FusedAdam, GraphedTrainStep  # noqa: F401
 
 __all__ = ["GraphConv", "GATAttention", "MultiHeadAttention", "GraphConvolution", "MultiGraphConvolution", "GraphHops",
            "EdgeFeatureProducer", "ClassifierHead", "GraphModelTail",
-           "manual_seed", "pair_bce_loss", "FusedAdam", "RelationEvaluator", "EvalResult", "evaluate", "evaluation", "functional", "models", "optim", "params"]
+           "manual_seed", "pair_bce_loss", "FusedAdam", "GraphedTrainStep", "RelationEvaluator", "EvalResult", "evaluate", "evaluation", "functional", "models", "optim", "params"]

@@ -452,6 +452,22 @@ int gcgcn_gemm_dyn(int M, int N, int K, const float* A, int64_t lda, int a_kc, c
  * parameter whose .grad is None and does not advance its t).  Arithmetic as torch.optim.Adam's single-tensor path. */
 int gcgcn_adam_step(int n_tensors, const void* table, int64_t total_blocks, double beta1, double beta2, double eps, void* stream);
 
+/* The same step with everything that changes from step to step read on the device, so that a hipGraph which holds the call
+ * trains when it is replayed.  The table keeps its 56-byte records, but their last 8 bytes are `float* step`: the tensor's own
+ * step counter, an fp32 device scalar (torch.optim.Adam(capturable=True)'s state["step"]).  One call, on `stream`:
+ *   1. max_norm > 0 only: total = sqrt(sum g^2) over every element of every tensor of the table (fp32, one partial per
+ *      workgroup in ws, added in a fixed order: bit-reproducible, no float atomics); *grad_norm = total (the norm BEFORE
+ *      clipping; grad_norm may be NULL); coef = min(1, max_norm / (total + 1e-6)), torch.nn.utils.clip_grad_norm_'s formula.
+ *      A non-finite norm propagates into the parameters (torch's error_if_nonfinite=False).
+ *   2. per tensor: *step += 1; step_size = *lr / (1 - beta1^t) and inv_bc2_sqrt = 1 / sqrt(1 - beta2^t) in double, rounded to
+ *      fp32, into ws.  lr is an fp32 device scalar.
+ *   3. gcgcn_adam_step's update with g * coef in place of g.  The gradients themselves are NOT modified.
+ * At most three launches (two when max_norm <= 0); no host read, no allocation, no stream synchronisation.  ws: device memory,
+ * 16-byte aligned, ws_bytes >= gcgcn_adam_ws_bytes(n_tensors, total_blocks); its contents need not survive between calls. */
+int64_t gcgcn_adam_ws_bytes(int n_tensors, int64_t total_blocks);
+int gcgcn_adam_step_dev(int n_tensors, const void* table, int64_t total_blocks, double beta1, double beta2, double eps,
+                        const float* lr, double max_norm, void* ws, int64_t ws_bytes, float* grad_norm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,12 @@ reported as documents/second with the per-part split.  Synthetic DocRED-shaped d
 tokens, entity counts ~ clip(round(N(19.5, 6^2)), 2, 42), one to three mentions per entity, an edge for every ordered pair
 of entities sharing a sentence (up to max_num = 5 sentence slots per pair), 3 % positive labels.
 
-    python tools/train_step_bench.py [--B 32] [--steps 10] [--skip-dead-hop] [--torch-adam]
+    python tools/train_step_bench.py [--B 32] [--steps 10] [--skip-dead-hop] [--torch-adam] [--capturable] [--max-grad-norm C]
+
+The graph mode replays gcgcn_amd.GraphedTrainStep objects over FusedAdam(capturable=True): the step counters and the learning
+rate are read on the device, so what is timed is a step that trains (the default FusedAdam, captured, would replay the bias
+correction of the step at which it was captured).  The eager steps use the default FusedAdam unless --capturable (or
+--max-grad-norm, which needs it) asks for the same optimiser there.
 """
 import argparse
 import ctypes
@@ -85,6 +90,9 @@ def main():
     ap.add_argument("--vocab", type=int, default=20000)
     ap.add_argument("--skip-dead-hop", action="store_true", help="do not compute the hop whose output never reaches the classifier")
     ap.add_argument("--torch-adam", action="store_true", help="A/B: torch.optim.Adam instead of FusedAdam")
+    ap.add_argument("--capturable", action="store_true", help="the eager steps use FusedAdam(capturable=True) too (the graph always does)")
+    ap.add_argument("--max-grad-norm", type=float, default=None, help="clip by the global gradient norm inside the optimiser step "
+                                                                       "(FusedAdam(capturable=True, max_grad_norm=...))")
     ap.add_argument("--mode", default="both", choices=["eager", "graph", "both"],
                     help="graph: additionally, forward -> loss -> backward -> optimiser step of each resident batch captured in one hipGraph "
                          "(collate stays on the host, outside the graph) and the replays timed; eager: launches from Python only")
@@ -103,7 +111,13 @@ def main():
     gcgcn_amd.manual_seed(1337, dev)
     F_.check_ids = False                     # the ids of these batches come from collate (validated once below)
     params = [p for p in model.parameters() if p.requires_grad]
-    opt = (torch.optim.Adam if a.torch_adam else FusedAdam)(params, lr=1e-4)          # Config.py:300, learn_rate 1e-4 (:72)
+    capturable = a.capturable or a.max_grad_norm is not None
+    if a.torch_adam and capturable:
+        ap.error("--torch-adam is the A/B against the default FusedAdam: not with --capturable / --max-grad-norm")
+    if a.torch_adam:
+        opt = torch.optim.Adam(params, lr=1e-4)                                       # Config.py:300, learn_rate 1e-4 (:72)
+    else:
+        opt = FusedAdam(params, lr=1e-4, capturable=capturable, max_grad_norm=a.max_grad_norm)
     order = ("document", "document_ner", "document_pos", "adj_matrix", "sen_matrix", "pos_matrix_h", "pos_matrix_t", "node_pos",
              "node_type", "node_relative_pos")
     parts = {}
@@ -137,28 +151,28 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.steps
     split = {n: round(sum(e0.elapsed_time(e1) for e0, e1 in evs) / a.steps, 3) for n, evs in parts.items()}
-    ms_mode = {"eager": round(dt * 1e3, 3)}
+    ms_mode, graph_opt = {"eager": round(dt * 1e3, 3)}, None
     if a.mode != "eager":                    # the device side of the step as one hipGraph per resident batch
         import _graph_mode
         resident = [collate(b, dev) for b in batches]
 
-        def model_step(bt):
+        def model_step(**bt):
             logits = model(*[bt[n] for n in order], n_valid=bt["n_valid"])
-            loss = gcgcn_amd.pair_bce_loss(logits, bt["label_matrix"], n_valid=bt["n_valid"]).sum() / a.B
-            opt.zero_grad(set_to_none=True)
-            loss.backward()
-            opt.step()
+            return gcgcn_amd.pair_bce_loss(logits, bt["label_matrix"], n_valid=bt["n_valid"]).sum() / a.B
 
-        graphs = [_graph_mode.capture(lambda bt=bt: model_step(bt)) for bt in resident]
-        if all(g is not None for g in graphs):
-            cnt = [0]
+        # one graph per resident batch, all over ONE optimiser whose counters every replay advances
+        gopt = opt if capturable else FusedAdam(params, lr=1e-4, capturable=True)
+        graphs = [gcgcn_amd.GraphedTrainStep(model_step, gopt, {k: v for k, v in bt.items() if k in order + ("n_valid", "label_matrix")})
+                  for bt in resident]
+        cnt = [0]
 
-            def replay():
-                graphs[cnt[0] % len(graphs)].replay()
-                cnt[0] += 1
-            for _ in range(3):
-                replay()
-            ms_mode["graph (collate outside)"] = round(_graph_mode.wall_ms(replay, a.steps), 3)
+        def replay():
+            graphs[cnt[0] % len(graphs)]()
+            cnt[0] += 1
+        for _ in range(3):
+            replay()
+        ms_mode["graph (collate outside)"] = round(_graph_mode.wall_ms(replay, a.steps), 3)
+        graph_opt = "FusedAdam(capturable=True" + (f", max_grad_norm={a.max_grad_norm})" if a.max_grad_norm else ")")
     # GPU time of the model's parts inside forward + backward (HIP events around the library's own launches)
     groups = {"encoder (PyTorch: embeddings, BiLSTM, linear_re) + everything outside the library": None,
               "edge-feature producers (f1)": ["prod_", "gemm_dyn"], "classifier head (f3)": ["head_"],
@@ -181,9 +195,9 @@ def main():
     nv = np.mean([d.n for b in batches for d in b])
     print(json.dumps({
         "metric": "docs/sec, full training step of GCGCN_glove (collate -> forward -> loss -> backward -> Adam)", "value": round(a.B / dt, 1),
-        "unit": "docs/s", "ms_per_step": round(dt * 1e3, 3), "ms_per_step_by_mode": ms_mode, "dtype": "f32", "data": "synthetic",
+        "unit": "docs/s", "ms_per_step": round(dt * 1e3, 3), "ms_per_step_by_mode": ms_mode, "graph_optimiser": graph_opt, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"B={a.B} DocRED-shaped documents (T=512, mean {nv:.1f} entities, padded per batch), vocabulary {a.vocab}, "
-                               f"train mode, {'FusedAdam (one launch)' if not a.torch_adam else 'torch.optim.Adam'}, eager launches, "
+                               f"train mode, {'torch.optim.Adam' if a.torch_adam else 'FusedAdam(capturable=True)' if capturable else 'FusedAdam (one launch)'}, eager launches, "
                                f"{a.batches} resident packed batches rotated" + (", dead last hop skipped" if a.skip_dead_hop else "")},
         "ms_per_step_by_stage (stream time between HIP events, includes launch gaps)": split,
         "gpu_ms_per_step_by_part (library kernels in forward + backward)": by_part,
