@@ -257,7 +257,8 @@ int gcgcn_edge_mean_fwd_compact(int B, int N, int D, const float* Ec, const int3
 
 int gcgcn_edge_mean_bwd_compact(int B, int N, int D, const int32_t* prow, const int32_t* n_valid, const float* dEbar, float* dEc,
                                 float* dbias, float* rowbuf, void* stream) {
-  GC_REQUIRE(B > 0 && N > 0 && D > 0 && D <= 64 * CMAXK, "edge_mean_bwd_compact: bad shape B=%d N=%d D=%d", B, N, D);
+  GC_REQUIRE(B > 0 && N > 0 && D > 0, "edge_mean_bwd_compact: bad shape B=%d N=%d D=%d", B, N, D);
+  GC_REQUIRE(D <= 64 * CMAXK, "edge_mean_bwd_compact: hidden width %d (compact rows support up to %d)", D, 64 * CMAXK);
   GC_REQUIRE(prow && dEbar && dEc && dbias && rowbuf, "edge_mean_bwd_compact: null pointer");
   const CmpE ce{nullptr, prow, nullptr};
   return cmp_bwd(ce, nullptr, n_valid, nullptr, dEbar, dEc, nullptr, rowbuf, dbias, B, N, D, (hipStream_t)stream);

@@ -188,7 +188,7 @@ class GatFn(torch.autograd.Function):
         call("gcgcn_gat_fwd", B, N, D, Dh, _p(x), _p(e), _p(n_valid), _p(flat), _p(snap), float(p), _p(uvc), _p(s),
              _p(P), _p(A), _p(ebar), _p(st), _p(sn), cnt, _p(mask), 1 if uvc_valid else 0, _stream())
         ctx.save_for_backward(x, e, flat, uvc, P)
-        ctx.n_valid, ctx.p, ctx.snap, ctx.Dh = n_valid, float(p), snap, Dh
+        ctx.n_valid, ctx.p, ctx.snap, ctx.Dh, ctx.mask = n_valid, float(p), snap, Dh, mask
         return (P if A is None else A), ebar, x.view_as(x)
 
     @staticmethod
@@ -197,6 +197,14 @@ class GatFn(torch.autograd.Function):
         B, N, D = x.shape
         dev = x.device
         dA = torch.zeros(B, N, N, device=dev) if dA is None else dA.contiguous()
+        if ctx.mask is not None:
+            # opt-in mask: masked_fill passes no gradient to a masked energy.  In a partially masked row those entries have
+            # P == 0 and the kernels' P (g - P.g) is zero by itself; a row whose real columns are ALL masked comes out
+            # uniform (P = 1/n), so its dA row is cleared here -- the kernels then give that row a zero logit gradient
+            gone = ctx.mask.bool()
+            if ctx.n_valid is not None:
+                gone = gone | (torch.arange(N, device=dev)[None, None, :] >= ctx.n_valid[:, None, None])
+            dA = dA.masked_fill(gone.all(-1, keepdim=True), 0.0)
         dEbar = None if dEbar is None else dEbar.contiguous()
         dXin = None if dXin is None else dXin.contiguous()
         dX = torch.empty_like(x)

@@ -108,8 +108,10 @@ int gcgcn_gat_layout(int D, int Dh, int64_t* out9);
  * point into rng_snaps): a hop loop draws the snapshots of all its dropout sites without a launch of its own.
  * mask: NULL (default: the reference DISCARDS its masked_fill result, glove:163-164, so its mask is a no-op), or a
  * uint8/bool [B,N,N] whose non-zero entries get energy -100000 before the softmax: the paper-faithful partially
- * connected adjacency, an explicit opt-in (GATAttention(apply_mask=True)).  The backward needs no mask: masked entries
- * have P == 0 exactly, hence a zero logit gradient.
+ * connected adjacency, an explicit opt-in (GATAttention(apply_mask=True)).  The backward needs no mask where a row keeps an
+ * unmasked real column: its masked entries have P == 0 exactly, hence a zero logit gradient.  A row whose real columns are
+ * ALL masked comes out uniform, and masked_fill passes no gradient through it: the caller of gcgcn_gat_bwd clears that row
+ * of dA (functional.GatFn does).
  * uvc_valid != 0: uvc already holds the folded projection of THESE parameters (a function of flat only: the caller may
  * keep it while flat is unchanged -- inference, several documents per optimiser step); the fold kernel is skipped. */
 int gcgcn_gat_fwd(int B, int N, int D, int Dh, const float* X, const float* E, const int32_t* n_valid, const float* flat,
