@@ -1007,7 +1007,8 @@ __global__ __launch_bounds__(256) void head_tables_bwd_kernel(const float* __res
 // =====================================================================================================================
 struct HeadLayout { long Wd, bd, Wc, bc, bb, Wb, total; int Fin; };
 // flat = [dense_layer W [128, Fin] | b | classification_layer_01 W [R, 256] | b | bili b [R] | bili W [R, 128, 128]]
-// (the bilinear weight last: the padded linear products read up to 31 rows past W_c, which must stay inside the buffer)
+// (the bilinear weight last: the padded linear products read up to 31 rows past W_c -- R rounded up to the 32-deep k-step,
+// head_bwd's KE -- which must stay inside the buffer: 31 x 256 floats < the 16384 of the bilinear weight's first row)
 static HeadLayout head_layout(int Hd, int nf, int Pt, int Pr, int R) {
   HeadLayout y;
   y.Fin = Hd * nf + Pt + Pr;
@@ -1099,9 +1100,13 @@ int head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int di
   }
   // The W_c products over the pair rows, side q = 0: eh, 1: et.  Compacted, the row count is on the device: the two sides share
   // one gemm_dyn_pair launch; dense, each is a launch of its own (the data gradients then need no workspace).
+  // K of dout W_c: R rounded up to the k-step, NOT the 128 columns of doutp -- the rows of W_c past R are whatever follows it in
+  // flat (head_layout keeps 31 rows inside the buffer; with K = 128 and R = 1 the product read 64 KB past the END of flat, and
+  // 0 x what it found there is NaN as soon as that memory holds one)
+  const int KE = (R + BK - 1) / BK * BK;
   GemmArgs dE_c[2], dW_c[2];
   for (int q = 0; q < 2; ++q) {
-    dE_c[q] = gemm_nn(w.doutp, HW, flat + y.Wc + q * HW, 2 * HW, q ? w.dET : w.dEH, HW, (int)pairs, HW, HW).tagged("head_gemm");
+    dE_c[q] = gemm_nn(w.doutp, HW, flat + y.Wc + q * HW, 2 * HW, q ? w.dET : w.dEH, HW, (int)pairs, HW, KE).tagged("head_gemm");
     dE_c[q].accumulate = 1;   // d e += dout W_c[:, q * 128 ...]
     if (compact) dE_c[q].split_ws(ws, wse);
     dW_c[q] = gemm_tn(w.doutp, HW, q ? w.ET : w.EH, HW, w.dW + q * HW, 2 * HW, HW, HW, (int)pairs).split_ws(ws, wse).tagged("head_gemm");
@@ -1264,6 +1269,7 @@ int gcgcn_head_fwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, 
                    const int64_t* node_type, const int64_t* node_relative_pos, const float* ner_emb, const float* dis_table,
                    const int32_t* n_valid, const float* flat, float* fbuf, int32_t* ibuf, float* logits, void* stream) {
   GC_REQUIRE(B > 0 && N > 0 && Hd > 0 && nf > 0 && nf <= 8 && Pt > 0 && Pr > 0 && R > 0 && ND > 0, "head_fwd: bad shape");
+  GC_REQUIRE(ND <= HT_IDS, "head_fwd: the distance table has %d rows, the head handles at most %d (gcgcn_head_bwd's per-id sums)", ND, HT_IDS);
   GC_REQUIRE(Hd % 4 == 0 && Pt % 4 == 0 && Pr % 4 == 0, "head_fwd: feature widths must be multiples of 4 (16-byte rows)");
   GC_REQUIRE(feats && node_type && node_relative_pos && ner_emb && dis_table && flat && fbuf && logits, "head_fwd: null pointer");
   GC_REQUIRE(!n_valid || ibuf, "head_fwd: n_valid given without ibuf");
@@ -1277,7 +1283,8 @@ int gcgcn_head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, 
                    const int64_t* node_type, const int64_t* node_relative_pos, const float* ner_emb, const float* dis_table,
                    const int32_t* n_valid, const float* flat, float* fbuf, int32_t* ibuf, float* bbuf, const float* dlogits,
                    float* const* dfeats, float* dner_emb, float* ddis_table, float* dflat, void* stream) {
-  GC_REQUIRE(B > 0 && N > 0 && Hd > 0 && nf > 0 && nf <= 8 && Pt > 0 && Pr > 0 && R > 0 && ND > 0 && ND <= HT_IDS, "head_bwd: bad shape");
+  GC_REQUIRE(B > 0 && N > 0 && Hd > 0 && nf > 0 && nf <= 8 && Pt > 0 && Pr > 0 && R > 0 && ND > 0, "head_bwd: bad shape");
+  GC_REQUIRE(ND <= HT_IDS, "head_bwd: the distance table has %d rows, the head handles at most %d (the per-id sums in LDS)", ND, HT_IDS);
   GC_REQUIRE(feats && node_type && node_relative_pos && ner_emb && dis_table && flat && fbuf && bbuf && dlogits && dfeats && dner_emb &&
                  ddis_table && dflat,
              "head_bwd: null pointer");

@@ -849,6 +849,7 @@ class HeadFn(torch.autograd.Function):
 # switch it off (``gcgcn_amd.functional.check_ids = False``).
 check_ids = True
 NER_ROWS = 7        # nn.Embedding(7, entity_type_size, padding_idx=0), GCGCN_glove.py:241 -- the head's kernels index 7 rows
+HEAD_MAX_DIS_ROWS = 32   # csrc/head.hip HT_IDS: rows of dis_embed the head's backward pass can sum
 
 
 def _check_id_range(checks):
@@ -876,6 +877,9 @@ def classifier_head(feats, node_type, node_relative_pos, ner_emb, dis_table, fla
         raise ValueError(f"ner_emb.weight: the head indexes {NER_ROWS} rows (nn.Embedding(7, .), glove:241), got {tuple(ner_emb.shape)}")
     if dis_table.dim() != 2 or dis_table.shape[0] < 2 * int(dis_plus) + 1:
         raise ValueError(f"dis_embed.weight: needs at least 2 * dis_plus + 1 = {2 * int(dis_plus) + 1} rows, got {tuple(dis_table.shape)}")
+    if dis_table.shape[0] > HEAD_MAX_DIS_ROWS:
+        raise ValueError(f"dis_embed.weight: the head handles at most {HEAD_MAX_DIS_ROWS} rows of the distance table (its backward "
+                         f"pass keeps one sum per id in LDS), got {tuple(dis_table.shape)}")
     _check_id_range([("node_type", node_type, 0, NER_ROWS - 1),
                      ("node_relative_pos", node_relative_pos, -int(dis_plus), int(dis_plus))])
     return HeadFn.apply(_chk(flat, "flat"), _chk(ner_emb, "ner_emb.weight", 2), _chk(dis_table, "dis_embed.weight", 2),

@@ -523,7 +523,12 @@ class ClassifierHead(_FlatBlock):
                 dis_embed_weight: Tensor, n_valid: Optional[Tensor] = None) -> Tensor:
         """node_feats: the model's list (``graph_hop + 1`` tensors ``[N,H]`` or ``[B,N,H]``, glove:311/338); node_type
         ``Long[N]``; node_relative_pos ``Long[N,N]`` in ``-dis_plus..dis_plus``.  Returns ``relation_before_softmax_01``:
-        ``[N,N,R]`` or ``[B,N,N,R]``."""
+        ``[N,N,R]`` or ``[B,N,N,R]``.
+
+        With ``n_valid`` (``int32[B]``) the ids and the incoming gradient of padding slots may hold anything in range / anything
+        at all, and the feature gradients of padding entities are exactly zero; the *feature rows* of padding entities must be
+        finite (the dense layer's weight gradient multiplies them by an exact zero).  ``dis_embed_weight`` has between
+        ``2 * dis_plus + 1`` and 32 rows."""
         if len(node_feats) != self.nf:
             raise ValueError(f"node_feats: expected {self.nf} tensors (graph_hop + 1), got {len(node_feats)}")
         batched = node_feats[0].dim() == 3

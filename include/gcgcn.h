@@ -363,7 +363,13 @@ int gcgcn_gat_bwd_compact(int B, int N, int D, int Dh, const float* X, const flo
  * n_valid (ABI v5): the reference runs these lines on ONE unpadded document (n x n pairs).  With n_valid the pair passes run on
  * the pairs that exist only -- rows of eh / et / their gradients compacted on the device (row off[b] + i n_b + j, off = prefix
  * sums of n_b^2; no host read, capturable), 2 x 128 x 128 x R flops per existing pair and pass instead of per pair slot of the
- * padded batch -- and logits of pairs with a padding entity are exactly zero.  n_valid == NULL: every slot is computed. */
+ * padded batch -- and logits of pairs with a padding entity are exactly zero.  n_valid == NULL: every slot is computed.
+ * Padding contents: node_type / node_relative_pos of padding slots may hold any id in range, dlogits of padding pairs anything
+ * (NaN included); no real result depends on them, and dfeats of padding entities are exactly zero.  The feats rows of padding
+ * entities must be FINITE: the dense layer's weight gradient is dUT^T feats over all B N rows with dUT exactly zero on the
+ * padding rows (0 x finite = 0, 0 x NaN = NaN), and for R outside 65..97 every pair slot is computed from them.
+ * dis_table: 2 dis_plus + 1 <= ND <= 32 rows (the backward pass keeps one table of partial sums per id in LDS); both entry
+ * points refuse more. */
 int gcgcn_head_layout(int Hd, int nf, int Pt, int Pr, int R, int64_t* out7);
 int gcgcn_head_sizes(int B, int N, int R, int ND, int64_t* out3);
 int gcgcn_head_fwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int dis_plus, const float* const* feats,
