@@ -10,6 +10,7 @@
 
 #include <stdlib.h>
 
+#include "compact.hpp"
 #include "gat_body.hpp"
 #include "gcn_plan.hpp"
 #include "gemm.hpp"
@@ -187,6 +188,56 @@ static GcnCtx make_ctx(int B, int N, int D, int L, int H, const GcnLayout& y, co
   return c;
 }
 
+// ---- GATAttention's node phase around the edge pass, once for dense E and for compact rows -------------------------------------
+struct EdgeOperand {   // the edge tensor of a GATAttention call: dense E[B, N, N, D], or compact rows (E == nullptr)
+  const float* E;
+  CmpE ce;
+};
+
+// uvc = the folded projections (unless the caller kept them from an earlier call with the same parameters), s = u . x + c.
+// The rng draw, if asked for, rides in whichever of the two launches comes first.
+static int gat_node_fwd(const float* X, const float* flat, float* uvc, float* s, long M, int D, int Dh, int uvc_valid, void* rng_state,
+                        void* rng_snaps, int rng_count, hipStream_t st) {
+  if (!uvc_valid) {
+    GC_TRY(gat_fold_fwd(flat, uvc, D, Dh, st, rng_state, rng_snaps, rng_count));  // + gcgcn_rng_next, if asked to
+    return node_score_fwd(X, uvc, s, M, D, st);
+  }
+  return node_score_fwd(X, uvc, s, M, D, st, rng_state, rng_snaps, rng_count);
+}
+
+// dlogit by the plan's route, the edge pass on either operand (dE: dE[B, N, N, D], or dEc with dbias for compact rows), then
+// du / dv / dc and the fold's backward
+static int gat_bwd(const EdgeOperand& eo, int B, int N, int D, int Dh, const float* X, const int* n_valid, const float* flat, Drop drop,
+                   const float* uvc, const float* P, const float* dA, const float* dEbar, const float* dX_in, float* dX, float* dE,
+                   float* dbias, float* dflat, float* dlogit, float* ds, float* dvpart, float* duvc, float* scratch, DeferQueue* dq,
+                   hipStream_t st) {
+  const bool compact = eo.E == nullptr;
+  const long M = (long)B * N;
+  const float* v = uvc + D;
+  const EdgePlan plan = edge_plan_bwd({B, N, D, compact, true, dE != nullptr, dEbar != nullptr,
+                                       compact ? 0u : edge_misalign(eo.E, v, dE, dEbar, nullptr)});
+  const GatTail tail{P, dA, uvc, dX_in, ds, dX, drop, B, plan.slices};
+  if (plan.route == EdgePlan::ONE) {
+    GC_TRY(gat_dlogit(P, dA, uvc, dX_in, dlogit, ds, dX, B, N, D, plan.slices, drop, st));
+  } else if (plan.route == EdgePlan::THREE) {
+    GC_TRY(softmax_bwd(P, dA, dlogit, M, N, drop, st));
+    // ds[b, j] = sum_i dlogit[b, i, j]
+    GC_TRY(colsum(dlogit, nullptr, ds, N, N, N, B, (long)N * N, 0, N, 0, nullptr, st));
+    GC_TRY(node_score_bwd(ds, uvc, dX_in, dX, M, D, st));
+  }  // RIDE: dlogit, ds and dX = ds u + dX_in ride in the dense edge pass below (`tail`; dlogit is never stored)
+  if (compact)
+    GC_TRY(cmp_bwd(eo.ce, v, n_valid, dlogit, dEbar, dE, dvpart, scratch + plan.rowbuf_off, dbias, plan, B, N, D, st));
+  else
+    GC_TRY(edge_bwd(eo.E, v, n_valid, dlogit, dEbar, dE, dvpart, plan, B, N, D, st, dq, &tail));  // + parked weight gradients
+  // du = sum_m ds[m] X[m,:],  dv = sum partials,  dc = sum_m ds[m]: row-slice partials in one launch; the fold's
+  // backward sums the slices itself (duvc stays unused)
+  long part_off[3];
+  int ns = 0;
+  GC_TRY(colsum3(X, ds, duvc, M, D, D, dvpart, nullptr, duvc + D, M, D, D, ds, nullptr, duvc + 2 * D, M, 1, 1, scratch,
+                 st, false, part_off, &ns));
+  return gat_fold_bwd(flat, duvc, dflat, D, Dh, st, scratch, part_off, ns);
+}
+
 }  // namespace gc
 
 using namespace gc;
@@ -269,7 +320,7 @@ int gcgcn_dropout(const float* x, float* y, int64_t n, const void* rng_snap, uin
 }
 
 // ---------------------------------------------------------------------------------------------
-// GATAttention
+// GATAttention and the edge mean, on a dense E or on the producer's compact rows (compact.hip)
 // ---------------------------------------------------------------------------------------------
 int gcgcn_gat_layout(int D, int Dh, int64_t* o) {
   GC_REQUIRE(D > 0 && Dh > 0 && o, "gat_layout: bad arguments");
@@ -295,56 +346,49 @@ int gcgcn_gat_fwd(int B, int N, int D, int Dh, const float* X, const float* E, c
   GC_REQUIRE(X && E && flat && uvc && s && P && Ebar, "gat_fwd: null pointer");
   const Drop drop = make_drop(rng_snap, GCGCN_SALT_GAT, p);
   GC_REQUIRE(!drop.snap || A, "gat_fwd: dropout on but A is NULL");
-  const long M = (long)B * N;
   GC_REQUIRE(!rng_state || (rng_snaps && rng_count > 0), "gat_fwd: rng_state given without snapshots to fill");
-  if (!uvc_valid) {
-    GC_TRY(gat_fold_fwd(flat, uvc, D, Dh, st, rng_state, rng_snaps, rng_count));  // + gcgcn_rng_next, if asked to
-    GC_TRY(node_score_fwd(X, uvc, s, M, D, st));
-  } else {  // the caller kept uvc from an earlier call with the same parameters: the draw rides in the next kernel instead
-    GC_TRY(node_score_fwd(X, uvc, s, M, D, st, rng_state, rng_snaps, rng_count));
-  }
-  GC_TRY(edge_fwd(E, uvc + D, n_valid, Ebar, s, P, A, drop, B, N, D, st, mask));  // + row softmax + dropout
-  return 0;
+  GC_TRY(gat_node_fwd(X, flat, uvc, s, (long)B * N, D, Dh, uvc_valid, rng_state, rng_snaps, rng_count, st));
+  return edge_fwd(E, uvc + D, n_valid, Ebar, s, P, A, drop, B, N, D, st, mask);  // + row softmax + dropout
 }
 
-int64_t gcgcn_gat_bwd_scratch(int B, int N, int D) {
-  const long a = colsum_scratch_elems((long)B * N, D, 1), b = 3L * 64 * (2 * D + 1);
-  return a > b ? a : b;
+int gcgcn_gat_fwd_compact(int B, int N, int D, int Dh, const float* X, const float* Ec, const int32_t* prow, const float* bias,
+                          const int32_t* n_valid, const float* flat, const void* rng_snap, float p, float* uvc, float* s, float* P,
+                          float* A, float* Ebar, void* rng_state, void* rng_snaps, int rng_count, int uvc_valid, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  GC_TRY(cmp_check("gat_fwd_compact", B, N, D, Ec, prow, bias));
+  GC_REQUIRE(Dh > 0 && X && flat && uvc && s && P && Ebar, "gat_fwd_compact: null pointer");
+  const Drop drop = make_drop(rng_snap, GCGCN_SALT_GAT, p);
+  GC_REQUIRE(!drop.snap || A, "gat_fwd_compact: dropout on but A is NULL");
+  GC_REQUIRE(!rng_state || (rng_snaps && rng_count > 0), "gat_fwd_compact: rng_state given without snapshots to fill");
+  GC_TRY(gat_node_fwd(X, flat, uvc, s, (long)B * N, D, Dh, uvc_valid, rng_state, rng_snaps, rng_count, st));
+  return cmp_fwd(CmpE{Ec, prow, bias}, uvc + D, n_valid, Ebar, s, P, A, drop, B, N, D, st);
 }
+
+int64_t gcgcn_gat_bwd_scratch(int B, int N, int D) { return edge_plan_bwd({B, N, D, false, true, false, false, 0}).scratch; }
+int64_t gcgcn_gat_bwd_compact_scratch(int B, int N, int D) { return edge_plan_bwd({B, N, D, true, true, false, false, 0}).scratch; }
 
 int gcgcn_gat_bwd(int B, int N, int D, int Dh, const float* X, const float* E, const int32_t* n_valid, const float* flat,
                   const void* rng_snap, float p, const float* uvc, const float* P, const float* dA, const float* dEbar,
                   const float* dX_in, float* dX, float* dE, float* dflat, float* dlogit, float* ds, float* dvpart,
                   float* duvc, float* scratch, void* defer_queue, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
   GC_TRY(check_dims("gat_bwd", B, N, D, 1, 1));
   GC_REQUIRE(Dh > 0, "gat_bwd: hidden_dim=%d", Dh);
   GC_REQUIRE(X && E && flat && uvc && P && dA && dX && dflat && dlogit && ds && dvpart && duvc,
              "gat_bwd: null pointer");
-  const Drop drop = make_drop(rng_snap, GCGCN_SALT_GAT, p);
-  const long M = (long)B * N;
   GC_REQUIRE(scratch, "gat_bwd: scratch is required");
-  const bool small = gat_dlogit_ok(N);
-  GatTail tail{P, dA, uvc, dX_in, ds, dX, drop, B, gat_dlogit_slices(D)};
-  if (small) {
-    // dlogit, ds and dX = ds u + dX_in ride in the edge pass below: its entity rows take their dlogit row from P and dA
-    // themselves, B * slices passenger workgroups produce ds and dX (dlogit is never stored)
-  } else {
-    GC_TRY(softmax_bwd(P, dA, dlogit, M, N, drop, st));
-    // ds[b, j] = sum_i dlogit[b, i, j]
-    GC_TRY(colsum(dlogit, nullptr, ds, N, N, N, B, (long)N * N, 0, N, 0, nullptr, st));
-    GC_TRY(node_score_bwd(ds, uvc, dX_in, dX, M, D, st));
-  }
-  GC_TRY(edge_bwd(E, uvc + D, n_valid, dlogit, dEbar, dE, dvpart, B, N, D, st, (DeferQueue*)defer_queue,  // + parked weight gradients
-                  small ? &tail : nullptr));
-  // du = sum_m ds[m] X[m,:],  dv = sum partials,  dc = sum_m ds[m]: row-slice partials in one launch; the fold's
-  // backward sums the slices itself (duvc stays unused)
-  long part_off[3];
-  int ns = 0;
-  GC_TRY(colsum3(X, ds, duvc, M, D, D, dvpart, nullptr, duvc + D, M, D, D, ds, nullptr, duvc + 2 * D, M, 1, 1, scratch,
-                 st, false, part_off, &ns));
-  GC_TRY(gat_fold_bwd(flat, duvc, dflat, D, Dh, st, scratch, part_off, ns));
-  return 0;
+  return gat_bwd(EdgeOperand{E, CmpE()}, B, N, D, Dh, X, n_valid, flat, make_drop(rng_snap, GCGCN_SALT_GAT, p), uvc, P, dA, dEbar, dX_in,
+                 dX, dE, nullptr, dflat, dlogit, ds, dvpart, duvc, scratch, (DeferQueue*)defer_queue, (hipStream_t)stream);
+}
+
+int gcgcn_gat_bwd_compact(int B, int N, int D, int Dh, const float* X, const float* Ec, const int32_t* prow, const float* bias,
+                          const int32_t* n_valid, const float* flat, const void* rng_snap, float p, const float* uvc, const float* P,
+                          const float* dA, const float* dEbar, const float* dX_in, float* dX, float* dEc, float* dbias, float* dflat,
+                          float* dlogit, float* ds, float* dvpart, float* duvc, float* scratch, void* stream) {
+  GC_TRY(cmp_check("gat_bwd_compact", B, N, D, Ec, prow, bias));
+  GC_REQUIRE(Dh > 0 && X && flat && uvc && P && dA && dX && dEc && dbias && dflat && dlogit && ds && dvpart && duvc && scratch,
+             "gat_bwd_compact: null pointer");
+  return gat_bwd(EdgeOperand{nullptr, CmpE{Ec, prow, bias}}, B, N, D, Dh, X, n_valid, flat, make_drop(rng_snap, GCGCN_SALT_GAT, p), uvc, P,
+                 dA, dEbar, dX_in, dX, dEc, dbias, dflat, dlogit, ds, dvpart, duvc, scratch, nullptr, (hipStream_t)stream);
 }
 
 int gcgcn_edge_mean_fwd(int B, int N, int D, const float* E, const int32_t* n_valid, float* Ebar, void* stream) {
@@ -354,6 +398,23 @@ int gcgcn_edge_mean_fwd(int B, int N, int D, const float* E, const int32_t* n_va
 int gcgcn_edge_mean_bwd(int B, int N, int D, const float* dEbar, const int32_t* n_valid, float* dE, void* stream) {
   GC_REQUIRE(B > 0 && N > 0 && D > 0, "edge_mean_bwd: bad shape");
   return edge_bcast(dEbar, n_valid, dE, B, N, D, (hipStream_t)stream);
+}
+
+int gcgcn_edge_mean_fwd_compact(int B, int N, int D, const float* Ec, const int32_t* prow, const float* bias, const int32_t* n_valid,
+                                float* Ebar, void* stream) {
+  GC_TRY(cmp_check("edge_mean_fwd_compact", B, N, D, Ec, prow, bias));
+  GC_REQUIRE(Ebar, "edge_mean_fwd_compact: null pointer");
+  return cmp_fwd(CmpE{Ec, prow, bias}, nullptr, n_valid, Ebar, nullptr, nullptr, nullptr, make_drop(nullptr, 0, 0.f), B, N, D,
+                 (hipStream_t)stream);
+}
+
+int gcgcn_edge_mean_bwd_compact(int B, int N, int D, const int32_t* prow, const int32_t* n_valid, const float* dEbar, float* dEc,
+                                float* dbias, float* rowbuf, void* stream) {
+  GC_REQUIRE(B > 0 && N > 0 && D > 0, "edge_mean_bwd_compact: bad shape B=%d N=%d D=%d", B, N, D);
+  GC_REQUIRE(D <= 64 * CMAXK, "edge_mean_bwd_compact: hidden width %d (compact rows support up to %d)", D, 64 * CMAXK);
+  GC_REQUIRE(prow && dEbar && dEc && dbias && rowbuf, "edge_mean_bwd_compact: null pointer");
+  return cmp_bwd(CmpE{nullptr, prow, nullptr}, nullptr, n_valid, nullptr, dEbar, dEc, nullptr, rowbuf, dbias,
+                 edge_plan_bcast({B, N, D, true, false, false, true, 0}), B, N, D, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -829,6 +890,33 @@ int gcgcn_debug_chain_plan(int bwd, int B, int N, int D, int L, int H, int ragge
   q.dout = at(2), q.dXres = at(2), q.dout_m = at(2);
   const ChainPlan p = bwd ? chain_plan_bwd(q) : chain_plan_fwd(q);
   out[0] = p.kind, out[1] = p.aligned, out[2] = p.full, out[3] = p.fuse, out[4] = p.attention, out[5] = p.ride;
+  return 0;
+}
+
+// The launch an edge pass of this shape gets, by the very plan functions the launchers call (edge.hip): pass 0 forward, 1 backward,
+// 2 the mean's backward alone; compact 0 / 1; att: P wanted (forward), a logit gradient comes in (backward: the GATAttention call;
+// a dense backward always has one).  misalign puts an operand off a 16-byte boundary: bit 0 E, 1 v, 2 dE, 3 dEbar, 4 Ebar.  The queue
+// summary (dense backward): parked_tiles = the tile workgroups gemm_take_deferred would hand over (0: nothing parked), any_rb, col_C
+// = the width of a parked column-sum second stage, or 0.  No decision depends on `ragged`.  out[0..16] = vec, att, dlogit route,
+// slices, ngat, LDS bytes, lds_ok, carry_ok, RB, grid, col_base, ncolwg, the Spread's na / cohort / stride, scratch elements, rowbuf
+// offset; -1 where a field does not apply.  Exposed for tests (no GPU needed).
+int gcgcn_debug_edge_plan(int pass, int compact, int B, int N, int D, int ragged, int att, int has_dE, int has_dEbar, int misalign,
+                          int parked_tiles, int any_rb, int col_C, int32_t* out) {
+  (void)ragged;
+  GC_REQUIRE(pass >= 0 && pass <= 2 && B > 0 && N > 0 && D > 0 && parked_tiles >= 0 && col_C >= 0 && out, "debug_edge_plan: bad arguments");
+  GC_REQUIRE((long)B * N * 9 + parked_tiles < (1L << 31) && (long)B * N * D < (1L << 31), "debug_edge_plan: shape too large");
+  GC_REQUIRE(!compact || D <= 64 * CMAXK, "debug_edge_plan: hidden width %d (compact rows support up to %d)", D, 64 * CMAXK);
+  const bool dense_bwd = pass == 1 && !compact;
+  GC_REQUIRE(!dense_bwd || att, "debug_edge_plan: a dense backward without a logit gradient is pass 2");
+  const EdgeQuery q = {B, N, D, compact != 0, att != 0, has_dE != 0, has_dEbar != 0, (unsigned)misalign};
+  EdgePlan p = pass == 0 ? edge_plan_fwd(q) : pass == 1 ? edge_plan_bwd(q) : edge_plan_bcast(q);
+  if (dense_bwd && p.carry_ok) edge_plan_carry(p, parked_tiles, any_rb != 0, col_C);
+  const int na = -1;
+  out[0] = p.compact ? na : p.vec, out[1] = p.att, out[2] = p.route, out[3] = p.slices, out[4] = dense_bwd ? p.ngat : na;
+  out[5] = (int)p.lds, out[6] = p.lds_limit ? (int)p.lds_ok() : na, out[7] = dense_bwd ? (int)p.carry_ok : na, out[8] = dense_bwd ? (int)p.RB : na;
+  out[9] = (int)p.grid, out[10] = dense_bwd ? p.col_base : na, out[11] = dense_bwd ? p.ncolwg : na;
+  out[12] = dense_bwd ? p.spread.na : na, out[13] = dense_bwd ? p.spread.cohort : na, out[14] = dense_bwd ? p.spread.stride : na;
+  out[15] = (int)p.scratch, out[16] = (int)p.rowbuf_off;
   return 0;
 }
 

@@ -16,21 +16,10 @@
 // E and dE never exist.  One workgroup of 4 waves per entity row (b, i), like the dense edge kernels; every sum has a fixed
 // order (bitwise reproducible).  Reference arithmetic: GATAttention.forward glove:154-168 (folded: energy = u.x_j + v.e_ij + c),
 // GraphConv's edge term glove:40-41 (mean commuted with the projection).
-#include "../../include/gcgcn.h"
-
-#include "gat_body.hpp"
-#include "rowops.hpp"
+#include "edge_body.hpp"
+#include "compact.hpp"
 
 namespace gc {
-
-constexpr int CW4 = 4;       // waves per workgroup
-constexpr int CMAXK = 8;     // columns per lane: D <= 64 * CMAXK
-
-struct CmpE {
-  const float* Ec;    // [Q, D] compact rows
-  const int* prow;    // [B, N, N]: row of Ec, or -1
-  const float* bias;  // [D]
-};
 
 // dynamic LDS: CW4 * D (+ N when ATT) floats
 template <bool ATT>
@@ -88,29 +77,7 @@ __global__ __launch_bounds__(64 * CW4) void cmp_edge_fwd_kernel(const CmpE ce, c
     for (int w = 0; w < CW4; ++w) s += cs[w * D + c];
     eb[c] = s * inv;
   }
-  if (ATT && wave == 0) {  // row softmax over the nv real columns (+ the node scores, + dropout): as edge_fwd_row
-    const float* ca = coladd + (long)b * N;
-    for (int j = lane; j < nv; j += 64) lg[j] += ca[j];
-    float m = -INFINITY;
-    for (int j = lane; j < nv; j += 64) m = fmaxf(m, lg[j]);
-    m = wave_max(m);
-    float sum = 0.f;
-    for (int j = lane; j < nv; j += 64) sum += expf(lg[j] - m);
-    sum = wave_sum(sum);
-    const float isum = 1.f / sum;
-    const bool dd = Aout && drop.snap;
-    const uint64_t key = dd ? drop_key(drop) : 0;
-    for (int j = lane; j < N; j += 64) {
-      float pv = 0.f;
-      if (j < nv) pv = expf(lg[j] - m) * isum;
-      const long o = (long)bi * N + j;
-      P[o] = pv;
-      if (Aout) {
-        if (dd) pv = (rng_u32(key, (uint64_t)o) >= drop.thresh) ? pv * drop.scale : 0.f;
-        Aout[o] = pv;
-      }
-    }
-  }
+  if (ATT && wave == 0) edge_softmax_tail(lg, coladd + (long)b * N, nullptr, P, Aout, drop, N, nv, (long)bi * N, lane);
 }
 
 // dEc[prow] = dlogit_ij v + dEbar_i / n for the live pairs of row (b, i); dvpart[bi] = sum_j dlogit_ij e_ij;
@@ -208,32 +175,32 @@ __global__ __launch_bounds__(256) void cmp_bias_grad_kernel(const float* __restr
   }
 }
 
-static int cmp_check(const char* who, int B, int N, int D, const float* Ec, const int* prow, const float* bias) {
+int cmp_check(const char* who, int B, int N, int D, const float* Ec, const int* prow, const float* bias) {
   GC_REQUIRE(B > 0 && N > 0 && D > 0 && (long)B * N <= 0x7fffffffL, "%s: bad shape B=%d N=%d D=%d", who, B, N, D);
   GC_REQUIRE(D <= 64 * CMAXK, "%s: hidden width %d (compact rows support up to %d)", who, D, 64 * CMAXK);
   GC_REQUIRE(Ec && prow && bias, "%s: null pointer", who);
   return 0;
 }
 
-static int cmp_fwd(const CmpE& ce, const float* v, const int* n_valid, float* Ebar, const float* coladd, float* P, float* A, Drop drop,
-                   int B, int N, int D, hipStream_t st) {
+int cmp_fwd(const CmpE& ce, const float* v, const int* n_valid, float* Ebar, const float* coladd, float* P, float* A, Drop drop,
+            int B, int N, int D, hipStream_t st) {
   const bool att = P != nullptr;
-  const size_t lds = ((size_t)CW4 * D + (att ? N : 0)) * sizeof(float);
-  GC_REQUIRE(lds <= 64 * 1024, "compact edge pass: N=%d D=%d needs %zu B of LDS", N, D, lds);
+  const EdgePlan p = edge_plan_fwd({B, N, D, true, att, false, false, 0});
+  GC_REQUIRE(p.lds_ok(), "compact edge pass: N=%d D=%d needs %zu B of LDS", N, D, p.lds);
   ProfScope ps(att ? "edge_fwd_att" : "edge_fwd_mean", st, 0.0);
-  if (att) hipLaunchKernelGGL(cmp_edge_fwd_kernel<true>, dim3((unsigned)((long)B * N)), dim3(64 * CW4), lds, st, ce, v, n_valid, Ebar, coladd, P, A, drop, N, D);
-  else hipLaunchKernelGGL(cmp_edge_fwd_kernel<false>, dim3((unsigned)((long)B * N)), dim3(64 * CW4), lds, st, ce, v, n_valid, Ebar, coladd, P, A, drop, N, D);
+  const dim3 grid((unsigned)p.grid), block(64 * CW4);
+  if (att) hipLaunchKernelGGL(cmp_edge_fwd_kernel<true>, grid, block, p.lds, st, ce, v, n_valid, Ebar, coladd, P, A, drop, N, D);
+  else hipLaunchKernelGGL(cmp_edge_fwd_kernel<false>, grid, block, p.lds, st, ce, v, n_valid, Ebar, coladd, P, A, drop, N, D);
   return check_launch("cmp_edge_fwd");
 }
 
-static int cmp_bwd(const CmpE& ce, const float* v, const int* n_valid, const float* dlogit, const float* dEbar, float* dEc, float* dvpart,
-                   float* rowbuf, float* dbias, int B, int N, int D, hipStream_t st) {
+int cmp_bwd(const CmpE& ce, const float* v, const int* n_valid, const float* dlogit, const float* dEbar, float* dEc, float* dvpart,
+            float* rowbuf, float* dbias, const EdgePlan& p, int B, int N, int D, hipStream_t st) {
   const long BN = (long)B * N;
   float *sd = rowbuf, *cw = rowbuf + BN;
-  const size_t lds = ((size_t)CW4 * D + 2 * CW4) * sizeof(float);
   {
     ProfScope ps("edge_bwd", st, 0.0);
-    hipLaunchKernelGGL(cmp_edge_bwd_kernel, dim3((unsigned)BN), dim3(64 * CW4), lds, st, ce, v, n_valid, dlogit, dEbar, dEc, dvpart, sd, cw, N, D);
+    hipLaunchKernelGGL(cmp_edge_bwd_kernel, dim3((unsigned)p.grid), dim3(64 * CW4), p.lds, st, ce, v, n_valid, dlogit, dEbar, dEc, dvpart, sd, cw, N, D);
     GC_TRY(check_launch("cmp_edge_bwd"));
   }
   ProfScope ps("colsum", st, 0.0);
@@ -242,75 +209,3 @@ static int cmp_bwd(const CmpE& ce, const float* v, const int* n_valid, const flo
 }
 
 }  // namespace gc
-
-using namespace gc;
-
-extern "C" {
-
-int gcgcn_edge_mean_fwd_compact(int B, int N, int D, const float* Ec, const int32_t* prow, const float* bias, const int32_t* n_valid,
-                                float* Ebar, void* stream) {
-  GC_TRY(cmp_check("edge_mean_fwd_compact", B, N, D, Ec, prow, bias));
-  GC_REQUIRE(Ebar, "edge_mean_fwd_compact: null pointer");
-  const CmpE ce{Ec, prow, bias};
-  return cmp_fwd(ce, nullptr, n_valid, Ebar, nullptr, nullptr, nullptr, make_drop(nullptr, 0, 0.f), B, N, D, (hipStream_t)stream);
-}
-
-int gcgcn_edge_mean_bwd_compact(int B, int N, int D, const int32_t* prow, const int32_t* n_valid, const float* dEbar, float* dEc,
-                                float* dbias, float* rowbuf, void* stream) {
-  GC_REQUIRE(B > 0 && N > 0 && D > 0, "edge_mean_bwd_compact: bad shape B=%d N=%d D=%d", B, N, D);
-  GC_REQUIRE(D <= 64 * CMAXK, "edge_mean_bwd_compact: hidden width %d (compact rows support up to %d)", D, 64 * CMAXK);
-  GC_REQUIRE(prow && dEbar && dEc && dbias && rowbuf, "edge_mean_bwd_compact: null pointer");
-  const CmpE ce{nullptr, prow, nullptr};
-  return cmp_bwd(ce, nullptr, n_valid, nullptr, dEbar, dEc, nullptr, rowbuf, dbias, B, N, D, (hipStream_t)stream);
-}
-
-int gcgcn_gat_fwd_compact(int B, int N, int D, int Dh, const float* X, const float* Ec, const int32_t* prow, const float* bias,
-                          const int32_t* n_valid, const float* flat, const void* rng_snap, float p, float* uvc, float* s, float* P,
-                          float* A, float* Ebar, void* rng_state, void* rng_snaps, int rng_count, int uvc_valid, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  GC_TRY(cmp_check("gat_fwd_compact", B, N, D, Ec, prow, bias));
-  GC_REQUIRE(Dh > 0 && X && flat && uvc && s && P && Ebar, "gat_fwd_compact: null pointer");
-  const Drop drop = make_drop(rng_snap, GCGCN_SALT_GAT, p);
-  GC_REQUIRE(!drop.snap || A, "gat_fwd_compact: dropout on but A is NULL");
-  GC_REQUIRE(!rng_state || (rng_snaps && rng_count > 0), "gat_fwd_compact: rng_state given without snapshots to fill");
-  const long M = (long)B * N;
-  if (!uvc_valid) {
-    GC_TRY(gat_fold_fwd(flat, uvc, D, Dh, st, rng_state, rng_snaps, rng_count));
-    GC_TRY(node_score_fwd(X, uvc, s, M, D, st));
-  } else {
-    GC_TRY(node_score_fwd(X, uvc, s, M, D, st, rng_state, rng_snaps, rng_count));
-  }
-  const CmpE ce{Ec, prow, bias};
-  return cmp_fwd(ce, uvc + D, n_valid, Ebar, s, P, A, drop, B, N, D, st);
-}
-
-int64_t gcgcn_gat_bwd_compact_scratch(int B, int N, int D) { return gcgcn_gat_bwd_scratch(B, N, D) + 2L * B * N; }
-
-int gcgcn_gat_bwd_compact(int B, int N, int D, int Dh, const float* X, const float* Ec, const int32_t* prow, const float* bias,
-                          const int32_t* n_valid, const float* flat, const void* rng_snap, float p, const float* uvc, const float* P,
-                          const float* dA, const float* dEbar, const float* dX_in, float* dX, float* dEc, float* dbias, float* dflat,
-                          float* dlogit, float* ds, float* dvpart, float* duvc, float* scratch, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  GC_TRY(cmp_check("gat_bwd_compact", B, N, D, Ec, prow, bias));
-  GC_REQUIRE(Dh > 0 && X && flat && uvc && P && dA && dX && dEc && dbias && dflat && dlogit && ds && dvpart && duvc && scratch,
-             "gat_bwd_compact: null pointer");
-  const Drop drop = make_drop(rng_snap, GCGCN_SALT_GAT, p);
-  const long M = (long)B * N;
-  if (gat_dlogit_ok(N)) {
-    GC_TRY(gat_dlogit(P, dA, uvc, dX_in, dlogit, ds, dX, B, N, D, drop, st));
-  } else {
-    GC_TRY(softmax_bwd(P, dA, dlogit, M, N, drop, st));
-    GC_TRY(colsum(dlogit, nullptr, ds, N, N, N, B, (long)N * N, 0, N, 0, nullptr, st));
-    GC_TRY(node_score_bwd(ds, uvc, dX_in, dX, M, D, st));
-  }
-  const CmpE ce{Ec, prow, bias};
-  float* rowbuf = scratch + gcgcn_gat_bwd_scratch(B, N, D);
-  GC_TRY(cmp_bwd(ce, uvc + D, n_valid, dlogit, dEbar, dEc, dvpart, rowbuf, dbias, B, N, D, st));
-  long part_off[3];
-  int ns = 0;
-  GC_TRY(colsum3(X, ds, duvc, M, D, D, dvpart, nullptr, duvc + D, M, D, D, ds, nullptr, duvc + 2 * D, M, 1, 1, scratch, st, false,
-                 part_off, &ns));
-  return gat_fold_bwd(flat, duvc, dflat, D, Dh, st, scratch, part_off, ns);
-}
-
-}  // extern "C"

@@ -19,8 +19,10 @@
 #include <string.h>
 
 #include "edge_body.hpp"
+#include "compact.hpp"
 #include "gat_body.hpp"
 #include "gemm_body.hpp"
+#include "rowops.hpp"
 
 namespace gc {
 
@@ -205,9 +207,84 @@ __global__ __launch_bounds__(64 * EW) void edge_bcast_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
-// host launchers
+// the plan (edge_plan.hpp): every launch decision of the passes in this file and in compact.hip, as pure host functions
 // ---------------------------------------------------------------------------------------------
 static inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+unsigned edge_misalign(const void* E, const void* v, const void* dE, const void* dEbar, const void* Ebar) {
+  return (al16(E) ? 0 : EDGE_MIS_E) | (al16(v) ? 0 : EDGE_MIS_V) | (al16(dE) ? 0 : EDGE_MIS_DE) | (al16(dEbar) ? 0 : EDGE_MIS_DEBAR) |
+         (al16(Ebar) ? 0 : EDGE_MIS_EBAR);
+}
+constexpr size_t EDGE_LDS_MAX = 160 * 1024;   // dense passes: the compute unit's LDS
+constexpr size_t CMP_LDS_MAX = 64 * 1024;     // compact forward
+constexpr size_t TILE_LDS = sizeof(float) * lds_floats<1, 1, true, true>();   // the carrying kernel's static image
+static_assert(sizeof(float) * GAT_DOC_LDS <= TILE_LDS, "GAT passenger needs more LDS than a tile");
+
+static EdgePlan plan_rows(const EdgeQuery& q, unsigned operands) {   // one workgroup per entity row; operands: the ones that must be 16-byte aligned
+  EdgePlan p;
+  p.compact = q.compact, p.att = q.att;
+  p.vec = (!q.compact && q.D % 4 == 0 && !(q.mis & operands)) ? 4 : 1;
+  p.grid = (long)q.B * q.N;
+  return p;
+}
+
+EdgePlan edge_plan_fwd(const EdgeQuery& q) {
+  EdgePlan p = plan_rows(q, EDGE_MIS_E | EDGE_MIS_EBAR | (q.att ? EDGE_MIS_V : 0));
+  p.lds = ((size_t)(q.compact ? CW4 : EW) * q.D + (q.att ? (size_t)q.N : 0)) * sizeof(float);
+  p.lds_limit = q.compact ? CMP_LDS_MAX : EDGE_LDS_MAX;
+  return p;
+}
+
+EdgePlan edge_plan_bwd(const EdgeQuery& q) {
+  EdgePlan p = plan_rows(q, EDGE_MIS_E | EDGE_MIS_V | (q.has_dE ? EDGE_MIS_DE : 0) | (q.has_dEbar ? EDGE_MIS_DEBAR : 0));
+  if (q.att) {
+    // N <= 64: dlogit, ds and dX = ds u + dX_in come from gat_dlogit_doc (gat_body.hpp) -- as B * slices passenger workgroups of the
+    // dense edge pass, whose entity rows take their dlogit row from P and dA themselves (dlogit is never stored), as a launch of
+    // its own in front of the compact one; larger graphs take the three generic launches
+    p.route = q.N > GT ? EdgePlan::THREE : (q.compact ? EdgePlan::ONE : EdgePlan::RIDE);
+    if (p.route != EdgePlan::THREE) p.slices = gat_dlogit_slices(q.D);
+    if (p.route == EdgePlan::RIDE) p.ngat = q.B * p.slices;
+    // [column-sum partials of colsum3 | compact: sd, cw of cmp_bwd]
+    const long a = colsum_scratch_elems((long)q.B * q.N, q.D, 1), b = 3L * 64 * (2 * q.D + 1);
+    p.scratch = a > b ? a : b;
+    if (q.compact) p.rowbuf_off = p.scratch, p.scratch += 2L * q.B * q.N;
+  }
+  if (q.compact) {
+    p.lds = ((size_t)CW4 * q.D + 2 * CW4) * sizeof(float);
+    return p;
+  }
+  const size_t lds_row = ((size_t)((q.N + 3) & ~3) + (size_t)EW * q.D) * sizeof(float);
+  p.lds = (p.ngat && lds_row < sizeof(float) * GAT_DOC_LDS) ? sizeof(float) * GAT_DOC_LDS : lds_row;   // a passenger needs more than a short row
+  p.lds_limit = EDGE_LDS_MAX;
+  p.carry_ok = p.vec == 4 && lds_row <= TILE_LDS;
+  p.grid += p.ngat;
+  return p;
+}
+
+EdgePlan edge_plan_bcast(const EdgeQuery& q) {
+  if (!q.compact) return plan_rows(q, EDGE_MIS_DE | EDGE_MIS_DEBAR);
+  EdgeQuery m = q;
+  m.att = false;
+  return edge_plan_bwd(m);
+}
+
+void edge_plan_carry(EdgePlan& p, int ntile, bool any_rb, int col_C) {
+  if (ntile <= 0) return;
+  const long rows = p.grid;   // entity rows + GAT passengers
+  p.ntile = ntile, p.RB = any_rb;
+  // one parked second stage of a column sum (a bias gradient's 64 partial rows -> its C columns) in trailing workgroups
+  p.ncolwg = col_C > 0 ? cdiv(col_C, 256) : 0;
+  p.col_base = col_C > 0 ? (int)(rows + ntile) : 0;
+  p.grid = rows + ntile + p.ncolwg;
+  // the tile cohorts (cohort tiles each) are spread over spread_pct % of the launch (0: all tiles first, the order until
+  // round 3); launches of fewer than spread_min tiles keep them in front
+  constexpr int spread_pct = 90, cohort = 256, spread_min = 1024;
+  p.spread = make_spread(ntile, rows, cohort, ntile >= spread_min ? spread_pct : 0);
+  p.lds = 0;   // rows, passengers and tiles share the kernel's static image
+}
+
+// ---------------------------------------------------------------------------------------------
+// host launchers: validate, plan, launch what the plan says
+// ---------------------------------------------------------------------------------------------
 // E is read once per pass and never again before something else has flushed the caches (a training step feeds new
 // documents): all E loads are non-temporal.  Ordinary loads for the attention pass over E1 were the round-1 setting, tuned
 // on a bench that replayed ONE batch (part of E1 still sat in the Infinity Cache from the previous backward); with rotating
@@ -221,15 +298,14 @@ int edge_fwd(const float* E, const float* v, const int* n_valid, float* Ebar, co
   GC_REQUIRE(B > 0 && N > 0 && D > 0, "edge_fwd: bad shape B=%d N=%d D=%d", B, N, D);
   const bool att = P != nullptr;
   GC_REQUIRE(!att || (v && coladd), "edge_fwd: attention requested without v / node scores");
-  const bool vec = (D % 4 == 0) && al16(E) && al16(Ebar) && (!att || al16(v));
-  const size_t lds = ((size_t)EW * D + (att ? (size_t)N : 0)) * sizeof(float);
-  GC_REQUIRE(lds <= 160 * 1024, "edge_fwd: N=%d D=%d needs %zu B of LDS", N, D, lds);
-  dim3 grid((unsigned)((long)B * N)), block(64 * EW);
+  const EdgePlan p = edge_plan_fwd({B, N, D, false, att, false, false, edge_misalign(E, v, nullptr, nullptr, Ebar)});
+  GC_REQUIRE(p.lds_ok(), "edge_fwd: N=%d D=%d needs %zu B of LDS", N, D, p.lds);
+  dim3 grid((unsigned)p.grid), block(64 * EW);
   const char* tag = att ? "edge_fwd_att" : "edge_fwd_mean";
   const double bytes = 4.0 * B * N * N * D;
 #define GC_EDGE_FWD(V, AT) \
-  GC_LAUNCH_TIMED(tag, bytes, (edge_fwd_kernel<V, AT>), grid, block, lds, st, E, v, n_valid, Ebar, coladd, P, A, drop, N, D, mask)
-  if (vec) {
+  GC_LAUNCH_TIMED(tag, bytes, (edge_fwd_kernel<V, AT>), grid, block, p.lds, st, E, v, n_valid, Ebar, coladd, P, A, drop, N, D, mask)
+  if (p.vec == 4) {
     if (att) GC_EDGE_FWD(4, true);
     else GC_EDGE_FWD(4, false);
   } else {
@@ -241,51 +317,43 @@ int edge_fwd(const float* E, const float* v, const int* n_valid, float* Ebar, co
 }
 
 int edge_bwd(const float* E, const float* v, const int* n_valid, const float* dlogit, const float* dEbar, float* dE,
-             float* dvpart, int B, int N, int D, hipStream_t st, DeferQueue* carry, const GatTail* tail) {
+             float* dvpart, const EdgePlan& plan, int B, int N, int D, hipStream_t st, DeferQueue* carry, const GatTail* tail) {
   GatTail gt;
   memset(&gt, 0, sizeof gt);
-  if (tail) gt = *tail;
+  if (tail && plan.route == EdgePlan::RIDE) gt = *tail;   // the passenger rides where the plan says so
   GC_REQUIRE(E && v && (dlogit || gt.P) && dvpart, "edge_bwd: null pointer");
-  GC_REQUIRE(!gt.P || (N <= GT && gt.B == B && gt.slices > 0 && gt.dA && gt.uvc && gt.ds && gt.dX), "edge_bwd: bad GAT passenger");
+  GC_REQUIRE(!gt.P || (N <= GT && gt.B == B && gt.slices == plan.slices && gt.dA && gt.uvc && gt.ds && gt.dX), "edge_bwd: bad GAT passenger");
+  GC_REQUIRE(!plan.compact && plan.ngat == (gt.P ? B * gt.slices : 0) &&
+                 (plan.vec == 4) == (D % 4 == 0 && !edge_misalign(E, v, dE, dEbar, nullptr)),
+             "edge_bwd: the plan was made for other operands");
   static_assert(sizeof(GatTail) + sizeof(GemmGroup) + 96 <= 4096, "edge_bwd_carry_kernel: kernel arguments exceed 4 KB");
-  static_assert(sizeof(float) * GAT_DOC_LDS <= sizeof(float) * lds_floats<1, 1, true, true>(), "GAT passenger needs more LDS than a tile");
-  const int ngat = gt.P ? B * gt.slices : 0;
-  const bool vec = (D % 4 == 0) && al16(E) && al16(v) && (!dE || al16(dE)) && (!dEbar || al16(dEbar));
-  const size_t lds_row = ((size_t)((N + 3) & ~3) + (size_t)EW * D) * sizeof(float);
-  GC_REQUIRE(lds_row <= 160 * 1024, "edge_bwd: N=%d D=%d needs %zu B of LDS", N, D, lds_row);
-  const size_t lds = (ngat && lds_row < sizeof(float) * GAT_DOC_LDS) ? sizeof(float) * GAT_DOC_LDS : lds_row;
+  GC_REQUIRE(plan.lds_ok(), "edge_bwd: N=%d D=%d needs %zu B of LDS", N, D, plan.lds);
+  EdgePlan p = plan;
   dim3 block(64 * EW);
+  const double bytes = (dE ? 8.0 : 4.0) * B * N * N * D;
   GemmGroup gg;
   double gflops = 0;
-  const int ntile = (carry && carry->n > 0 && vec && lds_row <= sizeof(float) * lds_floats<1, 1, true, true>())
-                        ? gemm_take_deferred(carry, gg, &gflops)
-                        : 0;
-  if (ntile > 0) {  // parked weight-gradient products ride along
-    // ... and one parked second stage of a column sum (a bias gradient's 64 partial rows -> its C columns), in trailing workgroups
-    const int col_base = gemm_take_deferred_col2(carry, gg.col) ? (int)((long)B * N + ngat + ntile) : 0;
-    const int ncolwg = col_base ? cdiv(gg.col.C, 256) : 0;
-    dim3 grid((unsigned)((long)B * N + ngat + ntile + ncolwg));
-    // the tile cohorts (cohort tiles each) are spread over spread_pct % of the launch (0: all tiles first, the order until
-    // round 3); launches of fewer than spread_min tiles keep them in front
-    constexpr int spread_pct = 90, cohort = 256, spread_min = 1024;
-    const Spread sp = make_spread(ntile, (long)B * N + ngat, cohort, ntile >= spread_min ? spread_pct : 0);
-    const double bytes = (dE ? 8.0 : 4.0) * B * N * N * D;
+  // eligibility first, then the take (it pops the queue), then the grid around what was taken
+  const int ntile = (p.carry_ok && carry && carry->n > 0) ? gemm_take_deferred(carry, gg, &gflops) : 0;
+  if (ntile > 0) {  // parked weight-gradient products ride along, and one parked second stage of a column sum
+    const bool col = gemm_take_deferred_col2(carry, gg.col);
     bool any_rb = false;
     for (int i = 0; i < gg.nprob; ++i) any_rb = any_rb || gg.p[i].rb != nullptr;
+    edge_plan_carry(p, ntile, any_rb, col ? gg.col.C : 0);
+    dim3 grid((unsigned)p.grid);
 #define GC_EDGE_CARRY(RBV)                                                                                                  \
   GC_LAUNCH_TIMED("edge_bwd", bytes, (edge_bwd_carry_kernel<4, RBV>), grid, block, 0, st, E, v, n_valid, dlogit, dEbar, dE, \
-                  dvpart, N, D, NT_STORE, sp, gt, gg, col_base)
-    if (any_rb) GC_EDGE_CARRY(true);
+                  dvpart, N, D, NT_STORE, p.spread, gt, gg, p.col_base)
+    if (p.RB) GC_EDGE_CARRY(true);
     else GC_EDGE_CARRY(false);
 #undef GC_EDGE_CARRY
     return check_launch("edge_bwd_carry");
   }
-  dim3 grid((unsigned)((long)B * N + ngat));
-  const double bytes = (dE ? 8.0 : 4.0) * B * N * N * D;
-#define GC_EDGE_BWD(V)                                                                                                           \
-  GC_LAUNCH_TIMED("edge_bwd", bytes, (edge_bwd_kernel<V>), grid, block, lds, st, E, v, n_valid, dlogit, dEbar, dE, dvpart, N, D, \
+  dim3 grid((unsigned)p.grid);
+#define GC_EDGE_BWD(V)                                                                                                             \
+  GC_LAUNCH_TIMED("edge_bwd", bytes, (edge_bwd_kernel<V>), grid, block, p.lds, st, E, v, n_valid, dlogit, dEbar, dE, dvpart, N, D, \
                   NT_STORE, gt)
-  if (vec) GC_EDGE_BWD(4);
+  if (p.vec == 4) GC_EDGE_BWD(4);
   else GC_EDGE_BWD(1);
 #undef GC_EDGE_BWD
   return check_launch("edge_bwd");
@@ -293,10 +361,10 @@ int edge_bwd(const float* E, const float* v, const int* n_valid, const float* dl
 
 int edge_bcast(const float* dEbar, const int* n_valid, float* dE, int B, int N, int D, hipStream_t st) {
   GC_REQUIRE(dEbar && dE, "edge_bcast: null pointer");
-  const bool vec = (D % 4 == 0) && al16(dE) && al16(dEbar);
-  dim3 grid((unsigned)((long)B * N)), block(64 * EW);
+  const EdgePlan p = edge_plan_bcast({B, N, D, false, false, true, true, edge_misalign(nullptr, nullptr, dE, dEbar, nullptr)});
+  dim3 grid((unsigned)p.grid), block(64 * EW);
   ProfScope ps("edge_bcast", st, 4.0 * B * N * N * D);
-  if (vec) hipLaunchKernelGGL((edge_bcast_kernel<4>), grid, block, 0, st, dEbar, n_valid, dE, N, D, NT_STORE);
+  if (p.vec == 4) hipLaunchKernelGGL((edge_bcast_kernel<4>), grid, block, 0, st, dEbar, n_valid, dE, N, D, NT_STORE);
   else hipLaunchKernelGGL((edge_bcast_kernel<1>), grid, block, 0, st, dEbar, n_valid, dE, N, D, NT_STORE);
   return check_launch("edge_bcast");
 }

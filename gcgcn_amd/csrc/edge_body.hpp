@@ -53,6 +53,35 @@ __device__ __forceinline__ void vstore_nt(float* p, const float (&r)[VEC]) {
 constexpr int EW = 4;    // waves per workgroup
 constexpr int EUNR = 4;  // rows in flight per wave (8 was tried: no faster in the step, 152 VGPRs in edge_bwd)
 
+// The end of an attention row, run by ONE wave once lg[0 .. nv) holds the raw logits v . e_ij: + the node scores ca[j] = u.x_j + c,
+// the opt-in mask, then the row softmax over the nv real columns (GATAttention glove:162-167); P gets the probabilities (zero
+// on padding columns), Aout (optional) the same after dropout.  Shared by the dense row body below and the compact-row kernel
+// (compact.hip, mask == nullptr).
+__device__ __forceinline__ void edge_softmax_tail(float* lg, const float* ca, const unsigned char* mask, float* P, float* Aout,
+                                                  const Drop& drop, int N, int nv, long row, int lane) {   // row = bi * N
+  // energies; opt-in, paper-faithful mask: energy.masked_fill(mask, -100000.0) (the in-place form glove:163-164 meant)
+  for (int j = lane; j < nv; j += 64) lg[j] = (mask && mask[row + j]) ? -100000.0f : lg[j] + ca[j];
+  float m = -INFINITY;
+  for (int j = lane; j < nv; j += 64) m = fmaxf(m, lg[j]);
+  m = wave_max(m);
+  float sum = 0.f;
+  for (int j = lane; j < nv; j += 64) sum += expf(lg[j] - m);
+  sum = wave_sum(sum);
+  const float isum = 1.f / sum;
+  const bool dd = Aout && drop.snap;
+  const uint64_t key = dd ? drop_key(drop) : 0;
+  for (int j = lane; j < N; j += 64) {
+    float pv = 0.f;
+    if (j < nv) pv = expf(lg[j] - m) * isum;
+    const long o = row + j;
+    P[o] = pv;
+    if (Aout) {
+      if (dd) pv = (rng_u32(key, (uint64_t)o) >= drop.thresh) ? pv * drop.scale : 0.f;
+      Aout[o] = pv;
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // forward: Ebar (always) and raw logits v.e_ij (ATT only).  dynamic LDS: EW * D floats.
 // ---------------------------------------------------------------------------------------------
@@ -144,30 +173,7 @@ __device__ __forceinline__ void edge_fwd_row(const float* __restrict__ E, const 
     for (int w = 0; w < EWT; ++w) s += cs[w * D + c];
     eb[c] = s * inv;
   }
-  if (ATT && wave == 0) {  // row softmax over the nv real columns
-    const float* ca = coladd + (long)b * N;
-    // energies; opt-in, paper-faithful mask: energy.masked_fill(mask, -100000.0) (the in-place form glove:163-164 meant)
-    for (int j = lane; j < nv; j += 64) lg[j] = (mask && mask[(long)bi * N + j]) ? -100000.0f : lg[j] + ca[j];
-    float m = -INFINITY;
-    for (int j = lane; j < nv; j += 64) m = fmaxf(m, lg[j]);
-    m = wave_max(m);
-    float sum = 0.f;
-    for (int j = lane; j < nv; j += 64) sum += expf(lg[j] - m);
-    sum = wave_sum(sum);
-    const float isum = 1.f / sum;
-    const bool dd = Aout && drop.snap;
-    const uint64_t key = dd ? drop_key(drop) : 0;
-    for (int j = lane; j < N; j += 64) {
-      float pv = 0.f;
-      if (j < nv) pv = expf(lg[j] - m) * isum;
-      const long o = (long)bi * N + j;
-      P[o] = pv;
-      if (Aout) {
-        if (dd) pv = (rng_u32(key, (uint64_t)o) >= drop.thresh) ? pv * drop.scale : 0.f;
-        Aout[o] = pv;
-      }
-    }
-  }
+  if (ATT && wave == 0) edge_softmax_tail(lg, coladd + (long)b * N, mask, P, Aout, drop, N, nv, (long)bi * N, lane);
 }
 
 

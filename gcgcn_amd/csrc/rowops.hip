@@ -724,12 +724,11 @@ int gat_fold_bwd(const float* flat, const float* duvc, float* dflat, int D, int 
                      ns > 0 ? part_off[1] : 0L, ns > 0 ? part_off[2] : 0L, ns);
   return check_launch("gat_fold_bwd");
 }
-bool gat_dlogit_ok(int N) { return N <= GT; }
 int gat_dlogit_slices(int D) { return D >= 256 ? 8 : (D >= 64 ? 4 : 1); }
 int gat_dlogit(const float* P, const float* dA, const float* uvc, const float* dXin, float* dlogit, float* ds, float* dX,
-               int B, int N, int D, Drop drop, hipStream_t st) {
+               int B, int N, int D, int slices, Drop drop, hipStream_t st) {
+  GC_REQUIRE(N <= GT && slices > 0, "gat_dlogit: N=%d slices=%d", N, slices);
   ProfScope ps("gat_dlogit", st);
-  const int slices = gat_dlogit_slices(D);
   hipLaunchKernelGGL(gat_dlogit_kernel, dim3(B, slices), dim3(256), 0, st, P, dA, uvc, dXin, dlogit, ds, dX, N, D, drop);
   return check_launch("gat_dlogit");
 }

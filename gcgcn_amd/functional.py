@@ -169,6 +169,36 @@ def dropout_keep_mask(snap: Tensor, salt: int, p: float, numel: int) -> Tensor:
 
 
 # ---- GATAttention + single pass over E -------------------------------------------------------------
+def _gat_fwd_buffers(x: Tensor, snap, pending, uvc, uvc_valid):
+    """What gcgcn_gat_fwd / gcgcn_gat_fwd_compact fill: (uvc, uvc_valid, s, P, A, ebar) and the pending-rng triple."""
+    B, N, D = x.shape
+    dev = x.device
+    rng = pending if pending is not None else (None, None, 0)
+    if uvc is None:
+        uvc, uvc_valid = torch.empty(2 * D + 1, device=dev), False
+    s = torch.empty(B, N, device=dev)
+    P = torch.empty(B, N, N, device=dev)
+    A = torch.empty(B, N, N, device=dev) if snap is not None else None
+    ebar = torch.empty(B, N, D, device=dev)
+    return uvc, uvc_valid, s, P, A, ebar, rng
+
+
+def _gat_bwd_buffers(x: Tensor, dA, dEbar, dXin, scratch_elems: str):
+    """The incoming gradients made contiguous (dA: zeros if absent) and the workspaces of gcgcn_gat_bwd / gcgcn_gat_bwd_compact:
+    (dA, dEbar, dXin, dlogit, ds, dvpart, duvc, scratch); scratch_elems names the size entry point that goes with the call."""
+    B, N, D = x.shape
+    dev = x.device
+    dA = torch.zeros(B, N, N, device=dev) if dA is None else dA.contiguous()
+    dEbar = None if dEbar is None else dEbar.contiguous()
+    dXin = None if dXin is None else dXin.contiguous()
+    dlogit = torch.empty(B, N, N, device=dev)
+    ds = torch.empty(B, N, device=dev)
+    dvpart = torch.empty(B * N, D, device=dev)
+    duvc = torch.empty(2 * D + 1, device=dev)
+    scratch = torch.empty(max(getattr(_lib.lib(), scratch_elems)(B, N, D), 1), device=dev)
+    return dA, dEbar, dXin, dlogit, ds, dvpart, duvc, scratch
+
+
 class GatFn(torch.autograd.Function):
     """(X[B,N,D], E[B,N,N,D], flat) -> (A[B,N,N], Ebar[B,N,D], X).  GCGCN_glove.py:154-168 (+ :40-41).
     The third output is X itself: a hop that hands THIS alias to its convolution lets the convolution's dX arrive
@@ -177,14 +207,7 @@ class GatFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, e, flat, n_valid, p, snap, pending, Dh, mask, uvc, uvc_valid):
         B, N, D = x.shape
-        dev = x.device
-        st, sn, cnt = pending if pending is not None else (None, None, 0)
-        if uvc is None:
-            uvc, uvc_valid = torch.empty(2 * D + 1, device=dev), False
-        s = torch.empty(B, N, device=dev)
-        P = torch.empty(B, N, N, device=dev)
-        A = torch.empty(B, N, N, device=dev) if snap is not None else None
-        ebar = torch.empty(B, N, D, device=dev)
+        uvc, uvc_valid, s, P, A, ebar, (st, sn, cnt) = _gat_fwd_buffers(x, snap, pending, uvc, uvc_valid)
         call("gcgcn_gat_fwd", B, N, D, Dh, _p(x), _p(e), _p(n_valid), _p(flat), _p(snap), float(p), _p(uvc), _p(s),
              _p(P), _p(A), _p(ebar), _p(st), _p(sn), cnt, _p(mask), 1 if uvc_valid else 0, _stream())
         ctx.save_for_backward(x, e, flat, uvc, P)
@@ -196,7 +219,7 @@ class GatFn(torch.autograd.Function):
         x, e, flat, uvc, P = ctx.saved_tensors
         B, N, D = x.shape
         dev = x.device
-        dA = torch.zeros(B, N, N, device=dev) if dA is None else dA.contiguous()
+        dA, dEbar, dXin, dlogit, ds, dvpart, duvc, scratch = _gat_bwd_buffers(x, dA, dEbar, dXin, "gcgcn_gat_bwd_scratch")
         if ctx.mask is not None:
             # opt-in mask: masked_fill passes no gradient to a masked energy.  In a partially masked row those entries have
             # P == 0 and the kernels' P (g - P.g) is zero by itself; a row whose real columns are ALL masked comes out
@@ -205,17 +228,9 @@ class GatFn(torch.autograd.Function):
             if ctx.n_valid is not None:
                 gone = gone | (torch.arange(N, device=dev)[None, None, :] >= ctx.n_valid[:, None, None])
             dA = dA.masked_fill(gone.all(-1, keepdim=True), 0.0)
-        dEbar = None if dEbar is None else dEbar.contiguous()
-        dXin = None if dXin is None else dXin.contiguous()
         dX = torch.empty_like(x)
         dE = torch.empty_like(e) if ctx.needs_input_grad[1] else None
         dflat = torch.empty_like(flat)
-        dlogit = torch.empty(B, N, N, device=dev)
-        ds = torch.empty(B, N, device=dev)
-        dvpart = torch.empty(B * N, D, device=dev)
-        duvc = torch.empty(2 * D + 1, device=dev)
-        nscr = _lib.lib().gcgcn_gat_bwd_scratch(B, N, D)
-        scratch = torch.empty(max(nscr, 1), device=dev)
         bp = _current_pass()                     # weight gradients parked earlier in this backward pass ride in the edge pass
         call("gcgcn_gat_bwd", B, N, D, ctx.Dh, _p(x), _p(e), _p(ctx.n_valid), _p(flat), _p(ctx.snap), ctx.p, _p(uvc), _p(P),
              _p(dA), _p(dEbar), _p(dXin), _p(dX), _p(dE), _p(dflat), _p(dlogit), _p(ds), _p(dvpart), _p(duvc),
@@ -739,14 +754,7 @@ class GatCompactFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, Ec, bias, flat, prow, n_valid, p, snap, pending, Dh, uvc, uvc_valid):
         B, N, D = x.shape
-        dev = x.device
-        st, sn, cnt = pending if pending is not None else (None, None, 0)
-        if uvc is None:
-            uvc, uvc_valid = torch.empty(2 * D + 1, device=dev), False
-        s = torch.empty(B, N, device=dev)
-        P = torch.empty(B, N, N, device=dev)
-        A = torch.empty(B, N, N, device=dev) if snap is not None else None
-        ebar = torch.empty(B, N, D, device=dev)
+        uvc, uvc_valid, s, P, A, ebar, (st, sn, cnt) = _gat_fwd_buffers(x, snap, pending, uvc, uvc_valid)
         call("gcgcn_gat_fwd_compact", B, N, D, Dh, _p(x), _p(Ec), _p(prow), _p(bias), _p(n_valid), _p(flat), _p(snap), float(p),
              _p(uvc), _p(s), _p(P), _p(A), _p(ebar), _p(st), _p(sn), cnt, 1 if uvc_valid else 0, _stream())
         ctx.save_for_backward(x, Ec, bias, flat, uvc, P, prow)
@@ -757,19 +765,11 @@ class GatCompactFn(torch.autograd.Function):
     def backward(ctx, dA, dEbar, dXin):
         x, Ec, bias, flat, uvc, P, prow = ctx.saved_tensors
         B, N, D = x.shape
-        dev = x.device
-        dA = torch.zeros(B, N, N, device=dev) if dA is None else dA.contiguous()
-        dEbar = None if dEbar is None else dEbar.contiguous()
-        dXin = None if dXin is None else dXin.contiguous()
+        dA, dEbar, dXin, dlogit, ds, dvpart, duvc, scratch = _gat_bwd_buffers(x, dA, dEbar, dXin, "gcgcn_gat_bwd_compact_scratch")
         dX = torch.empty_like(x)
         dEc = torch.zeros_like(Ec)                       # rows beyond the live pairs stay zero (the producer's GEMMs read them)
         dbias = torch.empty_like(bias)
         dflat = torch.empty_like(flat)
-        dlogit = torch.empty(B, N, N, device=dev)
-        ds = torch.empty(B, N, device=dev)
-        dvpart = torch.empty(B * N, D, device=dev)
-        duvc = torch.empty(2 * D + 1, device=dev)
-        scratch = torch.empty(max(_lib.lib().gcgcn_gat_bwd_compact_scratch(B, N, D), 1), device=dev)
         call("gcgcn_gat_bwd_compact", B, N, D, ctx.Dh, _p(x), _p(Ec), _p(prow), _p(bias), _p(ctx.n_valid), _p(flat), _p(ctx.snap), ctx.p,
              _p(uvc), _p(P), _p(dA), _p(dEbar), _p(dXin), _p(dX), _p(dEc), _p(dbias), _p(dflat), _p(dlogit), _p(ds), _p(dvpart), _p(duvc),
              _p(scratch), _stream())

@@ -423,6 +423,19 @@ int gcgcn_debug_chain_plan(int bwd, int B, int N, int D, int L, int H, int ragge
  * pair count selects one.  Host-only. */
 int gcgcn_debug_head_plan(int B, int N, int R, int ragged, int32_t* out);
 
+/* ---- test hook: which launch a pass over the edge tensor gets ----------------------------------------------------------
+ * Evaluates the plan functions the edge launchers call (csrc/edge_plan.hpp, csrc/edge.hip: edge_plan_fwd / _bwd / _bcast, then
+ * edge_plan_carry with what the defer queue would hand over).  pass: 0 forward, 1 backward, 2 the mean's backward alone; compact:
+ * the producer's compact rows instead of a dense E; att: GATAttention's pass (forward: P is wanted; backward: a logit gradient
+ * comes in -- a dense backward always has one); has_dE / has_dEbar: those operands given; misalign: bit 0 E, bit 1 v, bit 2 dE,
+ * bit 3 dEbar, bit 4 Ebar are NOT 16-byte aligned; parked_tiles: tile workgroups parked in the queue (0: nothing), any_rb: one of
+ * them walks row blocks, col_C: columns of a parked column-sum second stage (0: none).  ragged is accepted and decides nothing.
+ * out[17] = vec (4 / 1), att, dlogit route (0 passengers of the edge pass, 1 one gat_dlogit launch, 2 three launches), slices,
+ * ngat, dynamic LDS bytes, lds_ok, carry_ok, RB, grid, col_base, ncolwg, the Spread's na / cohort / stride, scratch floats, offset of
+ * the compact row buffer in them.  -1: does not apply.  Host-only. */
+int gcgcn_debug_edge_plan(int pass, int compact, int B, int N, int D, int ragged, int att, int has_dE, int has_dEbar, int misalign,
+                          int parked_tiles, int any_rb, int col_C, int32_t* out);
+
 /* ---- test hook: what the GEMM launcher decides for a problem ----------------------------------------------------------
  * Evaluates the plan function every launcher of csrc/gemm.hip calls (gemm_plan) under the current options, on made-up operand
  * addresses.  form: 0 a single launch (splits: the caller's request), 1 a member of a group launch of group_work tile-k-steps,

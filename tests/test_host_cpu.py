@@ -622,6 +622,129 @@ def test_head_plan_is_the_decision_the_scattered_predicates_made():
     assert not wrong, "\n".join(wrong[:40])
 
 
+# ---- the edge passes' plan ----------------------------------------------------------------------------------------------------
+EDGE_PLAN_FIELDS = ["vec", "att", "route", "slices", "ngat", "lds", "lds_ok", "carry_ok", "RB", "grid", "col_base", "ncolwg", "sp_na",
+                    "sp_cohort", "sp_stride", "scratch", "rowbuf_off"]
+EDGE_PLAN_ARGS = ["pass", "compact", "B", "N", "D", "ragged", "att", "has_dE", "has_dEbar", "misalign", "parked_tiles", "any_rb", "col_C"]
+# the constants the limits are computed from (not found by trial): EW / CW4 waves per workgroup, GT (gat_body.hpp), the 64 x 64 tile's
+# LDS image lds_floats<1, 1, true, true>() with BK = 32 (gemm_body.hpp), the two LDS limits of edge.hip
+EDGE_WAVES = 4
+EDGE_GAT_DOC_LDS = 64 * 65 + 64
+EDGE_TILE_LDS = ((2 * 32 * 65 + 3) & ~3) + 2 * 32 * 65
+EDGE_LDS_MAX, EDGE_CMP_LDS_MAX = 160 * 1024 // 4, 64 * 1024 // 4   # floats
+EDGE_CMP_MAX_D = 512
+
+
+def edge_plan_sweep():
+    """The argument rows (EDGE_PLAN_ARGS) of the plan table: every pass on dense and compact operands over the N and D steps, each
+    misalignment bit alone and none, ragged / att / has_dE / has_dEbar on and off, the defer-queue summaries around the
+    spread_min rule, and the sizes either side of each LDS threshold."""
+    NS, DS, MIS = (1, 63, 64, 65, 100, 256), (1, 3, 4, 63, 64, 66, 252, 256, 260, 512, 516), (0, 1, 2, 4, 8, 16)
+    B, rows = 3, []
+
+    def row(ps, compact, N, D, B=B, ragged=0, att=1, has_dE=1, has_dEbar=1, mis=0, parked=0, any_rb=0, col_C=0):
+        rows.append((ps, compact, B, N, D, ragged, att, has_dE, has_dEbar, mis, parked, any_rb, col_C))
+
+    for N in NS:
+        for D in DS:
+            for mis in MIS:
+                for att in (0, 1):
+                    row(0, 0, N, D, att=att, mis=mis)                      # dense forward
+                for has_dE in (0, 1):
+                    row(1, 0, N, D, has_dE=has_dE, mis=mis)                # dense backward, nothing parked
+                row(2, 0, N, D, att=0, mis=mis)                            # dense mean backward
+            for ragged in (0, 1):
+                for att in (0, 1):
+                    row(0, 0, N, D, ragged=ragged, att=att, has_dE=0, has_dEbar=0)
+                    if D <= EDGE_CMP_MAX_D:
+                        row(0, 1, N, D, ragged=ragged, att=att)           # compact forward, backward (att 0: the mean alone)
+                        row(1, 1, N, D, ragged=ragged, att=att)
+                row(1, 0, N, D, ragged=ragged, has_dEbar=0, mis=8)         # an absent dEbar's alignment does not count
+                row(1, 0, N, D, ragged=ragged, has_dE=0, mis=4)
+                if D <= EDGE_CMP_MAX_D:
+                    row(2, 1, N, D, ragged=ragged, att=0)
+    # the queue summary: around spread_min = 1024, with and without row blocks and a column-sum second stage (256 columns per
+    # workgroup), on shapes that may carry (vec 4) and that may not (D % 4 != 0, a misaligned E), with and without GAT passengers
+    for N in (64, 65, 100):
+        for D, mis in ((4, 0), (64, 0), (256, 0), (66, 0), (64, 1)):
+            for parked in (0, 1, 1023, 1024, 5000):
+                for any_rb in (0, 1):
+                    for col_C in (0, 256, 257):
+                        row(1, 0, N, D, mis=mis, parked=parked, any_rb=any_rb, col_C=col_C)
+    # dense backward: a row's LDS (N rounded up to 4, + EW * D floats) crosses the GAT passenger's image, the tile's, the 160 KB limit
+    for N in (64, 65, 256):
+        N4 = (N + 3) & ~3
+        for floats in (EDGE_GAT_DOC_LDS, EDGE_TILE_LDS, EDGE_LDS_MAX):
+            d = (floats - N4) // EDGE_WAVES
+            for D in (d - 4, d, d + 4):
+                for parked in (0, 1024):
+                    row(1, 0, N, D, B=1, parked=parked, col_C=256)
+    # forward: the dense 160 KB limit and the compact 64 KB limit (EW * D + N floats with attention, EW * D without)
+    for N in (64, 256):
+        d = (EDGE_LDS_MAX - N) // EDGE_WAVES
+        for D in (d - 4, d, d + 4, EDGE_LDS_MAX // EDGE_WAVES, EDGE_LDS_MAX // EDGE_WAVES + 4):
+            for att in (0, 1):
+                row(0, 0, N, D, B=1, att=att)
+    for D in (EDGE_CMP_MAX_D - 4, EDGE_CMP_MAX_D):
+        n = EDGE_CMP_LDS_MAX - EDGE_WAVES * D
+        for N in (n - 1, n, n + 1):
+            for att in (0, 1):
+                row(0, 1, N, D, B=1, att=att)
+                row(1, 1, N, D, B=1, att=att)
+    return rows
+
+
+def test_edge_plan_is_the_decision_the_scattered_expressions_made():
+    """gcgcn_debug_edge_plan (the plan functions edge_fwd / edge_bwd / edge_bcast / cmp_fwd / cmp_bwd and the GATAttention entry
+    points call) gives, for every row of edge_plan_sweep, the launch the code before it chose.  The expected table
+    (tests/golden/edge_plan_parent.npz) was recorded from the PARENT of the commit that introduced EdgePlan, not from the code under
+    test: in a scratch copy of the parent a throw-away function evaluated the parent's own expressions -- small / slices / the
+    scratch size of gcgcn_gat_bwd, then vec, lds_row, lds, the riding condition, col_base, ncolwg, the grid, the spread constants and
+    the RB choice of edge_bwd, then vec / lds / grid of edge_fwd and edge_bcast, att and the LDS sizes of cmp_fwd and cmp_bwd, the
+    route and the rowbuf carve of gcgcn_gat_bwd_compact, in that order -- on made-up operand addresses, over these same rows.  A
+    launch that carries nothing has RB, col_base, ncolwg and the Spread all 0.  No tolerance, no row left out."""
+    import ctypes
+    import numpy as np
+
+    def plan(args):
+        out = np.full(len(EDGE_PLAN_FIELDS), -7, np.int32)
+        _lib.call("gcgcn_debug_edge_plan", *args, out.ctypes.data_as(ctypes.c_void_p))
+        return out
+
+    rows = edge_plan_sweep()
+    want = np.load(os.path.join(ROOT, "tests", "golden", "edge_plan_parent.npz"))
+    assert want["args"].tolist() == [list(r) for r in rows], "the recorded table and edge_plan_sweep list different rows"
+    assert want["plan"].shape == (len(rows), len(EDGE_PLAN_FIELDS)) and len(rows) > 2500
+    f = {name: k for k, name in enumerate(EDGE_PLAN_FIELDS)}
+    wrong = []
+    for args, w in zip(rows, want["plan"]):
+        got = plan(args)
+        if not np.array_equal(got, w):
+            diff = {name: (int(w[k]), int(got[k])) for name, k in f.items() if w[k] != got[k]}
+            wrong.append(f"{dict(zip(EDGE_PLAN_ARGS, args))}: (want, got) {diff}")
+            continue
+        ps, compact, B, N = args[:4]
+        if ps == 1 and not compact:   # structure of a dense backward launch
+            ntile = got[f["sp_na"]]
+            assert got[f["grid"]] == B * N + got[f["ngat"]] + ntile + got[f["ncolwg"]], args
+            assert (got[f["col_base"]] == 0) == (got[f["ncolwg"]] == 0), args
+            assert got[f["col_base"]] in (0, B * N + got[f["ngat"]] + ntile), args
+            if got[f["vec"]] == 1 or not got[f["carry_ok"]]:
+                assert ntile == 0 and got[f["ncolwg"]] == 0 and got[f["RB"]] == 0, args
+            if ntile:
+                assert got[f["lds"]] == 0 and got[f["sp_cohort"]] == 256 and got[f["sp_stride"]] % 8 == 0, args
+        else:
+            assert got[f["grid"]] == B * N, args
+    assert not wrong, f"{len(wrong)} of {len(rows)} rows differ\n" + "\n".join(wrong[:40])
+    # every value of a decision occurs in the table
+    cols = {name: set(want["plan"][:, k].tolist()) for name, k in f.items()}
+    assert cols["vec"] == {-1, 1, 4} and cols["route"] == {-1, 0, 1, 2} and cols["slices"] == {-1, 1, 4, 8}
+    assert cols["lds_ok"] == {-1, 0, 1} and cols["carry_ok"] == {-1, 0, 1} and cols["RB"] == {-1, 0, 1}
+    # compact rows stop at D = 512: the hook refuses what cmp_check refuses
+    with pytest.raises(RuntimeError, match="compact rows support up to 512"):
+        plan((0, 1, 3, 16, EDGE_CMP_MAX_D + 1, 0, 1, 1, 1, 0, 0, 0, 0))
+
+
 # ---- the GEMM launcher's plan ---------------------------------------------------------------------------------------------------
 GEMM_WS = 16 << 20   # workspace elements that hold every split of these shapes
 
