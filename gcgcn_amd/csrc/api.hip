@@ -10,9 +10,9 @@
 
 #include <stdlib.h>
 
+#include "attn_plan.hpp"
 #include "compact.hpp"
 #include "gat_body.hpp"
-#include "gcn_plan.hpp"
 #include "gemm.hpp"
 #include "rowops.hpp"
 
@@ -136,9 +136,10 @@ static bool set_opt(const char* name, int value) {
   return false;
 }
 
-// option mha_core = 0 (GCGCN_MHA_CORE=0) sends small graphs through the generic batched-GEMM + row-softmax attention path as
-// well (A/B testing of mha_core.hip).
-static bool use_mha_core() { return option("mha_core", 1) != 0; }
+// What attn_plan_fwd / _bwd (mha_core.hip) decide on: the one place option mha_core (GCGCN_MHA_CORE) is read
+static AttnQuery make_attn_query(int N, int D, int H, const void* Q, const void* dQ, bool hook, bool chain_attends, bool core_done) {
+  return AttnQuery{N, D, H, attn_misalign(Q, dQ), hook, chain_attends, core_done, option("mha_core", 1)};
+}
 
 // gcgcn_edge_ride -> EdgeRide (kind 1: edge mean forward, 2: its backward); NULL = no passenger
 static int make_ride(const char* who, const gcgcn_edge_ride* ride, int kind, EdgeRide& r) {
@@ -434,27 +435,26 @@ int gcgcn_mha_fwd(int B, int N, int D, int H, const float* X, const int32_t* n_v
   GC_TRY(check_dims("mha_fwd", B, N, D, 1, H));
   const long wse = scratch ? gemm_scratch_elems(B, N, D, 1) : 0;
   GC_REQUIRE(X && flat && Q && P, "mha_fwd: null pointer");
-  const Drop drop = make_drop(rng_snap, GCGCN_SALT_MHA, p);
-  GC_REQUIRE(!drop.snap || A, "mha_fwd: dropout on but A is NULL");
+  const AttnPlan plan = attn_plan_fwd(make_attn_query(N, D, H, Q, nullptr, false, false, false));
+  const GcnCtx::MhaFwd m = attn_core(GcnCtx::MhaFwd{Q, P, A}, D, H, plan, rng_snap, p);
+  GC_REQUIRE(!m.drop.snap || A, "mha_fwd: dropout on but A is NULL");
   const long M = (long)B * N;
-  const int dh = D / H;
   {  // Q = X Wq^T + bq      (glove:136, all heads at once)
     GemmArgs g = gemm_nt(X, D, flat, D, Q, D, (int)M, D, D).split_ws(scratch, wse);
     g.bias = flat + (long)D * D;
     use_rows(g, live_rows(rowblk, N, n_valid != nullptr), 1, 1);
     GC_TRY(gemm(g, st));
   }
-  const float alpha = 1.f / sqrtf((float)dh);
-  if (use_mha_core() && mha_core_ok(N, D, H, Q, nullptr))  // small graph: scores stay in LDS
-    return mha_core_fwd(Q, n_valid, P, A, B, N, D, H, alpha, drop, st);
-  {  // S[b,h] = Q_h Q_h^T / sqrt(dh)   (glove:137-138: keys use the query projection)
-    GemmArgs g = gemm_nt(Q, D, Q, D, P, N, N, N, dh).split_ws(scratch, wse);
-    g.batch_z1(B, (long)N * D, (long)N * D, (long)H * N * N).batch_z2(H, dh, dh, (long)N * N);
-    g.alpha = alpha;
-    GC_TRY(gemm(g, st));
+  switch (plan.route) {
+    case AttnPlan::CORE: return mha_core_fwd(m, n_valid, B, N, D, H, st);
+    default: {  // GEMM: S[b,h] = Q_h Q_h^T / sqrt(dh)   (glove:137-138: keys use the query projection), then the row softmax
+      GemmArgs g = gemm_nt(Q, D, Q, D, P, N, N, N, m.dh).split_ws(scratch, wse);
+      g.batch_z1(B, (long)N * D, (long)N * D, (long)H * N * N).batch_z2(H, m.dh, m.dh, (long)N * N);
+      g.alpha = m.alpha;
+      GC_TRY(gemm(g, st));
+      return softmax_fwd(P, nullptr, n_valid, P, A, M * H, N, H, m.drop, st);
+    }
   }
-  GC_TRY(softmax_fwd(P, nullptr, n_valid, P, A, M * H, N, H, drop, st));
-  return 0;
 }
 
 int64_t gcgcn_mha_scratch(int B, int N, int D) { return scratch_elems(B, N, D, 1); }
@@ -466,22 +466,20 @@ int gcgcn_mha_bwd(int B, int N, int D, int H, const float* X, const float* flat,
   GC_TRY(check_dims("mha_bwd", B, N, D, 1, H));
   const long wse = scratch ? gemm_scratch_elems(B, N, D, 1) : 0;
   GC_REQUIRE(X && flat && Q && P && dA && dX && dflat && dS && dQ, "mha_bwd: null pointer");
-  const Drop drop = make_drop(rng_snap, GCGCN_SALT_MHA, p);
+  const AttnPlan plan = attn_plan_bwd(make_attn_query(N, D, H, Q, dQ, false, false, core_done != 0));
+  const MhaPass mp = attn_core(mha_pass(Q, P, dA, dQ, B, N, D, H), D, H, plan, rng_snap, p);
   const long M = (long)B * N;
-  const int dh = D / H;
-  const float alpha = 1.f / sqrtf((float)dh);
-  if (core_done) {  // dQ arrived with the call (computed as passengers of the convolution's backward, gcgcn_mha_hook)
-  } else if (use_mha_core() && mha_core_ok(N, D, H, Q, dQ)) {
-    GC_TRY(mha_core_bwd(Q, P, dA, dQ, B, N, D, H, alpha, drop, st));
-  } else {
-    GC_TRY(softmax_bwd(P, dA, dS, M * H, N, drop, st));
-    for (int pass = 0; pass < 2; ++pass) {  // dQ_h = alpha (dS + dS^T) Q_h: dS Q_h, then += dS^T Q_h
-      GemmArgs g = (pass == 0 ? gemm_nn : gemm_tn)(dS, N, Q, D, dQ, D, N, dh, N).split_ws(scratch, wse);
-      g.batch_z1(B, (long)H * N * N, (long)N * D, (long)N * D).batch_z2(H, (long)N * N, dh, dh);
-      g.alpha = alpha;
-      g.accumulate = pass;
-      GC_TRY(gemm(g, st));
-    }
+  switch (plan.route) {
+    case AttnPlan::DONE: break;
+    case AttnPlan::CORE: GC_TRY(mha_core_bwd(mp, st)); break;
+    default:  // GEMM
+      GC_TRY(softmax_bwd(P, dA, dS, M * H, N, mp.drop, st));
+      for (int pass = 0; pass < 2; ++pass) {  // dQ_h = alpha (dS + dS^T) Q_h: dS Q_h, then += dS^T Q_h
+        GemmArgs g = (pass == 0 ? gemm_nn : gemm_tn)(dS, N, Q, D, dQ, D, N, mp.dh, N).split_ws(scratch, wse);
+        g.batch_z1(B, (long)H * N * N, (long)N * D, (long)N * D).batch_z2(H, (long)N * N, mp.dh, mp.dh);
+        g.alpha = mp.alpha, g.accumulate = pass;
+        GC_TRY(gemm(g, st));
+      }
   }
   {  // one launch: dX = dQ Wq  and  dWq = dQ^T X
     GemmArgs gs[2] = {gemm_nn(dQ, D, flat, D, dX, D, (int)M, D, D).split_ws(scratch, wse),
@@ -550,11 +548,12 @@ int gcgcn_gcn_fwd(int B, int N, int D, int L, int H, const float* X, const float
                   const gcgcn_edge_ride* ride, const gcgcn_mha_hook* mha, const int32_t* rowblk, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   GC_TRY(check_dims("gcn_fwd", B, N, D, L, H));
-  if (mha) {
-    GC_REQUIRE(gcgcn_maggc_fusable(N, D, H) && mha->flat_q && mha->Q && mha->P, "gcn_fwd: attention hook on a shape it does not serve");
-    GC_REQUIRE(mha_core_ok(N, D, H, mha->Q, nullptr), "gcn_fwd: attention hook: misaligned Q");
-    A = mha->A ? mha->A : mha->P;   // what the attention core below writes
-  }
+  AttnQuery aq = make_attn_query(N, D, H, mha ? mha->Q : nullptr, nullptr, mha != nullptr, false, false);
+  const int refusal = attn_hook_refusal(aq);   // (no hook: served)
+  GC_REQUIRE(refusal != ATTN_REFUSED_SHAPE, "gcn_fwd: attention hook on a shape it does not serve");
+  GC_REQUIRE(!mha || (mha->flat_q && mha->Q && mha->P), "gcn_fwd: attention hook on a shape it does not serve");
+  GC_REQUIRE(refusal != ATTN_REFUSED_ALIGN, "gcn_fwd: attention hook: misaligned Q");
+  if (mha) A = mha->A ? mha->A : mha->P;   // what the attention core below writes
   EdgeRide er;
   GC_TRY(make_ride("gcn_fwd", ride, 1, er));
   const long wse = scratch ? gemm_scratch_elems(B, N, D, H) : 0;
@@ -570,6 +569,8 @@ int gcgcn_gcn_fwd(int B, int N, int D, int L, int H, const float* X, const float
   ChainQuery q = make_query(B, N, D, L, H, y, flat, n_valid != nullptr, scratch != nullptr, mha != nullptr, er, A, Pn, Y);
   q.G = G, q.HO = HO, q.X = X;
   const ChainPlan plan = chain_plan_fwd(q);
+  aq.chain_attends = plan.attention;   // the hook's core runs where the chain plan lets it
+  const AttnPlan ap = attn_plan_fwd(aq);
   GcnCtx c = make_ctx(B, N, D, L, H, y, X, A, flat, n_valid, drop);
   c.G = G, c.Pn = Pn, c.Y = Y, c.HO = HO, c.rinv = rinv;
   if (plan.ride) c.ride = er;
@@ -594,16 +595,13 @@ int gcgcn_gcn_fwd(int B, int N, int D, int L, int H, const float* X, const float
       GC_TRY(edge_fwd(er.in, nullptr, er.n_valid, er.out, nullptr, nullptr, nullptr, Drop(), er.B, er.N, er.D, st));
       er.kind = 0;
     }
-    if (mha) {  // the attention core: scores in LDS, P / A out (glove:137-140) -- in the chain workgroups' prologue where the
-                // shape's chain kernel can do that (plan.attention), as a launch of its own otherwise
-      const Drop adrop = make_drop(mha->rng_snap, GCGCN_SALT_MHA, mha->p);
-      GC_REQUIRE(!adrop.snap || mha->A, "gcn_fwd: attention dropout on but A is NULL");
-      const float alpha = 1.f / sqrtf((float)(D / H));
-      if (plan.attention)
-        c.mha.Q = mha->Q, c.mha.P = mha->P, c.mha.A = mha->A, c.mha.alpha = alpha, c.mha.drop = adrop, c.mha.dh = D / H,
-        c.mha.kchunk = mha_chunk(D / H);
-      else
-        GC_TRY(mha_core_fwd(mha->Q, n_valid, mha->P, mha->A, B, N, D, H, alpha, adrop, st));
+    if (mha) {  // the attention core: scores in LDS, P / A out (glove:137-140)
+      const GcnCtx::MhaFwd m = attn_core(GcnCtx::MhaFwd{mha->Q, mha->P, mha->A}, D, H, ap, mha->rng_snap, mha->p);
+      GC_REQUIRE(!m.drop.snap || mha->A, "gcn_fwd: attention dropout on but A is NULL");
+      switch (ap.route) {
+        case AttnPlan::CHAIN: c.mha = m; break;                              // the prologue of the chain launch below
+        default: GC_TRY(mha_core_fwd(m, n_valid, B, N, D, H, st));           // CORE: a launch of its own
+      }
     }
     if (plan.kind != ChainPlan::NONE) {
       GC_TRY(gcn_chain_fwd(c, plan, st));
@@ -642,13 +640,12 @@ int gcgcn_gcn_bwd(int B, int N, int D, int L, int H, const float* X, const float
                   void* stream) {
   DeferQueue* dq = (DeferQueue*)defer_queue;
   MhaPass mp;
+  AttnPlan ap;
   if (mha) {
-    GC_REQUIRE(gcgcn_maggc_fusable(N, D, H) && mha->Q && mha->P && mha->dQ && mha_core_ok(N, D, H, mha->Q, mha->dQ),
-               "gcn_bwd: attention hook on a shape it does not serve");
-    mp.Q = mha->Q, mp.P = mha->P, mp.dA = dA, mp.dQ = mha->dQ;
-    mp.N = N, mp.D = D, mp.H = H, mp.dh = D / H, mp.kchunk = mha_chunk(D / H), mp.count = B * H;
-    mp.alpha = 1.f / sqrtf((float)(D / H));
-    mp.drop = make_drop(mha->rng_snap, GCGCN_SALT_MHA, mha->p);
+    const AttnQuery aq = make_attn_query(N, D, H, mha->Q, mha->dQ, true, false, false);
+    GC_REQUIRE(!attn_hook_refusal(aq) && mha->Q && mha->P && mha->dQ, "gcn_bwd: attention hook on a shape it does not serve");
+    ap = attn_plan_bwd(aq);
+    mp = attn_core(mha_pass(mha->Q, mha->P, dA, mha->dQ, B, N, D, H), D, H, ap, mha->rng_snap, mha->p);
   }
   const Drop odrop = make_drop(out_rng_snap, GCGCN_SALT_GLUE, out_p);
   hipStream_t st = (hipStream_t)stream;
@@ -783,24 +780,17 @@ int gcgcn_gcn_bwd(int B, int N, int D, int L, int H, const float* X, const float
       weight_grad(gemm_tn(Y, HD, dP + (long)l * gh, HD, dflat + y.wd_off(0, l), gh, l * gh, gh, (int)M)
                       .batch_z2(H, (long)L * gh, (long)L * gh, y.wd_head));
     }
-    // + the attention core's backward: as passenger workgroups of this launch where a (document, head) pair's scratch fits
-    // the tile kernel's LDS (head width <= 32), as a launch of its own in front of it otherwise
-    const bool mha_rides = mha && gemm_group_can_carry_mha(D / H);
-    if (mha_rides) mp.kchunk = gemm_group_mha_chunk(D / H);
-    if (mha && !mha_rides)
-      GC_TRY(mha_core_bwd(mp.Q, mp.P, mp.dA, mp.dQ, B, N, D, H, mp.alpha, mp.drop, st));
-    GC_TRY(gemm_group(gs, n, st, col_pending ? &cr : nullptr, nullptr, mha_rides ? &mp : nullptr));
+    const MhaPass* riders = nullptr;   // + the attention core's backward, where attn_plan_bwd put it
+    if (mha) switch (ap.route) {
+        case AttnPlan::GROUP: riders = &mp; break;        // passenger workgroups of this launch
+        default: GC_TRY(mha_core_bwd(mp, st));            // CORE: a launch of its own in front of it
+      }
+    GC_TRY(gemm_group(gs, n, st, col_pending ? &cr : nullptr, nullptr, riders));
   }
   return 0;
 }
 
-int gcgcn_maggc_fusable(int N, int D, int H) {
-  if (N < 1 || N > 64 || H < 1 || D % H != 0) return 0;
-  const int dh = D / H;
-  // (the backward core rides in a group launch only for head widths up to 32; wider heads keep that launch, and still gain
-  // the query projection inside the forward group launch and the forward core inside the chain workgroups)
-  return use_mha_core() && dh % 4 == 0 && D % 4 == 0 ? 1 : 0;
-}
+int gcgcn_maggc_fusable(int N, int D, int H) { return attn_plan_fwd(make_attn_query(N, D, H, nullptr, nullptr, false, false, false)).fusable; }
 
 // ---------------------------------------------------------------------------------------------
 // GraphConv (the leaf layer, glove:18-50): out = (Ebar We + A X Wn (+ bias)) / rowsum(A)
@@ -890,6 +880,19 @@ int gcgcn_debug_chain_plan(int bwd, int B, int N, int D, int L, int H, int ragge
   q.dout = at(2), q.dXres = at(2), q.dout_m = at(2);
   const ChainPlan p = bwd ? chain_plan_bwd(q) : chain_plan_fwd(q);
   out[0] = p.kind, out[1] = p.aligned, out[2] = p.full, out[3] = p.fuse, out[4] = p.attention, out[5] = p.ride;
+  return 0;
+}
+
+// Where the attention core of a call of this shape runs, by the very plan functions the four entry points call (mha_core.hip), on
+// made-up operand addresses: misalign bit 0 puts Q off a 16-byte boundary, bit 1 dQ.  out[0..3] = AttnPlan's route, kchunk, fusable,
+// then attn_hook_refusal (the hooked gcgcn_gcn_fwd / _bwd fail on it: route and kchunk -1).  Exposed for tests (no GPU needed).
+int gcgcn_debug_attn_plan(int bwd, int N, int D, int H, int hook, int chain_attends, int core_done, int misalign, int32_t* out) {
+  GC_REQUIRE(N > 0 && D > 0 && H > 0 && D % H == 0 && out, "debug_attn_plan: bad arguments");
+  const void *Q = (const void*)(uintptr_t)(0x100000ul + ((misalign & 1) ? 4 : 0)), *dQ = (const void*)(uintptr_t)(0x200000ul + ((misalign & 2) ? 4 : 0));
+  const AttnQuery q = make_attn_query(N, D, H, Q, bwd ? dQ : nullptr, hook != 0, chain_attends != 0, core_done != 0);
+  const AttnPlan p = bwd ? attn_plan_bwd(q) : attn_plan_fwd(q);
+  out[3] = attn_hook_refusal(q);
+  out[0] = out[3] ? -1 : p.route, out[1] = out[3] ? -1 : p.kchunk, out[2] = p.fusable;
   return 0;
 }
 

@@ -22,8 +22,8 @@
 // separate instantiation with unconditional 16-byte loads; ragged shapes take the guarded one.
 #include <stdlib.h>
 
+#include "attn_plan.hpp"
 #include "edge_body.hpp"
-#include "gcn_plan.hpp"
 #include "gemm_body.hpp"
 #include "mha_body.hpp"
 #include "rowops.hpp"
@@ -405,9 +405,8 @@ int gemm(const GemmArgs& g_in, hipStream_t stream, int tile, int splits) {
 int gemm_group_mha_chunk(int dh) {
   const size_t room = sizeof(float) * lds_floats<1, 1, true, true>();
   const int c = mha_chunk(dh);
-  return sizeof(float) * (MT * MS + MT * (c + 1)) <= room ? c : 0;
+  return mha_lds_bytes_of(c) <= room ? c : 0;
 }
-bool gemm_group_can_carry_mha(int dh) { return gemm_group_mha_chunk(dh) > 0; }
 
 // What rides in the trailing workgroups of a group launch (the host's reading of a ColRide; the kernels read ready_slices themselves)
 enum RideKind {
@@ -501,7 +500,7 @@ int gemm_group(const GemmArgs* probs, int n, hipStream_t stream, const ColRide* 
   if (ride == RIDE_HEADS) GC_REQUIRE(col->X && col->out && col->R > 0 && col->ld > 0 && col->C == col->ld * col->ld, "gemm_group: bad head sum");
   static_assert(sizeof(GemmGroup) + sizeof(MhaPass) + 32 <= 4096, "gemm_group_pass_kernel: kernel arguments exceed 4 KB");
   if (gg.nprob == 0 && mha && mha->count > 0)   // nothing to ride on: the pairs get their launch
-    if (int e = mha_core_bwd(mha->Q, mha->P, mha->dA, mha->dQ, mha->count / mha->H, mha->N, mha->D, mha->H, mha->alpha, mha->drop, stream)) return e;
+    if (int e = mha_core_bwd(*mha, stream)) return e;
   if (gg.nprob == 0) {  // nothing to ride on
     if (ride == RIDE_HEADS) return mask_rows(nullptr, nullptr, 0, (int)col->ld, 1, nullptr, make_drop(nullptr, 0, 0.f), stream, col->X, col->out, (int)col->R);
     if (ride == RIDE_STAGE2) return colsum(col->part, nullptr, col->out, col->ready_slices, col->C, col->C, 1, 0, 0, 0, 0, nullptr, stream);

@@ -11,7 +11,8 @@ constexpr int MS = MT + 1;   // row stride of the score tile in LDS
 constexpr int MKC = 128;     // head-feature chunk held in LDS at a time
 
 static inline int mha_chunk(int dh) { return dh < MKC ? (dh + 31) / 32 * 32 : MKC; }
-static inline size_t mha_lds_bytes(int dh) { return sizeof(float) * (MT * MS + MT * (mha_chunk(dh) + 1)); }
+static inline size_t mha_lds_bytes_of(int kchunk) { return sizeof(float) * (MT * MS + MT * (kchunk + 1)); }   // score tile + one chunk of Q_h
+static inline size_t mha_lds_bytes(int dh) { return mha_lds_bytes_of(mha_chunk(dh)); }
 
 typedef float f16v __attribute__((ext_vector_type(16)));
 

@@ -52,13 +52,6 @@ constexpr int ROWBLK_HDR = 4;
 constexpr int ROWBLK_LIST_MAX = 512;   // live-block lists a tile body keeps in its lanes (eight registers): longer ones run dense
 static inline long row_blocks_ints(int B, int N) { return ROWBLK_HDR + (long)B * N / 16; }
 
-// mha_core.hip: fused attention core of MultiHeadAttention for N <= 64
-bool mha_core_ok(int N, int D, int H, const void* Q, const void* dQ);
-int mha_core_fwd(const float* Q, const int* n_valid, float* P, float* A, int B, int N, int D, int H, float alpha, Drop drop,
-                 hipStream_t st);
-int mha_core_bwd(const float* Q, const float* P, const float* dA, float* dQ, int B, int N, int D, int H, float alpha, Drop drop,
-                 hipStream_t st);
-
 // loss.hip: the trainer's per-document pair loss
 int pair_bce_fwd(const float* logits, const float* labels, const int* n_valid, float* loss, float* part, int B, int N, int R,
                  hipStream_t st);

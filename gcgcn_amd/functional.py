@@ -432,6 +432,77 @@ def _ride(inp, n_valid, out, B, N, D):
 head_sum_in_forward = True
 
 
+def _gcn_forward(ctx, x, ebar, adj, flat, n_valid, L, H, p, snap, e_next, out_p, out_snap, rowblk, hook=None, saved=()):
+    """The forward of GcnFn and MaggcFn: buffers, ride, the gcgcn_gcn_fwd call (``hook``: MaggcFn's gcgcn_mha_hook -- the call then
+    writes ``adj`` itself) and what _gcn_backward needs on ctx (``saved``: the caller's tensors, behind the block's)."""
+    B, N, D = x.shape
+    dev = x.device
+    HD = H * D
+    out = torch.empty(B, N, D, device=dev)
+    Pn, Y, HO = (torch.empty(B, N, HD, device=dev) for _ in range(3))
+    if hook is None:        # (GcnFn has always asked for rinv before G, MaggcFn after it: kept, so that the caching allocator of
+        rinv = torch.empty(B, H, N, device=dev)      # a captured step sees the request sequence it saw before)
+        G = torch.empty(B, N, HD, device=dev)
+    else:
+        G = torch.empty(B, N, HD, device=dev)
+        rinv = torch.empty(B, H, N, device=dev)
+    # sum over heads of the output projection's column blocks: a by-product of the first launch, used by backward
+    wsum = torch.empty(D, D, device=dev) if (H > 1 and head_sum_in_forward and any(ctx.needs_input_grad[:4])) else None
+    scratch = torch.empty(max(_lib.lib().gcgcn_gcn_scratch(B, N, D, H), 1), device=dev)
+    ebar_next, ride, ride_p = None, None, None
+    if e_next is not None:
+        ebar_next = torch.empty(e_next.shape[0], e_next.shape[1], e_next.shape[3], device=dev)
+        ride, ride_p = _ride(e_next, n_valid, ebar_next, *ebar_next.shape)
+    call("gcgcn_gcn_fwd", B, N, D, L, H, _p(x), _p(ebar), None if hook is not None else _p(adj), _p(n_valid), _p(flat), _p(snap),
+         float(p), _p(out_snap), float(out_p), _p(out), _p(Pn), _p(Y), _p(HO), _p(rinv), _p(G), _p(wsum), _p(scratch), ride_p,
+         None if hook is None else ctypes.cast(ctypes.pointer(hook), ctypes.c_void_p), _p(rowblk), _stream())
+    del ride
+    ctx.save_for_backward(x, ebar, adj, flat, Pn, Y, HO, rinv, *saved)
+    ctx.wsum, ctx.rowblk, ctx.n_valid, ctx.L, ctx.H = wsum, rowblk, n_valid, L, H
+    ctx.p, ctx.snap, ctx.out_p, ctx.out_snap = float(p), snap, float(out_p), out_snap
+    # to see in backward whether .grad will be installed or added to (never parked under DDP: see _under_ddp)
+    ctx.flat_leaf = flat if (flat.is_leaf and not _under_ddp()) else None
+    ctx.next_shape = None if e_next is None else tuple(e_next.shape)
+    return out, ebar_next
+
+
+def _gcn_backward(ctx, dout, debar_next, e_next_input, mha_hook=None):
+    """The backward of GcnFn and MaggcFn: workspaces, ride, parking -> (dX, dEbar, dA, dflat or None if parked, dE_next, dQ).
+    ``e_next_input``: E_next's place among the function's inputs; ``mha_hook``: MaggcFn's, dQ -> gcgcn_mha_hook (dQ[B,N,D] is
+    allocated here, behind the block's own workspaces, where it always was; None without a hook)."""
+    x, ebar, adj, flat, Pn, Y, HO, rinv = ctx.saved_tensors[:8]
+    B, N, D = x.shape
+    L, H, dev = ctx.L, ctx.H, x.device
+    HD = H * D
+    dout = dout.contiguous()
+    dX, dEbar = torch.empty_like(x), torch.empty_like(ebar)
+    dA = torch.empty_like(adj)
+    dflat = torch.empty_like(flat)
+    W1, W2, W3 = (torch.empty(B, N, HD, device=dev) for _ in range(3))
+    drow = torch.empty(B, H, N, device=dev)
+    dXres = torch.empty(B, N, D, device=dev)
+    dout_m = torch.empty(B, N, D, device=dev) if (ctx.n_valid is not None or ctx.out_snap is not None) else None
+    scratch = torch.empty(max(_lib.lib().gcgcn_gcn_scratch(B, N, D, H), 1), device=dev)
+    dQ = None if mha_hook is None else torch.empty(B, N, D, device=dev)
+    hook = None if mha_hook is None else mha_hook(dQ)
+    dE_next, ride, ride_p = None, None, None
+    if ctx.next_shape is not None and ctx.needs_input_grad[e_next_input] and debar_next is not None:
+        debar_next = debar_next.contiguous()
+        dE_next = torch.empty(ctx.next_shape, device=dev)
+        ride, ride_p = _ride(debar_next, ctx.n_valid, dE_next, *debar_next.shape)
+    bp = _pass_for_parking(ctx, 3)
+    call("gcgcn_gcn_bwd", B, N, D, L, H, _p(x), _p(ebar), _p(adj), _p(ctx.n_valid), _p(flat), _p(ctx.snap),
+         ctx.p, _p(ctx.out_snap), ctx.out_p, _p(Pn), _p(Y), _p(HO), _p(rinv), _p(ctx.wsum), _p(dout), _p(dX), _p(dEbar), _p(dA),
+         _p(dflat), _p(W1), _p(W2), _p(W3), _p(drow), _p(dXres), _p(dout_m), _p(scratch), ride_p,
+         None if hook is None else ctypes.cast(ctypes.pointer(hook), ctypes.c_void_p),
+         None if bp is None else bp.queue, _p(ctx.rowblk), _stream())
+    del ride, hook
+    if bp is not None:
+        bp.park(ctx.flat_leaf, dflat, (x, ebar, Y, HO, dout, dout_m, W2, W3, ctx.rowblk))
+        dflat = None                                # installed as .grad by the pass's end-of-backward callback
+    return dX, dEbar, dA, dflat, dE_next, dQ
+
+
 class GcnFn(torch.autograd.Function):
     """(X[B,N,D], Ebar[B,N,D], A[B,H,N,N], flat[, E_next[B,N,N,D]]) -> out[B,N,D][, mean_j E_next].
     GraphConvolution.forward (H = 1) / MultiGraphConvolution.forward, GCGCN_glove.py:63-80 / 97-120.  The optional
@@ -440,67 +511,11 @@ class GcnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ebar, adj, flat, n_valid, L, H, p, snap, e_next, out_p, out_snap, rowblk=None):
-        B, N, D = x.shape
-        dev = x.device
-        HD = H * D
-        out = torch.empty(B, N, D, device=dev)
-        Pn = torch.empty(B, N, HD, device=dev)
-        Y = torch.empty(B, N, HD, device=dev)
-        HO = torch.empty(B, N, HD, device=dev)
-        rinv = torch.empty(B, H, N, device=dev)
-        G = torch.empty(B, N, HD, device=dev)
-        # sum over heads of the output projection's column blocks: a by-product of the first launch, used by backward
-        wsum = torch.empty(D, D, device=dev) if (H > 1 and head_sum_in_forward and any(ctx.needs_input_grad[:4])) else None
-        scratch = torch.empty(max(_lib.lib().gcgcn_gcn_scratch(B, N, D, H), 1), device=dev)
-        ebar_next, ride, ride_p = None, None, None
-        if e_next is not None:
-            ebar_next = torch.empty(e_next.shape[0], e_next.shape[1], e_next.shape[3], device=dev)
-            ride, ride_p = _ride(e_next, n_valid, ebar_next, *ebar_next.shape)
-        call("gcgcn_gcn_fwd", B, N, D, L, H, _p(x), _p(ebar), _p(adj), _p(n_valid), _p(flat), _p(snap), float(p),
-             _p(out_snap), float(out_p), _p(out), _p(Pn), _p(Y), _p(HO), _p(rinv), _p(G), _p(wsum), _p(scratch), ride_p,
-             None, _p(rowblk), _stream())
-        del ride
-        ctx.save_for_backward(x, ebar, adj, flat, Pn, Y, HO, rinv)
-        ctx.wsum, ctx.rowblk = wsum, rowblk
-        ctx.n_valid, ctx.L, ctx.H, ctx.p, ctx.snap = n_valid, L, H, float(p), snap
-        ctx.out_p, ctx.out_snap = float(out_p), out_snap
-        # to see in backward whether .grad will be installed or added to (never parked under DDP: see _under_ddp)
-        ctx.flat_leaf = flat if (flat.is_leaf and not _under_ddp()) else None
-        ctx.next_shape = None if e_next is None else tuple(e_next.shape)
-        return out, ebar_next
+        return _gcn_forward(ctx, x, ebar, adj, flat, n_valid, L, H, p, snap, e_next, out_p, out_snap, rowblk)
 
     @staticmethod
     def backward(ctx, dout, debar_next):
-        x, ebar, adj, flat, Pn, Y, HO, rinv = ctx.saved_tensors
-        B, N, D = x.shape
-        L, H, dev = ctx.L, ctx.H, x.device
-        HD = H * D
-        dout = dout.contiguous()
-        dX = torch.empty_like(x)
-        dEbar = torch.empty_like(ebar)
-        dA = torch.empty_like(adj)
-        dflat = torch.empty_like(flat)
-        W1 = torch.empty(B, N, HD, device=dev)
-        W2 = torch.empty(B, N, HD, device=dev)
-        W3 = torch.empty(B, N, HD, device=dev)
-        drow = torch.empty(B, H, N, device=dev)
-        dXres = torch.empty(B, N, D, device=dev)
-        dout_m = torch.empty(B, N, D, device=dev) if (ctx.n_valid is not None or ctx.out_snap is not None) else None
-        scratch = torch.empty(max(_lib.lib().gcgcn_gcn_scratch(B, N, D, H), 1), device=dev)
-        dE_next, ride, ride_p = None, None, None
-        if ctx.next_shape is not None and ctx.needs_input_grad[9] and debar_next is not None:
-            debar_next = debar_next.contiguous()
-            dE_next = torch.empty(ctx.next_shape, device=dev)
-            ride, ride_p = _ride(debar_next, ctx.n_valid, dE_next, *debar_next.shape)
-        bp = _pass_for_parking(ctx, 3)
-        call("gcgcn_gcn_bwd", B, N, D, L, H, _p(x), _p(ebar), _p(adj), _p(ctx.n_valid), _p(flat), _p(ctx.snap),
-             ctx.p, _p(ctx.out_snap), ctx.out_p, _p(Pn), _p(Y), _p(HO), _p(rinv), _p(ctx.wsum), _p(dout), _p(dX), _p(dEbar), _p(dA),
-             _p(dflat), _p(W1), _p(W2), _p(W3), _p(drow), _p(dXres), _p(dout_m), _p(scratch), ride_p, None,
-             None if bp is None else bp.queue, _p(ctx.rowblk), _stream())
-        del ride
-        if bp is not None:
-            bp.park(ctx.flat_leaf, dflat, (x, ebar, Y, HO, dout, dout_m, W2, W3, ctx.rowblk))
-            dflat = None                                # installed as .grad by the pass's end-of-backward callback
+        dX, dEbar, dA, dflat, dE_next, _ = _gcn_backward(ctx, dout, debar_next, 9)
         return dX, dEbar, dA, dflat, None, None, None, None, None, dE_next, None, None, None
 
 
@@ -515,66 +530,22 @@ class MaggcFn(torch.autograd.Function):
     def forward(ctx, x, ebar, flat_mha, flat, n_valid, L, H, p_mha, snap_mha, p, snap, e_next, out_p, out_snap, rowblk=None):
         B, N, D = x.shape
         dev = x.device
-        HD = H * D
         Q = torch.empty(B, N, D, device=dev)
         P = torch.empty(B, H, N, N, device=dev)
         A = torch.empty(B, H, N, N, device=dev) if snap_mha is not None else None
-        out = torch.empty(B, N, D, device=dev)
-        Pn, Y, HO, G = (torch.empty(B, N, HD, device=dev) for _ in range(4))
-        rinv = torch.empty(B, H, N, device=dev)
-        wsum = torch.empty(D, D, device=dev) if (H > 1 and head_sum_in_forward and any(ctx.needs_input_grad[:4])) else None
-        scratch = torch.empty(max(_lib.lib().gcgcn_gcn_scratch(B, N, D, H), 1), device=dev)
-        ebar_next, ride, ride_p = None, None, None
-        if e_next is not None:
-            ebar_next = torch.empty(e_next.shape[0], e_next.shape[1], e_next.shape[3], device=dev)
-            ride, ride_p = _ride(e_next, n_valid, ebar_next, *ebar_next.shape)
         hook = _lib.MhaHook(flat_mha.data_ptr(), Q.data_ptr(), P.data_ptr(), _p(A), None, _p(snap_mha), float(p_mha))
-        call("gcgcn_gcn_fwd", B, N, D, L, H, _p(x), _p(ebar), None, _p(n_valid), _p(flat), _p(snap), float(p), _p(out_snap), float(out_p),
-             _p(out), _p(Pn), _p(Y), _p(HO), _p(rinv), _p(G), _p(wsum), _p(scratch), ride_p,
-             ctypes.cast(ctypes.pointer(hook), ctypes.c_void_p), _p(rowblk), _stream())
-        del ride, hook
-        adj = P if A is None else A
-        ctx.save_for_backward(x, ebar, adj, flat, Pn, Y, HO, rinv, flat_mha, Q, P)
-        ctx.wsum, ctx.rowblk = wsum, rowblk
-        ctx.n_valid, ctx.L, ctx.H, ctx.p, ctx.snap = n_valid, L, H, float(p), snap
         ctx.p_mha, ctx.snap_mha = float(p_mha), snap_mha
-        ctx.out_p, ctx.out_snap = float(out_p), out_snap
-        ctx.flat_leaf = flat if (flat.is_leaf and not _under_ddp()) else None
         ctx.flat_mha_leaf = flat_mha if (flat_mha.is_leaf and not _under_ddp()) else None
-        ctx.next_shape = None if e_next is None else tuple(e_next.shape)
-        return out, ebar_next
+        return _gcn_forward(ctx, x, ebar, P if A is None else A, flat, n_valid, L, H, p, snap, e_next, out_p, out_snap, rowblk,
+                            hook=hook, saved=(flat_mha, Q, P))
 
     @staticmethod
     def backward(ctx, dout, debar_next):
-        x, ebar, adj, flat, Pn, Y, HO, rinv, flat_mha, Q, P = ctx.saved_tensors
+        x, flat_mha, Q, P = ctx.saved_tensors[0], *ctx.saved_tensors[8:]
         B, N, D = x.shape
-        L, H, dev = ctx.L, ctx.H, x.device
-        HD = H * D
-        dout = dout.contiguous()
-        dXc, dEbar = torch.empty_like(x), torch.empty_like(ebar)        # dXc: the convolution's share of dX
-        dA = torch.empty_like(adj)
-        dflat = torch.empty_like(flat)
-        W1, W2, W3 = (torch.empty(B, N, HD, device=dev) for _ in range(3))
-        drow = torch.empty(B, H, N, device=dev)
-        dXres = torch.empty(B, N, D, device=dev)
-        dout_m = torch.empty(B, N, D, device=dev) if (ctx.n_valid is not None or ctx.out_snap is not None) else None
-        scratch = torch.empty(max(_lib.lib().gcgcn_gcn_scratch(B, N, D, H), 1), device=dev)
-        dQ = torch.empty(B, N, D, device=dev)
-        dE_next, ride, ride_p = None, None, None
-        if ctx.next_shape is not None and ctx.needs_input_grad[11] and debar_next is not None:
-            debar_next = debar_next.contiguous()
-            dE_next = torch.empty(ctx.next_shape, device=dev)
-            ride, ride_p = _ride(debar_next, ctx.n_valid, dE_next, *debar_next.shape)
-        bp = _pass_for_parking(ctx, 3)
-        hook = _lib.MhaHook(None, Q.data_ptr(), P.data_ptr(), None, dQ.data_ptr(), _p(ctx.snap_mha), ctx.p_mha)
-        call("gcgcn_gcn_bwd", B, N, D, L, H, _p(x), _p(ebar), _p(adj), _p(ctx.n_valid), _p(flat), _p(ctx.snap), ctx.p, _p(ctx.out_snap),
-             ctx.out_p, _p(Pn), _p(Y), _p(HO), _p(rinv), _p(ctx.wsum), _p(dout), _p(dXc), _p(dEbar), _p(dA), _p(dflat), _p(W1), _p(W2),
-             _p(W3), _p(drow), _p(dXres), _p(dout_m), _p(scratch), ride_p, ctypes.cast(ctypes.pointer(hook), ctypes.c_void_p),
-             None if bp is None else bp.queue, _p(ctx.rowblk), _stream())
-        del ride, hook
-        if bp is not None:
-            bp.park(ctx.flat_leaf, dflat, (x, ebar, Y, HO, dout, dout_m, W2, W3, ctx.rowblk))
-            dflat = None
+        H, dev = ctx.H, x.device
+        dXc, dEbar, dA, dflat, dE_next, dQ = _gcn_backward(         # dXc: the convolution's share of dX
+            ctx, dout, debar_next, 11, lambda dQ: _lib.MhaHook(None, Q.data_ptr(), P.data_ptr(), None, dQ.data_ptr(), _p(ctx.snap_mha), ctx.p_mha))
         # the rest of the attention's backward: dX = dQ Wq + dXc, dWq = dQ^T X, dbq (the core already ran, as passengers).
         # dWq and the second stage of dbq's column sums are needed by nobody before the end of backward: parked like the
         # convolution's weight gradients (round 5: the launch then has nothing to reduce -- one launch less, a shorter group)

@@ -276,22 +276,25 @@ class _GcnBase(_FlatBlock):
             ebar = F_.edge_mean(e, n_valid)
         return ebar
 
+    @staticmethod
+    def _with_ride(block, ride_edge, n_valid):
+        """``block(e_next=...)`` with the NEXT hop's edge tensor as its passenger: the mean comes back beside ``out`` and is parked
+        for that hop's call.  No ride_edge, or compact rows (nothing to stream: their mean is a segmented sum, computed when it
+        is asked for): the block alone."""
+        if ride_edge is None or isinstance(ride_edge, F_.CompactEdges):
+            return block(e_next=None)
+        out, ebar_next = block(e_next=_batched(ride_edge, 3)[0])
+        F_.park_edge_mean(ride_edge, n_valid, ebar_next)
+        return out
+
     def _stack(self, x, ebar, adj, n_valid, ride_edge, out_dropout, rowblk=None):
         """The fused block.  Extensions used by GraphHops: ``ride_edge`` is the edge tensor the NEXT hop's
         convolution will be called with -- its mean is computed inside this block's chain launch and parked for that
         call (functional.GcnFn); ``out_dropout`` applies the hop's output dropout (glove:341) in the block's last
         epilogue; ``rowblk``: the hop loop's row-block list of a ragged batch (functional.row_blocks; None: built here)."""
-        if ride_edge is None:
-            return F_.gcn_stack(x, ebar, adj, self.flat, self.layer_num, self.head_num, n_valid, self.p, self.training,
-                                out_dropout=out_dropout, rowblk=rowblk)
-        if isinstance(ride_edge, F_.CompactEdges):     # nothing to stream: its mean is a segmented sum, computed when it is asked for
-            return F_.gcn_stack(x, ebar, adj, self.flat, self.layer_num, self.head_num, n_valid, self.p, self.training,
-                                out_dropout=out_dropout, rowblk=rowblk)
-        e_next, _ = _batched(ride_edge, 3)
-        out, ebar_next = F_.gcn_stack(x, ebar, adj, self.flat, self.layer_num, self.head_num, n_valid, self.p,
-                                      self.training, e_next=e_next, out_dropout=out_dropout, rowblk=rowblk)
-        F_.park_edge_mean(ride_edge, n_valid, ebar_next)
-        return out
+        return self._with_ride(lambda e_next: F_.gcn_stack(x, ebar, adj, self.flat, self.layer_num, self.head_num, n_valid, self.p,
+                                                           self.training, e_next=e_next, out_dropout=out_dropout, rowblk=rowblk),
+                               ride_edge, n_valid)
 
 
 class GraphConv(nn.Module):
@@ -380,16 +383,9 @@ class MultiGraphConvolution(_GcnBase):
             al, xa = attention(node_feat, edge_feat, n_valid=n_valid, return_input_alias=True, rowblk=rowblk)
             return self(xa, edge_feat, al, n_valid=n_valid, ride_edge=ride_edge, out_dropout=out_dropout, rowblk=rowblk)
         ebar = self._edge_mean(edge_feat, n_valid)
-        e_next = None
-        if ride_edge is not None and not isinstance(ride_edge, F_.CompactEdges):
-            e_next, _ = _batched(ride_edge, 3)
-        r = F_.maggc_hop(x, ebar, attention.flat, self.flat, self.layer_num, self.head_num, n_valid, attention.p, self.p,
-                         self.training, e_next=e_next, out_dropout=out_dropout, rowblk=rowblk)
-        if e_next is not None:
-            out, ebar_next = r
-            F_.park_edge_mean(ride_edge, n_valid, ebar_next)
-        else:
-            out = r
+        out = self._with_ride(lambda e_next: F_.maggc_hop(x, ebar, attention.flat, self.flat, self.layer_num, self.head_num, n_valid,
+                                                          attention.p, self.p, self.training, e_next=e_next, out_dropout=out_dropout,
+                                                          rowblk=rowblk), ride_edge, n_valid)
         return out if batched else out.squeeze(0)
 
     def forward(self, node_feat: Tensor, edge_feat: Tensor, adj_matrix_list: Union[Tensor, Sequence[Tensor]],

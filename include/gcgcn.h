@@ -191,7 +191,7 @@ typedef struct gcgcn_edge_ride {
  * with core_done = 1 for the rest (dX = dQ Wq + dX_in, dWq, dbq).  Needs a graph of at most 64 entities and head width
  * D / H a multiple of 4 (gcgcn_maggc_fusable); results equal the separate calls bit for bit.  Where a chain kernel that
  * keeps its pair in LDS serves the shape, the forward core runs in that kernel's prologue instead of a launch; heads wider
- * than 32 features keep the backward core as a launch of its own (its scratch does not fit a tile workgroup's LDS). */
+ * than 64 features keep the backward core as a launch of its own (its scratch does not fit a tile workgroup's LDS). */
 typedef struct gcgcn_mha_hook {
   const float* flat_q;  /* MultiHeadAttention's flat parameters [Wq D*D | bq D] (gcgcn_mha_layout) */
   float* Q;             /* [B,N,D]   forward: out; backward: in */
@@ -435,6 +435,16 @@ int gcgcn_debug_head_plan(int B, int N, int R, int ragged, int32_t* out);
  * the compact row buffer in them.  -1: does not apply.  Host-only. */
 int gcgcn_debug_edge_plan(int pass, int compact, int B, int N, int D, int ragged, int att, int has_dE, int has_dEbar, int misalign,
                           int parked_tiles, int any_rb, int col_C, int32_t* out);
+
+/* ---- test hook: where the core of MultiHeadAttention runs ---------------------------------------------------------------
+ * Evaluates the plan functions gcgcn_mha_fwd / gcgcn_mha_bwd (hook = 0) and gcgcn_gcn_fwd / gcgcn_gcn_bwd with a gcgcn_mha_hook
+ * (hook = 1) call (csrc/attn_plan.hpp, csrc/mha_core.hip: attn_plan_fwd / _bwd) under the current "mha_core" option.
+ * chain_attends: the forward hook's chain kernel runs the core (gcgcn_debug_chain_plan's attention); core_done: gcgcn_mha_bwd's;
+ * misalign bit 0 puts Q off a 16-byte boundary, bit 1 dQ.  out[4] = route (0 batched GEMMs + softmax, 1 a mha_core launch, 2 the
+ * chain workgroups' prologue, 3 passengers of the convolution's last group launch, 4 nothing: dQ arrived), the head-feature chunk
+ * of that route's kernel (0: none), gcgcn_maggc_fusable, refused (0; a hook the entry point fails on: 1 a shape the core does not
+ * serve, 2 a misaligned Q / dQ -- route and chunk are then -1).  Host-only. */
+int gcgcn_debug_attn_plan(int bwd, int N, int D, int H, int hook, int chain_attends, int core_done, int misalign, int32_t* out);
 
 /* ---- test hook: what the GEMM launcher decides for a problem ----------------------------------------------------------
  * Evaluates the plan function every launcher of csrc/gemm.hip calls (gemm_plan) under the current options, on made-up operand

@@ -745,6 +745,63 @@ def test_edge_plan_is_the_decision_the_scattered_expressions_made():
         plan((0, 1, 3, 16, EDGE_CMP_MAX_D + 1, 0, 1, 1, 1, 0, 0, 0, 0))
 
 
+# ---- the attention core's plan ------------------------------------------------------------------------------------------------------
+ATTN_PLAN_ARGS = ["bwd", "N", "D", "H", "hook", "chain_attends", "core_done", "misalign", "mha_core"]
+ATTN_PLAN_FIELDS = ["route", "kchunk", "fusable", "refused"]
+ATTN_ROUTES = {"GEMM": 0, "CORE": 1, "CHAIN": 2, "GROUP": 3, "DONE": 4}
+
+
+def attn_plan_sweep():
+    """The argument rows (ATTN_PLAN_ARGS) of the plan table: graph sizes either side of the core's 64, head widths of 3, 4, 6, 10, 16,
+    32, 64, 128 and 192, every combination of the flags."""
+    import itertools
+    NS = (1, 16, 63, 64, 65, 128)
+    DH = ((8, 2), (12, 4), (24, 4), (64, 4), (128, 8), (256, 8), (256, 4), (256, 2), (768, 4), (512, 8), (30, 3))
+    assert sorted({D // H for D, H in DH}) == [3, 4, 6, 10, 16, 32, 64, 128, 192]
+    return [(bwd, N, D, H, hook, att, done, mis, core)
+            for N, (D, H), hook, att, done, mis, core, bwd in itertools.product(NS, DH, (0, 1), (0, 1), (0, 1), (0, 1, 2, 3), (1, 0), (0, 1))]
+
+
+def test_attn_plan_is_the_decision_the_scattered_predicates_made():
+    """gcgcn_debug_attn_plan (the plan functions gcgcn_mha_fwd / _bwd and the hooked gcgcn_gcn_fwd / _bwd call) gives, for every row of
+    attn_plan_sweep, the place the code before it ran the attention core in, the head-feature chunk it ran it with, and
+    gcgcn_maggc_fusable's answer.  The expected table (tests/golden/attn_plan_parent.npz) was recorded from the PARENT of the commit
+    that introduced AttnPlan, not from the code under test: in a scratch copy of the parent a throw-away function evaluated the
+    parent's own expressions in the order the entry points evaluated them -- use_mha_core and mha_core_ok of gcgcn_mha_fwd / _bwd
+    after core_done; gcgcn_maggc_fusable, then mha_core_ok, then plan.attention of gcgcn_gcn_fwd; gcgcn_maggc_fusable, mha_core_ok,
+    mha_chunk, gemm_group_can_carry_mha and gemm_group_mha_chunk of gcgcn_gcn_bwd -- on made-up operand addresses, over these same
+    rows.  A hook the parent refused is recorded with the check that refused it (gcgcn_maggc_fusable first: 1, then mha_core_ok's
+    alignment: 2; route and chunk -1) and must be refused by the same check (attn_hook_refusal, which the entry points ask).  No tolerance, no row left out."""
+    import ctypes
+    import numpy as np
+
+    def plan(*args):
+        out = np.full(len(ATTN_PLAN_FIELDS), -7, np.int32)
+        _lib.call("gcgcn_debug_attn_plan", *args, out.ctypes.data_as(ctypes.c_void_p))
+        return [int(v) for v in out]
+
+    rows = attn_plan_sweep()
+    want = np.load(os.path.join(ROOT, "tests", "golden", "attn_plan_parent.npz"))
+    assert want["args"].tolist() == [list(r) for r in rows], "the recorded table and attn_plan_sweep list different rows"
+    assert want["plan"].shape == (len(rows), len(ATTN_PLAN_FIELDS)) and len(rows) == 6 * 11 * 128
+    wrong = []
+    try:
+        for args, w in zip(rows, want["plan"].tolist()):
+            _lib.call("gcgcn_set_option", b"mha_core", args[8])
+            got = plan(*args[:8])
+            if got != w:
+                wrong.append(f"{dict(zip(ATTN_PLAN_ARGS, args))}: want {w} got {got}")
+    finally:
+        _lib.call("gcgcn_set_option", b"mha_core", 1)
+    assert not wrong, f"{len(wrong)} of {len(rows)} rows differ\n" + "\n".join(wrong[:40])
+    # every route, both refusals and both answers of fusable occur in the table; a chunk is 32, 64 or 128 features, or none
+    cols = {name: set(want["plan"][:, k].tolist()) for k, name in enumerate(ATTN_PLAN_FIELDS)}
+    assert cols["route"] == {-1, *ATTN_ROUTES.values()} and cols["refused"] == {0, 1, 2} and cols["fusable"] == {0, 1}
+    assert cols["kchunk"] == {-1, 0, 32, 64, 128}
+    # the wide head's backward core is the only hooked route that is a launch: the smallest such width is 68 (chunk 96), 64 still rides
+    assert plan(1, 16, 128, 2, 1, 0, 0, 0)[:2] == [ATTN_ROUTES["GROUP"], 64] and plan(1, 16, 136, 2, 1, 0, 0, 0)[:2] == [ATTN_ROUTES["CORE"], 96]
+
+
 # ---- the GEMM launcher's plan ---------------------------------------------------------------------------------------------------
 GEMM_WS = 16 << 20   # workspace elements that hold every split of these shapes
 
