@@ -103,6 +103,9 @@ SIGNATURES = {
     "gcgcn_adam_step_dev": (I, [I, P, L, ctypes.c_double, ctypes.c_double, ctypes.c_double, P, ctypes.c_double, P, L, P, P]),
     "gcgcn_gemm": (I, [I, I, I, P, L, I, P, L, I, P, L, I, L, L, L, F, P, I, I, I, I, P, L, P]),
     "gcgcn_gemm_dyn": (I, [I, I, I, P, L, I, P, L, I, P, L, P, I, P, I, L, P, L, P]),
+    "gcgcn_lstm_ws_bytes": (L, [I] * 5),
+    "gcgcn_lstm_fwd": (I, [I] * 5 + [P] * 10),
+    "gcgcn_lstm_bwd": (I, [I] * 5 + [P] * 17 + [L, P]),
 }
 
 _lib = None

@@ -14,6 +14,7 @@
 #include "compact.hpp"
 #include "gat_body.hpp"
 #include "gemm.hpp"
+#include "lstm.hpp"
 #include "rowops.hpp"
 
 namespace gc {
@@ -974,6 +975,44 @@ int gcgcn_gemm_dyn(int M, int N, int K, const float* A, int64_t lda, int a_kc, c
   GemmArgs g = gemm_stored(a_kc, b_kc, A, lda, B, ldb, C, ldc, M, N, K).split_ws(ws, ws_elems);
   g.bias = bias, g.accumulate = accumulate;
   return gemm_dyn(g, count, dyn, cap, (hipStream_t)stream);
+}
+
+// ---- the token encoder's LSTM layer (lstm.hip) ---------------------------------------------------------------------------------
+static int lstm_shape_ok(const char* who, int B, int T, int I, int H, int nd) {
+  GC_REQUIRE(H == LSTM_H, "%s: hidden width %d is not served (the recurrence kernels hold H = %d)", who, H, LSTM_H);
+  GC_REQUIRE(nd == 1 || nd == 2, "%s: %d directions (1 or 2)", who, nd);
+  GC_REQUIRE(B >= 1 && T >= 1 && I >= 1, "%s: bad shape B=%d T=%d I=%d", who, B, T, I);
+  GC_REQUIRE((long)B * T * nd * 4 * H <= 0x7fffffffL && (long)B * T * I <= 0x7fffffffL, "%s: B=%d T=%d I=%d is too large", who, B, T, I);
+  return 0;
+}
+
+int64_t gcgcn_lstm_ws_bytes(int B, int T, int I, int H, int nd) {
+  if (lstm_shape_ok("lstm_ws_bytes", B, T, I, H, nd)) return -1;
+  return (int64_t)sizeof(float) * lstm_ws_elems(B, T, I, nd);
+}
+
+int gcgcn_lstm_fwd(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* bias,
+                   const float* h0, const float* c0, float* out, float* gates, float* csave, void* stream) {
+  GC_TRY(lstm_shape_ok("lstm_fwd", B, T, I, H, nd));
+  GC_REQUIRE(x && w_ih && w_hh && bias && h0 && c0 && out && gates, "lstm_fwd: null pointer");
+  GC_REQUIRE((((uintptr_t)w_hh) & 15) == 0, "lstm_fwd: w_hh must be 16-byte aligned");
+  return lstm_fwd(B, T, I, nd, x, w_ih, w_hh, bias, h0, c0, out, gates, csave, (hipStream_t)stream);
+}
+
+int gcgcn_lstm_bwd(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* h0,
+                   const float* c0, const float* out, const float* gates, const float* csave, const float* dout, float* dgates,
+                   float* dx, float* dw_ih, float* dw_hh, float* db, float* dh0, float* dc0, void* ws, int64_t ws_bytes, void* stream) {
+  GC_TRY(lstm_shape_ok("lstm_bwd", B, T, I, H, nd));
+  GC_REQUIRE(x && w_ih && w_hh && h0 && c0 && out && gates && csave && dout && dgates && dx && dw_ih && dw_hh && db && dh0 && dc0 && ws,
+             "lstm_bwd: null pointer");
+  GC_REQUIRE(dout != out, "lstm_bwd: dout aliases the output (H_prev is read from the output after dout has been consumed)");
+  GC_REQUIRE(dgates != gates, "lstm_bwd: dgates aliases the saved gates");
+  GC_REQUIRE((((uintptr_t)ws) & 15) == 0 && (((uintptr_t)out) & 15) == 0 && (((uintptr_t)h0) & 15) == 0,
+             "lstm_bwd: ws, out and h0 must be 16-byte aligned");
+  GC_REQUIRE(ws_bytes >= gcgcn_lstm_ws_bytes(B, T, I, H, nd), "lstm_bwd: workspace of %lld bytes needed (gcgcn_lstm_ws_bytes)",
+             (long long)gcgcn_lstm_ws_bytes(B, T, I, H, nd));
+  return lstm_bwd(B, T, I, nd, x, w_ih, w_hh, h0, c0, out, gates, csave, dout, dgates, dx, dw_ih, dw_hh, db, dh0, dc0, (float*)ws,
+                  ws_bytes / (int64_t)sizeof(float), (hipStream_t)stream);
 }
 
 }  // extern "C"

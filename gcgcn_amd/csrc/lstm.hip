@@ -1,0 +1,280 @@
+// The token encoder's LSTM layer (EncoderLSTM, glove:377-428): nn.LSTM(input_size, 128, 1, batch_first=True), one or two
+// directions, every one of the T padded steps.  DESIGN.md section 8.7.
+//
+//   forward :  gates = X [W_ih_f; W_ih_r]^T + (b_ih + b_hh)      one product of the GEMM layer (gemm_nt + bias)
+//              lstm_fwd_kernel                                   the whole time loop, one workgroup per (direction, 16 batch rows)
+//   backward:  lstm_bwd_kernel                                   the time loop reversed, same grid: dgates, dh0, dc0
+//              lstm_hprev_kernel                                 H_prev = the output shifted one step, h0 at a direction's first step
+//              dW_ih = dgates^T X, dW_hh = dgates^T H_prev, dX = dgates W_ih, db = column sums of dgates: GEMM-layer launches
+//
+// A recurrence workgroup is eight waves.  Wave w owns hidden units [16 w, 16 w + 16) of ALL FOUR gates, so the cell update of a
+// unit happens inside one lane and c never leaves the registers.  The wave's slice of W_hh is the B operand of
+// v_mfma_f32_16x16x4_f32 and stays in 128 registers for the whole launch; the A operand (h_{t-1}, or dgates_t in the backward) is
+// read from a double-buffered LDS image, one __syncthreads() per step.  No workgroup reads what another one of the launch
+// writes, nothing is added atomically: two runs are bitwise equal.
+//
+// Lane maps of the 16x16x4 form (lane l, c16 = l & 15, q = l >> 4): A[row c16][k q], B[k q][col c16], C/D [row 4 q + r][col c16].
+// The sum over k may run in any order as long as A and B agree, so k-step s of lane group q takes k = q * (K / 4) + s: a lane's A
+// values are then CONTIGUOUS in the LDS row (ds_read_b128) and the forward's weights contiguous in W_hh's rows.
+#include "lstm.hpp"
+#include "gemm.hpp"
+
+namespace gc {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int LH = LSTM_H;
+constexpr int LROWS = 16;            // batch rows of a workgroup = rows of an MFMA tile
+constexpr int LHS = LH + 4;          // LDS row stride of the h image: rows 4 banks apart
+constexpr int LGS = 4 * LH + 4;      // ... of the dgates image
+static_assert(2 * LROWS * LGS * sizeof(float) <= 160 * 1024, "LDS of one compute unit");
+
+__device__ __forceinline__ float lstm_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+
+// ---- forward ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__ w_hh, const float* __restrict__ h0,
+                                                       const float* __restrict__ c0, float* __restrict__ gates, float* __restrict__ out,
+                                                       float* __restrict__ csave, const int B, const int T, const int nd) {
+  __shared__ __attribute__((aligned(16))) float hbuf[2][LROWS * LHS];
+  const int dir = blockIdx.y, b0 = blockIdx.x * LROWS;
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, c16 = l & 15, q = l >> 4;
+  const int u = 16 * w + c16;   // the hidden unit of this lane's accumulator column
+
+  // B operand: W_hh^T[k][g H + u] = W_hh[g H + u][k], k = 32 q + s
+  float wr[4][32];
+  const float* wd = w_hh + (long)dir * 4 * LH * LH;
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float4 v = *reinterpret_cast<const float4*>(wd + (long)(g * LH + u) * LH + 32 * q + 4 * j);
+      wr[g][4 * j] = v.x, wr[g][4 * j + 1] = v.y, wr[g][4 * j + 2] = v.z, wr[g][4 * j + 3] = v.w;
+    }
+
+  // the lane's four rows (C/D map): batch entries b0 + 4 q + r.  Rows past B read zeros (through a clamped address) and store nothing.
+  bool valid[4];
+  long grow[4], orow[4];   // element offsets of step 0 of the row in gates and in out / csave, this direction's column included
+  float c[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int b = b0 + 4 * q + r, bc = b < B ? b : B - 1;
+    valid[r] = b < B;
+    grow[r] = (long)bc * T * (nd * 4 * LH) + dir * 4 * LH + u;
+    orow[r] = (long)bc * T * (nd * LH) + dir * LH + u;
+    const long s0 = ((long)dir * B + bc) * LH + u;
+    c[r] = valid[r] ? c0[s0] : 0.f;
+    hbuf[0][(4 * q + r) * LHS + u] = valid[r] ? h0[s0] : 0.f;
+  }
+  const long gstep = (long)nd * 4 * LH, ostep = (long)nd * LH;
+
+  float gn[4][4];   // the input projection of the NEXT step, requested one step ahead
+  {
+    const int t0 = dir ? T - 1 : 0;
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) gn[g][r] = gates[grow[r] + t0 * gstep + g * LH];
+  }
+  __syncthreads();
+
+  for (int s = 0; s < T; ++s) {
+    const int t = dir ? T - 1 - s : s;
+    const int sn = s + 1 < T ? s + 1 : s, tn = dir ? T - 1 - sn : sn;   // the last step asks for itself again (unused)
+    f32x4 acc[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) acc[g][r] = valid[r] ? gn[g][r] : 0.f;
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) gn[g][r] = gates[grow[r] + tn * gstep + g * LH];
+
+    const float* hp = hbuf[s & 1] + c16 * LHS + 32 * q;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float4 a = *reinterpret_cast<const float4*>(hp + 4 * j);
+      const float av[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], wr[g][4 * j + e], acc[g], 0, 0, 0);
+    }
+
+    float* hn = hbuf[(s & 1) ^ 1];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float gi = lstm_sigmoid(acc[0][r]), gf = lstm_sigmoid(acc[1][r]), gg = tanhf(acc[2][r]), go = lstm_sigmoid(acc[3][r]);
+      c[r] = gf * c[r] + gi * gg;
+      const float h = go * tanhf(c[r]);
+      hn[(4 * q + r) * LHS + u] = h;
+      if (valid[r]) {
+        out[orow[r] + t * ostep] = h;
+        if (csave) {
+          float* gp = gates + grow[r] + t * gstep;
+          gp[0] = gi, gp[LH] = gf, gp[2 * LH] = gg, gp[3 * LH] = go;
+          csave[orow[r] + t * ostep] = c[r];
+        }
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ---- backward --------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__ w_hh, const float* __restrict__ c0,
+                                                       const float* __restrict__ gates, const float* __restrict__ csave,
+                                                       const float* __restrict__ dout, float* __restrict__ dgates, float* __restrict__ dh0,
+                                                       float* __restrict__ dc0, const int B, const int T, const int nd) {
+  __shared__ __attribute__((aligned(16))) float gbuf[2][LROWS * LGS];
+  const int dir = blockIdx.y, b0 = blockIdx.x * LROWS;
+  const int w = threadIdx.x >> 6, l = threadIdx.x & 63, c16 = l & 15, q = l >> 4;
+  const int u = 16 * w + c16;
+
+  // B operand of dh_rec = dgates W_hh: W_hh[k][u], k = 128 q + s over the 4H gate columns
+  float wr[128];
+  const float* wd = w_hh + (long)dir * 4 * LH * LH;
+#pragma unroll
+  for (int s = 0; s < 128; ++s) wr[s] = wd[(long)(128 * q + s) * LH + u];
+
+  bool valid[4];
+  long grow[4], orow[4], srow[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int b = b0 + 4 * q + r, bc = b < B ? b : B - 1;
+    valid[r] = b < B;
+    grow[r] = (long)bc * T * (nd * 4 * LH) + dir * 4 * LH + u;
+    orow[r] = (long)bc * T * (nd * LH) + dir * LH + u;
+    srow[r] = ((long)dir * B + bc) * LH + u;
+  }
+  const long gstep = (long)nd * 4 * LH, ostep = (long)nd * LH;
+
+  float dh[4] = {0.f, 0.f, 0.f, 0.f}, dc[4] = {0.f, 0.f, 0.f, 0.f};   // what the later step hands back
+  float gt[4][4], ct[4], cp[4], dy[4];                                  // step operands, requested one step ahead
+  // step s of this loop undoes forward step T - 1 - s, which ran at time t; the forward's previous time is tp
+#define LSTM_BWD_REQUEST(S)                                                                          \
+  {                                                                                                  \
+    const int fs_ = T - 1 - (S), t_ = dir ? T - 1 - fs_ : fs_, tp_ = dir ? t_ + 1 : t_ - 1;          \
+    _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                  \
+      _Pragma("unroll") for (int g = 0; g < 4; ++g) gt[g][r] = gates[grow[r] + t_ * gstep + g * LH]; \
+      ct[r] = csave[orow[r] + t_ * ostep];                                                           \
+      const float* pp_ = fs_ == 0 ? c0 + srow[r] : csave + orow[r] + tp_ * ostep;                    \
+      cp[r] = *pp_;                                                                                  \
+      dy[r] = dout[orow[r] + t_ * ostep];                                                            \
+    }                                                                                                \
+  }
+  LSTM_BWD_REQUEST(0)
+
+  for (int s = 0; s < T; ++s) {
+    const int fs = T - 1 - s, t = dir ? T - 1 - fs : fs;
+    float* gw = gbuf[s & 1];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float z = valid[r] ? 1.f : 0.f;
+      const float gi = z * gt[0][r], gf = z * gt[1][r], gg = z * gt[2][r], go = z * gt[3][r];
+      const float dhv = z * dy[r] + dh[r];
+      const float tc = tanhf(z * ct[r]);
+      const float dcv = dc[r] + dhv * go * (1.f - tc * tc);
+      const float da_i = dcv * gg * gi * (1.f - gi);
+      const float da_f = dcv * (z * cp[r]) * gf * (1.f - gf);
+      const float da_g = dcv * gi * (1.f - gg * gg);
+      const float da_o = dhv * tc * go * (1.f - go);
+      dc[r] = dcv * gf;
+      float* lp = gw + (4 * q + r) * LGS + u;
+      lp[0] = da_i, lp[LH] = da_f, lp[2 * LH] = da_g, lp[3 * LH] = da_o;
+      if (valid[r]) {
+        float* gp = dgates + grow[r] + t * gstep;
+        gp[0] = da_i, gp[LH] = da_f, gp[2 * LH] = da_g, gp[3 * LH] = da_o;
+      }
+    }
+    {
+      const int sn = s + 1 < T ? s + 1 : s;   // the last step asks for itself again (unused)
+      LSTM_BWD_REQUEST(sn)
+    }
+    __syncthreads();
+
+    f32x4 acc[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float* ap = gw + c16 * LGS + 128 * q;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+      const float4 a = *reinterpret_cast<const float4*>(ap + 4 * j);
+      acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, wr[4 * j], acc[0], 0, 0, 0);       // four independent chains: the
+      acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, wr[4 * j + 1], acc[1], 0, 0, 0);   // instruction's dependent latency
+      acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, wr[4 * j + 2], acc[2], 0, 0, 0);   // exceeds its issue interval
+      acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, wr[4 * j + 3], acc[3], 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dh[r] = (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
+  }
+#undef LSTM_BWD_REQUEST
+#pragma unroll
+  for (int r = 0; r < 4; ++r)
+    if (valid[r]) dh0[srow[r]] = dh[r], dc0[srow[r]] = dc[r];
+}
+
+// H_prev[b][t][dir H + u] = h of the direction's previous step: out one step back in the direction's own order, h0 at its first step
+__global__ __launch_bounds__(256) void lstm_hprev_kernel(const float* __restrict__ out, const float* __restrict__ h0, float* __restrict__ hprev,
+                                                         const int B, const int T, const int nd) {
+  const long n4 = (long)B * T * nd * (LH / 4);
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const int u4 = (int)(i % (LH / 4)), dir = (int)((i / (LH / 4)) % nd);
+  const long bt = i / ((LH / 4) * nd);
+  const int t = (int)(bt % T);
+  const long b = bt / T;
+  const bool first = dir ? t == T - 1 : t == 0;
+  const float* src = first ? h0 + ((long)dir * B + b) * LH + 4 * u4 : out + (bt + (dir ? 1 : -1)) * ((long)nd * LH) + dir * LH + 4 * u4;
+  *reinterpret_cast<float4*>(hprev + 4 * i) = *reinterpret_cast<const float4*>(src);
+}
+
+// ---- host --------------------------------------------------------------------------------------------------------------------
+int lstm_fwd(int B, int T, int I, int nd, const float* x, const float* w_ih, const float* w_hh, const float* bias, const float* h0,
+             const float* c0, float* out, float* gates, float* csave, hipStream_t st) {
+  const long BT = (long)B * T;
+  const int G = nd * 4 * LH;
+  GemmArgs g = gemm_nt(x, I, w_ih, I, gates, G, (int)BT, G, I).tagged("lstm_gemm");   // gates = X W_ih^T + b, both directions
+  g.bias = bias;
+  GC_TRY(gemm(g, st, 0, 1));
+  GC_LAUNCH_TIMED("lstm_fwd", 2.0 * BT * G * LH, lstm_fwd_kernel, dim3(cdiv(B, LROWS), nd), dim3(512), 0, st, w_hh, h0, c0, gates, out,
+                  csave, B, T, nd);
+  return check_launch("lstm_fwd");
+}
+
+static long lstm_col_elems(int nd) { return (long)COL_RIDE_SLICES * nd * 4 * LH; }
+static long lstm_split_elems(int I, int nd) { return gemm_ws_elems((long)nd * 4 * LH, I > LH ? I : LH); }
+
+long lstm_ws_elems(int B, int T, int I, int nd) { return (long)B * T * nd * LH + lstm_split_elems(I, nd) + lstm_col_elems(nd); }
+
+int lstm_bwd(int B, int T, int I, int nd, const float* x, const float* w_ih, const float* w_hh, const float* h0, const float* c0,
+             const float* out, const float* gates, const float* csave, const float* dout, float* dgates, float* dx, float* dw_ih,
+             float* dw_hh, float* db, float* dh0, float* dc0, float* ws, long ws_elems, hipStream_t st) {
+  const long BT = (long)B * T;
+  const int G = nd * 4 * LH;
+  GC_REQUIRE(ws_elems >= lstm_ws_elems(B, T, I, nd), "lstm_bwd: workspace of %ld floats needed", lstm_ws_elems(B, T, I, nd));
+  float* hprev = ws;
+  float* split = ws + BT * nd * LH;
+  const long split_elems = lstm_split_elems(I, nd);
+  float* part = split + split_elems;
+
+  GC_LAUNCH_TIMED("lstm_bwd", 2.0 * BT * G * LH, lstm_bwd_kernel, dim3(cdiv(B, LROWS), nd), dim3(512), 0, st, w_hh, c0, gates, csave, dout,
+                  dgates, dh0, dc0, B, T, nd);
+  GC_TRY(check_launch("lstm_bwd"));
+  {
+    ProfScope ps("lstm_hprev", st);
+    hipLaunchKernelGGL(lstm_hprev_kernel, dim3(cdiv(BT * nd * (LH / 4), 256)), dim3(256), 0, st, out, h0, hprev, B, T, nd);
+    GC_TRY(check_launch("lstm_hprev"));
+  }
+  // dW_ih = dgates^T X; dW_hh[dir] = dgates[:, dir]^T H_prev[:, dir]; dX = dgates W_ih; db = column sums of dgates (riding)
+  GemmArgs gs[3] = {
+      gemm_tn(dgates, G, x, I, dw_ih, I, G, I, (int)BT).split_ws(split, split_elems).tagged("lstm_gemm"),
+      gemm_tn(dgates, G, hprev, nd * LH, dw_hh, LH, 4 * LH, LH, (int)BT).batch_z2(nd, 4 * LH, LH, 4L * LH * LH).split_ws(split, split_elems).tagged("lstm_gemm"),
+      gemm_nn(dgates, G, w_ih, I, dx, I, (int)BT, I, G).split_ws(split, split_elems).tagged("lstm_gemm"),
+  };
+  ColRide cr;
+  cr.X = dgates, cr.out = db, cr.part = part, cr.R = BT, cr.ld = G, cr.C = G;
+  return gemm_group(gs, 3, st, &cr);
+}
+
+}  // namespace gc

@@ -1,0 +1,25 @@
+// One nn.LSTM(input_size, H, 1, batch_first=True) layer, uni- or bidirectional, all T padded steps (lstm.hip).  Internal header.
+#pragma once
+#include "common.hpp"
+
+namespace gc {
+
+constexpr int LSTM_H = 128;   // the hidden width the recurrence kernels serve (both reference models hard-code it)
+
+// Every buffer is the caller's, fp32, dense.  nd directions; the weights of the directions are stacked, gate order i, f, g, o:
+//   w_ih [nd * 4H][I], w_hh [nd * 4H][H], bias [nd * 4H] (= b_ih + b_hh), h0 / c0 [nd][B][H]
+//   out [B][T][nd * H]; gates [B * T][nd * 4H] (the input projection, then -- when csave is given -- the activated gates);
+//   csave [B][T][nd * H] = c_t, or nullptr: nothing is kept for a backward (gates is then scratch).
+int lstm_fwd(int B, int T, int I, int nd, const float* x, const float* w_ih, const float* w_hh, const float* bias, const float* h0,
+             const float* c0, float* out, float* gates, float* csave, hipStream_t st);
+
+// Floats of workspace lstm_bwd needs: H_prev [B * T][nd * H], the split-K partials of the weight gradients, the bias gradient's partials.
+long lstm_ws_elems(int B, int T, int I, int nd);
+
+// dgates [B * T][nd * 4H] receives the pre-activation gate gradients; dx [B * T][I], dw_ih / dw_hh / db stacked like the weights,
+// dh0 / dc0 [nd][B][H] per batch row.
+int lstm_bwd(int B, int T, int I, int nd, const float* x, const float* w_ih, const float* w_hh, const float* h0, const float* c0,
+             const float* out, const float* gates, const float* csave, const float* dout, float* dgates, float* dx, float* dw_ih,
+             float* dw_hh, float* db, float* dh0, float* dc0, float* ws, long ws_elems, hipStream_t st);
+
+}  // namespace gc

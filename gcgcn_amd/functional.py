@@ -13,6 +13,7 @@ import weakref
 from typing import Optional
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import SALT_GLUE, call
@@ -1089,3 +1090,81 @@ def pair_bce_loss(logits, labels, n_valid=None):
         raise ValueError(f"pair_bce_loss: logits {tuple(lg.shape)} vs labels {tuple(lb.shape)}")
     out = PairBceFn.apply(lg, lb, _nv(n_valid, lg.shape[0], lg.shape[1], lg.device))
     return out[0] if single else out
+
+
+# ---- the token encoder's LSTM layer (csrc/lstm.hip) ----------------------------------------------------------------------------
+def _lstm_ws(B: int, T: int, I: int, H: int, nd: int, dev) -> Tensor:
+    need = _lib.lib().gcgcn_lstm_ws_bytes(B, T, I, H, nd)
+    if need < 0:
+        raise RuntimeError(f"gcgcn_lstm_ws_bytes failed: {_lib.lib().gcgcn_last_error().decode()}")
+    return torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+
+
+class LstmFn(torch.autograd.Function):
+    """(x[B,T,I], w_ih[nd*4H,I], w_hh[nd*4H,H], bias[nd*4H], h0[nd,B,H], c0[nd,B,H]) -> out[B,T,nd*H]: one ``nn.LSTM`` layer over
+    all T steps with the directions' parameters stacked and ``bias = b_ih + b_hh`` (``lstm_layer`` stacks and splits them)."""
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, bias, h0, c0):
+        B, T, I = x.shape
+        nd, H = h0.shape[0], h0.shape[2]
+        need_grad = any(ctx.needs_input_grad)
+        out = torch.empty(B, T, nd * H, device=x.device)
+        gates = torch.empty(B * T, nd * 4 * H, device=x.device)
+        csave = torch.empty(B, T, nd * H, device=x.device) if need_grad else None
+        call("gcgcn_lstm_fwd", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(bias), _p(h0), _p(c0), _p(out), _p(gates), _p(csave), _stream())
+        written = (out, gates) if csave is None else (out, gates, csave)
+        torch.autograd.graph.increment_version(written)     # raw-pointer writes, as in optim._written
+        if need_grad:
+            ctx.save_for_backward(x, w_ih, w_hh, h0, c0, out, gates, csave)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        x, w_ih, w_hh, h0, c0, out, gates, csave = ctx.saved_tensors
+        B, T, I = x.shape
+        nd, H = h0.shape[0], h0.shape[2]
+        dout = dout.contiguous()
+        if dout.data_ptr() == out.data_ptr():
+            raise RuntimeError("lstm_layer: the output's gradient aliases the output itself")
+        dgates = torch.empty_like(gates)
+        dx, dw_ih, dw_hh = torch.empty_like(x), torch.empty_like(w_ih), torch.empty_like(w_hh)
+        db = torch.empty(nd * 4 * H, device=x.device)
+        dh0, dc0 = torch.empty_like(h0), torch.empty_like(c0)
+        ws = _lstm_ws(B, T, I, H, nd, x.device)
+        call("gcgcn_lstm_bwd", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(h0), _p(c0), _p(out), _p(gates), _p(csave), _p(dout), _p(dgates),
+             _p(dx), _p(dw_ih), _p(dw_hh), _p(db), _p(dh0), _p(dc0), _p(ws), ws.numel() * 4, _stream())
+        torch.autograd.graph.increment_version((dx, dw_ih, dw_hh, db, dh0, dc0))
+        return dx, dw_ih, dw_hh, db, dh0, dc0
+
+
+def lstm_layer(x, w_ih, w_hh, b_ih, b_hh, h0, c0, w_ih_r=None, w_hh_r=None, b_ih_r=None, b_hh_r=None):
+    """One ``nn.LSTM(input_size, H, 1, batch_first=True)`` layer in HIP: ``x[B,T,I]``, ``h0``/``c0`` ``[nd,B,H]`` (a ``[nd,1,H]``
+    state is broadcast over the batch) -> the output ``[B,T,nd*H]``.  Gate order i, f, g, o and all T padded steps, as torch runs
+    it.  The four ``*_r`` parameters of the reverse direction make it bidirectional (all four or none).  ``H = 128`` is served;
+    another width raises.  Gradients reach ``x``, every weight and bias, ``h0`` and ``c0``."""
+    rev = (w_ih_r, w_hh_r, b_ih_r, b_hh_r)
+    if any(t is None for t in rev) and not all(t is None for t in rev):
+        raise ValueError("lstm_layer: the reverse direction needs all of w_ih_r, w_hh_r, b_ih_r, b_hh_r")
+    nd = 1 if w_ih_r is None else 2
+    x = _chk(x, "x", 3)
+    for name, t in (("w_ih", w_ih), ("w_hh", w_hh), ("b_ih", b_ih), ("b_hh", b_hh), ("h0", h0), ("c0", c0)) + \
+            ((("w_ih_r", w_ih_r), ("w_hh_r", w_hh_r), ("b_ih_r", b_ih_r), ("b_hh_r", b_hh_r)) if nd == 2 else ()):
+        _chk(t, name)
+    B, T, I = x.shape
+    H = w_hh.shape[1]
+    if tuple(w_ih.shape) != (4 * H, I) or tuple(w_hh.shape) != (4 * H, H) or tuple(b_ih.shape) != (4 * H,) or tuple(b_hh.shape) != (4 * H,):
+        raise ValueError(f"lstm_layer: parameter shapes {tuple(w_ih.shape)}, {tuple(w_hh.shape)}, {tuple(b_ih.shape)}, {tuple(b_hh.shape)} "
+                         f"do not describe an LSTM of input {I}, width {H}")
+    if nd == 2 and (w_ih_r.shape != w_ih.shape or w_hh_r.shape != w_hh.shape or b_ih_r.shape != b_ih.shape or b_hh_r.shape != b_hh.shape):
+        raise ValueError("lstm_layer: the reverse direction's parameters differ in shape from the forward direction's")
+    if h0.dim() != 3 or c0.shape != h0.shape or h0.shape[0] != nd or h0.shape[2] != H or h0.shape[1] not in (1, B):
+        raise ValueError(f"lstm_layer: h0 {tuple(h0.shape)} / c0 {tuple(c0.shape)}, expected [{nd}, {B} or 1, {H}]")
+    # the directions' parameters stacked, the two biases added: a few small copies (autograd splits the gradients again)
+    if nd == 2:
+        W_ih, W_hh = torch.cat([w_ih, w_ih_r], 0), torch.cat([w_hh, w_hh_r], 0)
+        bias = torch.cat([b_ih + b_hh, b_ih_r + b_hh_r], 0)
+    else:
+        W_ih, W_hh, bias = w_ih.contiguous(), w_hh.contiguous(), b_ih + b_hh
+    return LstmFn.apply(x, W_ih, W_hh, bias, h0.expand(nd, B, H).contiguous(), c0.expand(nd, B, H).contiguous())

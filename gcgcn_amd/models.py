@@ -10,8 +10,8 @@ checkpoint loads with ``strict=True``.
 
 What runs where.  Everything from the entity pooling on (glove:293-360: edge-feature producers, CAGGC / MAGGC blocks, hop glue,
 classifier head) is :class:`gcgcn_amd.GraphModelTail`, i.e. the HIP kernels.  The token encoder in front of it -- embeddings,
-``EncoderLSTM`` (glove:377-428), ``linear_re`` + tanh, or BERT in the second model -- is plain PyTorch on purpose: it is not on
-the path this library accelerates and is restated here only so that the model is complete.
+``EncoderLSTM`` (glove:377-428), ``linear_re`` + tanh, or BERT in the second model -- is plain PyTorch by default, restated here
+so that the model is complete.  ``config.encoder_impl = "hip"`` opts the BiLSTM into ``functional.lstm_layer``.
 
 Extension: every ``forward`` also accepts a leading batch axis on all ten tensors (what ``gcgcn_amd.data.collate`` returns)
 plus ``n_valid[B]``; the reference's one-document call (``document[T]``, ``sen_matrix[N,N,S,T]`` ...) behaves as the reference's.
@@ -24,6 +24,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from .functional import lstm_layer
 from .modules import GraphModelTail
 
 Tensor = torch.Tensor
@@ -47,10 +48,15 @@ class LockedDropout(nn.Module):
 class EncoderLSTM(nn.Module):
     """The reference's BiLSTM token encoder (glove:377-428): ``nlayers`` ``nn.LSTM``s with learned initial states, locked dropout
     in front of every layer, layer outputs concatenated.  Parameter names as in the reference: ``rnns.{i}.*``, ``init_hidden.{i}``,
-    ``init_c.{i}``.  Plain PyTorch (MIOpen's LSTM on ROCm)."""
+    ``init_c.{i}``.  ``impl="torch"`` (the default) is plain PyTorch (MIOpen's LSTM on ROCm); ``impl="hip"`` runs every layer
+    through ``functional.lstm_layer`` on the same parameters -- the ``nn.LSTM`` modules stay as their holders, so the
+    ``state_dict`` is the same either way -- and raises on CPU tensors."""
 
-    def __init__(self, input_size, num_units, nlayers, concat, bidir, dropout, return_last):
+    def __init__(self, input_size, num_units, nlayers, concat, bidir, dropout, return_last, impl="torch"):
         super().__init__()
+        if impl not in ("torch", "hip"):
+            raise ValueError(f"EncoderLSTM: impl={impl!r} (\"torch\" or \"hip\")")
+        self.impl = impl
         self.rnns = nn.ModuleList(nn.LSTM(input_size if i == 0 else (num_units * 2 if bidir else num_units), num_units, 1,
                                           bidirectional=bidir, batch_first=True) for i in range(nlayers))
         nd = 2 if bidir else 1
@@ -63,6 +69,13 @@ class EncoderLSTM(nn.Module):
         bsz = input.size(0)
         output, outputs = input, []
         for i in range(self.nlayers):
+            if self.impl == "hip":
+                r = self.rnns[i]
+                rev = (r.weight_ih_l0_reverse, r.weight_hh_l0_reverse, r.bias_ih_l0_reverse, r.bias_hh_l0_reverse) if r.bidirectional else ()
+                output = lstm_layer(self.dropout(output), r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0,
+                                    self.init_hidden[i], self.init_c[i], *rev)
+                outputs.append(output)
+                continue
             h0 = self.init_hidden[i].expand(-1, bsz, -1).contiguous()
             c0 = self.init_c[i].expand(-1, bsz, -1).contiguous()
             output, _ = self.rnns[i](self.dropout(output), (h0, c0))
@@ -126,7 +139,8 @@ class GCGCN_glove(_GraphRelationModel):
         input_size = vec.shape[1] + config.entity_type_size + config.coref_size
         self.ner_emb = nn.Embedding(7, config.entity_type_size, padding_idx=0)               # glove:241
         self.entity_embed = nn.Embedding(config.max_length, config.coref_size, padding_idx=0)   # glove:246
-        self.rnn = EncoderLSTM(input_size, self.HIDDEN, 1, True, True, 1 - config.keep_prob, False)   # glove:248
+        self.rnn = EncoderLSTM(input_size, self.HIDDEN, 1, True, True, 1 - config.keep_prob, False,   # glove:248
+                               impl=getattr(config, "encoder_impl", "torch"))
         self.linear_re = nn.Linear(self.HIDDEN * 2, self.HIDDEN)                             # glove:264
         self.dis_embed = nn.Embedding(config.dis_num, config.dis_size)                       # glove:279
 

@@ -499,6 +499,24 @@ int64_t gcgcn_adam_ws_bytes(int n_tensors, int64_t total_blocks);
 int gcgcn_adam_step_dev(int n_tensors, const void* table, int64_t total_blocks, double beta1, double beta2, double eps,
                         const float* lr, double max_norm, void* ws, int64_t ws_bytes, float* grad_norm, void* stream);
 
+/* ---- the token encoder's LSTM layer (EncoderLSTM, glove:377-428) ----------------------------------------------------------
+ * One nn.LSTM(I, H, 1, batch_first=True) layer with nd = 1 or 2 directions over ALL T padded steps, gate order i, f, g, o,
+ * gates = x W_ih^T + b_ih + h W_hh^T + b_hh.  H = 128 is served; any other width is refused.  The directions' parameters are
+ * stacked: w_ih [nd * 4H][I], w_hh [nd * 4H][H], bias [nd * 4H] = b_ih + b_hh; h0 / c0 [nd][B][H]; x [B][T][I].
+ * gcgcn_lstm_fwd: out [B][T][nd * H]; gates [B * T][nd * 4H] is always needed (the input projection); with csave [B][T][nd * H]
+ * given, gates ends up holding the activated gates and csave the cell states, which is what gcgcn_lstm_bwd reads; csave = NULL
+ * (no-grad / eval) keeps nothing.  One GEMM launch + one recurrence launch.
+ * gcgcn_lstm_bwd: dout [B][T][nd * H] (must not alias out) -> dgates [B * T][nd * 4H] (scratch the caller owns), dx [B][T][I],
+ * dw_ih / dw_hh / db stacked like the parameters (db is the gradient of b_ih and of b_hh), dh0 / dc0 [nd][B][H] PER BATCH ROW
+ * (a broadcast initial state sums them over B).  ws: 16-byte aligned, gcgcn_lstm_ws_bytes(B, T, I, H, nd) bytes (-1: refused).
+ * No workgroup waits for another and nothing is added atomically: results are bit-reproducible.  Capturable. */
+int64_t gcgcn_lstm_ws_bytes(int B, int T, int I, int H, int nd);
+int gcgcn_lstm_fwd(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* bias,
+                   const float* h0, const float* c0, float* out, float* gates, float* csave, void* stream);
+int gcgcn_lstm_bwd(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* h0,
+                   const float* c0, const float* out, const float* gates, const float* csave, const float* dout, float* dgates,
+                   float* dx, float* dw_ih, float* dw_hh, float* db, float* dh0, float* dc0, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,125 @@
+"""EncoderLSTM forward + backward, impl="torch" (torch.nn.LSTM, MIOpen on ROCm) against impl="hip" (csrc/lstm.hip), in ONE process:
+same parameters, same input, same session.
+
+    python tools/encoder_bench.py [--B 32 --T 512 --I 140 --reps 30 --warmup 5] [--out profiles/encoder_bench.json]
+
+Timing: HIP events around each step on the current stream, warm-up steps first, the two sides INTERLEAVED rep by rep (so that a
+drift of the clocks hits both), median and min / max over the repetitions.  The hip side is additionally captured into a hipGraph
+(forward + backward) and its replays timed the same way.  The hip side's launches are timed on their own through the library's per-launch
+timer: "lstm_fwd" / "lstm_bwd" (the two recurrence kernels; the timer stamps the kernel's own begin and end), "lstm_hprev",
+"lstm_gemm" (the launches the GEMM layer makes one problem at a time: the input projection and the gradient problems a group
+launch cannot carry), "gemm_group" and "gemm_splitk_reduce" (the group launch of the remaining gradient problems and the reduce:
+only the encoder runs in this process, so these two tags are its own).
+Model beside it: a 16-row tile's step is 1024 v_mfma_f32_16x16x4_f32 on one compute unit, 32 cycles each per SIMD -> 3.4 us at
+2.4 GHz, 1.75 ms for T = 512; the backward recurrence has the same count.  Prints one JSON line."""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def stats(ms):
+    return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4), "reps": len(ms)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=32)
+    ap.add_argument("--T", type=int, default=512)
+    ap.add_argument("--I", type=int, default=140)
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "encoder_bench.json"), help="the JSON is also written there")
+    a = ap.parse_args()
+    from gcgcn_amd import _lib
+    from gcgcn_amd.models import EncoderLSTM
+    dev = torch.device("cuda:0")
+    H = 128
+    torch.manual_seed(7)
+    enc = {"torch": EncoderLSTM(a.I, H, 1, True, True, 0.0, False).to(dev).train()}
+    for p in enc["torch"].parameters():                        # the reference's reset_parameters: N(0, 0.1^2)
+        p.data.normal_(0, 0.1)
+    enc["hip"] = EncoderLSTM(a.I, H, 1, True, True, 0.0, False, impl="hip").to(dev).train()
+    enc["hip"].load_state_dict(enc["torch"].state_dict(), strict=True)
+    x = torch.randn(a.B, a.T, a.I, device=dev, requires_grad=True)
+    dy = torch.randn(a.B, a.T, 2 * H, device=dev)
+
+    def step(name):
+        m = enc[name]
+        for p in m.parameters():
+            p.grad = None
+        x.grad = None
+        m(x).backward(dy)
+
+    def event_ms(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        return e0, e1
+
+    for _ in range(a.warmup):
+        step("torch"), step("hip")
+    torch.cuda.synchronize()
+    # what the two compute, once (not a test: tests/test_lstm_gpu.py is)
+    step("torch")
+    gx_t = x.grad.clone()
+    step("hip")
+    diff = (x.grad - gx_t).abs().max().item()
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        step("hip")
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        step("hip")
+    torch.cuda.synchronize()
+    for _ in range(a.warmup):
+        graph.replay()
+
+    ev = {"torch": [], "hip": [], "hip, hipGraph replay": []}
+    for _ in range(a.reps):
+        ev["torch"].append(event_ms(lambda: step("torch")))
+        ev["hip"].append(event_ms(lambda: step("hip")))
+        ev["hip, hipGraph replay"].append(event_ms(graph.replay))
+    torch.cuda.synchronize()
+    res = {k: stats([e0.elapsed_time(e1) for e0, e1 in v]) for k, v in ev.items()}
+
+    kernels = {}
+    for tag in ("lstm_fwd", "lstm_bwd", "lstm_hprev", "lstm_gemm", "gemm_group", "gemm_splitk_reduce"):
+        _lib.call("gcgcn_prof_start", tag.encode(), 4096)
+        for _ in range(5):
+            step("hip")
+        torch.cuda.synchronize()
+        ms, n, w = ctypes.c_double(0), ctypes.c_int(0), ctypes.c_double(0)
+        _lib.call("gcgcn_prof_stop", ctypes.byref(ms), ctypes.byref(n), ctypes.byref(w))
+        kernels[tag] = {"ms_per_step": round(ms.value / 5, 4), "launches_per_step": n.value / 5}
+    for tag in ("lstm_fwd", "lstm_bwd"):
+        kernels[tag]["us_per_time_step"] = round(1e3 * kernels[tag]["ms_per_step"] / a.T, 3)
+    line = {"metric": "EncoderLSTM forward + backward, one bidirectional layer", "unit": "ms", "dtype": "f32",
+            "config": {"B": a.B, "T": a.T, "input": a.I, "H": H, "device": torch.cuda.get_device_name(0)},
+            "timing": "HIP events per step, sides interleaved, median (min, max)", "impl": res,
+            "hip_kernels (library timer, kernel begin to end)": kernels,
+            "model": {"us_per_time_step": 3.4, "ms_per_recurrence_launch": round(3.4e-3 * a.T, 3),
+                      "note": "1024 v_mfma_f32_16x16x4_f32 per step on one compute unit, 32 cycles per SIMD, 2.4 GHz"},
+            "max_abs_dx_difference_hip_vs_torch": diff}
+    print(json.dumps(line))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(line, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
