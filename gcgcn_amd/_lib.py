@@ -48,6 +48,7 @@ SIGNATURES = {
     "gcgcn_debug_gemm_plan": (I, [I, P, P, I, L, L, P]),
     "gcgcn_debug_edge_plan": (I, [I] * 13 + [P]),
     "gcgcn_debug_attn_plan": (I, [I] * 8 + [P]),
+    "gcgcn_debug_out_bwd_plan": (I, [I] * 12 + [P]),
     "gcgcn_prof_start": (I, [c_char_p, I]),
     "gcgcn_prof_enable": (I, [I]),
     "gcgcn_prof_stop": (I, [P, P, P]),

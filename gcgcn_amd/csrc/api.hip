@@ -240,6 +240,51 @@ static int gat_bwd(const EdgeOperand& eo, int B, int N, int D, int Dh, const flo
   return gat_fold_bwd(flat, duvc, dflat, D, Dh, st, scratch, part_off, ns);
 }
 
+// ---- the output projection's backward in gcgcn_gcn_bwd (OutBwdQuery -> OutBwdPlan, gcn_plan.hpp) --------------------------------
+// Pure.  q.fuse without q.scratch is not a query (chain_plan_bwd never fuses without workspace; the callers check).
+static OutBwdPlan out_bwd_plan(const OutBwdQuery& q) {
+  OutBwdPlan p = OutBwdPlan();
+  const bool masked = q.ragged || q.odrop;   // gradients arriving on padding rows are ignored; back through the output dropout
+  if (q.fuse) {  // the chain computes dHO = dout Wlin and dXres itself, masking / un-dropping dout while it stages it; only
+                 // sum_h Wlin_h is left to this call, and dWlin and the column sums wait for the launch behind the chain
+    p.mask = masked ? OutBwdPlan::MASK_CHAIN : OutBwdPlan::MASK_NONE;
+    p.wsum = q.H == 1 ? OutBwdPlan::WSUM_NONE : q.wsum_fwd ? OutBwdPlan::WSUM_FORWARD : OutBwdPlan::WSUM_HERE;
+    p.dwlin = OutBwdPlan::DWLIN_BACK;
+    const bool in_chain = 2 * q.B <= COL_RIDE_SLICES;   // stage 1 inside the chain (it holds dout_b in LDS): two slices a document
+    p.col1 = in_chain ? OutBwdPlan::COL1_CHAIN : OutBwdPlan::COL1_BACK;
+    p.chain_slices = in_chain ? 2 * q.B : 0;
+    return p;
+  }
+  p.mask = masked ? OutBwdPlan::MASK_LAUNCH : OutBwdPlan::MASK_NONE;
+  // Small blocks (launch-bound: cfg 1, the reference's own model) fold the head-sum / dropout-backward kernel into the front
+  // launch: dY = dropout_bwd(dHO) is the product's own epilogue (the forward mask: same site, same element offsets), and the
+  // residual gradient dXres = sum_h dHO_h = dout (sum_h Wlin_h) is one more small product (one head: dHO itself, written
+  // beside dY).  At cfg 3 the extra product and the second store cost more than the launch they save (round 2: +8 us).
+  constexpr long fold_max = 2L << 20;   // elements of dHO up to which the fold pays
+  const bool fold = q.scratch && (q.H == 1 || q.wsum_fwd) && (long)q.B * q.N * q.H * q.D <= fold_max && q.dxres_aligned;
+  p.fold = !fold ? OutBwdPlan::FOLD_NONE : q.H == 1 ? OutBwdPlan::FOLD_ONE_HEAD : OutBwdPlan::FOLD_HEADS;
+  p.fold_drop = fold && (q.H == 1 || q.drop);   // more heads: over C, the dropped value stays
+  p.head_sum_launch = !fold;
+  p.wsum = p.fold == OutBwdPlan::FOLD_HEADS ? OutBwdPlan::WSUM_FORWARD : OutBwdPlan::WSUM_NONE;
+  p.dwlin = OutBwdPlan::DWLIN_FRONT;
+  p.col1 = q.scratch ? OutBwdPlan::COL1_FRONT : OutBwdPlan::COL1_OWN_LAUNCH;
+  return p;
+}
+
+// Where stage 2 of dblin's column sums runs, once gemm_group has said whether the front launch had a reduce pass to do it in
+// (front_reduced; without a front launch it is not read).  Pure.
+static OutBwdCol2 out_bwd_plan_col2(const OutBwdPlan& p, bool front_reduced) {
+  switch (p.col1) {
+    case OutBwdPlan::COL1_OWN_LAUNCH: return {OutBwdCol2::DONE, 0};
+    case OutBwdPlan::COL1_CHAIN: return {OutBwdCol2::BACK_LAUNCH, p.chain_slices};
+    case OutBwdPlan::COL1_BACK: return {OutBwdCol2::BACK_REDUCE, 0};
+    default: break;  // FRONT
+  }
+  if (front_reduced) return {OutBwdCol2::FRONT_REDUCE, 0};
+  if (p.head_sum_launch) return {OutBwdCol2::HEAD_SUM_KERNEL, 0};   // trailing workgroups of head_sum_drop_bwd
+  return {OutBwdCol2::BACK_LAUNCH, COL_RIDE_SLICES};                // the fold left no kernel in between
+}
+
 }  // namespace gc
 
 using namespace gc;
@@ -490,16 +535,14 @@ int gcgcn_mha_bwd(int B, int N, int D, int H, const float* X, const float* flat,
     use_rows(gs[0], rows, 1, 1), use_rows(gs[1], rows, 2);
     const int ng = gemm_defer((DeferQueue*)defer_queue, gs[1]) ? 1 : 2;  // dWq parked (see gcgcn_gcn_bwd)
     if (scratch) {  // dbq = column sums of dQ ride in the same two launches
-      ColRide cr;
-      cr.X = dQ, cr.out = dflat + (long)D * D, cr.part = scratch + wse, cr.R = M, cr.ld = D, cr.C = D;
+      const ColRide cr = col_sum(dQ, M, D, D, dflat + (long)D * D, scratch + wse);
       // with dWq parked the launch has nothing to reduce: the sums' second stage (one workgroup) would be a launch of its own --
       // it is parked too (nobody reads dbq before the end of backward; `scratch` must then outlive the call like dQ and X)
       bool later = false;
       GC_TRY(gemm_group(gs, ng, st, &cr, (ng == 1 && defer_queue) ? &later : nullptr));
-      if (later) {
-        cr.ready_slices = COL_RIDE_SLICES;
-        if (!gemm_defer_col2((DeferQueue*)defer_queue, cr))
-          GC_TRY(colsum(cr.part, nullptr, cr.out, cr.ready_slices, cr.C, cr.C, 1, 0, 0, 0, 0, nullptr, st));
+      if (later) {  // finish stage 2: park it or run it now
+        const ColRide c2 = cr.stage2(COL_RIDE_SLICES);
+        if (!gemm_defer_col2((DeferQueue*)defer_queue, c2)) GC_TRY(col_sum_stage2_launch(c2, st));
       }
     } else {
       GC_TRY(gemm_group(gs, ng, st));
@@ -587,9 +630,9 @@ int gcgcn_gcn_fwd(int B, int N, int D, int L, int H, const float* X, const float
       g3[2].bias = mha->flat_q + (long)D * D;
     }
     for (int q = 0; q < ng; ++q) use_rows(g3[q], rows, 1, 1);   // (the attention core stages all N rows of Q: zeros past the live blocks)
-    ColRide hs;  // wsum = sum_h Wlin[:, h, :] (a by-product for gcgcn_gcn_bwd) in trailing workgroups of this launch
-    if (wsum && H > 1) hs.X = flat + y.oWlin, hs.out = wsum, hs.R = H, hs.ld = D, hs.C = D * D, hs.ready_slices = -1;
-    GC_TRY(gemm_group(g3, ng, st, hs.X ? &hs : nullptr));
+    // wsum = sum_h Wlin[:, h, :] (a by-product for gcgcn_gcn_bwd) in trailing workgroups of this launch
+    const ColRide hs = head_sum(flat + y.oWlin, H, D, wsum);
+    GC_TRY(gemm_group(g3, ng, st, (wsum && H > 1) ? &hs : nullptr));
   }
   {  // the dependent per-(doc, head) sequence: normaliser, then per sub-layer dense connection + aggregation
     if (er.kind && !plan.ride) {  // the riding pass as its own launch
@@ -672,7 +715,9 @@ int gcgcn_gcn_bwd(int B, int N, int D, int L, int H, const float* X, const float
   ChainQuery q = make_query(B, N, D, L, H, y, flat, n_valid != nullptr, scratch != nullptr, false, er, A, Pn, Y);
   q.dYa = dYa, q.dM = dM, q.dP = dP, q.dA = dA, q.dout = dout, q.dXres = dXres, q.dout_m = dout_m;
   const ChainPlan plan = chain_plan_bwd(q);
-  const bool fuse = plan.fuse;
+  GC_REQUIRE(!plan.fuse || scratch, "gcn_bwd: the fused chain backward without scratch");   // (chain_plan_bwd: fuse needs q.scratch)
+  const OutBwdPlan ob = out_bwd_plan({plan.fuse, B, N, D, H, scratch != nullptr, wsum_fwd != nullptr, n_valid != nullptr,
+                                      odrop.snap != nullptr, drop.snap != nullptr, al16(dXres)});
   GcnCtx c = make_ctx(B, N, D, L, H, y, X, A, flat, n_valid, drop);
   c.Pn = const_cast<float*>(Pn), c.Y = const_cast<float*>(Y), c.rinv = const_cast<float*>(rinv);
   c.dYa = dYa, c.dM = dM, c.dP = dP, c.dA = dA, c.drow = drow, c.oWlin = y.oWlin;
@@ -680,62 +725,52 @@ int gcgcn_gcn_bwd(int B, int N, int D, int L, int H, const float* X, const float
   if (plan.ride) c.ride = er;
   const int* rows = live_rows(rowblk, N, n_valid != nullptr);
   // sum_h Wlin_h: from the forward call if it left one, else summed here into dYa's buffer (free when the chain computes dHO)
-  const float* wsum = (fuse && H > 1) ? (wsum_fwd ? wsum_fwd : dYa) : nullptr;
+  const float* wsum = ob.wsum == OutBwdPlan::WSUM_FORWARD ? wsum_fwd : ob.wsum == OutBwdPlan::WSUM_HERE ? dYa : nullptr;
+  if (ob.wsum == OutBwdPlan::WSUM_HERE) GC_TRY(mask_rows(nullptr, nullptr, M, D, N, nullptr, odrop, st, flat + y.oWlin, dYa, H));
   const float* dout_raw = dout;
-  if (fuse) {  // the chain masks / un-drops dout while staging it (and writes dout_m back for dWlin); only sum_h Wlin_h is left
-    if (wsum && !wsum_fwd) GC_TRY(mask_rows(nullptr, nullptr, M, D, N, nullptr, odrop, st, flat + y.oWlin, dYa, H));
-    if (n_valid || odrop.snap) dout = dout_m;
-  } else if (n_valid || odrop.snap) {  // gradients arriving on padding rows are ignored; back through the output dropout
-    GC_TRY(mask_rows(dout, dout_m, M, D, N, n_valid, odrop, st));
-    dout = dout_m;
-  }
+  if (ob.mask == OutBwdPlan::MASK_LAUNCH) GC_TRY(mask_rows(dout, dout_m, M, D, N, n_valid, odrop, st));
+  if (ob.mask != OutBwdPlan::MASK_NONE) dout = dout_m;   // (MASK_CHAIN: the chain writes it back for dWlin)
   // dWlin = dout^T HO: a weight gradient nobody needs before the end of backward.  It is parked for a later launch with idle
   // matrix pipes, or runs in the launch in front of the chain -- where the chain computes dHO (fuse), in the one behind it
   GemmArgs dWlin = gemm_tn(dout, D, HO, HD, dflat + y.oWlin, HD, D, (int)HD, (int)M).split_ws(scratch, wse);
   use_rows(dWlin, rows, 2);
-  // dblin = column sums of dout: they ride in a launch of this call where it has workspace (`scratch`; unused otherwise)
-  ColRide cr;
-  cr.X = dout, cr.out = dflat + y.oblin, cr.part = scratch + wse, cr.R = M, cr.ld = D, cr.C = D;
-  bool col_later = false, col_pending = false;
-  if (fuse) {  // the sums ride in the launch after the chain
-    c.dout = dout_raw, c.dXres = dXres, c.Wsum = wsum, c.oWlin = y.oWlin;
+  // dblin = column sums of dout: they ride in launches of this call where it has workspace (every Col1 but OWN_LAUNCH)
+  const ColRide cr = ob.col1 != OutBwdPlan::COL1_OWN_LAUNCH ? col_sum(dout, M, D, D, dflat + y.oblin, scratch + wse) : ColRide();
+  bool front_reduced = false;
+  if (plan.fuse) {
+    c.dout = dout_raw, c.dXres = dXres, c.Wsum = wsum;
     if (dout != dout_raw) c.dout_m = dout_m, c.odrop = odrop;   // c.n_valid is set
-    col_pending = true;
-    if (2 * B <= COL_RIDE_SLICES) c.colpart = cr.part, cr.ready_slices = 2 * B;  // stage 1 inside the chain (it holds dout_b in LDS)
-  } else {
-    // Small blocks (launch-bound: cfg 1, the reference's own model) fold the head-sum / dropout-backward kernel into this
-    // launch: dY = dropout_bwd(dHO) is the product's own epilogue (the forward mask: same site, same element offsets), and the
-    // residual gradient dXres = sum_h dHO_h = dout (sum_h Wlin_h) is one more small product (one head: dHO itself, written
-    // beside dY).  At cfg 3 the extra product and the second store cost more than the launch they save (round 2: +8 us).
-    constexpr long fold_max = 2L << 20;   // elements of dHO up to which the fold pays
-    const bool fold_hs = scratch && (H == 1 || wsum_fwd) && (long)M * HD <= fold_max && (((uintptr_t)dXres) & 15) == 0;
-    {  // one launch: dHO = dout Wlin  and  dWlin = dout^T HO
-      GemmArgs run[3];
-      int nr = 1;
-      GemmArgs& dHO = run[0];
-      dHO = gemm_nn(dout, D, flat + y.oWlin, HD, dYa, HD, (int)M, (int)HD, D).split_ws(scratch, wse);
-      use_rows(dHO, rows, 1, 1);
-      if (fold_hs && H == 1) dHO.C = dXres, dHO.ldc = D;                                   // HD == D: the head sum is dHO
-      if (fold_hs && (H == 1 || drop.snap)) dHO.C2 = dYa, dHO.ldc2 = HD, dHO.drop = drop, dHO.drop_base = 0;   // H > 1: over C, the dropped value stays
-      if (!gemm_defer(dq, dWlin)) run[nr++] = dWlin;
-      if (fold_hs && H > 1) {  // dXres = dout (sum_h Wlin_h)
-        run[nr] = gemm_nn(dout, D, wsum_fwd, D, dXres, D, (int)M, D, D).split_ws(scratch, wse);
-        use_rows(run[nr++], rows, 1, 1);
-      }
-      if (scratch) {  // dblin's sums ride in this launch (stage 1) and in its reduce or the next kernel (stage 2)
-        GC_TRY(gemm_group(run, nr, st, &cr, &col_later));
-      } else {
-        GC_TRY(gemm_group(run, nr, st));
-        GC_TRY(colsum(dout, nullptr, dflat + y.oblin, M, D, D, 1, 0, 0, 0, 0, scratch, st));
-      }
+    if (ob.col1 == OutBwdPlan::COL1_CHAIN) c.colpart = cr.part;
+  } else {  // one launch: dHO = dout Wlin  and  dWlin = dout^T HO  (+ the fold: out_bwd_plan)
+    GemmArgs run[3];
+    int nr = 1;
+    GemmArgs& dHO = run[0];
+    dHO = gemm_nn(dout, D, flat + y.oWlin, HD, dYa, HD, (int)M, (int)HD, D).split_ws(scratch, wse);
+    use_rows(dHO, rows, 1, 1);
+    if (ob.fold == OutBwdPlan::FOLD_ONE_HEAD) dHO.C = dXres, dHO.ldc = D;   // HD == D: the head sum is dHO
+    if (ob.fold_drop) dHO.C2 = dYa, dHO.ldc2 = HD, dHO.drop = drop, dHO.drop_base = 0;
+    if (!gemm_defer(dq, dWlin)) run[nr++] = dWlin;
+    if (ob.fold == OutBwdPlan::FOLD_HEADS) {  // dXres = dout (sum_h Wlin_h)
+      run[nr] = gemm_nn(dout, D, wsum, D, dXres, D, (int)M, D, D).split_ws(scratch, wse);
+      use_rows(run[nr++], rows, 1, 1);
     }
-    if (fold_hs) {  // stage 2 of the bias column sums (if this launch had no reduce pass to do it) joins the launch after the chain
-      col_pending = col_later;
-      if (col_later) cr.ready_slices = COL_RIDE_SLICES;
+    if (ob.col1 == OutBwdPlan::COL1_FRONT) {  // stage 1 rides here; stage 2 in this launch's reduce, if it has one
+      bool later = false;
+      GC_TRY(gemm_group(run, nr, st, &cr, &later));
+      front_reduced = !later;
     } else {
-      GC_TRY(head_sum_drop_bwd(dYa, dYa, dXres, M, H, D, drop, st, col_later ? &cr : nullptr));  // residual + dropout backward
+      GC_TRY(gemm_group(run, nr, st));
+      GC_TRY(colsum(dout, nullptr, dflat + y.oblin, M, D, D, 1, 0, 0, 0, 0, scratch, st));
     }
   }
+  const OutBwdCol2 col2 = out_bwd_plan_col2(ob, front_reduced);
+  if (ob.head_sum_launch) {  // residual + dropout backward (+ stage 2 of the column sums in trailing workgroups)
+    const ColRide fin = cr.stage2(COL_RIDE_SLICES);
+    GC_TRY(head_sum_drop_bwd(dYa, dYa, dXres, M, H, D, drop, st, col2.where == OutBwdCol2::HEAD_SUM_KERNEL ? &fin : nullptr));
+  }
+  // what is left of the column sums rides in the launch behind the chain: their second stage, or both
+  const ColRide back = col2.where == OutBwdCol2::BACK_LAUNCH ? cr.stage2(col2.back_ready_slices) : cr;
+  const bool back_rides = col2.where == OutBwdCol2::BACK_LAUNCH || col2.where == OutBwdCol2::BACK_REDUCE;
 
   {  // the dependent per-(doc, head) sequence, last sub-layer first
     if (er.kind && !c.ride.kind) {
@@ -767,7 +802,7 @@ int gcgcn_gcn_bwd(int B, int N, int D, int L, int H, const float* X, const float
       use_rows(g.split_ws(scratch, wse), rows, 1, 1);
       return gs[n++] = g;
     };
-    if (fuse) weight_grad(dWlin);
+    if (ob.dwlin == OutBwdPlan::DWLIN_BACK) weight_grad(dWlin);
     weight_grad(gemm_tn(X, D, dP, HD, dflat + y.oWnX, HD, D, (int)HD, (int)M));
     weight_grad(gemm_tn(Ebar, D, dM, HD, dflat + y.oWe, HD, D, (int)HD, (int)M));
     GemmArgs& gx = data_grad(gemm_nt(dP, HD, flat + y.oWnX, HD, dX, D, (int)M, D, (int)HD));
@@ -786,7 +821,7 @@ int gcgcn_gcn_bwd(int B, int N, int D, int L, int H, const float* X, const float
         case AttnPlan::GROUP: riders = &mp; break;        // passenger workgroups of this launch
         default: GC_TRY(mha_core_bwd(mp, st));            // CORE: a launch of its own in front of it
       }
-    GC_TRY(gemm_group(gs, n, st, col_pending ? &cr : nullptr, nullptr, riders));
+    GC_TRY(gemm_group(gs, n, st, back_rides ? &back : nullptr, nullptr, riders));
   }
   return 0;
 }
@@ -881,6 +916,21 @@ int gcgcn_debug_chain_plan(int bwd, int B, int N, int D, int L, int H, int ragge
   q.dout = at(2), q.dXres = at(2), q.dout_m = at(2);
   const ChainPlan p = bwd ? chain_plan_bwd(q) : chain_plan_fwd(q);
   out[0] = p.kind, out[1] = p.aligned, out[2] = p.full, out[3] = p.fuse, out[4] = p.attention, out[5] = p.ride;
+  return 0;
+}
+
+// The output stage of a convolution backward call, by the very plan functions gcgcn_gcn_bwd calls (out_bwd_plan, then
+// out_bwd_plan_col2 with what the front group launch would report).  out[0..9] = mask, wsum, fold, fold_drop, head_sum_launch, dwlin,
+// col1, chain_slices (OutBwdPlan), then where stage 2 of dblin's sums runs and the slices the back launch's ride sums
+// (OutBwdCol2).  fuse without scratch is refused, as gcgcn_gcn_bwd refuses it.  Exposed for tests (no GPU needed).
+int gcgcn_debug_out_bwd_plan(int fuse, int B, int N, int D, int H, int scratch, int wsum_fwd, int ragged, int odrop, int drop,
+                             int dxres_misaligned, int front_reduced, int32_t* out) {
+  GC_REQUIRE(B > 0 && N > 0 && D > 0 && H > 0 && out, "debug_out_bwd_plan: bad arguments");
+  GC_REQUIRE(!fuse || scratch, "debug_out_bwd_plan: the fused chain backward without scratch");
+  const OutBwdPlan p = out_bwd_plan({fuse != 0, B, N, D, H, scratch != 0, wsum_fwd != 0, ragged != 0, odrop != 0, drop != 0, !dxres_misaligned});
+  const OutBwdCol2 c2 = out_bwd_plan_col2(p, front_reduced != 0);
+  out[0] = p.mask, out[1] = p.wsum, out[2] = p.fold, out[3] = p.fold_drop, out[4] = p.head_sum_launch, out[5] = p.dwlin, out[6] = p.col1;
+  out[7] = p.chain_slices, out[8] = c2.where, out[9] = c2.back_ready_slices;
   return 0;
 }
 

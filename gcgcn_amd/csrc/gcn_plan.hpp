@@ -159,6 +159,38 @@ inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 ChainPlan chain_plan_fwd(const ChainQuery& q);
 ChainPlan chain_plan_bwd(const ChainQuery& q);
 
+// ---- the output projection's backward (the first half of gcgcn_gcn_bwd) ----------------------------------------------------
+// Decided ONCE per call by out_bwd_plan (api.hip), after the chain plan: where dout is masked / un-dropped, where sum_h Wlin_h
+// comes from, whether the head sum and the dropout backward fold into the group launch in front of the chain, which launch dWlin
+// is offered to, and where the two stages of dblin's column sums run.  Stage 2 also depends on whether the front launch had a
+// split-K reduce, which gemm_group reports: out_bwd_plan_col2 is the second pure step.
+struct OutBwdQuery {
+  bool fuse;            // ChainPlan::fuse; it implies `scratch` (chain_plan_bwd fuses with workspace alone; gcgcn_gcn_bwd checks)
+  int B, N, D, H;
+  bool scratch;         // the call has workspace
+  bool wsum_fwd;        // the forward call left sum_h Wlin_h
+  bool ragged;          // n_valid given
+  bool odrop, drop;     // the output dropout / the block's dropout is on
+  bool dxres_aligned;   // dXres on a 16-byte boundary
+};
+struct OutBwdPlan {
+  enum Mask { MASK_NONE, MASK_LAUNCH, MASK_CHAIN };       // nothing to mask | a mask_rows launch | the chain, while it stages dout
+  enum Wsum { WSUM_NONE, WSUM_FORWARD, WSUM_HERE };       // not needed | the forward call's | a mask_rows launch into dYa's buffer
+  enum Fold { FOLD_NONE, FOLD_ONE_HEAD, FOLD_HEADS };     // - | dHO is the head sum: written to dXres | + the product dout (sum_h Wlin_h)
+  enum DWlin { DWLIN_FRONT, DWLIN_BACK };                 // offered to the queue or the launch in front of the chain | behind it
+  enum Col1 { COL1_CHAIN, COL1_FRONT, COL1_BACK, COL1_OWN_LAUNCH };   // stage 1 of dblin's sums (OWN_LAUNCH: a colsum, both stages)
+  int mask, wsum, fold;
+  bool fold_drop;       // a fold whose epilogue also writes dY = dropout_bwd(dHO) (one head: always; more: with dropout on)
+  bool head_sum_launch; // not fused, no fold: head_sum_drop_bwd follows the front launch
+  int dwlin, col1;
+  int chain_slices;     // COL1_CHAIN: the slices the chain leaves (2 B), else 0
+};
+struct OutBwdCol2 {
+  enum Where { FRONT_REDUCE, HEAD_SUM_KERNEL, BACK_LAUNCH, BACK_REDUCE, DONE };
+  int where;
+  int back_ready_slices;   // BACK_LAUNCH: the slices the back launch's ColRide::stage2 sums; else 0 (BACK_REDUCE: the whole sum rides)
+};
+
 // Each kernel generation answers for itself only, next to its kernels: "I serve this input" (shape + alignment), and for the
 // LDS-resident ones whether the backward can fuse the output projection's gradient / the forward can run the attention core.
 // Called from chain_plan_fwd / _bwd and from nowhere else; the preference between generations lives there.

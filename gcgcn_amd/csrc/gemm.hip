@@ -408,12 +408,13 @@ int gemm_group_mha_chunk(int dh) {
   return mha_lds_bytes_of(c) <= room ? c : 0;
 }
 
-// What rides in the trailing workgroups of a group launch (the host's reading of a ColRide; the kernels read ready_slices themselves)
+// What rides in the trailing workgroups of a group launch: which constructor of gemm.hpp built the ColRide (the kernels read
+// ready_slices themselves)
 enum RideKind {
   RIDE_NONE,
-  RIDE_COLSUM,   // stage 1 of a column sum here, stage 2 in the reduce launch (or with the caller: col_later)
-  RIDE_STAGE2,   // ready_slices > 0: the partials of an earlier launch are summed here
-  RIDE_HEADS     // ready_slices < 0: the sum over heads -- no partials, no second stage
+  RIDE_COLSUM,   // col_sum: stage 1 of a column sum here, stage 2 in the reduce launch (or with the caller: col_later)
+  RIDE_STAGE2,   // .stage2: the partials of an earlier launch are summed here
+  RIDE_HEADS     // head_sum: the sum over heads -- no partials, no second stage
 };
 static RideKind ride_kind(const ColRide* col) {
   if (!col || col->C <= 0) return RIDE_NONE;
@@ -426,6 +427,10 @@ static Kernel by_row_blocks(const GemmGroup& gg, Kernel with, Kernel without) {
   for (int i = 0; i < gg.nprob; ++i)
     if (gg.p[i].rb) return with;
   return without;
+}
+
+int col_sum_stage2_launch(const ColRide& c, hipStream_t stream) {
+  return colsum(c.part, nullptr, c.out, c.ready_slices, c.C, c.C, 1, 0, 0, 0, 0, nullptr, stream);
 }
 
 int gemm_group(const GemmArgs* probs, int n, hipStream_t stream, const ColRide* col, bool* col_later, const MhaPass* mha) {
@@ -503,7 +508,7 @@ int gemm_group(const GemmArgs* probs, int n, hipStream_t stream, const ColRide* 
     if (int e = mha_core_bwd(*mha, stream)) return e;
   if (gg.nprob == 0) {  // nothing to ride on
     if (ride == RIDE_HEADS) return mask_rows(nullptr, nullptr, 0, (int)col->ld, 1, nullptr, make_drop(nullptr, 0, 0.f), stream, col->X, col->out, (int)col->R);
-    if (ride == RIDE_STAGE2) return colsum(col->part, nullptr, col->out, col->ready_slices, col->C, col->C, 1, 0, 0, 0, 0, nullptr, stream);
+    if (ride == RIDE_STAGE2) return col_sum_stage2_launch(*col, stream);
     return ride == RIDE_COLSUM ? colsum(col->X, nullptr, col->out, col->R, col->C, col->ld, 1, 0, 0, 0, 0, col->part, stream) : 0;
   }
   gg.tile_begin[gg.nprob] = tiles;
@@ -798,7 +803,7 @@ int gemm_flush_deferred(DeferQueue* q, hipStream_t stream) {
   }
   ColRide c2;
   while (gemm_take_deferred_col2(q, c2))   // second stages of column sums that met no carrier
-    if (int e = colsum(c2.part, nullptr, c2.out, c2.ready_slices, c2.C, c2.C, 1, 0, 0, 0, 0, nullptr, stream)) return e;
+    if (int e = col_sum_stage2_launch(c2, stream)) return e;
   return 0;
 }
 

@@ -116,6 +116,13 @@ int gemm(const GemmArgs& g, hipStream_t stream, int tile = 0, int splits = 0);
 // A column sum riding in a group launch: out[c] = sum_{r < R} X[r * ld + c]  (bias gradients).  Stage 1 (COL_RIDE_SLICES
 // row slices -> part[slice][C]) runs in extra workgroups of the GEMM launch, stage 2 in extra workgroups of its
 // split-K reduce: the two launches of a stand-alone column sum disappear.  part: COL_RIDE_SLICES * C floats.
+// A ColRide is one of three things, and callers build it with the constructor of that name (the kernels tell them apart by
+// `ready_slices`, which only the constructors write):
+//   col_sum(X, R, ld, C, out, part)   the whole column sum: stage 1 in the launch, stage 2 in its reduce or with the caller
+//   .stage2(slices)                   of such a sum whose part[slices][C] an earlier launch (or the chain kernel) filled: only
+//                                     stage 2 rides, in the trailing workgroups of the group launch itself
+//   head_sum(W, H, D, out)            not a column sum but the sum over H interleaved blocks (heads) of D columns, in trailing
+//                                     workgroups of the launch: out[k * D + c] = sum_{h < H} W[(k * H + h) * D + c], k, c < D
 constexpr int COL_RIDE_SLICES = 64;
 struct ColRide {
   const float* X = nullptr;
@@ -123,11 +130,25 @@ struct ColRide {
   float* part = nullptr;
   long R = 0, ld = 0;
   int C = 0;
-  int ready_slices = 0;  // > 0: part[ready_slices][C] was filled by an earlier launch (X unused); only stage 2 rides, in the
-                         // trailing workgroups of the group launch itself
-                         // < 0: not a column sum but a sum over R interleaved blocks (heads) of ld columns, in trailing
-                         // workgroups of the launch: out[k * ld + c] = sum_{h < R} X[(k * R + h) * ld + c], k * ld + c < C
+  int ready_slices = 0;  // 0: col_sum, > 0: stage2 (the slices to sum; X unused), < 0: head_sum
+  ColRide stage2(int slices) const {
+    ColRide c = *this;
+    c.ready_slices = slices;
+    return c;
+  }
 };
+inline ColRide col_sum(const float* X, long R, long ld, int C, float* out, float* part) {
+  ColRide c;
+  c.X = X, c.out = out, c.part = part, c.R = R, c.ld = ld, c.C = C;
+  return c;
+}
+inline ColRide head_sum(const float* W, int H, int D, float* out) {
+  ColRide c;
+  c.X = W, c.out = out, c.R = H, c.ld = D, c.C = D * D, c.ready_slices = -1;
+  return c;
+}
+// Stage 2 as a launch of its own (nothing was left to carry it): out[c] = the sum of c.part's ready_slices slices, in order
+int col_sum_stage2_launch(const ColRide& c, hipStream_t stream);
 
 // Up to NP independent problems carried by one launch.
 template <int NP>
@@ -174,14 +195,14 @@ struct DeferQueue {
   GemmArgs p[CAP];
   int done[CAP] = {};  // tiles of p[i] already carried by an earlier launch
   int n = 0;
-  // second stages of riding column sums (bias gradients: ColRide::ready_slices > 0, the partials are in memory) that nobody
+  // second stages of riding column sums (bias gradients: ColRide::stage2, the partials are in memory) that nobody
   // needs before the end of backward either: the next carrying edge pass sums them in a trailing workgroup, or the flush does
   static constexpr int COLCAP = 4;
   ColRide col2[COLCAP];
   int ncol2 = 0;
 };
 bool gemm_defer(DeferQueue* q, const GemmArgs& g);  // q == nullptr: never parks
-bool gemm_defer_col2(DeferQueue* q, const ColRide& c);          // c.ready_slices > 0; false: run it now
+bool gemm_defer_col2(DeferQueue* q, const ColRide& c);          // c: a .stage2(); false: run it now
 bool gemm_take_deferred_col2(DeferQueue* q, ColRide& out);      // pops one parked second stage
 // Move up to MAXP parked problems into gg (longest K first, per-problem XCD-aligned tile ranges); returns the number
 // of workgroups (0: nothing parked).  flops (optional) accumulates 2MNK of the taken problems.

@@ -1185,8 +1185,7 @@ int head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int di
     GemmArgs gs[8];
     const long col_elems = ((long)COL_RIDE_SLICES * HW + 3) & ~3L;    // the riding column sum's partials: the workspace's tail
     for (int k = 0; k < nf; ++k) gs[2 * k] = dfeat(k, wse - col_elems), gs[2 * k + 1] = dWk(k, wse - col_elems);
-    ColRide cr;
-    cr.X = w.dUT, cr.out = dflat + y.bd, cr.part = ws + (wse - col_elems), cr.R = BN, cr.ld = HW, cr.C = HW;
+    const ColRide cr = col_sum(w.dUT, BN, HW, HW, dflat + y.bd, ws + (wse - col_elems));
     GC_TRY(gemm_group(gs, 2 * nf, st, &cr));
   } else {
     for (int k = 0; k < nf; ++k) {

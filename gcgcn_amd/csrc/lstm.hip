@@ -272,8 +272,7 @@ int lstm_bwd(int B, int T, int I, int nd, const float* x, const float* w_ih, con
       gemm_tn(dgates, G, hprev, nd * LH, dw_hh, LH, 4 * LH, LH, (int)BT).batch_z2(nd, 4 * LH, LH, 4L * LH * LH).split_ws(split, split_elems).tagged("lstm_gemm"),
       gemm_nn(dgates, G, w_ih, I, dx, I, (int)BT, I, G).split_ws(split, split_elems).tagged("lstm_gemm"),
   };
-  ColRide cr;
-  cr.X = dgates, cr.out = db, cr.part = part, cr.R = BT, cr.ld = G, cr.C = G;
+  const ColRide cr = col_sum(dgates, BT, G, G, db, part);
   return gemm_group(gs, 3, st, &cr);
 }
 

@@ -959,8 +959,7 @@ static int linear_bwd_all(const float* dY, const float* X, long M, int Nout, int
   }
   const GemmArgs gs[2] = {linear_dw(dY, X, M, Nout, K, dW, ws, wse - col_elems),   // (the workspace's tail: the column sums' partials)
                           linear_dx(dY, M, Nout, W, K, dX, accumulate_x, ws, wse - col_elems)};
-  ColRide cr;
-  cr.X = dY, cr.out = db, cr.part = ws + (wse - col_elems), cr.R = M, cr.ld = Nout, cr.C = Nout;
+  const ColRide cr = col_sum(dY, M, Nout, Nout, db, ws + (wse - col_elems));
   return gemm_group(gs, 2, st, &cr);
 }
 

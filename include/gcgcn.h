@@ -446,6 +446,20 @@ int gcgcn_debug_edge_plan(int pass, int compact, int B, int N, int D, int ragged
  * serve, 2 a misaligned Q / dQ -- route and chunk are then -1).  Host-only. */
 int gcgcn_debug_attn_plan(int bwd, int N, int D, int H, int hook, int chain_attends, int core_done, int misalign, int32_t* out);
 
+/* ---- test hook: the output stage of the convolution's backward -----------------------------------------------------------
+ * Evaluates the two plan functions gcgcn_gcn_bwd calls for its output projection's backward (csrc/gcn_plan.hpp: OutBwdPlan,
+ * OutBwdCol2; csrc/api.hip: out_bwd_plan, out_bwd_plan_col2).  fuse: gcgcn_debug_chain_plan's; scratch, wsum_fwd, ragged (n_valid),
+ * odrop (output dropout) and drop (the block's dropout): whether the call has them; dxres_misaligned: dXres off a 16-byte boundary;
+ * front_reduced: the group launch in front of the chain had a split-K reduce (not read where there is no such launch).
+ * out[10] = mask (0 none, 1 a mask_rows launch, 2 in the chain), wsum (0 none, 1 the forward call's, 2 summed here), fold (0 none,
+ * 1 one head, 2 several heads), fold_drop, head_sum_launch, dwlin (0 offered in front of the chain, 1 behind it), col1 (stage 1 of
+ * the dblin column sums: 0 in the chain, 1 the front launch, 2 the back launch, 3 a colsum launch of its own), the slices the chain
+ * leaves (2 B, else 0); then col2 (stage 2: 0 the front launch's reduce, 1 trailing workgroups of head_sum_drop_bwd, 2 of the back
+ * launch, 3 the back launch's reduce, 4 done with stage 1) and the slices the back launch's ride sums (else 0).  fuse without
+ * scratch fails, as in gcgcn_gcn_bwd.  Host-only. */
+int gcgcn_debug_out_bwd_plan(int fuse, int B, int N, int D, int H, int scratch, int wsum_fwd, int ragged, int odrop, int drop,
+                             int dxres_misaligned, int front_reduced, int32_t* out);
+
 /* ---- test hook: what the GEMM launcher decides for a problem ----------------------------------------------------------
  * Evaluates the plan function every launcher of csrc/gemm.hip calls (gemm_plan) under the current options, on made-up operand
  * addresses.  form: 0 a single launch (splits: the caller's request), 1 a member of a group launch of group_work tile-k-steps,

@@ -802,6 +802,69 @@ def test_attn_plan_is_the_decision_the_scattered_predicates_made():
     assert plan(1, 16, 128, 2, 1, 0, 0, 0)[:2] == [ATTN_ROUTES["GROUP"], 64] and plan(1, 16, 136, 2, 1, 0, 0, 0)[:2] == [ATTN_ROUTES["CORE"], 96]
 
 
+# ---- the plan of the convolution backward's output stage ------------------------------------------------------------------------
+OUT_BWD_ARGS = ["fuse", "B", "N", "D", "H", "scratch", "wsum_fwd", "ragged", "odrop", "drop", "dxres_misaligned", "front_reduced"]
+OUT_BWD_FIELDS = ["mask", "wsum", "fold", "fold_drop", "head_sum_launch", "dwlin", "col1", "chain_slices", "col2", "back_ready_slices"]
+OUT_BWD_MASK = {"NONE": 0, "LAUNCH": 1, "CHAIN": 2}
+OUT_BWD_WSUM = {"NONE": 0, "FORWARD": 1, "HERE": 2}
+OUT_BWD_FOLD = {"NONE": 0, "ONE_HEAD": 1, "HEADS": 2}
+OUT_BWD_DWLIN = {"FRONT": 0, "BACK": 1}
+OUT_BWD_COL1 = {"CHAIN": 0, "FRONT": 1, "BACK": 2, "OWN_LAUNCH": 3}
+OUT_BWD_COL2 = {"FRONT_REDUCE": 0, "HEAD_SUM_KERNEL": 1, "BACK_LAUNCH": 2, "BACK_REDUCE": 3, "DONE": 4}
+OUT_BWD_FOLD_MAX = 2 << 20   # elements of dHO = B N H D up to which the fold pays (out_bwd_plan)
+
+
+def out_bwd_plan_sweep():
+    """The argument rows (OUT_BWD_ARGS) of the plan table: one, 32 and 33 documents (2 B either side of the 64 slices the chain
+    may leave), one, two and eight heads, a small block and, at D = 256, the graph sizes that put B N H D just below, exactly on
+    and just above the fold threshold (33 documents never land on it: the sizes either side), every combination of the flags.
+    Rows with fuse = 1 and scratch = 0 are left out: chain_plan_bwd never fuses without workspace, and gcgcn_gcn_bwd refuses it."""
+    import itertools
+    rows = []
+    for fuse, H, B in itertools.product((0, 1), (1, 2, 8), (1, 32, 33)):
+        n_on = OUT_BWD_FOLD_MAX // (B * H * 256)
+        sizes = [(16, 64), (n_on, 256), (n_on + 1, 256)] + ([(n_on - 1, 256)] if B * n_on * H * 256 == OUT_BWD_FOLD_MAX else [])
+        for (N, D), scratch, rest in itertools.product(sizes, (0, 1), itertools.product((0, 1), repeat=6)):
+            if not (fuse and not scratch):
+                rows.append((fuse, B, N, D, H, scratch, *rest))
+    return rows
+
+
+def test_out_bwd_plan_is_the_decision_the_inline_code_made():
+    """gcgcn_debug_out_bwd_plan (out_bwd_plan, then out_bwd_plan_col2: the two plan functions gcgcn_gcn_bwd calls) gives, for every
+    row of out_bwd_plan_sweep, what the code before it decided inline.  The expected table (tests/golden/out_bwd_plan_parent.npz)
+    was recorded from the PARENT of the commit that introduced OutBwdPlan, not from the code under test: in a scratch copy of the
+    parent a throw-away function evaluated the parent's own expressions over these same rows, in the order gcgcn_gcn_bwd evaluated
+    them -- `wsum`, the two mask_rows conditions, fold_hs, the dHO.C / C2 conditions, where dWlin is offered, c.colpart /
+    ready_slices, col_later (from front_reduced, as gemm_group reports it), col_pending, and which call received &cr -- on made-up
+    operand addresses.  Rows with fuse = 1 and scratch = 0 are not in the sweep (chain_plan_bwd never produces them) and must be
+    refused.  No tolerance, no other row left out; every value of every enum occurs."""
+    import ctypes
+    import numpy as np
+
+    def plan(*args):
+        out = np.full(len(OUT_BWD_FIELDS), -7, np.int32)
+        _lib.call("gcgcn_debug_out_bwd_plan", *args, out.ctypes.data_as(ctypes.c_void_p))
+        return [int(v) for v in out]
+
+    rows = out_bwd_plan_sweep()
+    want = np.load(os.path.join(ROOT, "tests", "golden", "out_bwd_plan_parent.npz"))
+    assert want["args"].tolist() == [list(r) for r in rows], "the recorded table and out_bwd_plan_sweep list different rows"
+    assert want["plan"].shape == (len(rows), len(OUT_BWD_FIELDS)) and len(rows) == 3 * 11 * 64 * (2 + 1)   # heads, (B, size) pairs, flags, (scratch or not) + fused
+    elems = {r[1] * r[2] * r[3] * r[4] - OUT_BWD_FOLD_MAX for r in rows}
+    assert 0 in elems and min(e for e in elems if e > 0) <= 33 * 8 * 256 and max(e for e in elems if e < 0) >= -33 * 8 * 256
+    wrong = [f"{dict(zip(OUT_BWD_ARGS, args))}: want {w} got {plan(*args)}" for args, w in zip(rows, want["plan"].tolist()) if plan(*args) != w]
+    assert not wrong, f"{len(wrong)} of {len(rows)} rows differ\n" + "\n".join(wrong[:40])
+    cols = {name: set(want["plan"][:, k].tolist()) for k, name in enumerate(OUT_BWD_FIELDS)}
+    for name, enum in (("mask", OUT_BWD_MASK), ("wsum", OUT_BWD_WSUM), ("fold", OUT_BWD_FOLD), ("dwlin", OUT_BWD_DWLIN),
+                       ("col1", OUT_BWD_COL1), ("col2", OUT_BWD_COL2)):
+        assert cols[name] == set(enum.values()), name
+    assert cols["fold_drop"] == {0, 1} and cols["head_sum_launch"] == {0, 1}
+    assert cols["chain_slices"] == {0, 2, 64} and cols["back_ready_slices"] == {0, 2, 64}
+    with pytest.raises(Exception, match="without scratch"):    # fuse implies scratch
+        plan(1, 2, 16, 64, 4, 0, 0, 0, 0, 0, 0, 0)
+
+
 # ---- the GEMM launcher's plan ---------------------------------------------------------------------------------------------------
 GEMM_WS = 16 << 20   # workspace elements that hold every split of these shapes
 
