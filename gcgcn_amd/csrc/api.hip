@@ -15,6 +15,7 @@
 #include "gat_body.hpp"
 #include "gemm.hpp"
 #include "lstm.hpp"
+#include "frontend.hpp"
 #include "rowops.hpp"
 
 namespace gc {
@@ -1063,6 +1064,93 @@ int gcgcn_lstm_bwd(int B, int T, int I, int H, int nd, const float* x, const flo
              (long long)gcgcn_lstm_ws_bytes(B, T, I, H, nd));
   return lstm_bwd(B, T, I, nd, x, w_ih, w_hh, h0, c0, out, gates, csave, dout, dgates, dx, dw_ih, dw_hh, db, dh0, dc0, (float*)ws,
                   ws_bytes / (int64_t)sizeof(float), (hipStream_t)stream);
+}
+
+// ---- the token front end (frontend.hip) ------------------------------------------------------------------------------------------
+static int embed_shape_ok(const char* who, int B, int T, int V, int P, int R, int Dw, int Dc, int Dn) {
+  GC_REQUIRE(B >= 1 && T >= 1, "%s: bad shape B=%d T=%d", who, B, T);
+  GC_REQUIRE(V >= 1 && P >= 1 && R >= 1, "%s: a table without rows (V=%d P=%d R=%d)", who, V, P, R);
+  GC_REQUIRE(Dw >= 1 && Dc >= 1 && Dn >= 1, "%s: a width below 1 (Dw=%d Dc=%d Dn=%d)", who, Dw, Dc, Dn);
+  GC_REQUIRE((long)B * T <= 0x7fffff00L && (long)Dw + Dc + Dn <= 0x7fffffffL, "%s: B=%d T=%d is too large", who, B, T);
+  return 0;
+}
+static int context_shape_ok(const char* who, int B, int T, int N, int K, int Hd) {
+  GC_REQUIRE(Hd == FE_HD, "%s: token-state width %d is not served (Hd = %d)", who, Hd, FE_HD);
+  GC_REQUIRE(B >= 1 && T >= 1 && N >= 1 && K >= 1, "%s: bad shape B=%d T=%d N=%d K=%d", who, B, T, N, K);
+  GC_REQUIRE((long)B * T * (K > Hd ? K : Hd) <= 0x7fffffffL && (long)B * N * T <= 0x7fffffffL && B <= 65535,
+             "%s: B=%d T=%d N=%d K=%d is too large", who, B, T, N, K);
+  return 0;
+}
+static EmbedTables embed_tables(int V, int P, int R, int Dw, int Dc, int Dn, const int64_t* document, const int64_t* document_pos,
+                                const int64_t* document_ner) {
+  EmbedTables tb;
+  tb.t[0] = {document, nullptr, nullptr, V, Dw, -1};
+  tb.t[1] = {document_pos, nullptr, nullptr, P, Dc, -1};
+  tb.t[2] = {document_ner, nullptr, nullptr, R, Dn, -1};
+  return tb;
+}
+
+int64_t gcgcn_frontend_ws_bytes(int B, int T, int V, int P, int R, int Dw, int Dc, int Dn, int K) {
+  int64_t need = 0;
+  if (V == 0 && K == 0) {
+    set_error("frontend_ws_bytes: neither tables (V) nor a context width (K) given");
+    return -1;
+  }
+  if (V != 0) {
+    if (embed_shape_ok("frontend_ws_bytes", B, T, V, P, R, Dw, Dc, Dn)) return -1;
+    need = embed_ws_bytes((long)B * T, embed_tables(V, P, R, Dw, Dc, Dn, nullptr, nullptr, nullptr));
+  }
+  if (K != 0) {
+    if (context_shape_ok("frontend_ws_bytes", B, T, 1, K, FE_HD)) return -1;
+    const int64_t c = (int64_t)sizeof(float) * context_ws_elems(K);
+    need = c > need ? c : need;
+  }
+  return need;
+}
+
+int gcgcn_embed_fwd(int B, int T, int V, int P, int R, int Dw, int Dc, int Dn, const int64_t* document, const int64_t* document_pos,
+                    const int64_t* document_ner, const float* word_w, const float* coref_w, const float* ner_w, const float* scale,
+                    float* x, void* stream) {
+  GC_TRY(embed_shape_ok("embed_fwd", B, T, V, P, R, Dw, Dc, Dn));
+  GC_REQUIRE(document && document_pos && document_ner && word_w && coref_w && ner_w && x, "embed_fwd: null pointer");
+  EmbedTables tb = embed_tables(V, P, R, Dw, Dc, Dn, document, document_pos, document_ner);
+  tb.t[0].w = word_w, tb.t[1].w = coref_w, tb.t[2].w = ner_w;
+  return embed_fwd(B, T, tb, scale, x, (hipStream_t)stream);
+}
+
+int gcgcn_embed_bwd(int B, int T, int V, int P, int R, int Dw, int Dc, int Dn, const int64_t* document, const int64_t* document_pos,
+                    const int64_t* document_ner, const float* dx, const float* scale, int coref_padding_idx, int ner_padding_idx,
+                    float* dword, float* dcoref, float* dner, void* ws, int64_t ws_bytes, void* stream) {
+  GC_TRY(embed_shape_ok("embed_bwd", B, T, V, P, R, Dw, Dc, Dn));
+  GC_REQUIRE(document && document_pos && document_ner && dx && dword && dcoref && dner && ws, "embed_bwd: null pointer");
+  GC_REQUIRE((((uintptr_t)ws) & 15) == 0, "embed_bwd: ws must be 16-byte aligned");
+  GC_REQUIRE(ws_bytes >= gcgcn_frontend_ws_bytes(B, T, V, P, R, Dw, Dc, Dn, 0), "embed_bwd: workspace of %lld bytes needed (gcgcn_frontend_ws_bytes)",
+             (long long)gcgcn_frontend_ws_bytes(B, T, V, P, R, Dw, Dc, Dn, 0));
+  EmbedTables tb = embed_tables(V, P, R, Dw, Dc, Dn, document, document_pos, document_ner);
+  tb.t[0].dw = dword, tb.t[1].dw = dcoref, tb.t[2].dw = dner;
+  tb.t[1].pad = coref_padding_idx, tb.t[2].pad = ner_padding_idx;
+  return embed_bwd(B, T, tb, dx, scale, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int gcgcn_context_fwd(int B, int T, int N, int K, int Hd, const float* h, const float* w, const float* bias, const float* node_pos,
+                      float* pre, float* ctx, float* node_feat, void* stream) {
+  GC_TRY(context_shape_ok("context_fwd", B, T, N, K, Hd));
+  GC_REQUIRE(h && w && bias && node_pos && pre && ctx && node_feat, "context_fwd: null pointer");
+  GC_REQUIRE((((uintptr_t)pre) & 15) == 0 && (((uintptr_t)ctx) & 15) == 0, "context_fwd: pre and ctx must be 16-byte aligned");
+  GC_REQUIRE(pre != ctx, "context_fwd: ctx aliases pre (the pooling reads pre while ctx is being written)");
+  return context_fwd(B, T, N, K, h, w, bias, node_pos, pre, ctx, node_feat, (hipStream_t)stream);
+}
+
+int gcgcn_context_bwd(int B, int T, int N, int K, int Hd, const float* h, const float* w, const float* node_pos, const float* ctx,
+                      const float* dctx, const float* dnode_feat, float* dpre, float* dh, float* dw, float* db, void* ws,
+                      int64_t ws_bytes, void* stream) {
+  GC_TRY(context_shape_ok("context_bwd", B, T, N, K, Hd));
+  GC_REQUIRE(h && w && node_pos && ctx && dctx && dnode_feat && dpre && dh && dw && db && ws, "context_bwd: null pointer");
+  GC_REQUIRE((((uintptr_t)ws) & 15) == 0, "context_bwd: ws must be 16-byte aligned");
+  GC_REQUIRE(ws_bytes >= gcgcn_frontend_ws_bytes(B, T, 0, 0, 0, 0, 0, 0, K), "context_bwd: workspace of %lld bytes needed (gcgcn_frontend_ws_bytes)",
+             (long long)gcgcn_frontend_ws_bytes(B, T, 0, 0, 0, 0, 0, 0, K));
+  return context_bwd(B, T, N, K, h, w, node_pos, ctx, dctx, dnode_feat, dpre, dh, dw, db, (float*)ws, ws_bytes / (int64_t)sizeof(float),
+                     (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1168,3 +1168,111 @@ def lstm_layer(x, w_ih, w_hh, b_ih, b_hh, h0, c0, w_ih_r=None, w_hh_r=None, b_ih
     else:
         W_ih, W_hh, bias = w_ih.contiguous(), w_hh.contiguous(), b_ih + b_hh
     return LstmFn.apply(x, W_ih, W_hh, bias, h0.expand(nd, B, H).contiguous(), c0.expand(nd, B, H).contiguous())
+
+
+# ---- the token front end either side of the BiLSTM (csrc/frontend.hip) -----------------------------------------------------------
+def _frontend_ws(dev, B, T, V=0, P=0, R=0, Dw=0, Dc=0, Dn=0, K=0) -> Tensor:
+    need = _lib.lib().gcgcn_frontend_ws_bytes(B, T, V, P, R, Dw, Dc, Dn, K)
+    if need < 0:
+        raise RuntimeError(f"gcgcn_frontend_ws_bytes failed: {_lib.lib().gcgcn_last_error().decode()}")
+    return torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+
+
+class TokenEmbedFn(torch.autograd.Function):
+    """(word_w[V,Dw], coref_w[P,Dc], ner_w[R,Dn], document, document_pos, document_ner int64 [B,T], scale[B,I] or None) ->
+    x[B,T,I]: the three gathers side by side, times the locked-dropout factor."""
+
+    @staticmethod
+    def forward(ctx, word_w, coref_w, ner_w, document, document_pos, document_ner, scale, coref_pad, ner_pad):
+        B, T = document.shape
+        dims = (B, T, word_w.shape[0], coref_w.shape[0], ner_w.shape[0], word_w.shape[1], coref_w.shape[1], ner_w.shape[1])
+        x = torch.empty(B, T, dims[5] + dims[6] + dims[7], device=word_w.device)
+        call("gcgcn_embed_fwd", *dims, _p(document), _p(document_pos), _p(document_ner), _p(word_w), _p(coref_w), _p(ner_w), _p(scale), _p(x),
+             _stream())
+        torch.autograd.graph.increment_version((x,))
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(document, document_pos, document_ner, scale)
+            ctx.dims, ctx.pads = dims, (coref_pad, ner_pad)
+        return x
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dx):
+        document, document_pos, document_ner, scale = ctx.saved_tensors
+        B, T, V, P, R, Dw, Dc, Dn = ctx.dims
+        dx = dx.contiguous()
+        dev = dx.device
+        dword, dcoref, dner = torch.empty(V, Dw, device=dev), torch.empty(P, Dc, device=dev), torch.empty(R, Dn, device=dev)
+        ws = _frontend_ws(dev, B, T, V, P, R, Dw, Dc, Dn)
+        call("gcgcn_embed_bwd", *ctx.dims, _p(document), _p(document_pos), _p(document_ner), _p(dx), _p(scale), ctx.pads[0], ctx.pads[1],
+             _p(dword), _p(dcoref), _p(dner), _p(ws), ws.numel() * 4, _stream())
+        torch.autograd.graph.increment_version((dword, dcoref, dner))
+        return dword, dcoref, dner, None, None, None, None, None, None
+
+
+def token_embed(document, document_pos, document_ner, word_w, coref_w, ner_w, scale=None, coref_padding_idx=0, ner_padding_idx=0):
+    """``x[B,T,Dw+Dc+Dn] = word_w[document] | coref_w[document_pos] | ner_w[document_ner]`` (glove:282-289) in HIP, every element
+    times ``scale[b, i]`` when ``scale`` (``[B,I]`` or ``[B,1,I]``: the ``LockedDropout`` factor) is given.  Ids are int64
+    ``[B,T]``.  The gradients of the three tables come back dense and bit-reproducible; the row at a padding index (``None``:
+    the table has none; ``word_w`` never has one) stays exactly zero.  ``scale`` gets no gradient."""
+    tabs = [_chk(w, nm, 2) for nm, w in (("word_w", word_w), ("coref_w", coref_w), ("ner_w", ner_w))]
+    ids = []
+    for nm, t in (("document", document), ("document_pos", document_pos), ("document_ner", document_ner)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or t.dim() != 2 or t.shape != document.shape:
+            raise ValueError(f"{nm}: expected a GPU int64 tensor of shape [B,T]")
+        ids.append(t.contiguous())
+    B, T = ids[0].shape
+    I = sum(w.shape[1] for w in tabs)
+    if scale is not None:
+        scale = _chk(scale, "scale")
+        if tuple(scale.shape) not in ((B, I), (B, 1, I)):
+            raise ValueError(f"scale: expected [{B},{I}] or [{B},1,{I}], got {tuple(scale.shape)}")
+        scale = scale.detach().reshape(B, I)
+    _check_id_range([(nm, t, 0, w.shape[0] - 1) for nm, t, w in zip(("document", "document_pos", "document_ner"), ids, tabs)])
+    pads = [-1 if p is None else int(p) for p in (coref_padding_idx, ner_padding_idx)]
+    return TokenEmbedFn.apply(*tabs, *ids, scale, *pads)
+
+
+class TokenContextFn(torch.autograd.Function):
+    """(h[B,T,K], weight[128,K], bias[128], node_pos[B,N,T]) -> (ctx[B,T,128], node_feat[B,N,128])."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, node_pos):
+        B, T, K = h.shape
+        N, Hd = node_pos.shape[1], weight.shape[0]
+        pre, out = torch.empty(B, T, Hd, device=h.device), torch.empty(B, T, Hd, device=h.device)
+        node_feat = torch.empty(B, N, Hd, device=h.device)
+        call("gcgcn_context_fwd", B, T, N, K, Hd, _p(h), _p(weight), _p(bias), _p(node_pos), _p(pre), _p(out), _p(node_feat), _stream())
+        torch.autograd.graph.increment_version((out, node_feat))
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(h, weight, node_pos, out)
+        return out, node_feat
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dctx, dnode):
+        h, weight, node_pos, out = ctx.saved_tensors
+        B, T, K = h.shape
+        N, Hd = node_pos.shape[1], weight.shape[0]
+        dctx, dnode = dctx.contiguous(), dnode.contiguous()
+        dpre, dh, dw = torch.empty_like(out), torch.empty_like(h), torch.empty_like(weight)
+        db = torch.empty(Hd, device=h.device)
+        ws = _frontend_ws(h.device, B, T, K=K)
+        call("gcgcn_context_bwd", B, T, N, K, Hd, _p(h), _p(weight), _p(node_pos), _p(out), _p(dctx), _p(dnode), _p(dpre), _p(dh), _p(dw),
+             _p(db), _p(ws), ws.numel() * 4, _stream())
+        torch.autograd.graph.increment_version((dh, dw, db))
+        return dh, dw, db, None
+
+
+def token_context(h, weight, bias, node_pos):
+    """``ctx[B,T,128] = tanh(h weight^T + bias)`` (``linear_re`` + tanh, glove:290-292) and the entity pooling
+    ``node_feat[B,N,128] = bmm(node_pos, ctx)`` (glove:293-298) in HIP.  ``h[B,T,K]``, ``weight[128,K]``, ``bias[128]``,
+    ``node_pos[B,N,T]`` (mention spans: the pooling visits its non-zeros only).  Gradients reach ``h``, ``weight`` and ``bias``;
+    ``node_pos`` gets none.  A width other than 128 raises."""
+    h, weight, bias, node_pos = _chk(h, "h", 3), _chk(weight, "weight", 2), _chk(bias, "bias", 1), _chk(node_pos.detach(), "node_pos", 3)
+    B, T, K = h.shape
+    if weight.shape[1] != K or bias.shape[0] != weight.shape[0]:
+        raise ValueError(f"token_context: weight {tuple(weight.shape)} / bias {tuple(bias.shape)} do not project h {tuple(h.shape)}")
+    if node_pos.shape[0] != B or node_pos.shape[2] != T:
+        raise ValueError(f"token_context: node_pos {tuple(node_pos.shape)}, expected [{B}, N, {T}]")
+    return TokenContextFn.apply(h, weight, bias, node_pos)

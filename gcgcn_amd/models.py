@@ -11,7 +11,9 @@ checkpoint loads with ``strict=True``.
 What runs where.  Everything from the entity pooling on (glove:293-360: edge-feature producers, CAGGC / MAGGC blocks, hop glue,
 classifier head) is :class:`gcgcn_amd.GraphModelTail`, i.e. the HIP kernels.  The token encoder in front of it -- embeddings,
 ``EncoderLSTM`` (glove:377-428), ``linear_re`` + tanh, or BERT in the second model -- is plain PyTorch by default, restated here
-so that the model is complete.  ``config.encoder_impl = "hip"`` opts the BiLSTM into ``functional.lstm_layer``.
+so that the model is complete.  ``config.encoder_impl = "hip"`` opts the BiLSTM into ``functional.lstm_layer`` (DESIGN.md 8.7);
+``config.frontend_impl = "hip"``, independently, opts the embeddings with their locked dropout into ``functional.token_embed`` and
+``linear_re`` + tanh + the entity pooling into ``functional.token_context``.
 
 Extension: every ``forward`` also accepts a leading batch axis on all ten tensors (what ``gcgcn_amd.data.collate`` returns)
 plus ``n_valid[B]``; the reference's one-document call (``document[T]``, ``sen_matrix[N,N,S,T]`` ...) behaves as the reference's.
@@ -24,7 +26,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from .functional import lstm_layer
+from .functional import lstm_layer, token_context, token_embed
 from .modules import GraphModelTail
 
 Tensor = torch.Tensor
@@ -37,12 +39,16 @@ class LockedDropout(nn.Module):
         super().__init__()
         self.dropout = float(dropout)
 
-    def forward(self, x: Tensor) -> Tensor:
+    def factor(self, batch: int, features: int, dtype, device) -> Optional[Tensor]:
+        """The mask over ``[batch, 1, features]`` divided by the keep probability, or ``None`` where ``forward`` is the identity."""
         if not self.training or self.dropout <= 0.0:
-            return x
+            return None
         keep = 1.0 - self.dropout
-        m = torch.empty(x.size(0), 1, x.size(2), dtype=x.dtype, device=x.device).bernoulli_(keep) / keep
-        return m.expand_as(x) * x
+        return torch.empty(batch, 1, features, dtype=dtype, device=device).bernoulli_(keep) / keep
+
+    def forward(self, x: Tensor) -> Tensor:
+        m = self.factor(x.size(0), x.size(2), x.dtype, x.device)
+        return x if m is None else m.expand_as(x) * x
 
 
 class EncoderLSTM(nn.Module):
@@ -65,20 +71,22 @@ class EncoderLSTM(nn.Module):
         self.dropout = LockedDropout(dropout)
         self.concat, self.nlayers, self.return_last = concat, nlayers, return_last
 
-    def forward(self, input: Tensor, input_lengths=None) -> Tensor:
+    def forward(self, input: Tensor, input_lengths=None, input_dropped: bool = False) -> Tensor:
+        """``input_dropped``: the caller has applied the first layer's locked dropout to ``input`` already (``token_embed``'s scale)."""
         bsz = input.size(0)
         output, outputs = input, []
         for i in range(self.nlayers):
+            drop = (lambda x: x) if i == 0 and input_dropped else self.dropout
             if self.impl == "hip":
                 r = self.rnns[i]
                 rev = (r.weight_ih_l0_reverse, r.weight_hh_l0_reverse, r.bias_ih_l0_reverse, r.bias_hh_l0_reverse) if r.bidirectional else ()
-                output = lstm_layer(self.dropout(output), r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0,
+                output = lstm_layer(drop(output), r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0,
                                     self.init_hidden[i], self.init_c[i], *rev)
                 outputs.append(output)
                 continue
             h0 = self.init_hidden[i].expand(-1, bsz, -1).contiguous()
             c0 = self.init_c[i].expand(-1, bsz, -1).contiguous()
-            output, _ = self.rnns[i](self.dropout(output), (h0, c0))
+            output, _ = self.rnns[i](drop(output), (h0, c0))
             outputs.append(output)
         return torch.cat(outputs, dim=2) if self.concat else outputs[-1]
 
@@ -95,6 +103,9 @@ class _GraphRelationModel(GraphModelTail):
                          alpha=config.alpha, dis_size=config.dis_size, entity_type_size=config.entity_type_size,
                          relation_num=config.relation_num, dis_plus=config.dis_plus, dropout=0.2)
         self.config = config
+        self.frontend_impl = getattr(config, "frontend_impl", "torch")
+        if self.frontend_impl not in ("torch", "hip"):
+            raise ValueError(f"config.frontend_impl={self.frontend_impl!r} (\"torch\" or \"hip\")")
         self.layerNum, self.headNum = layer_num, head_num
         self._register_state_dict_hook(self._reference_order_hook)
 
@@ -114,9 +125,10 @@ class _GraphRelationModel(GraphModelTail):
             state_dict[mine[i][0]] = mine[i][1]
 
     def _graph_forward(self, context_output, adj_matrix, sen_matrix, pos_matrix_h, pos_matrix_t, node_pos, node_type,
-                       node_relative_pos, n_valid, batched, **caps):
-        # entity pooling (glove:293-298): node_feat[n] = sum_t node_pos[n, t] * context_output[t]
-        node_feat = torch.bmm(node_pos, context_output) if batched else node_pos @ context_output.squeeze(0)
+                       node_relative_pos, n_valid, batched, node_feat=None, **caps):
+        # entity pooling (glove:293-298): node_feat[n] = sum_t node_pos[n, t] * context_output[t]; the hip front end hands it in
+        if node_feat is None:
+            node_feat = torch.bmm(node_pos, context_output) if batched else node_pos @ context_output.squeeze(0)
         return GraphModelTail.forward(self, context_output, node_feat, adj_matrix, sen_matrix, pos_matrix_h, pos_matrix_t, node_type,
                                       node_relative_pos, self.dis_embed.weight, self.ner_emb.weight, n_valid=n_valid, **caps)
 
@@ -146,17 +158,35 @@ class GCGCN_glove(_GraphRelationModel):
 
     def encode(self, document: Tensor, document_ner: Tensor, document_pos: Tensor) -> Tensor:
         """Token states ``context_output`` ``[B,T,128]`` (glove:282-292)."""
+        if self.frontend_impl == "hip":
+            return self._encode_pooled(document, document_ner, document_pos, document.new_zeros(document.size(0), 1, document.size(1),
+                                                                                                dtype=torch.float32))[0]
         doc = torch.cat([self.word_emb(document), self.entity_embed(document_pos), self.ner_emb(document_ner)], dim=-1)
         return torch.tanh(self.linear_re(self.rnn(doc, doc.size(1))))
+
+    def _encode_pooled(self, document, document_ner, document_pos, node_pos):
+        """The hip front end: ``(context_output [B,T,128], node_feat [B,N,128])``.  The locked dropout in front of the first LSTM
+        layer is drawn here, by the same torch call, and applied inside ``token_embed``."""
+        I = self.word_emb.embedding_dim + self.entity_embed.embedding_dim + self.ner_emb.embedding_dim
+        scale = self.rnn.dropout.factor(document.size(0), I, self.word_emb.weight.dtype, document.device)
+        doc = token_embed(document, document_pos, document_ner, self.word_emb.weight, self.entity_embed.weight, self.ner_emb.weight,
+                          scale, self.entity_embed.padding_idx, self.ner_emb.padding_idx)
+        h = self.rnn(doc, doc.size(1), input_dropped=True)
+        return token_context(h, self.linear_re.weight, self.linear_re.bias, node_pos)
 
     def forward(self, document, document_ner, document_pos, adj_matrix, sen_matrix, pos_matrix_h, pos_matrix_t, node_pos, node_type,
                 node_relative_pos, n_valid: Optional[Tensor] = None, **caps):
         batched = document.dim() == 2
         if not batched:
             document, document_ner, document_pos = (t.unsqueeze(0) for t in (document, document_ner, document_pos))
-        ctx = self.encode(document, document_ner, document_pos)
+        node_feat = None
+        if self.frontend_impl == "hip":
+            ctx, node_feat = self._encode_pooled(document, document_ner, document_pos, node_pos if batched else node_pos.unsqueeze(0))
+            node_feat = node_feat if batched else node_feat[0]
+        else:
+            ctx = self.encode(document, document_ner, document_pos)
         return self._graph_forward(ctx, adj_matrix, sen_matrix, pos_matrix_h, pos_matrix_t, node_pos, node_type, node_relative_pos,
-                                   n_valid, batched, **caps)
+                                   n_valid, batched, node_feat=node_feat, **caps)
 
 
 class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
@@ -198,9 +228,14 @@ class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
         doc, _ = self.bert(document, output_all_encoded_layers=False)                        # bert:275
         cls_feat = doc[:, 0, :]                                                              # bert:277
         doc = torch.cat([doc, self.entity_embed(document_pos), self.ner_emb(document_ner)], dim=-1)
-        ctx = torch.tanh(self.linear_re(doc))                                                # bert:283
+        node_feat = None
+        if self.frontend_impl == "hip":
+            ctx, node_feat = token_context(doc, self.linear_re.weight, self.linear_re.bias, node_pos if batched else node_pos.unsqueeze(0))
+            node_feat = node_feat if batched else node_feat[0]
+        else:
+            ctx = torch.tanh(self.linear_re(doc))                                            # bert:283
         logits = self._graph_forward(ctx, adj_matrix, sen_matrix, pos_matrix_h, pos_matrix_t, node_pos, node_type,
-                                     node_relative_pos, n_valid, batched, **caps)
+                                     node_relative_pos, n_valid, batched, node_feat=node_feat, **caps)
         cls = self.linear_cls(cls_feat)                                                      # bert:345
         if not batched:
             return logits + cls[0]

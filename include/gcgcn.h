@@ -531,6 +531,40 @@ int gcgcn_lstm_bwd(int B, int T, int I, int H, int nd, const float* x, const flo
                    const float* c0, const float* out, const float* gates, const float* csave, const float* dout, float* dgates,
                    float* dx, float* dw_ih, float* dw_hh, float* db, float* dh0, float* dc0, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- the token front end, either side of the BiLSTM (glove:282-298, bert:275-290) -------------------------------------------
+ * Embeddings.  x [B][T][I], I = Dw + Dc + Dn, = word_emb[document] | entity_embed[document_pos] | ner_emb[document_ner] in that
+ * column order; tables word_w [V][Dw], coref_w [P][Dc], ner_w [R][Dn]; ids int64 [B][T] inside their table (the caller checks:
+ * an id outside its table reads zeros and adds to no gradient).  scale [B][I] or NULL: every element is multiplied by
+ * scale[b][i], the locked-dropout factor shared by all T steps.  Without a scale x is a plain copy of the table rows.
+ * gcgcn_embed_bwd: dx [B][T][I] (and the same scale) -> dword [V][Dw], dcoref [P][Dc], dner [R][Dn], every row written, zeros
+ * included (no memset is needed); the row at coref_padding_idx / ner_padding_idx (-1: none) is exactly zero, word_emb has no
+ * padding row.  Each row is summed by one owner in ascending token position b * T + t, in pieces of at most 32 tokens inside
+ * chunks of 256 consecutive tokens, the pieces added in ascending position.  Three launches and a memset of the workspace's
+ * flags; the workspace's contents need not survive between calls.
+ * Context.  gcgcn_context_fwd: h [B][T][K], w [Hd][K], bias [Hd], node_pos [B][N][T] -> ctx [B][T][Hd] = tanh(h w^T + bias) and
+ * node_feat [B][N][Hd] = sum_t node_pos[b][n][t] ctx[b][t][:] in ascending t over the non-zeros of the row (a row of zeros
+ * gives zeros).  pre [B][T][Hd] is scratch the caller owns (the product before the tanh; it must not alias ctx).  One GEMM
+ * launch + one launch.  gcgcn_context_bwd: dctx [B][T][Hd], dnode_feat [B][N][Hd] -> dpre [B][T][Hd] (scratch the caller owns)
+ * = (dctx + sum_n node_pos[b][n][t] dnode_feat[b][n][:], ascending n) (1 - ctx^2), then dh [B][T][K], dw [Hd][K], db [Hd]:
+ * one launch + one GEMM group launch (+ its split-K reduce).  node_pos gets no gradient.  Hd = 128 is served.
+ * ws: 16-byte aligned, gcgcn_frontend_ws_bytes bytes: enough for gcgcn_embed_bwd at these tables (V = 0: leave them out) and
+ * for gcgcn_context_bwd at inner width K (K = 0: leave it out); -1: refused.
+ * Refused before anything is launched: a null pointer (scale excepted), B, T, N, K, a table's rows or a width below 1,
+ * Hd != 128, a workspace that is too small or not 16-byte aligned, pre or ctx not 16-byte aligned.
+ * No workgroup waits for another, no float is added atomically: results are bit-reproducible.  Capturable. */
+int64_t gcgcn_frontend_ws_bytes(int B, int T, int V, int P, int R, int Dw, int Dc, int Dn, int K);
+int gcgcn_embed_fwd(int B, int T, int V, int P, int R, int Dw, int Dc, int Dn, const int64_t* document, const int64_t* document_pos,
+                    const int64_t* document_ner, const float* word_w, const float* coref_w, const float* ner_w, const float* scale,
+                    float* x, void* stream);
+int gcgcn_embed_bwd(int B, int T, int V, int P, int R, int Dw, int Dc, int Dn, const int64_t* document, const int64_t* document_pos,
+                    const int64_t* document_ner, const float* dx, const float* scale, int coref_padding_idx, int ner_padding_idx,
+                    float* dword, float* dcoref, float* dner, void* ws, int64_t ws_bytes, void* stream);
+int gcgcn_context_fwd(int B, int T, int N, int K, int Hd, const float* h, const float* w, const float* bias, const float* node_pos,
+                      float* pre, float* ctx, float* node_feat, void* stream);
+int gcgcn_context_bwd(int B, int T, int N, int K, int Hd, const float* h, const float* w, const float* node_pos, const float* ctx,
+                      const float* dctx, const float* dnode_feat, float* dpre, float* dh, float* dw, float* db, void* ws,
+                      int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

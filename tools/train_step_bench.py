@@ -98,6 +98,9 @@ def main():
                          "(collate stays on the host, outside the graph) and the replays timed; eager: launches from Python only")
     ap.add_argument("--encoder", default="torch", choices=["torch", "hip"],
                     help="the BiLSTM token encoder: torch.nn.LSTM (the default model) or config.encoder_impl = \"hip\" (csrc/lstm.hip)")
+    ap.add_argument("--frontend", default="torch", choices=["torch", "hip"],
+                    help="embeddings + locked dropout and linear_re + tanh + entity pooling: PyTorch (the default model) or "
+                         "config.frontend_impl = \"hip\" (csrc/frontend.hip)")
     a = ap.parse_args()
     import gcgcn_amd
     from gcgcn_amd import _lib, functional as F_
@@ -111,6 +114,8 @@ def main():
     cfg = Cfg(a.vocab)
     if a.encoder == "hip":
         cfg.encoder_impl = "hip"
+    if a.frontend == "hip":
+        cfg.frontend_impl = "hip"
     model = GCGCN_glove(cfg).to(dev).train()
     model.skip_dead_hop = a.skip_dead_hop
     gcgcn_amd.manual_seed(1337, dev)
@@ -182,6 +187,8 @@ def main():
     groups = {"encoder (PyTorch: embeddings, BiLSTM, linear_re) + everything outside the library": None,
               "encoder BiLSTM in HIP (--encoder hip: the two recurrence kernels, H_prev, the GEMM layer's single launches; its grouped "
               "gradient GEMMs are gemm_group / gemm_splitk_reduce launches and are booked under the graph blocks)": ["lstm_"],
+              "token front end in HIP (--frontend hip: embeddings, tanh + pooling and their backward, the projection's single GEMM launch; "
+              "its grouped gradient GEMMs are booked under the graph blocks)": ["fe_"],
               "edge-feature producers (f1)": ["prod_", "gemm_dyn"], "classifier head (f3)": ["head_"],
               "graph blocks (hot path)": ["gemm_group", "gemm_single", "gcn_chain", "edge_", "mha_core", "head_sum", "gat_", "node_score",
                                           "mask_rows", "softmax", "rowsum", "relu_norm", "dropout", "gemm_splitk_reduce", "colsum"]}
@@ -204,7 +211,7 @@ def main():
         "metric": "docs/sec, full training step of GCGCN_glove (collate -> forward -> loss -> backward -> Adam)", "value": round(a.B / dt, 1),
         "unit": "docs/s", "ms_per_step": round(dt * 1e3, 3), "ms_per_step_by_mode": ms_mode, "graph_optimiser": graph_opt, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"B={a.B} DocRED-shaped documents (T=512, mean {nv:.1f} entities, padded per batch), vocabulary {a.vocab}, "
-                               f"encoder {a.encoder}, train mode, {'torch.optim.Adam' if a.torch_adam else 'FusedAdam(capturable=True)' if capturable else 'FusedAdam (one launch)'}, eager launches, "
+                               f"encoder {a.encoder}, front end {a.frontend}, train mode, {'torch.optim.Adam' if a.torch_adam else 'FusedAdam(capturable=True)' if capturable else 'FusedAdam (one launch)'}, eager launches, "
                                f"{a.batches} resident packed batches rotated" + (", dead last hop skipped" if a.skip_dead_hop else "")},
         "ms_per_step_by_stage (stream time between HIP events, includes launch gaps)": split,
         "gpu_ms_per_step_by_part (library kernels in forward + backward)": by_part,
