@@ -107,6 +107,8 @@ SIGNATURES = {
     "gcgcn_lstm_ws_bytes": (L, [I] * 5),
     "gcgcn_lstm_fwd": (I, [I] * 5 + [P] * 10),
     "gcgcn_lstm_bwd": (I, [I] * 5 + [P] * 17 + [L, P]),
+    "gcgcn_lstm_fwd_len": (I, [I] * 5 + [P] * 11),
+    "gcgcn_lstm_bwd_len": (I, [I] * 5 + [P] * 17 + [L, P, P]),
     "gcgcn_frontend_ws_bytes": (L, [I] * 9),
     "gcgcn_embed_fwd": (I, [I] * 8 + [P] * 9),
     "gcgcn_embed_bwd": (I, [I] * 8 + [P] * 5 + [I, I] + [P] * 4 + [L, P]),

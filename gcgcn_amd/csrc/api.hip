@@ -1044,15 +1044,28 @@ int64_t gcgcn_lstm_ws_bytes(int B, int T, int I, int H, int nd) {
 
 int gcgcn_lstm_fwd(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* bias,
                    const float* h0, const float* c0, float* out, float* gates, float* csave, void* stream) {
+  return gcgcn_lstm_fwd_len(B, T, I, H, nd, x, w_ih, w_hh, bias, h0, c0, out, gates, csave, nullptr, stream);
+}
+
+int gcgcn_lstm_fwd_len(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* bias,
+                       const float* h0, const float* c0, float* out, float* gates, float* csave, const int* lens, void* stream) {
   GC_TRY(lstm_shape_ok("lstm_fwd", B, T, I, H, nd));
   GC_REQUIRE(x && w_ih && w_hh && bias && h0 && c0 && out && gates, "lstm_fwd: null pointer");
   GC_REQUIRE((((uintptr_t)w_hh) & 15) == 0, "lstm_fwd: w_hh must be 16-byte aligned");
-  return lstm_fwd(B, T, I, nd, x, w_ih, w_hh, bias, h0, c0, out, gates, csave, (hipStream_t)stream);
+  return lstm_fwd(B, T, I, nd, x, w_ih, w_hh, bias, h0, c0, out, gates, csave, lens, (hipStream_t)stream);
 }
 
 int gcgcn_lstm_bwd(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* h0,
                    const float* c0, const float* out, const float* gates, const float* csave, const float* dout, float* dgates,
                    float* dx, float* dw_ih, float* dw_hh, float* db, float* dh0, float* dc0, void* ws, int64_t ws_bytes, void* stream) {
+  return gcgcn_lstm_bwd_len(B, T, I, H, nd, x, w_ih, w_hh, h0, c0, out, gates, csave, dout, dgates, dx, dw_ih, dw_hh, db, dh0, dc0, ws,
+                            ws_bytes, nullptr, stream);
+}
+
+int gcgcn_lstm_bwd_len(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* h0,
+                       const float* c0, const float* out, const float* gates, const float* csave, const float* dout, float* dgates,
+                       float* dx, float* dw_ih, float* dw_hh, float* db, float* dh0, float* dc0, void* ws, int64_t ws_bytes,
+                       const int* lens, void* stream) {
   GC_TRY(lstm_shape_ok("lstm_bwd", B, T, I, H, nd));
   GC_REQUIRE(x && w_ih && w_hh && h0 && c0 && out && gates && csave && dout && dgates && dx && dw_ih && dw_hh && db && dh0 && dc0 && ws,
              "lstm_bwd: null pointer");
@@ -1063,7 +1076,7 @@ int gcgcn_lstm_bwd(int B, int T, int I, int H, int nd, const float* x, const flo
   GC_REQUIRE(ws_bytes >= gcgcn_lstm_ws_bytes(B, T, I, H, nd), "lstm_bwd: workspace of %lld bytes needed (gcgcn_lstm_ws_bytes)",
              (long long)gcgcn_lstm_ws_bytes(B, T, I, H, nd));
   return lstm_bwd(B, T, I, nd, x, w_ih, w_hh, h0, c0, out, gates, csave, dout, dgates, dx, dw_ih, dw_hh, db, dh0, dc0, (float*)ws,
-                  ws_bytes / (int64_t)sizeof(float), (hipStream_t)stream);
+                  ws_bytes / (int64_t)sizeof(float), lens, (hipStream_t)stream);
 }
 
 // ---- the token front end (frontend.hip) ------------------------------------------------------------------------------------------

@@ -1,5 +1,7 @@
 // The token encoder's LSTM layer (EncoderLSTM, glove:377-428): nn.LSTM(input_size, 128, 1, batch_first=True), one or two
-// directions, every one of the T padded steps.  DESIGN.md section 8.7.
+// directions, every one of the T padded steps -- or, with per-row lengths (lens), the semantics of a packed sequence: row b is
+// active at time t iff t < lens[b]; an inactive step leaves the row's h and c alone and puts 0 into the output; the reverse
+// direction of row b starts at t = lens[b] - 1 from h0 / c0.  DESIGN.md section 8.7.
 //
 //   forward :  gates = X [W_ih_f; W_ih_r]^T + (b_ih + b_hh)      one product of the GEMM layer (gemm_nt + bias)
 //              lstm_fwd_kernel                                   the whole time loop, one workgroup per (direction, 16 batch rows)
@@ -12,6 +14,12 @@
 // v_mfma_f32_16x16x4_f32 and stays in 128 registers for the whole launch; the A operand (h_{t-1}, or dgates_t in the backward) is
 // read from a double-buffered LDS image, one __syncthreads() per step.  No workgroup reads what another one of the launch
 // writes, nothing is added atomically: two runs are bitwise equal.
+//
+// Lengths.  The recurrence kernels are templates on LEN; LEN = false (lens == nullptr) is the code without lengths.  With LEN a
+// workgroup loops Lt = the largest length among its 16 rows (uniform) instead of T, the reverse direction from t = Lt - 1, and
+// zero-fills [Lt, T) of what it owns afterwards, so every element is written by the launch.  Lengths are clamped into [0, T].
+// Freezing a row is a select in the cell update; nothing branches around an MFMA.  What the forward leaves unwritten at inactive
+// steps (csave, the activated gates) the backward reads only through selects, as it does dout there: NaN in it reaches nothing.
 //
 // Lane maps of the 16x16x4 form (lane l, c16 = l & 15, q = l >> 4): A[row c16][k q], B[k q][col c16], C/D [row 4 q + r][col c16].
 // The sum over k may run in any order as long as A and B agree, so k-step s of lane group q takes k = q * (K / 4) + s: a lane's A
@@ -30,11 +38,26 @@ constexpr int LGS = 4 * LH + 4;      // ... of the dgates image
 static_assert(2 * LROWS * LGS * sizeof(float) <= 160 * 1024, "LDS of one compute unit");
 
 __device__ __forceinline__ float lstm_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+__device__ __forceinline__ int lstm_len(const int* __restrict__ lens, int b, int T) {
+  const int n = lens[b];
+  return n < 0 ? 0 : n > T ? T : n;
+}
+// the largest length among the workgroup's rows [b0, b0 + 16) that exist: the same value in every lane
+__device__ __forceinline__ int lstm_tile_len(const int* __restrict__ lens, int b0, int B, int T) {
+  int lt = 0;
+  for (int j = 0; j < LROWS && b0 + j < B; ++j) {
+    const int n = lstm_len(lens, b0 + j, T);
+    lt = n > lt ? n : lt;
+  }
+  return __builtin_amdgcn_readfirstlane(lt);
+}
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
+template <bool LEN>
 __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__ w_hh, const float* __restrict__ h0,
                                                        const float* __restrict__ c0, float* __restrict__ gates, float* __restrict__ out,
-                                                       float* __restrict__ csave, const int B, const int T, const int nd) {
+                                                       float* __restrict__ csave, const int* __restrict__ lens, const int B, const int T,
+                                                       const int nd) {
   __shared__ __attribute__((aligned(16))) float hbuf[2][LROWS * LHS];
   const int dir = blockIdx.y, b0 = blockIdx.x * LROWS;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, c16 = l & 15, q = l >> 4;
@@ -55,6 +78,9 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
   bool valid[4];
   long grow[4], orow[4];   // element offsets of step 0 of the row in gates and in out / csave, this direction's column included
   float c[4];
+  float hk[4];   // LEN: the row's h, carried into the next LDS buffer over an inactive step
+  int len[4];    // LEN: the row's length
+  const int Lt = LEN ? lstm_tile_len(lens, b0, B, T) : T;   // steps of this workgroup
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int b = b0 + 4 * q + r, bc = b < B ? b : B - 1;
@@ -63,13 +89,15 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
     orow[r] = (long)bc * T * (nd * LH) + dir * LH + u;
     const long s0 = ((long)dir * B + bc) * LH + u;
     c[r] = valid[r] ? c0[s0] : 0.f;
-    hbuf[0][(4 * q + r) * LHS + u] = valid[r] ? h0[s0] : 0.f;
+    hk[r] = valid[r] ? h0[s0] : 0.f;
+    hbuf[0][(4 * q + r) * LHS + u] = hk[r];
+    len[r] = LEN ? lstm_len(lens, bc, T) : T;
   }
   const long gstep = (long)nd * 4 * LH, ostep = (long)nd * LH;
 
   float gn[4][4];   // the input projection of the NEXT step, requested one step ahead
   {
-    const int t0 = dir ? T - 1 : 0;
+    const int t0 = LEN ? (dir && Lt > 0 ? Lt - 1 : 0) : (dir ? T - 1 : 0);   // Lt = 0: nothing runs, the request stays in bounds
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -77,9 +105,9 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
   }
   __syncthreads();
 
-  for (int s = 0; s < T; ++s) {
-    const int t = dir ? T - 1 - s : s;
-    const int sn = s + 1 < T ? s + 1 : s, tn = dir ? T - 1 - sn : sn;   // the last step asks for itself again (unused)
+  for (int s = 0; s < Lt; ++s) {
+    const int t = dir ? Lt - 1 - s : s;
+    const int sn = s + 1 < Lt ? s + 1 : s, tn = dir ? Lt - 1 - sn : sn;   // the last step asks for itself again (unused)
     f32x4 acc[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g)
@@ -105,27 +133,56 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float gi = lstm_sigmoid(acc[0][r]), gf = lstm_sigmoid(acc[1][r]), gg = tanhf(acc[2][r]), go = lstm_sigmoid(acc[3][r]);
-      c[r] = gf * c[r] + gi * gg;
-      const float h = go * tanhf(c[r]);
-      hn[(4 * q + r) * LHS + u] = h;
-      if (valid[r]) {
-        out[orow[r] + t * ostep] = h;
-        if (csave) {
-          float* gp = gates + grow[r] + t * gstep;
-          gp[0] = gi, gp[LH] = gf, gp[2 * LH] = gg, gp[3 * LH] = go;
-          csave[orow[r] + t * ostep] = c[r];
+      if constexpr (LEN) {
+        const bool act = t < len[r];
+        const float cn = __builtin_fmaf(gf, c[r], gi * gg);   // spelled out: both instantiations round alike
+        c[r] = act ? cn : c[r];
+        const float h = go * tanhf(cn);
+        hk[r] = act ? h : hk[r];
+        hn[(4 * q + r) * LHS + u] = hk[r];
+        if (valid[r]) {
+          out[orow[r] + t * ostep] = act ? h : 0.f;
+          if (csave && act) {
+            float* gp = gates + grow[r] + t * gstep;
+            gp[0] = gi, gp[LH] = gf, gp[2 * LH] = gg, gp[3 * LH] = go;
+            csave[orow[r] + t * ostep] = cn;
+          }
+        }
+      } else {
+        c[r] = __builtin_fmaf(gf, c[r], gi * gg);
+        const float h = go * tanhf(c[r]);
+        hn[(4 * q + r) * LHS + u] = h;
+        if (valid[r]) {
+          out[orow[r] + t * ostep] = h;
+          if (csave) {
+            float* gp = gates + grow[r] + t * gstep;
+            gp[0] = gi, gp[LH] = gf, gp[2 * LH] = gg, gp[3 * LH] = go;
+            csave[orow[r] + t * ostep] = c[r];
+          }
         }
       }
     }
     __syncthreads();
   }
+  if constexpr (LEN) {   // the tile's tail: no row of it is active there
+    for (int t = Lt; t < T; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (valid[r]) out[orow[r] + t * ostep] = 0.f;
+  }
 }
 
 // ---- backward --------------------------------------------------------------------------------------------------------------
+// LEN: an inactive step has dgates_t = 0 (LDS image and global memory) and hands dh and dc on unchanged -- the zero LDS row adds
+// nothing to the product, so the row keeps its old dh.  c_prev is c0 at the ROW's first step: t = lens[b] - 1 in the reverse
+// direction.  Whatever is read at an inactive step (the saved gates, csave, dout: possibly never written, possibly NaN) is
+// replaced by 0 through a select, never multiplied by a 0 / 1 flag.
+template <bool LEN>
 __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__ w_hh, const float* __restrict__ c0,
                                                        const float* __restrict__ gates, const float* __restrict__ csave,
                                                        const float* __restrict__ dout, float* __restrict__ dgates, float* __restrict__ dh0,
-                                                       float* __restrict__ dc0, const int B, const int T, const int nd) {
+                                                       float* __restrict__ dc0, const int* __restrict__ lens, const int B, const int T,
+                                                       const int nd) {
   __shared__ __attribute__((aligned(16))) float gbuf[2][LROWS * LGS];
   const int dir = blockIdx.y, b0 = blockIdx.x * LROWS;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, c16 = l & 15, q = l >> 4;
@@ -139,6 +196,8 @@ __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__
 
   bool valid[4];
   long grow[4], orow[4], srow[4];
+  int len[4];   // LEN: the row's length, 0 for a row past B (never active)
+  const int Lt = LEN ? lstm_tile_len(lens, b0, B, T) : T;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int b = b0 + 4 * q + r, bc = b < B ? b : B - 1;
@@ -146,40 +205,56 @@ __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__
     grow[r] = (long)bc * T * (nd * 4 * LH) + dir * 4 * LH + u;
     orow[r] = (long)bc * T * (nd * LH) + dir * LH + u;
     srow[r] = ((long)dir * B + bc) * LH + u;
+    len[r] = LEN ? (valid[r] ? lstm_len(lens, bc, T) : 0) : T;
   }
   const long gstep = (long)nd * 4 * LH, ostep = (long)nd * LH;
 
   float dh[4] = {0.f, 0.f, 0.f, 0.f}, dc[4] = {0.f, 0.f, 0.f, 0.f};   // what the later step hands back
   float gt[4][4], ct[4], cp[4], dy[4];                                  // step operands, requested one step ahead
-  // step s of this loop undoes forward step T - 1 - s, which ran at time t; the forward's previous time is tp
+  // step s of this loop undoes forward step Lt - 1 - s, which ran at time t; the forward's previous time is tp.  An inactive
+  // row's c_prev address is c0's: t + 1 may lie past the row's end, and the value is dropped anyway.
 #define LSTM_BWD_REQUEST(S)                                                                          \
   {                                                                                                  \
-    const int fs_ = T - 1 - (S), t_ = dir ? T - 1 - fs_ : fs_, tp_ = dir ? t_ + 1 : t_ - 1;          \
+    const int fs_ = Lt - 1 - (S), t_ = dir ? Lt - 1 - fs_ : fs_, tp_ = dir ? t_ + 1 : t_ - 1;        \
     _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                  \
       _Pragma("unroll") for (int g = 0; g < 4; ++g) gt[g][r] = gates[grow[r] + t_ * gstep + g * LH]; \
       ct[r] = csave[orow[r] + t_ * ostep];                                                           \
-      const float* pp_ = fs_ == 0 ? c0 + srow[r] : csave + orow[r] + tp_ * ostep;                    \
+      const bool first_ = LEN ? (dir ? t_ >= len[r] - 1 : t_ == 0) : fs_ == 0;                       \
+      const float* pp_ = first_ ? c0 + srow[r] : csave + orow[r] + tp_ * ostep;                      \
       cp[r] = *pp_;                                                                                  \
       dy[r] = dout[orow[r] + t_ * ostep];                                                            \
     }                                                                                                \
   }
-  LSTM_BWD_REQUEST(0)
+  if (!LEN || Lt > 0) LSTM_BWD_REQUEST(0)
 
-  for (int s = 0; s < T; ++s) {
-    const int fs = T - 1 - s, t = dir ? T - 1 - fs : fs;
+  for (int s = 0; s < Lt; ++s) {
+    const int fs = Lt - 1 - s, t = dir ? Lt - 1 - fs : fs;
     float* gw = gbuf[s & 1];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const float z = valid[r] ? 1.f : 0.f;
-      const float gi = z * gt[0][r], gf = z * gt[1][r], gg = z * gt[2][r], go = z * gt[3][r];
-      const float dhv = z * dy[r] + dh[r];
-      const float tc = tanhf(z * ct[r]);
+      float gi, gf, gg, go, dyv, cv, cpv;
+      const bool act = LEN ? t < len[r] : valid[r];
+      if constexpr (LEN) {
+        gi = act ? gt[0][r] : 0.f, gf = act ? gt[1][r] : 0.f, gg = act ? gt[2][r] : 0.f, go = act ? gt[3][r] : 0.f;
+        dyv = act ? dy[r] : 0.f, cv = act ? ct[r] : 0.f, cpv = act ? cp[r] : 0.f;
+      } else {
+        const float z = valid[r] ? 1.f : 0.f;
+        gi = z * gt[0][r], gf = z * gt[1][r], gg = z * gt[2][r], go = z * gt[3][r];
+        dyv = z * dy[r], cv = z * ct[r], cpv = z * cp[r];
+      }
+      const float dhv = dyv + dh[r];
+      const float tc = tanhf(cv);
       const float dcv = dc[r] + dhv * go * (1.f - tc * tc);
-      const float da_i = dcv * gg * gi * (1.f - gi);
-      const float da_f = dcv * (z * cp[r]) * gf * (1.f - gf);
-      const float da_g = dcv * gi * (1.f - gg * gg);
-      const float da_o = dhv * tc * go * (1.f - go);
-      dc[r] = dcv * gf;
+      float da_i = dcv * gg * gi * (1.f - gi);
+      float da_f = dcv * cpv * gf * (1.f - gf);
+      float da_g = dcv * gi * (1.f - gg * gg);
+      float da_o = dhv * tc * go * (1.f - go);
+      if constexpr (LEN) {
+        da_i = act ? da_i : 0.f, da_f = act ? da_f : 0.f, da_g = act ? da_g : 0.f, da_o = act ? da_o : 0.f;
+        dc[r] = act ? dcv * gf : dc[r];
+      } else {
+        dc[r] = dcv * gf;
+      }
       float* lp = gw + (4 * q + r) * LGS + u;
       lp[0] = da_i, lp[LH] = da_f, lp[2 * LH] = da_g, lp[3 * LH] = da_o;
       if (valid[r]) {
@@ -188,7 +263,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__
       }
     }
     {
-      const int sn = s + 1 < T ? s + 1 : s;   // the last step asks for itself again (unused)
+      const int sn = s + 1 < Lt ? s + 1 : s;   // the last step asks for itself again (unused)
       LSTM_BWD_REQUEST(sn)
     }
     __syncthreads();
@@ -206,17 +281,32 @@ __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__
       acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, wr[4 * j + 3], acc[3], 0, 0, 0);
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) dh[r] = (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
+    for (int r = 0; r < 4; ++r) {
+      const float rec = (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
+      dh[r] = !LEN || t < len[r] ? rec : dh[r];
+    }
   }
 #undef LSTM_BWD_REQUEST
 #pragma unroll
   for (int r = 0; r < 4; ++r)
     if (valid[r]) dh0[srow[r]] = dh[r], dc0[srow[r]] = dc[r];
+  if constexpr (LEN) {   // the tile's tail: the gradient products read all B * T rows of dgates
+    for (int t = Lt; t < T; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (valid[r]) {
+          float* gp = dgates + grow[r] + t * gstep;
+          gp[0] = 0.f, gp[LH] = 0.f, gp[2 * LH] = 0.f, gp[3 * LH] = 0.f;
+        }
+  }
 }
 
-// H_prev[b][t][dir H + u] = h of the direction's previous step: out one step back in the direction's own order, h0 at its first step
+// H_prev[b][t][dir H + u] = h of the direction's previous step: out one step back in the direction's own order, h0 at its first step.
+// With lengths the reverse direction's first step is t = lens[b] - 1, and every later (padded) t takes h0 too: dgates is zero
+// there, so any finite value serves, and out[t + 1] would lie past the row at t = T - 1.  The forward direction's padded rows
+// read the output's zeros.
 __global__ __launch_bounds__(256) void lstm_hprev_kernel(const float* __restrict__ out, const float* __restrict__ h0, float* __restrict__ hprev,
-                                                         const int B, const int T, const int nd) {
+                                                         const int* __restrict__ lens, const int B, const int T, const int nd) {
   const long n4 = (long)B * T * nd * (LH / 4);
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n4) return;
@@ -224,21 +314,26 @@ __global__ __launch_bounds__(256) void lstm_hprev_kernel(const float* __restrict
   const long bt = i / ((LH / 4) * nd);
   const int t = (int)(bt % T);
   const long b = bt / T;
-  const bool first = dir ? t == T - 1 : t == 0;
+  const int len = lens ? lstm_len(lens, (int)b, T) : T;
+  const bool first = dir ? t >= len - 1 : t == 0;
   const float* src = first ? h0 + ((long)dir * B + b) * LH + 4 * u4 : out + (bt + (dir ? 1 : -1)) * ((long)nd * LH) + dir * LH + 4 * u4;
   *reinterpret_cast<float4*>(hprev + 4 * i) = *reinterpret_cast<const float4*>(src);
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
 int lstm_fwd(int B, int T, int I, int nd, const float* x, const float* w_ih, const float* w_hh, const float* bias, const float* h0,
-             const float* c0, float* out, float* gates, float* csave, hipStream_t st) {
+             const float* c0, float* out, float* gates, float* csave, const int* lens, hipStream_t st) {
   const long BT = (long)B * T;
   const int G = nd * 4 * LH;
   GemmArgs g = gemm_nt(x, I, w_ih, I, gates, G, (int)BT, G, I).tagged("lstm_gemm");   // gates = X W_ih^T + b, both directions
   g.bias = bias;
   GC_TRY(gemm(g, st, 0, 1));
-  GC_LAUNCH_TIMED("lstm_fwd", 2.0 * BT * G * LH, lstm_fwd_kernel, dim3(cdiv(B, LROWS), nd), dim3(512), 0, st, w_hh, h0, c0, gates, out,
-                  csave, B, T, nd);
+  if (lens)
+    GC_LAUNCH_TIMED("lstm_fwd", 2.0 * BT * G * LH, lstm_fwd_kernel<true>, dim3(cdiv(B, LROWS), nd), dim3(512), 0, st, w_hh, h0, c0, gates,
+                    out, csave, lens, B, T, nd);
+  else
+    GC_LAUNCH_TIMED("lstm_fwd", 2.0 * BT * G * LH, lstm_fwd_kernel<false>, dim3(cdiv(B, LROWS), nd), dim3(512), 0, st, w_hh, h0, c0, gates,
+                    out, csave, lens, B, T, nd);
   return check_launch("lstm_fwd");
 }
 
@@ -249,7 +344,7 @@ long lstm_ws_elems(int B, int T, int I, int nd) { return (long)B * T * nd * LH +
 
 int lstm_bwd(int B, int T, int I, int nd, const float* x, const float* w_ih, const float* w_hh, const float* h0, const float* c0,
              const float* out, const float* gates, const float* csave, const float* dout, float* dgates, float* dx, float* dw_ih,
-             float* dw_hh, float* db, float* dh0, float* dc0, float* ws, long ws_elems, hipStream_t st) {
+             float* dw_hh, float* db, float* dh0, float* dc0, float* ws, long ws_elems, const int* lens, hipStream_t st) {
   const long BT = (long)B * T;
   const int G = nd * 4 * LH;
   GC_REQUIRE(ws_elems >= lstm_ws_elems(B, T, I, nd), "lstm_bwd: workspace of %ld floats needed", lstm_ws_elems(B, T, I, nd));
@@ -258,12 +353,16 @@ int lstm_bwd(int B, int T, int I, int nd, const float* x, const float* w_ih, con
   const long split_elems = lstm_split_elems(I, nd);
   float* part = split + split_elems;
 
-  GC_LAUNCH_TIMED("lstm_bwd", 2.0 * BT * G * LH, lstm_bwd_kernel, dim3(cdiv(B, LROWS), nd), dim3(512), 0, st, w_hh, c0, gates, csave, dout,
-                  dgates, dh0, dc0, B, T, nd);
+  if (lens)
+    GC_LAUNCH_TIMED("lstm_bwd", 2.0 * BT * G * LH, lstm_bwd_kernel<true>, dim3(cdiv(B, LROWS), nd), dim3(512), 0, st, w_hh, c0, gates, csave,
+                    dout, dgates, dh0, dc0, lens, B, T, nd);
+  else
+    GC_LAUNCH_TIMED("lstm_bwd", 2.0 * BT * G * LH, lstm_bwd_kernel<false>, dim3(cdiv(B, LROWS), nd), dim3(512), 0, st, w_hh, c0, gates, csave,
+                    dout, dgates, dh0, dc0, lens, B, T, nd);
   GC_TRY(check_launch("lstm_bwd"));
   {
     ProfScope ps("lstm_hprev", st);
-    hipLaunchKernelGGL(lstm_hprev_kernel, dim3(cdiv(BT * nd * (LH / 4), 256)), dim3(256), 0, st, out, h0, hprev, B, T, nd);
+    hipLaunchKernelGGL(lstm_hprev_kernel, dim3(cdiv(BT * nd * (LH / 4), 256)), dim3(256), 0, st, out, h0, hprev, lens, B, T, nd);
     GC_TRY(check_launch("lstm_hprev"));
   }
   // dW_ih = dgates^T X; dW_hh[dir] = dgates[:, dir]^T H_prev[:, dir]; dX = dgates W_ih; db = column sums of dgates (riding)

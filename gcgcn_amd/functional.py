@@ -1102,27 +1102,34 @@ def _lstm_ws(B: int, T: int, I: int, H: int, nd: int, dev) -> Tensor:
 
 class LstmFn(torch.autograd.Function):
     """(x[B,T,I], w_ih[nd*4H,I], w_hh[nd*4H,H], bias[nd*4H], h0[nd,B,H], c0[nd,B,H]) -> out[B,T,nd*H]: one ``nn.LSTM`` layer over
-    all T steps with the directions' parameters stacked and ``bias = b_ih + b_hh`` (``lstm_layer`` stacks and splits them)."""
+    all T steps with the directions' parameters stacked and ``bias = b_ih + b_hh`` (``lstm_layer`` stacks and splits them).
+    ``lens``: ``None`` or the rows' lengths, int32 ``[B]`` on the device (saved for the backward)."""
 
     @staticmethod
-    def forward(ctx, x, w_ih, w_hh, bias, h0, c0):
+    def forward(ctx, x, w_ih, w_hh, bias, h0, c0, lens=None):
         B, T, I = x.shape
         nd, H = h0.shape[0], h0.shape[2]
         need_grad = any(ctx.needs_input_grad)
         out = torch.empty(B, T, nd * H, device=x.device)
         gates = torch.empty(B * T, nd * 4 * H, device=x.device)
         csave = torch.empty(B, T, nd * H, device=x.device) if need_grad else None
-        call("gcgcn_lstm_fwd", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(bias), _p(h0), _p(c0), _p(out), _p(gates), _p(csave), _stream())
+        if lens is None:
+            call("gcgcn_lstm_fwd", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(bias), _p(h0), _p(c0), _p(out), _p(gates), _p(csave), _stream())
+        else:
+            call("gcgcn_lstm_fwd_len", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(bias), _p(h0), _p(c0), _p(out), _p(gates), _p(csave),
+                 _p(lens), _stream())
         written = (out, gates) if csave is None else (out, gates, csave)
         torch.autograd.graph.increment_version(written)     # raw-pointer writes, as in optim._written
+        ctx.has_lens = lens is not None
         if need_grad:
-            ctx.save_for_backward(x, w_ih, w_hh, h0, c0, out, gates, csave)
+            ctx.save_for_backward(x, w_ih, w_hh, h0, c0, out, gates, csave, *(() if lens is None else (lens,)))
         return out
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dout):
-        x, w_ih, w_hh, h0, c0, out, gates, csave = ctx.saved_tensors
+        x, w_ih, w_hh, h0, c0, out, gates, csave = ctx.saved_tensors[:8]
+        lens = ctx.saved_tensors[8] if ctx.has_lens else None
         B, T, I = x.shape
         nd, H = h0.shape[0], h0.shape[2]
         dout = dout.contiguous()
@@ -1133,17 +1140,41 @@ class LstmFn(torch.autograd.Function):
         db = torch.empty(nd * 4 * H, device=x.device)
         dh0, dc0 = torch.empty_like(h0), torch.empty_like(c0)
         ws = _lstm_ws(B, T, I, H, nd, x.device)
-        call("gcgcn_lstm_bwd", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(h0), _p(c0), _p(out), _p(gates), _p(csave), _p(dout), _p(dgates),
-             _p(dx), _p(dw_ih), _p(dw_hh), _p(db), _p(dh0), _p(dc0), _p(ws), ws.numel() * 4, _stream())
+        args = (B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(h0), _p(c0), _p(out), _p(gates), _p(csave), _p(dout), _p(dgates),
+                _p(dx), _p(dw_ih), _p(dw_hh), _p(db), _p(dh0), _p(dc0), _p(ws), ws.numel() * 4)
+        if lens is None:
+            call("gcgcn_lstm_bwd", *args, _stream())
+        else:
+            call("gcgcn_lstm_bwd_len", *args, _p(lens), _stream())
         torch.autograd.graph.increment_version((dx, dw_ih, dw_hh, db, dh0, dc0))
-        return dx, dw_ih, dw_hh, db, dh0, dc0
+        return dx, dw_ih, dw_hh, db, dh0, dc0, None
 
 
-def lstm_layer(x, w_ih, w_hh, b_ih, b_hh, h0, c0, w_ih_r=None, w_hh_r=None, b_ih_r=None, b_hh_r=None):
+def _lstm_lengths(lengths, B: int, T: int, dev) -> Tensor:
+    """The rows' lengths as the kernels take them: int32 ``[B]`` on the device, converted there.  Values outside [1, T] raise --
+    ONE host read, skipped inside a hipGraph capture and with ``check_ids = False`` (the kernels clamp into [0, T] regardless)."""
+    if not isinstance(lengths, Tensor) or lengths.dtype not in (torch.int32, torch.int64) or tuple(lengths.shape) != (B,) \
+            or lengths.device != dev:
+        got = f"{lengths.dtype} {tuple(lengths.shape)} on {lengths.device}" if isinstance(lengths, Tensor) else type(lengths).__name__
+        raise ValueError(f"lstm_layer: lengths must be an int32 or int64 tensor of shape ({B},) on {dev}, got {got}")
+    if check_ids and not torch.cuda.is_current_stream_capturing():
+        lo_hi = torch.stack([lengths.min(), lengths.max()]).tolist()
+        if lo_hi[0] < 1 or lo_hi[1] > T:
+            raise IndexError(f"lstm_layer: lengths must lie in [1, {T}], got min {lo_hi[0]} / max {lo_hi[1]}")
+    return lengths.to(torch.int32).contiguous()
+
+
+def lstm_layer(x, w_ih, w_hh, b_ih, b_hh, h0, c0, w_ih_r=None, w_hh_r=None, b_ih_r=None, b_hh_r=None, lengths=None):
     """One ``nn.LSTM(input_size, H, 1, batch_first=True)`` layer in HIP: ``x[B,T,I]``, ``h0``/``c0`` ``[nd,B,H]`` (a ``[nd,1,H]``
     state is broadcast over the batch) -> the output ``[B,T,nd*H]``.  Gate order i, f, g, o and all T padded steps, as torch runs
     it.  The four ``*_r`` parameters of the reverse direction make it bidirectional (all four or none).  ``H = 128`` is served;
-    another width raises.  Gradients reach ``x``, every weight and bias, ``h0`` and ``c0``."""
+    another width raises.  Gradients reach ``x``, every weight and bias, ``h0`` and ``c0``.
+
+    ``lengths``: ``None``, or an int32 / int64 tensor ``[B]`` on ``x``'s device, every value in ``[1, T]`` (checked with one host
+    read outside a capture).  The layer then computes what ``pack_padded_sequence`` -> ``nn.LSTM`` ->
+    ``pad_packed_sequence(total_length=T)`` computes: row ``b`` runs its own ``lengths[b]`` steps (the reverse direction from
+    ``t = lengths[b] - 1``), the output is exactly 0 at ``t >= lengths[b]``, and so is the gradient to ``x`` there, whatever the
+    output's gradient holds at those positions.  ``x`` itself must be finite there."""
     rev = (w_ih_r, w_hh_r, b_ih_r, b_hh_r)
     if any(t is None for t in rev) and not all(t is None for t in rev):
         raise ValueError("lstm_layer: the reverse direction needs all of w_ih_r, w_hh_r, b_ih_r, b_hh_r")
@@ -1167,7 +1198,10 @@ def lstm_layer(x, w_ih, w_hh, b_ih, b_hh, h0, c0, w_ih_r=None, w_hh_r=None, b_ih
         bias = torch.cat([b_ih + b_hh, b_ih_r + b_hh_r], 0)
     else:
         W_ih, W_hh, bias = w_ih.contiguous(), w_hh.contiguous(), b_ih + b_hh
-    return LstmFn.apply(x, W_ih, W_hh, bias, h0.expand(nd, B, H).contiguous(), c0.expand(nd, B, H).contiguous())
+    if lengths is None:
+        return LstmFn.apply(x, W_ih, W_hh, bias, h0.expand(nd, B, H).contiguous(), c0.expand(nd, B, H).contiguous())
+    return LstmFn.apply(x, W_ih, W_hh, bias, h0.expand(nd, B, H).contiguous(), c0.expand(nd, B, H).contiguous(),
+                        _lstm_lengths(lengths, B, T, x.device))
 
 
 # ---- the token front end either side of the BiLSTM (csrc/frontend.hip) -----------------------------------------------------------

@@ -25,6 +25,7 @@ from typing import Optional
 import numpy as np
 import torch
 from torch import nn
+from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
 
 from .functional import lstm_layer, token_context, token_embed
 from .modules import GraphModelTail
@@ -56,7 +57,11 @@ class EncoderLSTM(nn.Module):
     in front of every layer, layer outputs concatenated.  Parameter names as in the reference: ``rnns.{i}.*``, ``init_hidden.{i}``,
     ``init_c.{i}``.  ``impl="torch"`` (the default) is plain PyTorch (MIOpen's LSTM on ROCm); ``impl="hip"`` runs every layer
     through ``functional.lstm_layer`` on the same parameters -- the ``nn.LSTM`` modules stay as their holders, so the
-    ``state_dict`` is the same either way -- and raises on CPU tensors."""
+    ``state_dict`` is the same either way -- and raises on CPU tensors.
+
+    ``forward(input, input_lengths)``: a TENSOR ``input_lengths`` (int ``[B]``, values in ``[1, T]``) makes every layer run each
+    row at its own length, as a packed sequence: ``impl="hip"`` hands it to ``lstm_layer``, ``impl="torch"`` packs and pads back to
+    ``T`` (the output is 0 past a row's length).  Anything else there (the reference passes ``doc.size(1)``) is ignored."""
 
     def __init__(self, input_size, num_units, nlayers, concat, bidir, dropout, return_last, impl="torch"):
         super().__init__()
@@ -74,6 +79,7 @@ class EncoderLSTM(nn.Module):
     def forward(self, input: Tensor, input_lengths=None, input_dropped: bool = False) -> Tensor:
         """``input_dropped``: the caller has applied the first layer's locked dropout to ``input`` already (``token_embed``'s scale)."""
         bsz = input.size(0)
+        lengths = input_lengths if isinstance(input_lengths, Tensor) else None
         output, outputs = input, []
         for i in range(self.nlayers):
             drop = (lambda x: x) if i == 0 and input_dropped else self.dropout
@@ -81,11 +87,16 @@ class EncoderLSTM(nn.Module):
                 r = self.rnns[i]
                 rev = (r.weight_ih_l0_reverse, r.weight_hh_l0_reverse, r.bias_ih_l0_reverse, r.bias_hh_l0_reverse) if r.bidirectional else ()
                 output = lstm_layer(drop(output), r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0,
-                                    self.init_hidden[i], self.init_c[i], *rev)
+                                    self.init_hidden[i], self.init_c[i], *rev, lengths=lengths)
                 outputs.append(output)
                 continue
             h0 = self.init_hidden[i].expand(-1, bsz, -1).contiguous()
             c0 = self.init_c[i].expand(-1, bsz, -1).contiguous()
+            if lengths is not None:                   # torch wants the lengths on the host
+                packed = pack_padded_sequence(drop(output), lengths.cpu(), batch_first=True, enforce_sorted=False)
+                output, _ = pad_packed_sequence(self.rnns[i](packed, (h0, c0))[0], batch_first=True, total_length=input.size(1))
+                outputs.append(output)
+                continue
             output, _ = self.rnns[i](drop(output), (h0, c0))
             outputs.append(output)
         return torch.cat(outputs, dim=2) if self.concat else outputs[-1]
@@ -156,35 +167,40 @@ class GCGCN_glove(_GraphRelationModel):
         self.linear_re = nn.Linear(self.HIDDEN * 2, self.HIDDEN)                             # glove:264
         self.dis_embed = nn.Embedding(config.dis_num, config.dis_size)                       # glove:279
 
-    def encode(self, document: Tensor, document_ner: Tensor, document_pos: Tensor) -> Tensor:
-        """Token states ``context_output`` ``[B,T,128]`` (glove:282-292)."""
+    def encode(self, document: Tensor, document_ner: Tensor, document_pos: Tensor, t_valid: Optional[Tensor] = None) -> Tensor:
+        """Token states ``context_output`` ``[B,T,128]`` (glove:282-292).  ``t_valid``: the documents' token counts ``[B]``
+        (``data.collate``); the encoder then runs each document at its own length."""
         if self.frontend_impl == "hip":
             return self._encode_pooled(document, document_ner, document_pos, document.new_zeros(document.size(0), 1, document.size(1),
-                                                                                                dtype=torch.float32))[0]
+                                                                                                dtype=torch.float32), t_valid)[0]
         doc = torch.cat([self.word_emb(document), self.entity_embed(document_pos), self.ner_emb(document_ner)], dim=-1)
-        return torch.tanh(self.linear_re(self.rnn(doc, doc.size(1))))
+        return torch.tanh(self.linear_re(self.rnn(doc, doc.size(1) if t_valid is None else t_valid)))
 
-    def _encode_pooled(self, document, document_ner, document_pos, node_pos):
+    def _encode_pooled(self, document, document_ner, document_pos, node_pos, t_valid=None):
         """The hip front end: ``(context_output [B,T,128], node_feat [B,N,128])``.  The locked dropout in front of the first LSTM
         layer is drawn here, by the same torch call, and applied inside ``token_embed``."""
         I = self.word_emb.embedding_dim + self.entity_embed.embedding_dim + self.ner_emb.embedding_dim
         scale = self.rnn.dropout.factor(document.size(0), I, self.word_emb.weight.dtype, document.device)
         doc = token_embed(document, document_pos, document_ner, self.word_emb.weight, self.entity_embed.weight, self.ner_emb.weight,
                           scale, self.entity_embed.padding_idx, self.ner_emb.padding_idx)
-        h = self.rnn(doc, doc.size(1), input_dropped=True)
+        h = self.rnn(doc, doc.size(1) if t_valid is None else t_valid, input_dropped=True)
         return token_context(h, self.linear_re.weight, self.linear_re.bias, node_pos)
 
     def forward(self, document, document_ner, document_pos, adj_matrix, sen_matrix, pos_matrix_h, pos_matrix_t, node_pos, node_type,
-                node_relative_pos, n_valid: Optional[Tensor] = None, **caps):
+                node_relative_pos, n_valid: Optional[Tensor] = None, t_valid: Optional[Tensor] = None, **caps):
+        """``t_valid``: the token count of every document of a batch, ``[B]`` (``data.collate`` returns it).  With it the BiLSTM
+        runs each document at its own length, which is what the one-document call computes; without it every document runs all
+        ``T`` padded steps."""
         batched = document.dim() == 2
         if not batched:
             document, document_ner, document_pos = (t.unsqueeze(0) for t in (document, document_ner, document_pos))
         node_feat = None
         if self.frontend_impl == "hip":
-            ctx, node_feat = self._encode_pooled(document, document_ner, document_pos, node_pos if batched else node_pos.unsqueeze(0))
+            ctx, node_feat = self._encode_pooled(document, document_ner, document_pos, node_pos if batched else node_pos.unsqueeze(0),
+                                                 t_valid)
             node_feat = node_feat if batched else node_feat[0]
         else:
-            ctx = self.encode(document, document_ner, document_pos)
+            ctx = self.encode(document, document_ner, document_pos, t_valid)
         return self._graph_forward(ctx, adj_matrix, sen_matrix, pos_matrix_h, pos_matrix_t, node_pos, node_type, node_relative_pos,
                                    n_valid, batched, node_feat=node_feat, **caps)
 
@@ -221,11 +237,17 @@ class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
         self.dis_embed = nn.Embedding(config.dis_num, config.dis_size)
 
     def forward(self, document, document_ner, document_pos, adj_matrix, sen_matrix, pos_matrix_h, pos_matrix_t, node_pos, node_type,
-                node_relative_pos, n_valid: Optional[Tensor] = None, **caps):
+                node_relative_pos, n_valid: Optional[Tensor] = None, t_valid: Optional[Tensor] = None, **caps):
+        """``t_valid``: the token count of every document of a batch, ``[B]``; the encoder is then called with
+        ``attention_mask = arange(T) < t_valid[:, None]``, so that real tokens do not attend to padding."""
         batched = document.dim() == 2
         if not batched:
             document, document_ner, document_pos = (t.unsqueeze(0) for t in (document, document_ner, document_pos))
-        doc, _ = self.bert(document, output_all_encoded_layers=False)                        # bert:275
+        if t_valid is None:
+            doc, _ = self.bert(document, output_all_encoded_layers=False)                    # bert:275
+        else:
+            mask = torch.arange(document.size(1), device=document.device) < t_valid.to(document.device)[:, None]
+            doc, _ = self.bert(document, attention_mask=mask, output_all_encoded_layers=False)
         cls_feat = doc[:, 0, :]                                                              # bert:277
         doc = torch.cat([doc, self.entity_embed(document_pos), self.ner_emb(document_ner)], dim=-1)
         node_feat = None

@@ -523,13 +523,27 @@ int gcgcn_adam_step_dev(int n_tensors, const void* table, int64_t total_blocks, 
  * gcgcn_lstm_bwd: dout [B][T][nd * H] (must not alias out) -> dgates [B * T][nd * 4H] (scratch the caller owns), dx [B][T][I],
  * dw_ih / dw_hh / db stacked like the parameters (db is the gradient of b_ih and of b_hh), dh0 / dc0 [nd][B][H] PER BATCH ROW
  * (a broadcast initial state sums them over B).  ws: 16-byte aligned, gcgcn_lstm_ws_bytes(B, T, I, H, nd) bytes (-1: refused).
- * No workgroup waits for another and nothing is added atomically: results are bit-reproducible.  Capturable. */
+ * No workgroup waits for another and nothing is added atomically: results are bit-reproducible.  Capturable.
+ * gcgcn_lstm_fwd_len / gcgcn_lstm_bwd_len: the same calls with per-row lengths, lens = device int32 [B] or NULL (NULL: every row
+ * has length T; gcgcn_lstm_fwd / gcgcn_lstm_bwd are these with NULL).  The semantics are those of a packed sequence padded back to
+ * T: row b is active at time t iff t < lens[b]; an inactive step leaves the row's h and c as they are; the reverse direction of row
+ * b takes its first step at t = lens[b] - 1 from h0 / c0.  The kernels clamp every length into [0, T] (callers check the range;
+ * a bad value cannot address out of bounds).  Written: EVERY element of out (exactly 0 at t >= lens[b]) and, in the backward, of
+ * dgates (0 there, hence dx exactly 0 there), dx, the parameter gradients, dh0, dc0; no memset is needed.  gates and csave are NOT
+ * written at inactive steps, and the backward lets neither them nor dout at those positions reach any result (NaN included).
+ * x must be finite at padded positions (it is multiplied by the zero dgates).  Both calls of a pair take the same lens. */
 int64_t gcgcn_lstm_ws_bytes(int B, int T, int I, int H, int nd);
 int gcgcn_lstm_fwd(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* bias,
                    const float* h0, const float* c0, float* out, float* gates, float* csave, void* stream);
 int gcgcn_lstm_bwd(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* h0,
                    const float* c0, const float* out, const float* gates, const float* csave, const float* dout, float* dgates,
                    float* dx, float* dw_ih, float* dw_hh, float* db, float* dh0, float* dc0, void* ws, int64_t ws_bytes, void* stream);
+int gcgcn_lstm_fwd_len(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* bias,
+                       const float* h0, const float* c0, float* out, float* gates, float* csave, const int* lens, void* stream);
+int gcgcn_lstm_bwd_len(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* h0,
+                       const float* c0, const float* out, const float* gates, const float* csave, const float* dout, float* dgates,
+                       float* dx, float* dw_ih, float* dw_hh, float* db, float* dh0, float* dc0, void* ws, int64_t ws_bytes,
+                       const int* lens, void* stream);
 
 /* ---- the token front end, either side of the BiLSTM (glove:282-298, bert:275-290) -------------------------------------------
  * Embeddings.  x [B][T][I], I = Dw + Dc + Dn, = word_emb[document] | entity_embed[document_pos] | ner_emb[document_ner] in that

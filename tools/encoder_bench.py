@@ -2,6 +2,12 @@
 same parameters, same input, same session.
 
     python tools/encoder_bench.py [--B 32 --T 512 --I 140 --reps 30 --warmup 5] [--out profiles/encoder_bench.json]
+    python tools/encoder_bench.py --lengths [--lib-old build/ab_old.so] --out profiles/encoder_bench_lengths.json
+
+--lengths: per-document lengths (a fixed-seed draw, uniform in [T/4, T], the first document at T as in a collated batch; kept on the
+device, written into the JSON) go to both implementations, and impl="hip" without them is timed in the same interleaved loop as
+"hip, lengths=None".  --lib-old: the library of another revision (tools/ab_build.sh) is loaded next to this tree's and the two are
+timed through the C ABI (gcgcn_lstm_fwd + gcgcn_lstm_bwd, no lengths, the same buffers), interleaved rep by rep: "abi" in the JSON.
 
 Timing: HIP events around each step on the current stream, warm-up steps first, the two sides INTERLEAVED rep by rep (so that a
 drift of the clocks hits both), median and min / max over the repetitions.  The hip side is additionally captured into a hipGraph
@@ -29,6 +35,48 @@ def stats(ms):
     return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4), "reps": len(ms)}
 
 
+def ab_abi(a, _lib, enc, x, dy, event_ms):
+    """gcgcn_lstm_fwd + gcgcn_lstm_bwd of this tree's library and of a.lib_old on the same buffers, interleaved rep by rep."""
+    from gcgcn_amd import functional as F_
+    H, nd, B, T, I = 128, 2, a.B, a.T, a.I
+    r = enc.rnns[0]
+    w_ih, w_hh = torch.cat([r.weight_ih_l0, r.weight_ih_l0_reverse]).detach(), torch.cat([r.weight_hh_l0, r.weight_hh_l0_reverse]).detach()
+    bias = torch.cat([r.bias_ih_l0 + r.bias_hh_l0, r.bias_ih_l0_reverse + r.bias_hh_l0_reverse]).detach()
+    h0, c0 = (p.detach().expand(nd, B, H).contiguous() for p in (enc.init_hidden[0], enc.init_c[0]))
+    xd = x.detach()
+    e = lambda *s: torch.empty(*s, device=x.device)
+    out, csave, gates, dgates = e(B, T, nd * H), e(B, T, nd * H), e(B * T, nd * 4 * H), e(B * T, nd * 4 * H)
+    dx, dw_ih, dw_hh, db, dh0, dc0 = e(B, T, I), e(nd * 4 * H, I), e(nd * 4 * H, H), e(nd * 4 * H), e(nd, B, H), e(nd, B, H)
+    ws = e(_lib.lib().gcgcn_lstm_ws_bytes(B, T, I, H, nd) // 4 + 4)
+    p, st = F_._p, F_._stream
+    libs = {"this tree": _lib.lib(), "old": ctypes.CDLL(os.path.abspath(a.lib_old))}
+    for name in ("gcgcn_lstm_fwd", "gcgcn_lstm_bwd"):
+        fn = getattr(libs["old"], name)
+        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
+
+    def step(h):
+        rc = h.gcgcn_lstm_fwd(B, T, I, H, nd, p(xd), p(w_ih), p(w_hh), p(bias), p(h0), p(c0), p(out), p(gates), p(csave), st())
+        rc |= h.gcgcn_lstm_bwd(B, T, I, H, nd, p(xd), p(w_ih), p(w_hh), p(h0), p(c0), p(out), p(gates), p(csave), p(dy), p(dgates), p(dx),
+                               p(dw_ih), p(dw_hh), p(db), p(dh0), p(dc0), p(ws), ws.numel() * 4, st())
+        assert rc == 0, h.gcgcn_last_error()
+
+    got = {}
+    for k, h in libs.items():
+        for _ in range(a.warmup):
+            step(h)
+        torch.cuda.synchronize()
+        got[k] = (out.clone(), dx.clone(), dw_hh.clone())
+    same = all(torch.equal(u, v) for u, v in zip(got["this tree"], got["old"]))
+    ev = {k: [] for k in libs}
+    for _ in range(a.reps):
+        for k, h in libs.items():
+            ev[k].append(event_ms(lambda: step(h)))
+    torch.cuda.synchronize()
+    res = {k: stats([e0.elapsed_time(e1) for e0, e1 in v]) for k, v in ev.items()}
+    res["out, dx, dw_hh bitwise equal"] = same
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=32)
@@ -36,6 +84,8 @@ def main():
     ap.add_argument("--I", type=int, default=140)
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--lengths", action="store_true", help="hand per-document lengths (fixed seed) to the encoders")
+    ap.add_argument("--lib-old", default=None, help="another revision's library: gcgcn_lstm_fwd + _bwd of both, interleaved")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "encoder_bench.json"), help="the JSON is also written there")
     a = ap.parse_args()
     from gcgcn_amd import _lib
@@ -50,13 +100,18 @@ def main():
     enc["hip"].load_state_dict(enc["torch"].state_dict(), strict=True)
     x = torch.randn(a.B, a.T, a.I, device=dev, requires_grad=True)
     dy = torch.randn(a.B, a.T, 2 * H, device=dev)
+    lens = None
+    if a.lengths:
+        lens = torch.randint(max(1, a.T // 4), a.T + 1, (a.B,), generator=torch.Generator().manual_seed(11))
+        lens[0] = a.T
+        lens = lens.to(device=dev, dtype=torch.int32)
 
-    def step(name):
+    def step(name, lengths="as asked"):
         m = enc[name]
         for p in m.parameters():
             p.grad = None
         x.grad = None
-        m(x).backward(dy)
+        m(x, lens if lengths == "as asked" else lengths).backward(dy)
 
     def event_ms(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -88,12 +143,19 @@ def main():
         graph.replay()
 
     ev = {"torch": [], "hip": [], "hip, hipGraph replay": []}
+    if a.lengths:
+        ev["hip, lengths=None"] = []
+        for _ in range(a.warmup):
+            step("hip", None)
     for _ in range(a.reps):
         ev["torch"].append(event_ms(lambda: step("torch")))
         ev["hip"].append(event_ms(lambda: step("hip")))
         ev["hip, hipGraph replay"].append(event_ms(graph.replay))
+        if a.lengths:
+            ev["hip, lengths=None"].append(event_ms(lambda: step("hip", None)))
     torch.cuda.synchronize()
     res = {k: stats([e0.elapsed_time(e1) for e0, e1 in v]) for k, v in ev.items()}
+    abi = ab_abi(a, _lib, enc["hip"], x, dy, event_ms) if a.lib_old else None
 
     kernels = {}
     for tag in ("lstm_fwd", "lstm_bwd", "lstm_hprev", "lstm_gemm", "gemm_group", "gemm_splitk_reduce"):
@@ -113,6 +175,10 @@ def main():
             "model": {"us_per_time_step": 3.4, "ms_per_recurrence_launch": round(3.4e-3 * a.T, 3),
                       "note": "1024 v_mfma_f32_16x16x4_f32 per step on one compute unit, 32 cycles per SIMD, 2.4 GHz"},
             "max_abs_dx_difference_hip_vs_torch": diff}
+    if a.lengths:
+        line["lengths"] = lens.tolist()
+    if abi:
+        line["abi (gcgcn_lstm_fwd + gcgcn_lstm_bwd, lengths=None, this tree against --lib-old, interleaved)"] = abi
     print(json.dumps(line))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
