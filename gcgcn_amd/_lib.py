@@ -89,6 +89,8 @@ SIGNATURES = {
     "gcgcn_producer_sizes": (I, [I, I, I, I, I, I, I, L, L, P]),
     "gcgcn_producer_fwd": (I, [I, I, I, I, I, I, I, P, P, P, P, I, P, P, P, P, L, L, P, P, P, L, P, P]),
     "gcgcn_producer_bwd": (I, [I, I, I, I, I, I, I, P, P, P, P, I, P, P, P, P, L, L, P, P, P, P, P, P, P, P, P, P]),
+    "gcgcn_producer_det_elems": (I, [I, I, I, L, P]),
+    "gcgcn_producer_bwd_det": (I, [I, I, I, I, I, I, I, P, P, P, P, I, P, P, P, P, L, L, P, P, P, P, P, P, P, P, P, P, L, P]),
     "gcgcn_edge_mean_fwd_compact": (I, [I, I, I, P, P, P, P, P, P]),
     "gcgcn_edge_mean_bwd_compact": (I, [I, I, I, P, P, P, P, P, P, P]),
     "gcgcn_gat_fwd_compact": (I, [I, I, I, I, P, P, P, P, P, P, P, F, P, P, P, P, P, P, P, I, I, P]),

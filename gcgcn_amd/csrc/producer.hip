@@ -17,8 +17,10 @@
 //
 // Per-slot / per-pair arithmetic runs in wave-per-row kernels (lanes over the Hd feature columns, token states read
 // from L2).  Backward sums shared by many slots are owner-computed where the owner is cheap to find (token-state and
-// score-table gradients: one workgroup per (document, token) scans the document's live rows); the per-entity node-term
-// gradient and a few parameter-sized partials still use fp32 atomics (reproducible up to summation order).
+// score-table gradients: one workgroup per (document, token) scans the document's live rows).  On the default entry the
+// per-entity node-term gradient and the sentence attention's vector / bias gradient are scatter-added with fp32 atomics
+// (reproducible up to summation order); the opt-in deterministic entry (gcgcn_producer_bwd_det) owner-computes those two as
+// well -- prod_sent_bwd_det / prod_nterm_owner / prod_dwb_fin, no float atomics -- and is bit-reproducible.
 #include <string.h>
 
 #include "gemm.hpp"
@@ -544,6 +546,180 @@ __global__ __launch_bounds__(64 * PW) void prod_sent_bwd_kernel(const float* __r
   }
 }
 
+// ---- the same backward without atomics (opt-in, gcgcn_producer_bwd_det): three launches, every sum in a fixed order -------------
+// Stage 1, prod_sent_bwd_det_kernel: the per-pair / per-row arithmetic of prod_sent_bwd_kernel, statement for statement.  The wave
+// that owns compact pair prow STORES its two node-term rows, dnpair[prow][0] = dnh (for entity j), dnpair[prow][1] = dnt (for entity
+// i); each wave keeps its d w | d c in its own LDS row and the workgroup stores their sum (waves ascending) as ITS row of dwpart --
+// every workgroup writes its row, zeros where it owned no pair.  dynamic LDS: PW * (Hd + 1) floats.
+template <int HC>
+__global__ __launch_bounds__(64 * PW) void prod_sent_bwd_det_kernel(const float* __restrict__ sfeat, const float* __restrict__ cwa,
+                                                                    const float* __restrict__ nterm, const float* __restrict__ wsa,
+                                                                    const float* __restrict__ score, const float* __restrict__ dCS,
+                                                                    ProdIdx ix, float* __restrict__ dcwa, float* __restrict__ dsfeat,
+                                                                    float* __restrict__ dnpair, float* __restrict__ dwpart, int N, int Hd) {
+  extern __shared__ float sacc[];  // [PW][Hd + 1]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int npairs = ix.counts[1], nrows = ix.counts[0];
+  const long NN = (long)N * N;
+  float w[HC], dw[HC];
+#pragma unroll
+  for (int cc = 0; cc < HC; ++cc) w[cc] = (lane + 64 * cc) < Hd ? wsa[lane + 64 * cc] : 0.f, dw[cc] = 0.f;
+  float dbias = 0.f;
+  for (int prow = blockIdx.x * PW + wave; prow < npairs; prow += gridDim.x * PW) {
+    const long pair = ix.prow_pair[prow];
+    const long b = pair / NN;
+    const int ij = (int)(pair - b * NN), i = ij / N, j = ij - i * N;
+    const int row0 = ix.pair_row0[pair], n = __popc(ix.pair_bits[pair]);
+    const float div = ix.pair_div[pair];
+    const long oj = (b * N + j) * Hd, oi = (b * N + i) * Hd;
+    float nh[HC], nt[HC], gh[HC], gt[HC], dnh[HC], dnt[HC];
+#pragma unroll
+    for (int cc = 0; cc < HC; ++cc) {
+      const int c = lane + 64 * cc;
+      nh[cc] = c < Hd ? nterm[oj + c] : 0.f, nt[cc] = c < Hd ? nterm[oi + c] : 0.f;
+      gh[cc] = c < Hd ? dCS[(long)prow * 2 * Hd + c] / div : 0.f;
+      gt[cc] = c < Hd ? dCS[(long)prow * 2 * Hd + Hd + c] / div : 0.f;
+      dnh[cc] = 0.f, dnt[cc] = 0.f;
+    }
+    for (int k = 0; k < n; ++k) {
+      const long row = row0 + k;
+      const float sh = score[2 * row], st = score[2 * row + 1];
+      const float ah = fmaxf(sh, 0.f), at = fmaxf(st, 0.f);
+      float cw[HC], zh[HC], zt[HC], ph = 0.f, pt = 0.f;
+#pragma unroll
+      for (int cc = 0; cc < HC; ++cc) {
+        const int c = lane + 64 * cc;
+        cw[cc] = 0.f, zh[cc] = 0.f, zt[cc] = 0.f;
+        if (c < Hd) {
+          const float sf = sfeat[row * Hd + c];
+          cw[cc] = cwa[row * Hd + c];
+          zh[cc] = tanhf(sf + nh[cc]), zt[cc] = tanhf(sf + nt[cc]);
+          ph = fmaf(gh[cc], cw[cc], ph), pt = fmaf(gt[cc], cw[cc], pt);
+        }
+      }
+      const float dsh = sh > 0.f ? wave_sum(ph) : 0.f, dst = st > 0.f ? wave_sum(pt) : 0.f;
+      dbias += dsh + dst;
+#pragma unroll
+      for (int cc = 0; cc < HC; ++cc) {
+        const int c = lane + 64 * cc;
+        if (c < Hd) {
+          const float dzh = dsh * w[cc] * (1.f - zh[cc] * zh[cc]), dzt = dst * w[cc] * (1.f - zt[cc] * zt[cc]);
+          dcwa[row * Hd + c] = ah * gh[cc] + at * gt[cc];
+          dsfeat[row * Hd + c] = dzh + dzt;
+          dnh[cc] += dzh, dnt[cc] += dzt;
+          dw[cc] = fmaf(dsh, zh[cc], fmaf(dst, zt[cc], dw[cc]));
+        }
+      }
+    }
+#pragma unroll
+    for (int cc = 0; cc < HC; ++cc) {
+      const int c = lane + 64 * cc;
+      if (c < Hd) dnpair[(long)prow * 2 * Hd + c] = dnh[cc], dnpair[(long)prow * 2 * Hd + Hd + c] = dnt[cc];
+    }
+  }
+  float* mine = sacc + wave * (Hd + 1);
+#pragma unroll
+  for (int cc = 0; cc < HC; ++cc)
+    if ((lane + 64 * cc) < Hd) mine[lane + 64 * cc] = dw[cc];
+  if (lane == 0) mine[Hd] = dbias;   // every lane holds the same dbias
+  __syncthreads();
+  for (int c = threadIdx.x; c <= Hd; c += 64 * PW) {
+    float v = 0.f;
+#pragma unroll
+    for (int q = 0; q < PW; ++q) v += sacc[q * (Hd + 1) + c];
+    dwpart[(long)blockIdx.x * (Hd + 1) + c] = v;
+  }
+  if (blockIdx.x == 0) {
+    const int hi = (nrows + 63) & ~63;
+    for (long e = (long)nrows * Hd + threadIdx.x; e < (long)hi * Hd; e += 64 * PW) dcwa[e] = 0.f, dsfeat[e] = 0.f;
+  }
+}
+
+// Stage 2, prod_nterm_owner_kernel: one wave per entity (b, n), the OWNER of dnterm[b, n, :].  It walks i = 0 .. N-1 ascending and
+// adds, for each i, first the head-side row of pair (i, n) (that pair's column entity is n), then the tail-side row of pair (n, i)
+// (its row entity is n) -- at i = n both rows of the one pair (n, n).  The order is a function of the pair index alone: not of the
+// grid, not of the prow numbering.  The live rows of 64 entities at a time are listed in LDS (wave prefix over two ballots), so that
+// eight row loads are in flight and every load address is a row stage 1 wrote.  dnterm is WRITTEN (zeros for entities without a
+// live pair, padding entities, and everywhere when the index is over capacity: counts[1] == 0 then).  LDS: PW * 128 ints.
+template <int HC>
+__global__ __launch_bounds__(64 * PW) void prod_nterm_owner_kernel(const float* __restrict__ dnpair, const int* __restrict__ pair_prow,
+                                                                   const int* __restrict__ counts, float* __restrict__ dnterm,
+                                                                   long BN, int N, int Hd) {
+  __shared__ int items[PW][128];   // dnpair row ids (2 prow + side) of the chunk's live terms, in summation order
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long bn = (long)blockIdx.x * PW + wave;
+  if (bn >= BN) return;            // (no barrier below: each wave reads only its own list)
+  const long b = bn / N;
+  const int n = (int)(bn - b * N);
+  const int npairs = counts[1];
+  const int* pp = pair_prow + b * N * N;
+  float acc[HC];
+#pragma unroll
+  for (int cc = 0; cc < HC; ++cc) acc[cc] = 0.f;
+  for (int i0 = 0; i0 < N; i0 += 64) {
+    const int i = i0 + lane;
+    const int p1 = i < N ? pp[(long)i * N + n] : -1, p2 = i < N ? pp[(long)n * N + i] : -1;
+    const bool l1 = p1 >= 0 && p1 < npairs, l2 = p2 >= 0 && p2 < npairs;
+    const unsigned long long m1 = __ballot(l1), m2 = __ballot(l2), below = (1ull << lane) - 1;
+    const int at = __popcll(m1 & below) + __popcll(m2 & below), cnt = __popcll(m1) + __popcll(m2);
+    if (l1) items[wave][at] = 2 * p1;
+    if (l2) items[wave][at + (l1 ? 1 : 0)] = 2 * p2 + 1;
+    __builtin_amdgcn_wave_barrier();
+    for (int k = 0; k < cnt; k += 8) {
+      float x[8][HC];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const long r = items[wave][min(k + u, cnt - 1)];
+#pragma unroll
+        for (int cc = 0; cc < HC; ++cc) {
+          const int c = lane + 64 * cc;
+          x[u][cc] = c < Hd ? dnpair[r * Hd + c] : 0.f;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int cc = 0; cc < HC; ++cc) acc[cc] += (k + u < cnt) ? x[u][cc] : 0.f;
+    }
+    __builtin_amdgcn_wave_barrier();   // before the next chunk overwrites the list
+  }
+#pragma unroll
+  for (int cc = 0; cc < HC; ++cc)
+    if ((lane + 64 * cc) < Hd) dnterm[bn * Hd + lane + 64 * cc] = acc[cc];
+}
+
+// Stage 3, prod_dwb_fin_kernel: d w | d c = the sum of the dwpart rows that can be non-empty -- the first min(PGRID, ceil(pairs / PW))
+// workgroups of stage 1, from the device-side count.  16 columns x 16 row slices per workgroup: slice q adds rows q, q + 16, ...
+// ascending (eight requests in flight), then the slices are added in ascending order.  The order is a function of the row count
+// alone.  Hd + 1 floats are WRITTEN.
+constexpr int DWC = 16;
+__global__ __launch_bounds__(256) void prod_dwb_fin_kernel(const float* __restrict__ dwpart, const int* __restrict__ counts, int nparts,
+                                                           int C, float* __restrict__ out) {
+  __shared__ float red[DWC][DWC];
+  const int cl = threadIdx.x & (DWC - 1), q = threadIdx.x / DWC;
+  const int c = blockIdx.x * DWC + cl;
+  const int live = min(nparts, (counts[1] + PW - 1) / PW);
+  float v = 0.f;
+  if (c < C && q < live) {
+    const int last = q + ((live - 1 - q) / DWC) * DWC;
+    for (int r = q; r < live; r += 8 * DWC) {
+      float x[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) x[u] = dwpart[(long)min(r + DWC * u, last) * C + c];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v += (r + DWC * u < live) ? x[u] : 0.f;
+    }
+  }
+  red[q][cl] = v;
+  __syncthreads();
+  if (q == 0 && c < C) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < DWC; ++k) s += red[k][cl];
+    out[c] = s;
+  }
+}
+
 // ---- backward of the word attention, two passes, no atomics -------------------------------------------------------------
 //   dcw = dCW[row, side]:  g[t] = dcw . ctx[t];  dscore[t] = att[t] (g[t] - sum_t att g)
 //   dtable[b, pos[t], t] += dscore,  dctx[b, t, :] += att[t] dcw     -- sums over MANY (row, side) per (document, token)
@@ -906,6 +1082,11 @@ ProdLayout prod_layout(int Hd, int P) {
 
 static long up64(long v) { return (v + 63) & ~63L; }
 
+// The deterministic backward's extra workspace (gcgcn_producer_bwd_det): dnpair[up64(cap_pairs)][2][Hd] | dwpart[PGRID][Hd + 1],
+// each piece rounded to 16 bytes.
+static long prod_det_dnpair_elems(int Hd, long cap_pairs) { return (up64(cap_pairs) * 2 * Hd + 3) & ~3L; }
+static long prod_det_elems(int Hd, long cap_pairs) { return prod_det_dnpair_elems(Hd, cap_pairs) + (((long)PGRID * (Hd + 1) + 3) & ~3L); }
+
 int prod_index(const unsigned char* sen, const int* n_valid, ProdIdx ix, int B, int N, int S, int T, long cap_rows, long cap_pairs,
                hipStream_t st) {
   GC_REQUIRE(S >= 1 && S <= 31, "producer: %d sentence slots per pair (1..31 supported)", S);
@@ -1034,20 +1215,21 @@ static int colsum_dyn(const float* X, const int* cnt, int C, float* part, float*
 int prod_bwd(int B, int N, int S, int T, int Hd, int P, int ND, const float* ctx, const unsigned char* sen, const void* pos_h,
              const void* pos_t, int pos_bytes, const float* node, const float* dis_table, const int* n_valid, const float* flat,
              ProdIdx ix, long cap_rows, long cap_pairs, ProdBufs w, const float* dE, ProdGrads g, float* dctx, float* dnode,
-             float* ddis_table, float* dflat, float* ws, long wse, hipStream_t st, const float* dEc_in = nullptr) {
+             float* ddis_table, float* dflat, float* ws, long wse, hipStream_t st, const float* dEc_in = nullptr, bool det = false,
+             float* detbuf = nullptr) {
   const ProdLayout y = prod_layout(Hd, P);
   const long BT = (long)B * T, BN = (long)B * N, BNN = BN * N;
   const int* nrows = ix.counts;
   const int* npairs = ix.counts + 1;
   GC_REQUIRE(sizeof(float) * PW * ((size_t)ND * Hd + Hd + 1) <= 150 * 1024, "producer_bwd: hidden width %d exceeds the LDS budget of the table backward", Hd);
-  // zero the atomics' targets
-  GC_REQUIRE(hipMemsetAsync(g.dnterm, 0, sizeof(float) * BN * Hd, st) == hipSuccess, "producer: memset failed");
+  // zero the atomics' targets (det: dnterm and dws are written by their owners, prod_nterm_owner / prod_dwb_fin -- no memset)
+  if (!det) GC_REQUIRE(hipMemsetAsync(g.dnterm, 0, sizeof(float) * BN * Hd, st) == hipSuccess, "producer: memset failed");
   // the two attention vectors' gradients (d w | d b, Hd + 1 floats each) are accumulated / written straight into dflat where the
   // layout keeps each pair adjacent (Hd a multiple of 4: always, for the reference's 128); through g.dwb + four copies otherwise
   const bool adj = y.ba == y.wa + Hd && y.bsa == y.wsa + Hd;
   float* const dws = adj ? dflat + y.wsa : g.dwb;             // sentence attention: accumulated by prod_sent_bwd (zeroed here)
   float* const dww = adj ? dflat + y.wa : g.dwb + Hd + 1;     // word attention: written by prod_table_fin
-  GC_REQUIRE(hipMemsetAsync(dws, 0, sizeof(float) * (Hd + 1), st) == hipSuccess, "producer: memset failed");
+  if (!det) GC_REQUIRE(hipMemsetAsync(dws, 0, sizeof(float) * (Hd + 1), st) == hipSuccess, "producer: memset failed");
   // linear_sentence_att: E = CS W_ls^T + b_ls on live pairs, b_ls on every other real pair
   if (dE) {
     {
@@ -1064,11 +1246,31 @@ int prod_bwd(int B, int N, int S, int T, int Hd, int P, int ND, const float* ctx
     GC_TRY(colsum(dEc_in, nullptr, dflat + y.bls, up64(cap_pairs), Hd, Hd, 1, 0, 0, 0, 0, ws, st));
   }
   GC_TRY(linear_bwd_wx_dyn(g.dEc, w.CS, Hd, 2 * Hd, flat + y.Wls, dflat + y.Wls, g.dCS, 0, ws, wse, st, npairs, cap_pairs));
-  {
+  if (!det) {
     ProfScope ps("prod_sent", st);
     PROD_LAUNCH(prod_sent_bwd_kernel, Hd, dim3(PGRID), dim3(64 * PW), sizeof(float) * (Hd + 1), st, w.sfeat, w.cwa, w.nterm,
                        flat + y.wsa, w.score, g.dCS, ix, g.dcwa, g.dsfeat, g.dnterm, dws, N, Hd);
     GC_TRY(check_launch("prod_sent_bwd"));
+  } else {  // owner-computes: per-pair rows and per-workgroup partials, then the two owners (kernels above)
+    float* const dnpair = detbuf;
+    float* const dwpart = detbuf + prod_det_dnpair_elems(Hd, cap_pairs);
+    {
+      ProfScope ps("prod_det_sent", st);
+      PROD_LAUNCH(prod_sent_bwd_det_kernel, Hd, dim3(PGRID), dim3(64 * PW), sizeof(float) * PW * (Hd + 1), st, w.sfeat, w.cwa, w.nterm,
+                  flat + y.wsa, w.score, g.dCS, ix, g.dcwa, g.dsfeat, dnpair, dwpart, N, Hd);
+      GC_TRY(check_launch("prod_sent_bwd_det"));
+    }
+    {
+      ProfScope ps("prod_det_nterm", st);
+      PROD_LAUNCH(prod_nterm_owner_kernel, Hd, dim3(cdiv(BN, PW)), dim3(64 * PW), 0, st, dnpair, ix.pair_prow, ix.counts, g.dnterm, BN, N,
+                  Hd);
+      GC_TRY(check_launch("prod_nterm_owner"));
+    }
+    {
+      ProfScope ps("prod_det_dwb", st);
+      hipLaunchKernelGGL(prod_dwb_fin_kernel, dim3(cdiv(Hd + 1, DWC)), dim3(256), 0, st, dwpart, ix.counts, PGRID, Hd + 1, dws);
+      GC_TRY(check_launch("prod_dwb_fin"));
+    }
   }
   if (!adj)
     GC_REQUIRE(hipMemcpyAsync(dflat + y.wsa, g.dwb, sizeof(float) * Hd, hipMemcpyDeviceToDevice, st) == hipSuccess &&
@@ -1267,6 +1469,38 @@ int gcgcn_producer_bwd(int B, int N, int S, int T, int Hd, int P, int ND, const 
   if (n_valid && dE) GC_TRY(prod_wpair(n_valid, o.g.wpair, B, N, st));
   return prod_bwd(B, N, S, T, Hd, P, ND, ctx, sen, pos_h, pos_t, pos_bytes, node, dis_table, n_valid, flat, o.ix, cap_rows, cap_pairs,
                   o.w, dE, o.g, dctx, dnode, ddis_table, dflat, o.scratch, prod_scratch_elems(B, N, T, Hd), st, dE ? nullptr : dEc);
+}
+
+int gcgcn_producer_det_elems(int B, int N, int Hd, int64_t cap_pairs, int64_t* out) {
+  GC_REQUIRE(B > 0 && N > 0, "producer_det_elems: bad shape");
+  GC_REQUIRE(Hd >= 1 && Hd <= 64 * HCLIM, "producer_det_elems: hidden width Hd=%d (1..%d supported)", Hd, 64 * HCLIM);
+  GC_REQUIRE(cap_pairs >= 0 && cap_pairs < (1L << 30), "producer_det_elems: bad capacity cap_pairs");
+  GC_REQUIRE(out, "producer_det_elems: null pointer out");
+  *out = prod_det_elems(Hd, cap_pairs);
+  return 0;
+}
+
+int gcgcn_producer_bwd_det(int B, int N, int S, int T, int Hd, int P, int ND, const float* ctx, const uint8_t* sen, const void* pos_h,
+                           const void* pos_t, int pos_bytes, const float* node, const float* dis_table, const int32_t* n_valid,
+                           const float* flat, int64_t cap_rows, int64_t cap_pairs, int32_t* ibuf, float* fbuf, float* bbuf,
+                           const float* dE, const float* dEc, float* dctx, float* dnode, float* ddis_table, float* dflat, float* detbuf,
+                           int64_t det_elems, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  GC_REQUIRE(B > 0 && N > 0 && T > 0 && Hd >= 1 && Hd <= 64 * HCLIM && P > 0 && ND > 0, "producer_bwd_det: bad shape");
+  GC_REQUIRE(ctx && sen && pos_h && pos_t && node && dis_table && flat && ibuf && fbuf && bbuf && (dE || dEc) && dctx && dnode &&
+                 ddis_table && dflat,
+             "producer_bwd_det: null pointer");
+  GC_REQUIRE(cap_rows >= 0 && cap_pairs >= 0 && cap_rows < (1L << 30) && cap_pairs < (1L << 30), "producer_bwd_det: bad capacities");
+  // refused before anything is launched
+  GC_REQUIRE(detbuf, "producer_bwd_det: detbuf is null");
+  GC_REQUIRE(((uintptr_t)detbuf & 15) == 0, "producer_bwd_det: detbuf is not 16-byte aligned");
+  GC_REQUIRE(det_elems >= prod_det_elems(Hd, cap_pairs), "producer_bwd_det: det_elems=%ld is smaller than gcgcn_producer_det_elems (%ld)",
+             (long)det_elems, prod_det_elems(Hd, cap_pairs));
+  const ProdBound o = prod_bind(ibuf, fbuf, bbuf, true, B, N, S, T, Hd, P, ND, cap_rows, cap_pairs);
+  if (n_valid && dE) GC_TRY(prod_wpair(n_valid, o.g.wpair, B, N, st));
+  return prod_bwd(B, N, S, T, Hd, P, ND, ctx, sen, pos_h, pos_t, pos_bytes, node, dis_table, n_valid, flat, o.ix, cap_rows, cap_pairs,
+                  o.w, dE, o.g, dctx, dnode, ddis_table, dflat, o.scratch, prod_scratch_elems(B, N, T, Hd), st, dE ? nullptr : dEc, true,
+                  detbuf);
 }
 
 }  // extern "C"

@@ -648,7 +648,7 @@ class ProducerFn(torch.autograd.Function):
     a live sentence slot) and the pair -> row index, for the consumers in csrc/compact.hip (CompactEdges)."""
 
     @staticmethod
-    def forward(ctx_, tok, node, dis_table, flat, sen, pos_h, pos_t, n_valid, cap_rows, cap_pairs, compact):
+    def forward(ctx_, tok, node, dis_table, flat, sen, pos_h, pos_t, n_valid, cap_rows, cap_pairs, compact, deterministic):
         B, T, Hd = tok.shape
         N, S = sen.shape[1], sen.shape[3]
         ND, P = dis_table.shape
@@ -665,6 +665,11 @@ class ProducerFn(torch.autograd.Function):
              _p(n_valid), _p(flat), cap_rows, cap_pairs, _p(ibuf), _p(fbuf), None, 0, _p(E), _stream())
         ctx_.save_for_backward(tok, node, dis_table, flat, sen, pos_h, pos_t, ibuf, fbuf)
         ctx_.n_valid, ctx_.caps, ctx_.nbwd, ctx_.compact = n_valid, (cap_rows, cap_pairs), int(sizes[2]), bool(compact)
+        ctx_.ndet = None                                    # deterministic backward: floats of its extra workspace
+        if deterministic:
+            ndet = ctypes.c_int64()
+            call("gcgcn_producer_det_elems", B, N, Hd, cap_pairs, ctypes.cast(ctypes.pointer(ndet), ctypes.c_void_p))
+            ctx_.ndet = int(ndet.value)
         counts = ibuf[int(sizes[3]):int(sizes[3]) + 4]      # {live rows, live pairs, over capacity, 0}, on the device
         if not compact:
             ctx_.mark_non_differentiable(counts)
@@ -686,10 +691,15 @@ class ProducerFn(torch.autograd.Function):
         bbuf = torch.empty(ctx_.nbwd, device=dev)
         dtok, dnode = torch.empty_like(tok), torch.empty_like(node)
         dtab, dflat = torch.empty_like(dis_table), torch.zeros_like(flat)       # (zeros: the layout's alignment gaps)
-        call("gcgcn_producer_bwd", B, N, S, T, Hd, P, ND, _p(tok), _p(sen), _p(pos_h), _p(pos_t), pos_h.element_size(), _p(node),
-             _p(dis_table), _p(ctx_.n_valid), _p(flat), ctx_.caps[0], ctx_.caps[1], _p(ibuf), _p(fbuf), _p(bbuf),
-             None if ctx_.compact else _p(dE), _p(dE) if ctx_.compact else None, _p(dtok), _p(dnode), _p(dtab), _p(dflat), _stream())
-        return dtok, dnode, dtab, dflat, None, None, None, None, None, None, None
+        args = (B, N, S, T, Hd, P, ND, _p(tok), _p(sen), _p(pos_h), _p(pos_t), pos_h.element_size(), _p(node),
+                _p(dis_table), _p(ctx_.n_valid), _p(flat), ctx_.caps[0], ctx_.caps[1], _p(ibuf), _p(fbuf), _p(bbuf),
+                None if ctx_.compact else _p(dE), _p(dE) if ctx_.compact else None, _p(dtok), _p(dnode), _p(dtab), _p(dflat))
+        if ctx_.ndet is None:
+            call("gcgcn_producer_bwd", *args, _stream())
+        else:                                      # owner-computes, no float atomics: bit-reproducible (csrc/producer.hip)
+            detbuf = torch.empty(ctx_.ndet, device=dev)
+            call("gcgcn_producer_bwd_det", *args, _p(detbuf), ctx_.ndet, _stream())
+        return dtok, dnode, dtab, dflat, None, None, None, None, None, None, None, None
 
 
 class CompactEdges:
@@ -879,7 +889,7 @@ class ProducerCapacityError(RuntimeError):
 
 
 def edge_features(tok, sen, pos_h, pos_t, node, dis_table, flat, n_valid=None, max_live_slots=None, max_live_pairs=None,
-                  check_capacity=False, return_counts=False, compact=False):
+                  check_capacity=False, return_counts=False, compact=False, deterministic=False):
     """E[B,N,N,Hd] of one hop from token states tok[B,T,Hd], sentence masks sen[B,N,N,S,T] (bool / uint8), distance ids
     pos_h / pos_t [B,N,N,S,T] (int64 as the reference passes them, or int32 / uint8), entity features node[B,N,Hd] and
     the distance-embedding table dis_table[ND,P].  Without ``max_live_*`` the live slots are counted first (one host
@@ -888,7 +898,9 @@ def edge_features(tok, sen, pos_h, pos_t, node, dis_table, flat, n_valid=None, m
     and write NaN into every real pair of E (so a captured graph fails loudly downstream); ``check_capacity=True`` reads the
     device-side flag back (one synchronisation) and raises :class:`ProducerCapacityError`; ``return_counts=True`` also returns
     the device tensor ``int32[4] = {live slots, live pairs, over capacity, 0}`` for a check of the caller's own timing.
-    ``compact=True``: returns ``(Ec[rows,Hd], prow[B,N,N])`` instead of E -- E is never written (see CompactEdges)."""
+    ``compact=True``: returns ``(Ec[rows,Hd], prow[B,N,N])`` instead of E -- E is never written (see CompactEdges).
+    ``deterministic=True``: the backward sums the per-entity node-term gradient and the sentence attention's vector / bias gradient
+    by their owners instead of with fp32 atomics (two more launches, one more workspace): every gradient is bit-reproducible."""
     tok, node, dis_table = _chk(tok, "context_output", 3), _chk(node, "node_feat", 3), _chk(dis_table, "dis_embed.weight", 2)
     B, T, Hd = tok.shape
     if sen.dim() != 5 or sen.shape[0] != B or sen.shape[4] != T or sen.shape[1] != sen.shape[2]:
@@ -917,7 +929,7 @@ def edge_features(tok, sen, pos_h, pos_t, node, dis_table, flat, n_valid=None, m
         max_live_slots = r if max_live_slots is None else max_live_slots
         max_live_pairs = q if max_live_pairs is None else max_live_pairs
     out = ProducerFn.apply(tok, node, dis_table, _chk(flat, "flat"), sen, pos_h.contiguous(), pos_t.contiguous(), nv,
-                           int(max_live_slots), int(max_live_pairs), bool(compact))
+                           int(max_live_slots), int(max_live_pairs), bool(compact), bool(deterministic))
     if compact:
         E, counts = (out[0], out[2]), out[1]          # (Ec, prow): the caller adds the bias and wraps them in CompactEdges
     else:

@@ -117,6 +117,7 @@ class _GraphRelationModel(GraphModelTail):
         self.frontend_impl = getattr(config, "frontend_impl", "torch")
         if self.frontend_impl not in ("torch", "hip"):
             raise ValueError(f"config.frontend_impl={self.frontend_impl!r} (\"torch\" or \"hip\")")
+        self.deterministic = bool(getattr(config, "deterministic", False))   # GraphModelTail.deterministic: bit-reproducible producers
         self.layerNum, self.headNum = layer_num, head_num
         self._register_state_dict_hook(self._reference_order_hook)
 

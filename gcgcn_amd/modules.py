@@ -446,7 +446,7 @@ class EdgeFeatureProducer(_FlatBlock):
     def forward(self, context_output: Tensor, sen_matrix: Tensor, pos_matrix_h: Tensor, pos_matrix_t: Tensor,
                 node_feat: Tensor, dis_embed_weight: Tensor, n_valid: Optional[Tensor] = None,
                 max_live_slots: Optional[int] = None, max_live_pairs: Optional[int] = None,
-                check_capacity: Optional[bool] = None, compact: bool = False):
+                check_capacity: Optional[bool] = None, compact: bool = False, deterministic: Optional[bool] = None):
         """context_output ``[T,H]`` / ``[1,T,H]`` (the reference's shapes, glove:292) or ``[B,T,H]``; sen_matrix / pos_matrix_*
         ``[N,N,S,T]`` or ``[B,N,N,S,T]``; node_feat ``[N,H]`` / ``[B,N,H]``; dis_embed_weight = ``model.dis_embed.weight``.
         Returns ``context_sent_att``: ``[N,N,H]`` or ``[B,N,N,H]``.
@@ -457,7 +457,9 @@ class EdgeFeatureProducer(_FlatBlock):
 
         ``compact=True``: returns a :class:`gcgcn_amd.functional.CompactEdges` handle instead of the tensor -- the rows of the
         pairs with a live sentence slot, the pair index and the bias every other pair equals; the graph blocks take it wherever
-        they take ``edge_feat`` and the ``[N,N,hidden]`` tensor (and its gradient) is never written."""
+        they take ``edge_feat`` and the ``[N,N,hidden]`` tensor (and its gradient) is never written.
+
+        ``deterministic`` (default: ``self.deterministic``, off): the bit-reproducible backward, see the class attribute."""
         batched = sen_matrix.dim() == 5
         tok = context_output
         if tok.dim() == 2:
@@ -468,7 +470,8 @@ class EdgeFeatureProducer(_FlatBlock):
         chk = self.check_capacity if check_capacity is None else check_capacity
         e, self.last_counts = F_.edge_features(tok, sen_matrix, pos_matrix_h, pos_matrix_t, node_feat, dis_embed_weight, self.flat,
                                                n_valid, max_live_slots, max_live_pairs, check_capacity=chk, return_counts=True,
-                                               compact=compact)
+                                               compact=compact,
+                                               deterministic=self.deterministic if deterministic is None else deterministic)
         if compact:
             o = P_.producer_layout(self.hidden, self.dis_size)[15]          # linear_sentence_att.bias inside flat
             nv = None if n_valid is None else n_valid.to(device=tok.device, dtype=torch.int32)
@@ -477,6 +480,9 @@ class EdgeFeatureProducer(_FlatBlock):
 
     check_capacity = False      # read the over-capacity flag back after every call with caller-given capacities (one sync)
     last_counts = None          # device int32[4] of the last call: {live slots, live pairs, over capacity, 0}
+    # Opt-in: the backward sums the node-term and the sentence-attention vector / bias gradients by their owners instead of with fp32
+    # atomics -- every gradient bit-reproducible, two more small launches per backward.  Same values up to rounding.
+    deterministic = False
 
 
 # ======================================================================================================
@@ -695,6 +701,9 @@ class GraphModelTail(nn.Module):
     # per hop; same logits and gradients (tests/test_tail_gpu.py), no E / dE tensors.  Default: the dense tensor, the reference's
     # own call pattern.
     compact_edges = False
+    # Opt-in: every edge-feature producer runs its bit-reproducible backward (EdgeFeatureProducer.deterministic) -- with it the whole
+    # tail, dropout included (counter-based, gcgcn_amd.manual_seed), repeats to the last bit.  Default: the producers' own setting.
+    deterministic = False
 
     def forward(self, context_output: Tensor, node_feat: Tensor, adj_matrix: Optional[Tensor], sen_matrix: Tensor,
                 pos_matrix_h: Tensor, pos_matrix_t: Tensor, node_type: Tensor, node_relative_pos: Tensor,
@@ -715,7 +724,8 @@ class GraphModelTail(nn.Module):
             for i in range(hops):
                 e = self.producers[i](context_output, sen_matrix, pos_matrix_h, pos_matrix_t, x, dis_embed_weight, n_valid=n_valid,
                                       max_live_slots=max_live_slots, max_live_pairs=max_live_pairs,
-                                      compact=self.compact_edges and not self.get_weighted_adj_matrix.apply_mask)
+                                      compact=self.compact_edges and not self.get_weighted_adj_matrix.apply_mask,
+                                      deterministic=True if self.deterministic else None)
                 if i < 1:
                     if self.get_weighted_adj_matrix.apply_mask and adj_matrix is not None:
                         mask = torch.eq(adj_matrix, 0)                                          # glove:330

@@ -308,9 +308,11 @@ int gcgcn_eval_curve(const uint64_t* ranked, int64_t m, int64_t n_records, const
  * beyond a capacity is NOT computed: ibuf[sizes[3] + 2] becomes 1 and every real pair of E is written as NaN, so an
  * undersized capacity is loud even inside a captured hipGraph).  Buffers (caller-owned): ibuf int32[sizes[0]], fbuf
  * float[sizes[1]] (written by forward, read by backward), bbuf float[sizes[2]] (backward workspace) from
- * gcgcn_producer_sizes.  Two small sums of the backward -- the gradient of the per-entity node terms and of the sentence
- * attention's vector / bias -- are scatter-added with fp32 atomics (reproducible up to summation order); every other sum
- * (ctx, the score table, the weight gradients) is computed by its owner in a fixed order. */
+ * gcgcn_producer_sizes.  Reproducibility: the forward is bit-reproducible.  In gcgcn_producer_bwd two small sums -- the
+ * gradient of the per-entity node terms and of the sentence attention's vector / bias -- are scatter-added with fp32 atomics,
+ * so dnode, dctx and dflat are reproducible up to summation order; every other sum (ctx, the score table, the weight
+ * gradients) is computed by its owner in a fixed order.  gcgcn_producer_bwd_det computes those two sums by their owners
+ * too (no float atomics anywhere): every output is bit-reproducible from run to run, for the dense and the compact entry. */
 int gcgcn_producer_layout(int Hd, int P, int64_t* out17);
 int gcgcn_producer_count(int B, int N, int S, int T, const uint8_t* sen, const int32_t* n_valid, int32_t* counts2, void* stream);
 int gcgcn_producer_sizes(int B, int N, int S, int T, int Hd, int P, int ND, int64_t cap_rows, int64_t cap_pairs, int64_t* out7);
@@ -328,6 +330,19 @@ int gcgcn_producer_bwd(int B, int N, int S, int T, int Hd, int P, int ND, const 
                        const void* pos_t, int pos_bytes, const float* node, const float* dis_table, const int32_t* n_valid,
                        const float* flat, int64_t cap_rows, int64_t cap_pairs, int32_t* ibuf, float* fbuf, float* bbuf,
                        const float* dE, const float* dEc, float* dctx, float* dnode, float* ddis_table, float* dflat, void* stream);
+/* The bit-reproducible backward (opt-in): the arguments and results of gcgcn_producer_bwd plus one workspace.  Each live pair's
+ * wave stores its head- and tail-side node-term rows (dnpair[rows of Ec][2][Hd]) and each workgroup its partial of the attention
+ * vector / bias gradient (2048 x (Hd + 1)); one wave per entity then sums its pairs' rows in pair-index order and one small
+ * kernel sums the partials in a fixed order.  Three launches instead of one launch and two memsets; no host read, capturable.
+ * *out of gcgcn_producer_det_elems (host; no GPU needed) = floats of detbuf = rows of Ec x 2 Hd + 2048 (Hd + 1), each piece
+ * rounded up to 16 bytes.  detbuf must be non-null, 16-byte aligned and hold det_elems >= that many floats: anything else is
+ * refused (gcgcn_last_error) before a kernel is launched.  Its contents need not be initialised and are not kept. */
+int gcgcn_producer_det_elems(int B, int N, int Hd, int64_t cap_pairs, int64_t* out);
+int gcgcn_producer_bwd_det(int B, int N, int S, int T, int Hd, int P, int ND, const float* ctx, const uint8_t* sen, const void* pos_h,
+                           const void* pos_t, int pos_bytes, const float* node, const float* dis_table, const int32_t* n_valid,
+                           const float* flat, int64_t cap_rows, int64_t cap_pairs, int32_t* ibuf, float* fbuf, float* bbuf,
+                           const float* dE, const float* dEc, float* dctx, float* dnode, float* ddis_table, float* dflat,
+                           float* detbuf, int64_t det_elems, void* stream);
 
 /* ---- consumers of the compact rows: a hop's graph blocks without a dense E (compact.hip) -------------------------------
  * e_ij = Ec[prow[b,i,j]] where prow >= 0, else bias.  Mean-only hop (MultiGraphConvolution's edge term): Ebar = mean_j e_ij;

@@ -42,6 +42,30 @@ def wall_ms(fn, steps):
     return (time.perf_counter() - t0) / steps * 1e3
 
 
+def interleaved(sides, reps, warmup=5):
+    """A/B in one process: sides = {name: callable}; every repetition times each side once, in turn, with a pair of HIP events (so a
+    drift of the clocks hits all sides alike).  -> {name: {"median_ms", "min_ms", "max_ms", "reps"}} (the method of encoder_bench.py)."""
+    import statistics
+    for _ in range(warmup):
+        for fn in sides.values():
+            fn()
+    torch.cuda.synchronize()
+    ev = {k: [] for k in sides}
+    for _ in range(reps):
+        for k, fn in sides.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            ev[k].append((e0, e1))
+    torch.cuda.synchronize()
+    out = {}
+    for k, v in ev.items():
+        ms = [e0.elapsed_time(e1) for e0, e1 in v]
+        out[k] = {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4), "reps": len(ms)}
+    return out
+
+
 def timed(step, graph, steps, mode="both"):
     out = {}
     if mode in ("eager", "both") or graph is None:

@@ -4,6 +4,7 @@ gcgcn_amd.EdgeFeatureProducer on DocRED-shaped synthetic batches, with per-kerne
 roofline of the kernel that bounds it.
 
     python tools/producer_bench.py [--B 32] [--N 42] [--S 5] [--T 512] [--H 128] [--live 0.15] [--steps 20] [--cpu]
+                                   [--deterministic [--reps 200]] [--lib-old build/ab_old.so] [--out FILE]
 
 --live: fraction of sentence slots that contain token 0 -- the only slots the reference keeps (glove:305); DocRED-like
 ~0.1-0.2 (pairs that co-occur in the first sentence), 1.0 = the dense stress case.
@@ -68,6 +69,81 @@ def word_roofline(wbytes, rng_tokens, word_ms):
     return r
 
 
+def lib_timer(_lib, tag, fn, n=5):
+    """Summed library-timer interval (events around every launch whose tag starts with `tag`) of one call of fn, and its launches."""
+    _lib.call("gcgcn_prof_start", tag.encode(), 64 * 8)
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize()
+    ms, cnt, w = ctypes.c_double(0), ctypes.c_int(0), ctypes.c_double(0)
+    _lib.call("gcgcn_prof_stop", ctypes.byref(ms), ctypes.byref(cnt), ctypes.byref(w))
+    return {"us_per_step": round(1e3 * ms.value / n, 2), "launches_per_step": cnt.value / n}
+
+
+def ab_deterministic(a, _lib, _graph_mode, prod, step):
+    """The default backward (prod_sent_bwd with fp32 atomics, two memsets) against the deterministic one (prod_sent_bwd_det,
+    prod_nterm_owner, prod_dwb_fin, no memset) on the same buffers, interleaved rep by rep."""
+    def side(det):
+        def fn():
+            prod.deterministic = det
+            step()
+        return fn
+    sides = {"default": side(False), "deterministic": side(True)}
+    res = {"timing": "HIP events per step (forward + backward), sides interleaved rep by rep, median (min, max)",
+           "eager": _graph_mode.interleaved(sides, a.reps)}
+    if a.mode != "eager":
+        graphs = {k: _graph_mode.capture(fn) for k, fn in sides.items()}
+        if all(g is not None for g in graphs.values()):
+            res["hipGraph replay"] = _graph_mode.interleaved({k: g.replay for k, g in graphs.items()}, a.reps)
+    for k in ("eager", "hipGraph replay"):
+        if k in res:
+            res[k]["deterministic - default, median, us"] = round(1e3 * (res[k]["deterministic"]["median_ms"] - res[k]["default"]["median_ms"]), 2)
+    # library timer: tag prod_sent is the forward's and the default backward's sentence kernel; the deterministic backward's three
+    # launches carry tags of their own (prod_det_*), so under it prod_sent is the forward's kernel alone
+    k = {"default: prod_sent (prod_sent_fwd + prod_sent_bwd)": lib_timer(_lib, "prod_sent", sides["default"]),
+         "deterministic: prod_sent (prod_sent_fwd alone)": lib_timer(_lib, "prod_sent", sides["deterministic"])}
+    for tag, name in (("prod_det_sent", "prod_sent_bwd_det"), ("prod_det_nterm", "prod_nterm_owner"), ("prod_det_dwb", "prod_dwb_fin")):
+        k[f"deterministic: {name}"] = lib_timer(_lib, tag, sides["deterministic"])
+    res["library timer (events around each launch: kernel + dispatch gap)"] = k
+    prod.deterministic = False
+    return res
+
+
+def ab_abi(a, _lib, _graph_mode, prod, inputs, cot, rows, pairs):
+    """gcgcn_producer_fwd + gcgcn_producer_bwd (the default entry) of this tree's library and of a.lib_old, same buffers."""
+    ctx, node, table, sen, ph, pt = inputs
+    B, T, Hd = ctx.shape
+    N, S = sen.shape[1], sen.shape[3]
+    ND, P = table.shape
+    dev = ctx.device
+    old = ctypes.CDLL(a.lib_old)
+    for name in ("gcgcn_producer_sizes", "gcgcn_producer_fwd", "gcgcn_producer_bwd"):
+        fn = getattr(old, name)
+        fn.restype, fn.argtypes = _lib.SIGNATURES[name]
+    sizes = (ctypes.c_int64 * 7)()
+    _lib.call("gcgcn_producer_sizes", B, N, S, T, Hd, P, ND, rows, pairs, ctypes.cast(sizes, ctypes.c_void_p))
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    ibuf, fbuf, bbuf = torch.empty(sizes[0], dtype=torch.int32, device=dev), torch.empty(sizes[1], device=dev), torch.empty(sizes[2], device=dev)
+    E = torch.empty(B, N, N, Hd, device=dev)
+    flat = prod.flat.detach()
+    outs = [torch.empty_like(t) for t in (ctx, node, table)] + [torch.zeros_like(flat)]
+    sen8 = sen.view(torch.uint8)
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    head = (B, N, S, T, Hd, P, ND, p(ctx), p(sen8), p(ph), p(pt), ph.element_size(), p(node), p(table), None, p(flat), rows, pairs, p(ibuf),
+            p(fbuf))
+
+    def side(h):
+        def fn():
+            rc = h.gcgcn_producer_fwd(*head, None, 0, p(E), st) or \
+                 h.gcgcn_producer_bwd(*head, p(bbuf), p(cot), None, *(p(o) for o in outs), st)
+            assert rc == 0
+        return fn
+    res = _graph_mode.interleaved({"this tree": side(_lib.lib()), "lib_old": side(old)}, a.reps)
+    lo, hi, med = res["lib_old"]["min_ms"], res["lib_old"]["max_ms"], res["this tree"]["median_ms"]
+    res["this tree's median within lib_old's min..max"] = bool(lo <= med <= hi)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=32)
@@ -82,6 +158,15 @@ def main():
     ap.add_argument("--cpu", action="store_true", help="also time the CPU oracle (reference op sequence) on a reduced document")
     ap.add_argument("--mode", default="both", choices=["eager", "graph", "both"],
                     help="graph: the step captured in one hipGraph and replayed (how bench.py times the hot path); eager: launches from Python")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="also time EdgeFeatureProducer.deterministic (the owner-computes backward) against the default in this process, "
+                         "the two sides interleaved rep by rep: median (min, max) per side, eager and as hipGraph replays (--mode), and "
+                         "the library timer of the kernels concerned")
+    ap.add_argument("--reps", type=int, default=200, help="repetitions per side of the interleaved timings")
+    ap.add_argument("--lib-old", default=None,
+                    help="another revision's library (tools/ab_build.sh): gcgcn_producer_fwd + gcgcn_producer_bwd of both on the same "
+                         "buffers, interleaved rep by rep")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
     import gcgcn_amd
     from gcgcn_amd import _lib, functional as F_
@@ -143,6 +228,11 @@ def main():
             "roofline_expand": {"bound": "hbm", "kernel": "gc::prod_expand_kernel (writes E[B,N,N,hidden])", "work_per_launch": ebytes,
                          "achieved": round(ebytes / (exp_ms * 1e-3) / 1e9, 1) if exp_ms else None, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
                          "frac": round(ebytes / (exp_ms * 1e-3) / HBM_PEAK, 4) if exp_ms else None}}
+    if a.deterministic:
+        line["deterministic_vs_default"] = ab_deterministic(a, _lib, _graph_mode, prod, step)
+    if a.lib_old:
+        line["abi (gcgcn_producer_fwd + gcgcn_producer_bwd, this tree against --lib-old, interleaved)"] = ab_abi(
+            a, _lib, _graph_mode, prod, (ctx, node, table, sen, ph, pt), cot, rows, pairs)
     if a.cpu:
         from oracle import gcgcn_oracle as O
         torch.set_num_threads(min(os.cpu_count() or 1, 16))
@@ -162,6 +252,11 @@ def main():
                                           f"(materialises [N,N,S,T,hidden]); the full N={N} S={S} T={T} document needs "
                                           f"{4 * N * N * S * T * Hd / 1e9:.1f} GB per intermediate tensor"}
     print(json.dumps(line))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(line, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":

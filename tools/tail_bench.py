@@ -3,6 +3,7 @@
 (f2), forward + backward, on DocRED-shaped synthetic batches: documents/second and where the time goes.
 
     python tools/tail_bench.py [--B 32] [--N 42] [--S 5] [--T 512] [--live 0.15] [--steps 10] [--ragged] [--layers 2] [--heads 8]
+                               [--deterministic [--reps 100]] [--out FILE]
 
 --ragged: DocRED-like entity counts n_valid ~ clip(round(N(19.5, 6^2)), 2, N) in a batch padded to N (what a real batch looks like;
 the default computes N entities in every document).  --layers / --heads: sub-layers and heads of the graph blocks (the GloVe model:
@@ -38,6 +39,11 @@ def main():
     ap.add_argument("--mode", default="both", choices=["eager", "graph", "both"],
                     help="graph: the whole step (producer -> CAGGC -> producer -> MAGGC -> head -> loss, forward + backward) captured in ONE "
                          "hipGraph and replayed, as bench.py times the hot path; eager: launches issued from Python; both (default)")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="also time GraphModelTail.deterministic (the producers' owner-computes backward) against the default in this "
+                         "process, the two sides interleaved rep by rep: median (min, max) per side, eager and as hipGraph replays")
+    ap.add_argument("--reps", type=int, default=100, help="repetitions per side of the interleaved timing")
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
     import gcgcn_amd
     from gcgcn_amd import _lib
@@ -92,13 +98,39 @@ def main():
             _lib.call("gcgcn_prof_stop", ctypes.byref(ms), ctypes.byref(n), ctypes.byref(w))
             tot += ms.value / 2
         shares[name] = round(tot, 3)
-    print(json.dumps({"metric": "docs/sec fwd+bwd through the whole post-encoder model + loss", "value": round(B / dt, 1), "unit": "docs/s",
+    ab = None
+    if a.deterministic:
+        def side(det):
+            def fn():
+                tail.deterministic = det
+                step()
+            return fn
+        sides = {"default": side(False), "deterministic": side(True)}
+        ab = {"timing": "HIP events per step (forward + backward), sides interleaved rep by rep, median (min, max)",
+              "eager": _graph_mode.interleaved(sides, a.reps)}
+        if a.mode != "eager":
+            graphs = {k: _graph_mode.capture(fn) for k, fn in sides.items()}
+            if all(g_ is not None for g_ in graphs.values()):
+                ab["hipGraph replay"] = _graph_mode.interleaved({k: g_.replay for k, g_ in graphs.items()}, a.reps)
+        for k in ("eager", "hipGraph replay"):
+            if k in ab:
+                ab[k]["deterministic - default, median, us"] = round(1e3 * (ab[k]["deterministic"]["median_ms"] - ab[k]["default"]["median_ms"]), 2)
+        tail.deterministic = False
+    line = {"metric": "docs/sec fwd+bwd through the whole post-encoder model + loss", "value": round(B / dt, 1), "unit": "docs/s",
                       "ms_per_step": round(dt * 1e3, 3), "ms_per_step_by_mode": {k: round(v, 3) for k, v in ms_mode.items()},
                       "config": {"workload": f"GraphModelTail (2 hops, hidden 128, L={a.layers}, H={a.heads}, R=97) + pair_bce_loss, train mode, B={B} N={N} "
                                              + (f"(ragged: mean n_valid {n_valid.float().mean().item():.1f}) " if a.ragged else "") +
                                              f"S={S} T={T}, {a.live:.0%} of the sentence slots start at token 0, uint8 position ids, " + ("one hipGraph per step (replays)" if "graph" in ms_mode else "eager launches")
                                              + (", compact edge rows (no E / dE tensors)" if a.compact else "") + (", dead last hop skipped" if a.skip_dead_hop else "")},
-                      "gpu_ms_per_step_by_part": shares}))
+                      "gpu_ms_per_step_by_part": shares}
+    if ab:
+        line["deterministic_vs_default"] = ab
+    print(json.dumps(line))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(line, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":
