@@ -6,11 +6,14 @@ gfx950 behind a C ABI (``include/gcgcn.h`` -> ``gcgcn_amd/lib/libgcgcn_hip.so``)
 """
 from .modules import (ClassifierHead, EdgeFeatureProducer, GraphModelTail, GATAttention, GraphConv, GraphConvolution, GraphHops,  # noqa: F401
                       MultiGraphConvolution, MultiHeadAttention)
-from .functional import lstm_layer, manual_seed, pair_bce_loss, token_context, token_embed  # noqa: F401
-from . import evaluation, functional, models, optim, params  # noqa: F401
+from .functional import (TrainStats, TrainStatsResult, lstm_layer, manual_seed, pair_bce_loss, token_context,  # noqa: F401
+                         token_embed)
+from . import evaluation, functional, models, optim, params, training  # noqa: F401
 from .evaluation import EvalResult, RelationEvaluator, evaluate  # noqa: F401
 from .optim import FusedAdam, GraphedTrainStep  # noqa: F401
+from .training import TrainEpochResult, train_epoch  # noqa: F401
 
 __all__ = ["GraphConv", "GATAttention", "MultiHeadAttention", "GraphConvolution", "MultiGraphConvolution", "GraphHops",
            "EdgeFeatureProducer", "ClassifierHead", "GraphModelTail",
-           "manual_seed", "pair_bce_loss", "lstm_layer", "token_embed", "token_context", "FusedAdam", "GraphedTrainStep", "RelationEvaluator", "EvalResult", "evaluate", "evaluation", "functional", "models", "optim", "params"]
+           "manual_seed", "pair_bce_loss", "lstm_layer", "token_embed", "token_context", "FusedAdam", "GraphedTrainStep", "RelationEvaluator", "EvalResult", "evaluate", "TrainStats", "TrainStatsResult", "train_epoch", "TrainEpochResult",
+           "evaluation", "functional", "models", "optim", "params", "training"]

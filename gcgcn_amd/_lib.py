@@ -80,6 +80,7 @@ SIGNATURES = {
     "gcgcn_graphconv_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "gcgcn_pair_bce_fwd": (I, [I, I, I, P, P, P, P, P, P]),
     "gcgcn_pair_bce_bwd": (I, [I, I, I, P, P, P, P, P, P]),
+    "gcgcn_pair_stats": (I, [I, I, I, P, P, P, P, P]),
     "gcgcn_eval_ws_bytes": (L, [L, L]),
     "gcgcn_eval_scan": (I, [I, I, I, P, P, P, P, P, P, L, P, P]),
     "gcgcn_eval_rank": (I, [P, L, P, L, P, P]),

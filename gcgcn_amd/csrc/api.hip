@@ -576,6 +576,14 @@ int gcgcn_pair_bce_bwd(int B, int N, int R, const float* logits, const float* la
   return pair_bce_bwd(logits, labels, n_valid, dloss, dlogits, B, N, R, (hipStream_t)stream);
 }
 
+int gcgcn_pair_stats(int B, int N, int R, const float* logits, const float* labels, const int32_t* n_valid, int64_t* counters,
+                     void* stream) {
+  GC_REQUIRE(B > 0 && N > 0 && R > 0 && (long)B * N <= 0x7fffffffL && (long)N * R <= 0x7fffffffL,
+             "pair_stats: bad shape B=%d N=%d R=%d", B, N, R);
+  GC_REQUIRE(logits && labels && counters, "pair_stats: null pointer");
+  return pair_stats(logits, labels, n_valid, counters, B, N, R, (hipStream_t)stream);
+}
+
 // ---------------------------------------------------------------------------------------------
 // GraphConvolution / MultiGraphConvolution
 // ---------------------------------------------------------------------------------------------

@@ -57,6 +57,8 @@ int pair_bce_fwd(const float* logits, const float* labels, const int* n_valid, f
                  hipStream_t st);
 int pair_bce_bwd(const float* logits, const float* labels, const int* n_valid, const float* dloss, float* dlogits, int B, int N,
                  int R, hipStream_t st);
+int pair_stats(const float* logits, const float* labels, const int* n_valid, int64_t* counters, int B, int N, int R,
+               hipStream_t st);
 
 // eval.hip: the trainer's evaluation (Config.test): record scan, stable radix ranking, PR curve / F1 / AUC
 int64_t eval_ws_bytes(int64_t n_records, int64_t n_keep);

@@ -10,6 +10,7 @@ import ctypes
 import os
 import threading
 import weakref
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -1089,18 +1090,116 @@ def take_edge_mean(e: Tensor, n_valid) -> Optional[Tensor]:
     return None
 
 
-def pair_bce_loss(logits, labels, n_valid=None):
+def _pair_inputs(logits, labels, n_valid, who: str):
+    """(logits[B,N,N,R], labels[B,N,N,R], n_valid int32[B] or None, unbatched?) of a pair-wise call, checked."""
+    single = isinstance(logits, torch.Tensor) and logits.dim() == 3
+    lg = _chk(logits.unsqueeze(0) if single else logits, "logits", 4)
+    if not isinstance(labels, torch.Tensor):
+        raise TypeError(f"labels: expected a tensor, got {type(labels).__name__}")
+    lb = _chk((labels.unsqueeze(0) if single else labels).to(torch.float32), "labels", 4)
+    if lb.shape != lg.shape or lg.shape[1] != lg.shape[2]:
+        raise ValueError(f"{who}: logits {tuple(lg.shape)} vs labels {tuple(lb.shape)}")
+    return lg, lb, _nv(n_valid, lg.shape[0], lg.shape[1], lg.device), single
+
+
+@dataclass(frozen=True)
+class TrainStatsResult:
+    """The eight counters of ``gcgcn_pair_stats`` after one read-back.  ``na_*``, ``not_na_*`` and ``correct`` / ``total`` are
+    the ``correct`` / ``total`` fields of the trainer's ``acc_NA``, ``acc_not_NA`` and ``acc_total`` (config/Config.py:388-393);
+    ``nan_pairs`` counts the entity pairs whose row of logits holds a NaN (they are in no other counter)."""
+    na_correct: int
+    na_total: int
+    not_na_correct: int
+    not_na_total: int
+    correct: int
+    total: int
+    nan_pairs: int
+    documents: int
+
+    @property
+    def counters(self) -> tuple:
+        return (self.na_correct, self.na_total, self.not_na_correct, self.not_na_total, self.correct, self.total, self.nan_pairs,
+                self.documents)
+
+    # Accuracy.get() (Config.py:48-52): 0.0 on an empty total
+    @property
+    def na_acc(self) -> float:
+        return float(self.na_correct) / self.na_total if self.na_total else 0.0
+
+    @property
+    def not_na_acc(self) -> float:
+        return float(self.not_na_correct) / self.not_na_total if self.not_na_total else 0.0
+
+    @property
+    def total_acc(self) -> float:
+        return float(self.correct) / self.total if self.total else 0.0
+
+
+class TrainStats:
+    """The trainer's per-epoch accuracy bookkeeping (``acc_NA``, ``acc_not_NA``, ``acc_total``: config/Config.py:376-393) kept in
+    a device ``int64[8]`` buffer instead of a host copy of every document's probabilities and a Python loop over its pairs::
+
+        stats = TrainStats(device)
+        for batch in loader:
+            loss = pair_bce_loss(logits, labels, n_valid, stats=stats).sum() / B     # or stats.update(logits, labels, n_valid)
+            ...
+        r = stats.get()                 # the one host read: r.na_acc, r.not_na_acc, r.total_acc, the eight integers
+        stats.reset()                   # next epoch (Config.py:332-334)
+
+    ``update`` is one launch on the current stream; it does not synchronise and can be captured in a graph (the buffer is the
+    graph's from then on).  ``GraphedTrainStep`` runs its warm-up steps and the capture for real, so a ``step_fn`` that updates
+    a ``TrainStats`` has counted those steps by the time the constructor returns: call ``reset()`` after constructing it.
+
+    Per ordered pair the predicted relation is the first maximum of ``sigmoid(sigmoid(logit))`` in fp32, as in the reference
+    (the trainer applies the sigmoid twice; saturated logits tie and the lowest index wins)."""
+
+    def __init__(self, device=None):
+        dev = torch.device("cuda" if device is None else device)
+        if dev.type != "cuda":
+            raise RuntimeError(f"TrainStats: gcgcn_amd runs on MI355X only; got device {dev} (no CPU fallback)")
+        # allocated here, never inside a captured step; without a GPU the object exists but every use raises
+        self._counters = torch.zeros(8, dtype=torch.int64, device=dev) if torch.cuda.is_available() else None
+
+    def _buf(self) -> Tensor:
+        if self._counters is None:
+            raise RuntimeError("TrainStats: gcgcn_amd runs on MI355X only; no GPU is available (no CPU fallback)")
+        return self._counters
+
+    def reset(self) -> None:
+        """Zero the counters, in stream order."""
+        self._buf().zero_()
+
+    def _launch(self, lg: Tensor, lb: Tensor, nv: Optional[Tensor]) -> None:
+        buf = self._buf()
+        if lg.device != buf.device:
+            raise ValueError(f"TrainStats: counters on {buf.device}, logits on {lg.device}")
+        B, N, _, R = lg.shape
+        if B:
+            call("gcgcn_pair_stats", B, N, R, _p(lg), _p(lb), _p(nv), _p(buf), _stream())
+
+    def update(self, logits, labels, n_valid=None) -> None:
+        """Add the pairs of ``logits`` / ``labels`` (``[B,N,N,R]`` or one ``[N,N,R]`` document; ``n_valid[B]`` for ragged batches)."""
+        lg, lb, nv, _ = _pair_inputs(logits, labels, n_valid, "TrainStats.update")
+        self._launch(lg.detach(), lb.detach(), nv)
+
+    def get(self) -> TrainStatsResult:
+        """One read-back (synchronises with the work queued before it)."""
+        return TrainStatsResult(*self._buf().cpu().tolist())
+
+
+def pair_bce_loss(logits, labels, n_valid=None, stats=None):
     """Per-document loss of the reference trainer (config/Config.py:355-366): sigmoid, BCE averaged over the relation
     axis, summed over ordered entity pairs h != t and divided by n^2 - n.  ``logits``/``labels``: ``[N,N,R]`` (returns
     a scalar, like the trainer's ``temp_loss``) or ``[B,N,N,R]`` (returns ``[B]``; ``n_valid[B]`` for ragged batches).
     The reference accumulates ``total_loss`` over documents and divides by ``batch_size`` (:366-369): that is
-    ``pair_bce_loss(...).sum() / batch_size``."""
-    single = logits.dim() == 3
-    lg = _chk(logits.unsqueeze(0) if single else logits, "logits", 4)
-    lb = _chk((labels.unsqueeze(0) if single else labels).to(torch.float32), "labels", 4)
-    if lb.shape != lg.shape or lg.shape[1] != lg.shape[2]:
-        raise ValueError(f"pair_bce_loss: logits {tuple(lg.shape)} vs labels {tuple(lb.shape)}")
-    out = PairBceFn.apply(lg, lb, _nv(n_valid, lg.shape[0], lg.shape[1], lg.device))
+    ``pair_bce_loss(...).sum() / batch_size``.  ``stats``: a ``TrainStats`` that counts the same pairs (one more launch on the
+    same stream, just before the loss kernel); the loss returned is the same either way."""
+    if stats is not None and not isinstance(stats, TrainStats):
+        raise TypeError(f"pair_bce_loss: stats must be a TrainStats, got {type(stats).__name__}")
+    lg, lb, nv, single = _pair_inputs(logits, labels, n_valid, "pair_bce_loss")
+    if stats is not None:
+        stats._launch(lg.detach(), lb.detach(), nv)
+    out = PairBceFn.apply(lg, lb, nv)
     return out[0] if single else out
 
 

@@ -253,6 +253,16 @@ int gcgcn_pair_bce_fwd(int B, int N, int R, const float* logits, const float* la
 /* dlogits[B,N,N,R] = dloss[b] * d loss[b] / d logits (dloss NULL = ones); zero on the diagonal and on padding. */
 int gcgcn_pair_bce_bwd(int B, int N, int R, const float* logits, const float* labels, const int32_t* n_valid,
                        const float* dloss, float* dlogits, void* stream);
+/* The trainer's accuracy bookkeeping (config/Config.py:376-393) over the same logits / labels [B,N,N,R], without the host
+ * copy.  For every document b, n = clamp(n_valid[b], 0, N) (NULL: N), and every ordered pair h != t, both < n:
+ *   p = 1 / (1 + expf(-x)),  q = 1 / (1 + expf(-p))   (fp32; the reference applies the sigmoid at :355 and again at :377),
+ *   r* = the FIRST maximum of q over 0..R-1 (numpy's argmax: saturated logits tie and the lowest index wins, so this is
+ *   not the argmax of the logits),  hit = labels[b,h,t,r*] == 1,  na = labels[b,h,t,0] == 1.
+ * counters (device int64[8], ADDED to, never overwritten): [0]/[1] acc_NA correct/total (pairs with na), [2]/[3] acc_not_NA
+ * correct/total, [4]/[5] acc_total correct/total, [6] pairs whose row holds a NaN (counted here and in no other counter),
+ * [7] documents seen (B per call).  One launch, integer atomics only: the result is exact and independent of their order. */
+int gcgcn_pair_stats(int B, int N, int R, const float* logits, const float* labels, const int32_t* n_valid, int64_t* counters,
+                     void* stream);
 
 /* ---- trainer evaluation  config/Config.py:432-561 (test), config/Config_bert.py:488-656 (ignore-train-facts curve) ---------
  * The reference copies every document's probabilities to the host, appends one Python tuple per (head, tail, relation != NA),
