@@ -8,12 +8,13 @@ from .modules import (ClassifierHead, EdgeFeatureProducer, GraphModelTail, GATAt
                       MultiGraphConvolution, MultiHeadAttention)
 from .functional import (TrainStats, TrainStatsResult, lstm_layer, manual_seed, pair_bce_loss, token_context,  # noqa: F401
                          token_embed)
-from . import evaluation, functional, models, optim, params, training  # noqa: F401
+from .bert import BertConfig, BertModel, load_pretrained_state_dict  # noqa: F401
+from . import bert, evaluation, functional, models, optim, params, training  # noqa: F401
 from .evaluation import EvalResult, RelationEvaluator, evaluate  # noqa: F401
 from .optim import FusedAdam, GraphedTrainStep  # noqa: F401
 from .training import TrainEpochResult, train_epoch  # noqa: F401
 
-__all__ = ["GraphConv", "GATAttention", "MultiHeadAttention", "GraphConvolution", "MultiGraphConvolution", "GraphHops",
+__all__ = ["BertConfig", "BertModel", "load_pretrained_state_dict", "GraphConv", "GATAttention", "MultiHeadAttention", "GraphConvolution", "MultiGraphConvolution", "GraphHops",
            "EdgeFeatureProducer", "ClassifierHead", "GraphModelTail",
            "manual_seed", "pair_bce_loss", "lstm_layer", "token_embed", "token_context", "FusedAdam", "GraphedTrainStep", "RelationEvaluator", "EvalResult", "evaluate", "TrainStats", "TrainStatsResult", "train_epoch", "TrainEpochResult",
-           "evaluation", "functional", "models", "optim", "params", "training"]
+           "bert", "evaluation", "functional", "models", "optim", "params", "training"]

@@ -19,6 +19,10 @@ SALT_GAT = 0x47415431
 SALT_MHA = 0x4D484131
 SALT_GCN = 0x47434E31
 SALT_GLUE = 0x474C5531
+SALT_BERT_ATTN = 0x42415431
+SALT_BERT_AO = 0x42414F31
+SALT_BERT_OUT = 0x424F5531
+SALT_BERT_EMB = 0x42454D31
 
 P = c_void_p  # every device pointer crosses the ABI as void*
 I = c_int
@@ -117,6 +121,16 @@ SIGNATURES = {
     "gcgcn_embed_bwd": (I, [I] * 8 + [P] * 5 + [I, I] + [P] * 4 + [L, P]),
     "gcgcn_context_fwd": (I, [I] * 5 + [P] * 8),
     "gcgcn_context_bwd": (I, [I] * 5 + [P] * 11 + [L, P]),
+    "gcgcn_bert_attn_fwd": (I, [I] * 4 + [P] * 5 + [c_uint64, F, P]),
+    "gcgcn_bert_attn_bwd": (I, [I] * 4 + [P] * 8 + [c_uint64, F, P]),
+    "gcgcn_res_ln_ws_bytes": (L, [I]),
+    "gcgcn_res_ln_fwd": (I, [L, I] + [P] * 9 + [c_uint64, F, P]),
+    "gcgcn_res_ln_bwd": (I, [L, I] + [P] * 12 + [L, P, c_uint64, F, P]),
+    "gcgcn_bias_gelu_fwd": (I, [L, I, P, P, P, P]),
+    "gcgcn_bias_gelu_bwd": (I, [L, I, P, P, P, P, P]),
+    "gcgcn_bert_layer_ws_bytes": (L, [I] * 6),
+    "gcgcn_bert_layer_fwd": (I, [I] * 5 + [P] * 5 + [L, P, F, F, P]),
+    "gcgcn_bert_layer_bwd": (I, [I] * 5 + [P] * 4 + [L, P, P, P, P, L, P, F, F, P]),
 }
 
 _lib = None

@@ -1,0 +1,238 @@
+"""A self-contained BERT encoder with the call contract and the ``state_dict`` keys of ``pytorch_pretrained_bert`` 0.6 ``BertModel``.
+
+``BertModel(config, impl="torch")`` is the contract in plain PyTorch (any device, any float dtype; the reference of the tests).
+``BertModel(config, impl="hip")`` runs every encoder layer through ``functional.bert_layer`` (csrc/bert.hip: masked attention
+core, LayerNorm with residual and dropout, erf GELU, forward and backward, the Linears on the fp32-MFMA GEMM layer) and the
+embeddings' LayerNorm through ``functional.res_layer_norm`` (their dropout is the library's elementwise kernel); it raises on CPU tensors.  The three embedding gathers
+(word, position, token type) and the pooler (one ``[B, D] x [D, D]`` product and a tanh) stay PyTorch in both implementations:
+three gathers and one small product.  Parameters live in ordinary ``nn.Embedding`` / ``nn.Linear`` / ``nn.LayerNorm`` holders
+under the package's names, so both implementations share one ``state_dict``.  DESIGN.md section 8.9."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Callable, Optional
+
+import torch
+from torch import nn
+from torch.nn import functional as F
+
+LN_EPS = 1e-12
+MASK_PENALTY = -10000.0
+
+
+@dataclass
+class BertConfig:
+    """bert-base-uncased by default."""
+    vocab_size: int = 30522
+    hidden_size: int = 768
+    num_hidden_layers: int = 12
+    num_attention_heads: int = 12
+    intermediate_size: int = 3072
+    max_position_embeddings: int = 512
+    type_vocab_size: int = 2
+    hidden_dropout_prob: float = 0.1
+    attention_probs_dropout_prob: float = 0.1
+
+
+def gelu(z):
+    return z * 0.5 * (1.0 + torch.erf(z / math.sqrt(2.0)))
+
+
+def layer_norm(x, weight, bias):
+    """Over the last axis, biased variance, eps = 1e-12 inside the root."""
+    u = x.mean(-1, keepdim=True)
+    s = (x - u).pow(2).mean(-1, keepdim=True)
+    return weight * ((x - u) / torch.sqrt(s + LN_EPS)) + bias
+
+
+def _holder_ln(d):
+    return nn.LayerNorm(d, eps=LN_EPS)      # a parameter holder (weight, bias); the arithmetic is layer_norm() above
+
+
+class _Embeddings(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.word_embeddings = nn.Embedding(c.vocab_size, c.hidden_size)
+        self.position_embeddings = nn.Embedding(c.max_position_embeddings, c.hidden_size)
+        self.token_type_embeddings = nn.Embedding(c.type_vocab_size, c.hidden_size)
+        self.LayerNorm = _holder_ln(c.hidden_size)
+
+
+class _SelfAttention(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.query, self.key, self.value = (nn.Linear(c.hidden_size, c.hidden_size) for _ in range(3))
+
+
+class _DenseLN(nn.Module):
+    def __init__(self, n_in, n_out):
+        super().__init__()
+        self.dense = nn.Linear(n_in, n_out)
+        self.LayerNorm = _holder_ln(n_out)
+
+
+class _Attention(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.self = _SelfAttention(c)
+        self.output = _DenseLN(c.hidden_size, c.hidden_size)
+
+
+class _Dense(nn.Module):
+    def __init__(self, n_in, n_out):
+        super().__init__()
+        self.dense = nn.Linear(n_in, n_out)
+
+
+class _Layer(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.attention = _Attention(c)
+        self.intermediate = _Dense(c.hidden_size, c.intermediate_size)
+        self.output = _DenseLN(c.intermediate_size, c.hidden_size)
+
+    def tensors(self):
+        """The 16 parameter tensors in functional.bert_layer's order."""
+        a, o = self.attention, self.output
+        return (a.self.query.weight, a.self.query.bias, a.self.key.weight, a.self.key.bias, a.self.value.weight, a.self.value.bias,
+                a.output.dense.weight, a.output.dense.bias, a.output.LayerNorm.weight, a.output.LayerNorm.bias,
+                self.intermediate.dense.weight, self.intermediate.dense.bias, o.dense.weight, o.dense.bias, o.LayerNorm.weight,
+                o.LayerNorm.bias)
+
+
+class _Encoder(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.layer = nn.ModuleList(_Layer(c) for _ in range(c.num_hidden_layers))
+
+
+def torch_layer(x, key_bias, params, heads, drop: Callable):
+    """One encoder layer in plain PyTorch.  ``key_bias``: ``[B, T]`` additive penalty or None.  ``drop(site, t)``: the dropout of
+    site "attn" (on P ``[B, H, T, T]``), "ao" or "out" (on ``[B, T, D]``)."""
+    wq, bq, wk, bk, wv, bv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2 = params
+    B, T, D = x.shape
+    dh = D // heads
+    split = lambda t: t.view(B, T, heads, dh).permute(0, 2, 1, 3)
+    q, k, v = split(F.linear(x, wq, bq)), split(F.linear(x, wk, bk)), split(F.linear(x, wv, bv))
+    s = q @ k.transpose(-1, -2) / math.sqrt(dh)
+    if key_bias is not None:
+        s = s + key_bias[:, None, None, :]
+    p = drop("attn", torch.softmax(s, dim=-1))
+    ctx = (p @ v).permute(0, 2, 1, 3).reshape(B, T, D)
+    a = layer_norm(drop("ao", F.linear(ctx, wo, bo)) + x, g1, b1)
+    i = gelu(F.linear(a, wi, bi))
+    return layer_norm(drop("out", F.linear(i, wo2, bo2)) + a, g2, b2)
+
+
+class BertModel(nn.Module):
+    """``forward(input_ids[B,T], token_type_ids=None, attention_mask=None, output_all_encoded_layers=True) -> (encoded, pooled)``:
+    ``encoded`` is the last layer's ``[B,T,D]``, or the list of every layer's output when the flag is true;
+    ``pooled = tanh(pooler.dense(encoded_last[:, 0]))``.  ``attention_mask`` ``[B,T]`` (1 = a token, 0 = padding) becomes the additive
+    penalty ``(1 - mask) * -10000`` on the scores: a row whose keys are all masked is a finite softmax.
+
+    ``dropout_override``: None, or ``f(layer, site, t) -> t`` replacing the dropout of site "emb" (layer -1), "attn", "ao", "out" of
+    the torch implementation -- how a test replays the masks the HIP kernels drew.  After a training forward of ``impl="hip"``,
+    ``last_rng_snaps`` holds the snapshots it used: ``[0]`` for the embeddings, ``[1 + l]`` for layer ``l``."""
+
+    def __init__(self, config: Optional[BertConfig] = None, impl: str = "torch"):
+        super().__init__()
+        config = BertConfig() if config is None else config
+        if impl not in ("torch", "hip"):
+            raise ValueError(f"BertModel: impl must be 'torch' or 'hip', got {impl!r}")
+        if config.hidden_size % config.num_attention_heads:
+            raise ValueError(f"BertModel: hidden size {config.hidden_size} is no multiple of {config.num_attention_heads} heads")
+        if impl == "hip" and config.hidden_size != 64 * config.num_attention_heads:
+            raise ValueError(f"BertModel(impl='hip'): the attention kernels serve a head width of 64, not "
+                             f"{config.hidden_size // config.num_attention_heads}")
+        self.config, self.impl = config, impl
+        self.embeddings = _Embeddings(config)
+        self.encoder = _Encoder(config)
+        self.pooler = _Dense(config.hidden_size, config.hidden_size)
+        self.dropout_override = None
+        self.last_rng_snaps = None
+        self.apply(self._init)
+
+    @staticmethod
+    def _init(m):   # pytorch_pretrained_bert's init_bert_weights
+        if isinstance(m, (nn.Linear, nn.Embedding)):
+            m.weight.data.normal_(mean=0.0, std=0.02)
+        if isinstance(m, nn.Linear) and m.bias is not None:
+            m.bias.data.zero_()
+
+    def _drop(self, layer, site, t, p):
+        if self.dropout_override is not None:
+            return self.dropout_override(layer, site, t)
+        return F.dropout(t, p, self.training)
+
+    def forward(self, input_ids, token_type_ids=None, attention_mask=None, output_all_encoded_layers=True):
+        c, e = self.config, self.embeddings
+        B, T = input_ids.shape
+        if T > c.max_position_embeddings:
+            raise ValueError(f"BertModel: {T} tokens exceed max_position_embeddings = {c.max_position_embeddings}")
+        tt = torch.zeros_like(input_ids) if token_type_ids is None else token_type_ids
+        pos = torch.arange(T, device=input_ids.device)
+        emb = e.word_embeddings(input_ids) + e.position_embeddings(pos)[None] + e.token_type_embeddings(tt)
+        key_bias = None if attention_mask is None else (1.0 - attention_mask.to(emb.dtype)) * MASK_PENALTY
+        if self.impl == "hip":
+            outs = self._encode_hip(emb, key_bias)
+        else:
+            x = self._drop(-1, "emb", layer_norm(emb, e.LayerNorm.weight, e.LayerNorm.bias), c.hidden_dropout_prob)
+            outs = []
+            for li, layer in enumerate(self.encoder.layer):
+                probs = {"attn": c.attention_probs_dropout_prob, "ao": c.hidden_dropout_prob, "out": c.hidden_dropout_prob}
+                x = torch_layer(x, key_bias, layer.tensors(), c.num_attention_heads, lambda s, t: self._drop(li, s, t, probs[s]))
+                outs.append(x)
+        last = outs[-1] if outs else x
+        pooled = torch.tanh(self.pooler.dense(last[:, 0]))
+        return (outs if output_all_encoded_layers else last), pooled
+
+    def _encode_hip(self, emb, key_bias):
+        from . import _lib, functional as Fn
+        c, e = self.config, self.embeddings
+        if not emb.is_cuda:
+            raise RuntimeError(f"BertModel(impl='hip') runs on MI355X only; got {emb.device} tensors (impl='torch' runs anywhere)")
+        training = self.training
+        n = len(self.encoder.layer)
+        snaps = []
+        with Fn.rng_scope(emb.device, n + 1, enabled=training):
+            snap = Fn.rng_snapshot(emb.device) if training and c.hidden_dropout_prob > 0 else None
+            snaps.append(snap)
+            x = Fn.res_layer_norm(emb, e.LayerNorm.weight, e.LayerNorm.bias)      # the dropout follows the LayerNorm here
+            if snap is not None:
+                x = Fn.DropoutFn.apply(x, c.hidden_dropout_prob, snap, _lib.SALT_BERT_EMB)
+            outs = []
+            kb = None if key_bias is None else key_bias.contiguous()
+            for layer in self.encoder.layer:
+                snap = Fn.rng_snapshot(emb.device) if training else None
+                snaps.append(snap)
+                x = Fn.bert_layer(x, kb, *layer.tensors(), p_attn=c.attention_probs_dropout_prob, p_hidden=c.hidden_dropout_prob,
+                                  training=training, snap=snap)
+                outs.append(x)
+        self.last_rng_snaps = snaps if training else None
+        if not outs:
+            outs = [x]
+        return outs
+
+
+def load_pretrained_state_dict(model: nn.Module, path: str, strict: bool = True):
+    """Load a LOCAL checkpoint file (``torch.load``; nothing is downloaded) into ``model``.  Checkpoints of the original TensorFlow
+    conversion spell the LayerNorm parameters ``gamma`` / ``beta``: they are renamed to ``weight`` / ``bias``.  A ``bert.`` prefix
+    (a checkpoint of a model that wraps the encoder) is dropped when every key carries it."""
+    sd = torch.load(path, map_location="cpu")
+    if isinstance(sd, dict) and "state_dict" in sd and not any(torch.is_tensor(v) for v in sd.values()):
+        sd = sd["state_dict"]
+    if sd and all(k.startswith("bert.") for k in sd):
+        sd = {k[len("bert."):]: v for k, v in sd.items()}
+    return model.load_state_dict(rename_gamma_beta(sd), strict=strict)
+
+
+def rename_gamma_beta(sd: dict) -> dict:
+    out = {}
+    for k, v in sd.items():
+        if k.endswith(".gamma"):
+            k = k[:-len("gamma")] + "weight"
+        elif k.endswith(".beta"):
+            k = k[:-len("beta")] + "bias"
+        out[k] = v
+    return out

@@ -16,6 +16,7 @@
 #include "gemm.hpp"
 #include "lstm.hpp"
 #include "frontend.hpp"
+#include "bert.hpp"
 #include "rowops.hpp"
 
 namespace gc {
@@ -1172,6 +1173,137 @@ int gcgcn_context_bwd(int B, int T, int N, int K, int Hd, const float* h, const 
              (long long)gcgcn_frontend_ws_bytes(B, T, 0, 0, 0, 0, 0, 0, K));
   return context_bwd(B, T, N, K, h, w, node_pos, ctx, dctx, dnode_feat, dpre, dh, dw, db, (float*)ws, ws_bytes / (int64_t)sizeof(float),
                      (hipStream_t)stream);
+}
+
+// ---- the BERT encoder layer (bert.hip) ---------------------------------------------------------------------------------------------
+static int bert_attn_shape_ok(const char* who, int B, int T, int H, int dh) {
+  GC_REQUIRE(dh == BERT_DH, "%s: head width %d is not served (the attention kernels hold dh = %d)", who, dh, BERT_DH);
+  GC_REQUIRE(T >= 1 && T <= BERT_MAX_T, "%s: T = %d is outside [1, %d]", who, T, BERT_MAX_T);
+  GC_REQUIRE(B >= 1 && B <= 65535 && H >= 1 && H <= 65535, "%s: bad shape B=%d H=%d", who, B, H);
+  GC_REQUIRE((long)B * T * 3 * H * dh <= 0x7fffffffL, "%s: B=%d T=%d H=%d is too large", who, B, T, H);
+  return 0;
+}
+static int bert_drop_ok(const char* who, const void* snap, float p) {
+  GC_REQUIRE(p >= 0.f && p < 1.f, "%s: p=%f out of [0,1)", who, p);
+  GC_REQUIRE(!(p > 0.f) || snap, "%s: dropout without an rng snapshot", who);
+  return 0;
+}
+static int bert_layer_shape_ok(const char* who, int B, int T, int D, int H, int Dff) {
+  GC_REQUIRE(H >= 1 && D == H * BERT_DH, "%s: D = %d with %d heads is a head width other than %d", who, D, H, BERT_DH);
+  GC_TRY(bert_attn_shape_ok(who, B, T, H, BERT_DH));
+  GC_REQUIRE(D <= BERT_LN_MAX_D, "%s: D = %d exceeds %d", who, D, BERT_LN_MAX_D);
+  GC_REQUIRE(Dff >= 4 && Dff % 4 == 0 && (long)B * T * Dff <= 0x7fffffffL, "%s: intermediate size %d (a multiple of 4; B T Dff < 2^31)", who, Dff);
+  return 0;
+}
+
+int gcgcn_bert_attn_fwd(int B, int T, int H, int dh, const float* qkv, const float* key_bias, float* ctx, float* lse, const void* rng_snap,
+                        uint64_t salt, float p, void* stream) {
+  GC_TRY(bert_attn_shape_ok("bert_attn_fwd", B, T, H, dh));
+  GC_TRY(bert_drop_ok("bert_attn_fwd", rng_snap, p));
+  GC_REQUIRE(qkv && ctx && lse, "bert_attn_fwd: null pointer");
+  GC_REQUIRE(al16(qkv), "bert_attn_fwd: qkv must be 16-byte aligned");
+  return bert_attn_fwd(B, T, H, qkv, key_bias, ctx, lse, make_drop(rng_snap, salt, p), (hipStream_t)stream);
+}
+int gcgcn_bert_attn_bwd(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const float* ctx, const float* lse,
+                        const float* dctx, float* dqkv, float* delta, const void* rng_snap, uint64_t salt, float p, void* stream) {
+  GC_TRY(bert_attn_shape_ok("bert_attn_bwd", B, T, H, dh));
+  GC_TRY(bert_drop_ok("bert_attn_bwd", rng_snap, p));
+  GC_REQUIRE(qkv && ctx && lse && dctx && dqkv && delta, "bert_attn_bwd: null pointer");
+  GC_REQUIRE(al16(qkv) && al16(dctx), "bert_attn_bwd: qkv and dctx must be 16-byte aligned");
+  return bert_attn_bwd(B, T, H, qkv, key_bias, ctx, lse, dctx, dqkv, delta, make_drop(rng_snap, salt, p), (hipStream_t)stream);
+}
+
+static int res_ln_shape_ok(const char* who, int64_t rows, int D) {
+  GC_REQUIRE(D >= 64 && D % 64 == 0 && D <= BERT_LN_MAX_D, "%s: D = %d (a multiple of 64, at most %d)", who, D, BERT_LN_MAX_D);
+  GC_REQUIRE(rows >= 1 && rows * D <= 0x7fffffffL, "%s: %lld rows", who, (long long)rows);
+  return 0;
+}
+int64_t gcgcn_res_ln_ws_bytes(int D) {
+  if (res_ln_shape_ok("res_ln_ws_bytes", 1, D)) return -1;
+  return (int64_t)sizeof(float) * res_ln_ws_elems(D);
+}
+int gcgcn_res_ln_fwd(int64_t rows, int D, const float* x, const float* bias, const float* res, const float* weight, const float* lnb,
+                     float* y, float* mean, float* rstd, const void* rng_snap, uint64_t salt, float p, void* stream) {
+  GC_TRY(res_ln_shape_ok("res_ln_fwd", rows, D));
+  GC_TRY(bert_drop_ok("res_ln_fwd", rng_snap, p));
+  GC_REQUIRE(x && weight && lnb && y && (!mean == !rstd), "res_ln_fwd: null pointer");
+  return res_ln_fwd(rows, D, x, bias, res, weight, lnb, y, mean, rstd, make_drop(rng_snap, salt, p), (hipStream_t)stream);
+}
+int gcgcn_res_ln_bwd(int64_t rows, int D, const float* dy, const float* x, const float* bias, const float* res, const float* weight,
+                     const float* mean, const float* rstd, float* dx, float* dres, float* dweight, float* dlnb, void* ws, int64_t ws_bytes,
+                     const void* rng_snap, uint64_t salt, float p, void* stream) {
+  GC_TRY(res_ln_shape_ok("res_ln_bwd", rows, D));
+  GC_TRY(bert_drop_ok("res_ln_bwd", rng_snap, p));
+  GC_REQUIRE(dy && x && weight && mean && rstd && dx && dweight && dlnb && ws, "res_ln_bwd: null pointer");
+  GC_REQUIRE(ws_bytes >= gcgcn_res_ln_ws_bytes(D), "res_ln_bwd: workspace of %lld bytes needed (gcgcn_res_ln_ws_bytes)",
+             (long long)gcgcn_res_ln_ws_bytes(D));
+  return res_ln_bwd(rows, D, dy, x, bias, res, weight, mean, rstd, dx, dres, dweight, dlnb, (float*)ws, make_drop(rng_snap, salt, p),
+                    (hipStream_t)stream);
+}
+
+static int gelu_shape_ok(const char* who, int64_t rows, int C, const void* a, const void* b, const void* c) {
+  GC_REQUIRE(rows >= 1 && C >= 4 && C % 4 == 0, "%s: rows = %lld, C = %d (a multiple of 4)", who, (long long)rows, C);
+  GC_REQUIRE(al16(a) && al16(b) && al16(c), "%s: buffers must be 16-byte aligned", who);
+  return 0;
+}
+int gcgcn_bias_gelu_fwd(int64_t rows, int C, const float* x, const float* bias, float* y, void* stream) {
+  GC_REQUIRE(x && y, "bias_gelu_fwd: null pointer");
+  GC_TRY(gelu_shape_ok("bias_gelu_fwd", rows, C, x, bias, y));
+  return bias_gelu_fwd(rows, C, x, bias, y, (hipStream_t)stream);
+}
+int gcgcn_bias_gelu_bwd(int64_t rows, int C, const float* dy, const float* x, const float* bias, float* dx, void* stream) {
+  GC_REQUIRE(dy && x && dx, "bias_gelu_bwd: null pointer");
+  GC_TRY(gelu_shape_ok("bias_gelu_bwd", rows, C, x, bias, dx));
+  GC_REQUIRE(al16(dy), "bias_gelu_bwd: buffers must be 16-byte aligned");
+  return bias_gelu_bwd(rows, C, dy, x, bias, dx, (hipStream_t)stream);
+}
+
+int64_t gcgcn_bert_layer_ws_bytes(int B, int T, int D, int H, int Dff, int which) {
+  if (bert_layer_shape_ok("bert_layer_ws_bytes", B, T, D, H, Dff)) return -1;
+  if (which != 0 && which != 1) {
+    set_error("bert_layer_ws_bytes: which = %d (0: what the forward saves, 1: the backward's workspace)", which);
+    return -1;
+  }
+  return (int64_t)sizeof(float) * (which ? bert_layer_ws_elems(B, T, D, H, Dff) : bert_layer_saved_elems(B, T, D, H, Dff));
+}
+static int bert_params_ok(const char* who, const float* const* p) {
+  GC_REQUIRE(p, "%s: null parameter list", who);
+  for (int i = 0; i < GCGCN_BERT_LAYER_PARAMS; ++i) GC_REQUIRE(p[i] && al16(p[i]), "%s: parameter %d is null or not 16-byte aligned", who, i);
+  return 0;
+}
+int gcgcn_bert_layer_fwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const float* const* params, float* y,
+                         void* saved, int64_t saved_bytes, const void* rng_snap, float p_attn, float p_hidden, void* stream) {
+  GC_TRY(bert_layer_shape_ok("bert_layer_fwd", B, T, D, H, Dff));
+  GC_TRY(bert_drop_ok("bert_layer_fwd", rng_snap, p_attn));
+  GC_TRY(bert_drop_ok("bert_layer_fwd", rng_snap, p_hidden));
+  GC_TRY(bert_params_ok("bert_layer_fwd", params));
+  GC_REQUIRE(x && y && saved && al16(x) && al16(y) && al16(saved), "bert_layer_fwd: x, y, saved must be given and 16-byte aligned");
+  GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "bert_layer_fwd: %lld bytes of saved activations needed "
+             "(gcgcn_bert_layer_ws_bytes, which = 0)", (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
+  const BertLayerParams p = {params[0], params[1], params[2], params[3], params[4], params[5],
+                             params[6], params[7], params[8], params[9], params[10], params[11]};
+  return bert_layer_fwd(B, T, D, H, Dff, x, key_bias, p, y, (float*)saved, rng_snap, p_attn, p_hidden, (hipStream_t)stream);
+}
+int gcgcn_bert_layer_bwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const float* const* params,
+                         const void* saved, int64_t saved_bytes, const float* dy, float* dx, float* const* grads, void* ws, int64_t ws_bytes,
+                         const void* rng_snap, float p_attn, float p_hidden, void* stream) {
+  GC_TRY(bert_layer_shape_ok("bert_layer_bwd", B, T, D, H, Dff));
+  GC_TRY(bert_drop_ok("bert_layer_bwd", rng_snap, p_attn));
+  GC_TRY(bert_drop_ok("bert_layer_bwd", rng_snap, p_hidden));
+  GC_TRY(bert_params_ok("bert_layer_bwd", params));
+  GC_TRY(bert_params_ok("bert_layer_bwd", grads));
+  GC_REQUIRE(x && saved && dy && dx && ws && al16(x) && al16(saved) && al16(dy) && al16(dx) && al16(ws),
+             "bert_layer_bwd: x, saved, dy, dx, ws must be given and 16-byte aligned");
+  GC_REQUIRE(dx != dy, "bert_layer_bwd: dx aliases dy");
+  GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "bert_layer_bwd: %lld bytes of saved activations needed",
+             (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
+  GC_REQUIRE(ws_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1), "bert_layer_bwd: workspace of %lld bytes needed "
+             "(gcgcn_bert_layer_ws_bytes, which = 1)", (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1));
+  const BertLayerParams p = {params[0], params[1], params[2], params[3], params[4], params[5],
+                             params[6], params[7], params[8], params[9], params[10], params[11]};
+  const BertLayerGrads g = {grads[0], grads[1], grads[2], grads[3], grads[4], grads[5], grads[6], grads[7], grads[8], grads[9], grads[10], grads[11]};
+  return bert_layer_bwd(B, T, D, H, Dff, x, key_bias, p, (const float*)saved, dy, dx, g, (float*)ws, ws_bytes / (int64_t)sizeof(float), rng_snap,
+                        p_attn, p_hidden, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1421,3 +1421,149 @@ def token_context(h, weight, bias, node_pos):
     if node_pos.shape[0] != B or node_pos.shape[2] != T:
         raise ValueError(f"token_context: node_pos {tuple(node_pos.shape)}, expected [{B}, N, {T}]")
     return TokenContextFn.apply(h, weight, bias, node_pos)
+
+
+# ---- the BERT encoder layer (csrc/bert.hip) --------------------------------------------------------------------------------------
+def _bytes_or_raise(name: str, *dims) -> int:
+    need = getattr(_lib.lib(), name)(*dims)
+    if need < 0:
+        raise RuntimeError(f"{name} failed: {_lib.lib().gcgcn_last_error().decode()}")
+    return need
+
+
+def _f32_buf(nbytes: int, dev) -> Tensor:
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+
+
+class ResLayerNormFn(torch.autograd.Function):
+    """y = LayerNorm(dropout(x + bias) + res) over the last axis (eps = 1e-12, biased variance); bias, res, dropout optional."""
+
+    @staticmethod
+    def forward(ctx, x, bias, res, weight, lnb, p, snap, salt):
+        D = x.shape[-1]
+        rows = x.numel() // D
+        y = torch.empty_like(x)
+        mean, rstd = torch.empty(rows, device=x.device), torch.empty(rows, device=x.device)
+        call("gcgcn_res_ln_fwd", rows, D, _p(x), _p(bias), _p(res), _p(weight), _p(lnb), _p(y), _p(mean), _p(rstd), _p(snap), salt, float(p),
+             _stream())
+        torch.autograd.graph.increment_version((y, mean, rstd))
+        ctx.p, ctx.snap, ctx.salt, ctx.has = float(p), snap, salt, (bias is not None, res is not None)
+        ctx.save_for_backward(x, weight, mean, rstd, *(t for t in (bias, res) if t is not None))
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, weight, mean, rstd = ctx.saved_tensors[:4]
+        rest = list(ctx.saved_tensors[4:])
+        bias = rest.pop(0) if ctx.has[0] else None
+        res = rest.pop(0) if ctx.has[1] else None
+        D = x.shape[-1]
+        rows = x.numel() // D
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        dres = torch.empty_like(x) if res is not None else None
+        dw, db = torch.empty_like(weight), torch.empty_like(weight)
+        ws = _f32_buf(_bytes_or_raise("gcgcn_res_ln_ws_bytes", D), x.device)
+        call("gcgcn_res_ln_bwd", rows, D, _p(dy), _p(x), _p(bias), _p(res), _p(weight), _p(mean), _p(rstd), _p(dx), _p(dres), _p(dw), _p(db),
+             _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.salt, ctx.p, _stream())
+        torch.autograd.graph.increment_version((dx, dw, db) + (() if dres is None else (dres,)))
+        dbias = dx.reshape(rows, D).sum(0) if bias is not None and ctx.needs_input_grad[1] else None
+        return dx, dbias, dres, dw, db, None, None, None
+
+
+def res_layer_norm(x, weight, bias, lin_bias=None, res=None, p=0.0, training=False, snap=None, salt=_lib.SALT_BERT_EMB):
+    """``LayerNorm(dropout(x + lin_bias) + res)`` over the last axis in HIP, with the contract's LayerNorm: biased variance,
+    ``weight * (v - mean) / sqrt(var + 1e-12) + bias``.  ``lin_bias`` ``[D]``, ``res`` (``x``'s shape) and the dropout are each
+    optional.  ``D`` a multiple of 64, at most 1024.  ``snap``: the rng snapshot of the dropout site (default: a fresh one)."""
+    x = _chk(x, "x")
+    weight, bias = _chk(weight, "weight", 1), _chk(bias, "bias", 1)
+    D = x.shape[-1]
+    if weight.shape != (D,) or bias.shape != (D,):
+        raise ValueError(f"res_layer_norm: weight {tuple(weight.shape)} / bias {tuple(bias.shape)} for rows of {D}")
+    if lin_bias is not None and _chk(lin_bias, "lin_bias", 1).shape != (D,):
+        raise ValueError(f"res_layer_norm: lin_bias {tuple(lin_bias.shape)} for rows of {D}")
+    if res is not None:
+        res = _chk(res, "res")
+        if res.shape != x.shape:
+            raise ValueError(f"res_layer_norm: res {tuple(res.shape)} against x {tuple(x.shape)}")
+    p = float(p) if training else 0.0
+    if p > 0 and snap is None:
+        snap = rng_snapshot(x.device)
+    return ResLayerNormFn.apply(x, None if lin_bias is None else lin_bias.contiguous(), res, weight, bias, p, snap if p > 0 else None, salt)
+
+
+BERT_LAYER_TENSORS = ("query.weight", "query.bias", "key.weight", "key.bias", "value.weight", "value.bias", "attention.output.dense.weight",
+                      "attention.output.dense.bias", "attention.output.LayerNorm.weight", "attention.output.LayerNorm.bias",
+                      "intermediate.dense.weight", "intermediate.dense.bias", "output.dense.weight", "output.dense.bias",
+                      "output.LayerNorm.weight", "output.LayerNorm.bias")
+
+
+def _ptr_array(tensors):
+    return (ctypes.c_void_p * len(tensors))(*(t.data_ptr() for t in tensors))
+
+
+class BertLayerFn(torch.autograd.Function):
+    """(x[B,T,D], key_bias[B,T] | None, the 12 tensors of gcgcn_bert_layer_fwd's parameter list) -> y[B,T,D]."""
+
+    @staticmethod
+    def forward(ctx, x, key_bias, H, p_attn, p_hidden, snap, *params):
+        B, T, D = x.shape
+        Dff = params[6].shape[0]
+        dims = (B, T, D, H, Dff)
+        saved = _f32_buf(_bytes_or_raise("gcgcn_bert_layer_ws_bytes", *dims, 0), x.device)
+        y = torch.empty_like(x)
+        call("gcgcn_bert_layer_fwd", *dims, _p(x), _p(key_bias), _ptr_array(params), _p(y), _p(saved), saved.numel() * 4, _p(snap),
+             float(p_attn), float(p_hidden), _stream())
+        torch.autograd.graph.increment_version((y, saved))
+        ctx.dims, ctx.ps, ctx.snap, ctx.has_kb = dims, (float(p_attn), float(p_hidden)), snap, key_bias is not None
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(x, saved, *params, *(() if key_bias is None else (key_bias,)))
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        x, saved = ctx.saved_tensors[:2]
+        params = ctx.saved_tensors[2:14]
+        key_bias = ctx.saved_tensors[14] if ctx.has_kb else None
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        grads = tuple(torch.empty_like(t) for t in params)
+        ws = _f32_buf(_bytes_or_raise("gcgcn_bert_layer_ws_bytes", *ctx.dims, 1), x.device)
+        call("gcgcn_bert_layer_bwd", *ctx.dims, _p(x), _p(key_bias), _ptr_array(params), _p(saved), saved.numel() * 4, _p(dy), _p(dx),
+             _ptr_array(grads), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.ps[0], ctx.ps[1], _stream())
+        torch.autograd.graph.increment_version((dx,) + grads)
+        return (dx, None, None, None, None, None) + grads
+
+
+def bert_layer(x, key_bias, wq, bq, wk, bk, wv, bv, wo, bo, ln1_w, ln1_b, wi, bi, wo2, bo2, ln2_w, ln2_b, p_attn=0.1, p_hidden=0.1,
+               training=False, snap=None):
+    """One BERT encoder layer (``pytorch_pretrained_bert`` 0.6 ``BertLayer``) in HIP: ``x[B,T,D]`` -> ``[B,T,D]``.  ``key_bias``:
+    ``[B,T]`` additive score penalty per key (``(1 - mask) * -10000``) or None.  The 16 parameter tensors in ``BERT_LAYER_TENSORS``'
+    order, Linear weights ``[out, in]``; the number of heads is ``D / 64`` (the attention kernels serve a head width of 64) and
+    ``T <= 512``.  In training mode three dropout sites draw from one rng snapshot (``snap``, default a fresh one, inside an
+    ``rng_scope`` the scope's next): the attention probabilities (``p_attn``, salt ``SALT_BERT_ATTN``, index = offset in
+    ``[B,H,T,T]``) and the two Linear outputs in front of the LayerNorms (``p_hidden``, ``SALT_BERT_AO`` / ``SALT_BERT_OUT``,
+    index = offset in ``[B,T,D]``).  Gradients reach ``x`` and all 16 tensors; two runs from one seed are bitwise equal."""
+    x = _chk(x, "x", 3)
+    names = ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo", "ln1_w", "ln1_b", "wi", "bi", "wo2", "bo2", "ln2_w", "ln2_b")
+    ts = [_chk(t, n) for n, t in zip(names, (wq, bq, wk, bk, wv, bv, wo, bo, ln1_w, ln1_b, wi, bi, wo2, bo2, ln2_w, ln2_b))]
+    B, T, D = x.shape
+    if D % 64:
+        raise ValueError(f"bert_layer: D = {D} is no multiple of the head width 64")
+    Dff = ts[10].shape[0]
+    want = [(D, D), (D,)] * 3 + [(D, D), (D,), (D,), (D,), (Dff, D), (Dff,), (D, Dff), (D,), (D,), (D,)]
+    for n, t, s in zip(names, ts, want):
+        if tuple(t.shape) != s:
+            raise ValueError(f"bert_layer: {n} has shape {tuple(t.shape)}, expected {s}")
+    if key_bias is not None:
+        key_bias = _chk(key_bias, "key_bias", 2)
+        if key_bias.shape != (B, T):
+            raise ValueError(f"bert_layer: key_bias {tuple(key_bias.shape)}, expected ({B}, {T})")
+    p_attn, p_hidden = (float(p_attn), float(p_hidden)) if training else (0.0, 0.0)
+    if (p_attn > 0 or p_hidden > 0) and snap is None:
+        snap = rng_snapshot(x.device)
+    # query | key | value stacked: one product instead of three (autograd splits the gradients again), as lstm_layer stacks directions
+    wqkv, bqkv = torch.cat([ts[0], ts[2], ts[4]], 0), torch.cat([ts[1], ts[3], ts[5]], 0)
+    return BertLayerFn.apply(x, key_bias, D // 64, p_attn, p_hidden, snap if (p_attn > 0 or p_hidden > 0) else None, wqkv, bqkv, *ts[6:])

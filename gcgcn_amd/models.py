@@ -213,7 +213,11 @@ class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
     ``bert``: the encoder module, called as the reference calls it -- ``bert(document[B,T], output_all_encoded_layers=False)`` ->
     ``(states[B,T,768], pooled)``.  Default: ``pytorch_pretrained_bert.BertModel.from_pretrained('./bert/bert-base-uncased')``
     exactly as bert:228; that package / those weights are third-party and are not part of this library, so without them the
-    constructor raises ImportError unless an encoder is passed in."""
+    constructor raises ImportError unless an encoder is passed in.
+
+    ``config.bert_impl = "torch" | "hip"`` builds this library's own encoder instead: ``gcgcn_amd.BertModel(config.bert_config or
+    BertConfig(), impl=...)``, its weights loaded from the LOCAL file ``config.bert_weights`` when that is set; the token width
+    follows ``bert_config.hidden_size``.  Without ``bert_impl`` nothing changes."""
 
     WORD_VEC_SIZE = 768
     _KEY_ORDER = ("bert", "ner_emb", "entity_embed", "get_weighted_adj_matrix", "get_adj_matrix", "graphcnn", "linear_re",
@@ -222,6 +226,16 @@ class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
 
     def __init__(self, config, bert: Optional[nn.Module] = None):
         super().__init__(config, layer_num=4, head_num=4)                                   # bert:247-248
+        impl = getattr(config, "bert_impl", None)
+        if bert is None and impl is not None:                                                # this library's own encoder (bert.py)
+            from .bert import BertConfig, BertModel as OwnBert, load_pretrained_state_dict
+            if impl not in ("torch", "hip"):
+                raise ValueError(f"config.bert_impl must be 'torch' or 'hip', got {impl!r}")
+            bert = OwnBert(getattr(config, "bert_config", None) or BertConfig(), impl=impl)
+            if getattr(config, "bert_weights", None):
+                load_pretrained_state_dict(bert, config.bert_weights)
+            if bert.config.hidden_size != self.WORD_VEC_SIZE:
+                self.WORD_VEC_SIZE = bert.config.hidden_size
         if bert is None:
             try:
                 from pytorch_pretrained_bert import BertModel

@@ -604,6 +604,52 @@ int gcgcn_context_bwd(int B, int T, int N, int K, int Hd, const float* h, const 
                       const float* dctx, const float* dnode_feat, float* dpre, float* dh, float* dw, float* db, void* ws,
                       int64_t ws_bytes, void* stream);
 
+/* ---- the BERT encoder layer (pytorch_pretrained_bert 0.6 BertLayer; bert.hip) --------------------------
+ * Attention core on PACKED qkv [B][T][3 D], D = H * dh: row (b, t) holds q | k | v, head h in columns [dh h, dh h + dh) of each.
+ *   S = q k^T / sqrt(dh) + key_bias[b][key]      key_bias [B][T] (the additive penalty, finite) or NULL
+ *   P = dropout(softmax over keys of S)          element (b, h, i, j) draws index ((b H + h) T + i) T + j of site (rng_snap, salt)
+ *   ctx [B][T][D] = P v, heads concatenated;  lse [B][H][T] = log sum_j exp(S_ij - c_b), c_b = max_j key_bias[b][j] (0 without
+ *   key_bias): the log-sum-exp of the row is lse + c_b.  The kernels subtract c_b from the penalties first (a softmax does not see a
+ *   shift common to its keys), so a document whose keys are ALL masked keeps the scores' low bits.
+ * gcgcn_bert_attn_bwd: dctx [B][T][D] -> dqkv [B][T][3 D] = dq | dk | dv; delta: [B][H][T] floats of scratch.  P is recomputed from q, k
+ * and lse, the dropout decisions from the same (rng_snap, salt, p); no [T][T] tensor is written to memory in either direction.
+ * dh = 64 and T <= 512 are served; anything else is refused (gcgcn_last_error).  rng_snap may be NULL when p = 0.
+ * y = LayerNorm(dropout(x + bias) + res) over rows of D (a multiple of 64, <= 1024), biased variance, eps = 1e-12: bias [D], res
+ * [rows][D] and the dropout (p = 0) are each optional; dropout index = row D + col.  mean / rstd [rows]: both or neither; the
+ * backward needs them.  gcgcn_res_ln_bwd: dx (the gradient of x; its column sums are the gradient of bias), dres (or NULL),
+ * dweight / dlnb [D] by a two-stage column sum in a fixed order through ws (gcgcn_res_ln_ws_bytes(D) bytes).
+ * y = gelu(x + bias[col]) with gelu(z) = z / 2 (1 + erf(z / sqrt 2)), C a multiple of 4, bias [C] or NULL; dx may alias dy.
+ * One encoder layer.  params / grads: HOST arrays of GCGCN_BERT_LAYER_PARAMS device pointers, in this order (Linear weights [out][in]):
+ *   wqkv [3 D][D] (query | key | value stacked), bqkv [3 D], attention.output.dense weight [D][D], bias [D], attention.output.LayerNorm
+ *   weight, bias [D], intermediate.dense weight [Dff][D], bias [Dff], output.dense weight [D][Dff], bias [D], output.LayerNorm weight, bias.
+ * x, y, dy, dx [B][T][D].  saved: gcgcn_bert_layer_ws_bytes(..., 0) bytes the forward fills and the backward reads (7 D + 2 Dff + H + 4
+ * floats per token, beside the layer's input x); ws: gcgcn_bert_layer_ws_bytes(..., 1) bytes of scratch for the backward.  -1: the shape is refused.  Three dropout
+ * sites with salts of their own draw from one rng_snap: P (p_attn), the two Linear outputs in front of the LayerNorms (p_hidden).
+ * Nothing is allocated, the host never waits: capturable.  No float is added atomically: results are bit-reproducible. */
+#define GCGCN_BERT_LAYER_PARAMS 12
+#define GCGCN_SALT_BERT_ATTN 0x42415431ull
+#define GCGCN_SALT_BERT_AO 0x42414f31ull
+#define GCGCN_SALT_BERT_OUT 0x424f5531ull
+#define GCGCN_SALT_BERT_EMB 0x42454d31ull /* the embeddings' dropout, after their LayerNorm (gcgcn_amd.BertModel: gcgcn_dropout) */
+int gcgcn_bert_attn_fwd(int B, int T, int H, int dh, const float* qkv, const float* key_bias, float* ctx, float* lse, const void* rng_snap,
+                        uint64_t salt, float p, void* stream);
+int gcgcn_bert_attn_bwd(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const float* ctx, const float* lse,
+                        const float* dctx, float* dqkv, float* delta, const void* rng_snap, uint64_t salt, float p, void* stream);
+int64_t gcgcn_res_ln_ws_bytes(int D);
+int gcgcn_res_ln_fwd(int64_t rows, int D, const float* x, const float* bias, const float* res, const float* weight, const float* lnb,
+                     float* y, float* mean, float* rstd, const void* rng_snap, uint64_t salt, float p, void* stream);
+int gcgcn_res_ln_bwd(int64_t rows, int D, const float* dy, const float* x, const float* bias, const float* res, const float* weight,
+                     const float* mean, const float* rstd, float* dx, float* dres, float* dweight, float* dlnb, void* ws, int64_t ws_bytes,
+                     const void* rng_snap, uint64_t salt, float p, void* stream);
+int gcgcn_bias_gelu_fwd(int64_t rows, int C, const float* x, const float* bias, float* y, void* stream);
+int gcgcn_bias_gelu_bwd(int64_t rows, int C, const float* dy, const float* x, const float* bias, float* dx, void* stream);
+int64_t gcgcn_bert_layer_ws_bytes(int B, int T, int D, int H, int Dff, int which);
+int gcgcn_bert_layer_fwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const float* const* params, float* y,
+                         void* saved, int64_t saved_bytes, const void* rng_snap, float p_attn, float p_hidden, void* stream);
+int gcgcn_bert_layer_bwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const float* const* params,
+                         const void* saved, int64_t saved_bytes, const float* dy, float* dx, float* const* grads, void* ws, int64_t ws_bytes,
+                         const void* rng_snap, float p_attn, float p_hidden, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

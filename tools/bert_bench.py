@@ -1,0 +1,126 @@
+#!/usr/bin/env python3
+"""Forward + backward time of the BERT encoder (gcgcn_amd.BertModel), impl="hip" against impl="torch" (fp32) on the same device in
+the same process: one encoder layer and the 12-layer base encoder at (B, T) = (4, 512) and (8, 256), eval-mode arithmetic with
+gradients (dropout off: both implementations then compute the same function), eager and as one replayed hipGraph; and the HIP
+layer's time split: each non-GEMM kernel timed on its own through the C ABI, the rest is the GEMM layer.
+
+    python tools/bert_bench.py [--layers 12] [--iters 20] [--json out.json]
+
+Prints one table and, with --json, writes the numbers.  DESIGN.md section 8.9 holds the table of record."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import gcgcn_amd  # noqa: E402
+from gcgcn_amd import _lib, BertConfig, BertModel  # noqa: E402
+
+
+def timed(fn, iters, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms)
+
+
+def model_step(layers, impl, B, T, dev):
+    cfg = BertConfig(num_hidden_layers=layers, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
+    torch.manual_seed(0)
+    model = BertModel(cfg, impl=impl).to(dev).train()
+    g = torch.Generator().manual_seed(1)
+    ids = torch.randint(0, cfg.vocab_size, (B, T), generator=g).to(dev)
+    mask = (torch.arange(T)[None, :] < torch.tensor([T - 37 * (b % 3) for b in range(B)])[:, None]).float().to(dev)
+    dy = torch.randn(B, T, cfg.hidden_size, generator=g).to(dev)
+
+    def step():
+        model.zero_grad(set_to_none=True)
+        out, pooled = model(ids, attention_mask=mask, output_all_encoded_layers=False)
+        ((out * dy).sum() + pooled.sum()).backward()
+    return step
+
+
+def graphed(step):
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        step()
+        step()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        step()
+    return graph.replay
+
+
+def kernel_split(B, T, dev, iters):
+    """ms of each non-GEMM kernel of one HIP layer at base size, forward and backward, timed alone (random data)."""
+    D, H, I = 768, 12, 3072
+    R = B * T
+    st = torch.cuda.current_stream().cuda_stream
+    p = lambda t: t.data_ptr()
+    qkv, dqkv = torch.randn(B, T, 3 * D, device=dev), torch.empty(B, T, 3 * D, device=dev)
+    kb = torch.zeros(B, T, device=dev)
+    ctx, dctx = torch.empty(B, T, D, device=dev), torch.randn(B, T, D, device=dev)
+    lse, delta = torch.empty(B, H, T, device=dev), torch.empty(B, H, T, device=dev)
+    x, res, y, dx, dres = (torch.randn(R, D, device=dev) for _ in range(5))
+    w, b, dw, db = (torch.randn(D, device=dev) for _ in range(4))
+    mean, rstd = torch.empty(R, device=dev), torch.empty(R, device=dev)
+    ws = torch.empty(_lib.lib().gcgcn_res_ln_ws_bytes(D) // 4, device=dev)
+    z, gz, bi = torch.randn(R, I, device=dev), torch.empty(R, I, device=dev), torch.randn(I, device=dev)
+    out = {}
+    out["attn_fwd"] = timed(lambda: _lib.call("gcgcn_bert_attn_fwd", B, T, H, 64, p(qkv), p(kb), p(ctx), p(lse), None, 0, 0.0, st), iters)
+    out["attn_bwd"] = timed(lambda: _lib.call("gcgcn_bert_attn_bwd", B, T, H, 64, p(qkv), p(kb), p(ctx), p(lse), p(dctx), p(dqkv), p(delta), None, 0,
+                                              0.0, st), iters)
+    out["res_ln_fwd x2"] = 2 * timed(lambda: _lib.call("gcgcn_res_ln_fwd", R, D, p(x), p(b), p(res), p(w), p(b), p(y), p(mean), p(rstd), None, 0, 0.0,
+                                                       st), iters)
+    out["res_ln_bwd x2"] = 2 * timed(lambda: _lib.call("gcgcn_res_ln_bwd", R, D, p(y), p(x), p(b), p(res), p(w), p(mean), p(rstd), p(dx), p(dres),
+                                                       p(dw), p(db), p(ws), ws.numel() * 4, None, 0, 0.0, st), iters)
+    out["gelu_fwd"] = timed(lambda: _lib.call("gcgcn_bias_gelu_fwd", R, I, p(z), p(bi), p(gz), st), iters)
+    out["gelu_bwd"] = timed(lambda: _lib.call("gcgcn_bias_gelu_bwd", R, I, p(gz), p(z), p(bi), p(gz), st), iters)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--layers", type=int, default=12)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--json")
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    torch.backends.cuda.matmul.allow_tf32 = False
+    rows = []
+    for B, T in ((4, 512), (8, 256)):
+        for layers in (1, a.layers):
+            r = {"B": B, "T": T, "layers": layers}
+            for impl in ("torch", "hip"):
+                step = model_step(layers, impl, B, T, dev)
+                r[f"{impl}_eager_ms"] = timed(step, a.iters)
+                r[f"{impl}_graph_ms"] = timed(graphed(step), a.iters)
+                del step
+                torch.cuda.empty_cache()
+            rows.append(r)
+            print(f"B={B} T={T} layers={layers:2d}: " + "  ".join(f"{k}={v:.3f}" for k, v in r.items() if k.endswith("_ms")), flush=True)
+        split = kernel_split(B, T, dev, a.iters)
+        rows.append({"B": B, "T": T, "split_ms": split})
+        print(f"B={B} T={T} one HIP layer, non-GEMM kernels alone: " + "  ".join(f"{k}={v:.3f}" for k, v in split.items()), flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
