@@ -131,6 +131,14 @@ SIGNATURES = {
     "gcgcn_bert_layer_ws_bytes": (L, [I] * 6),
     "gcgcn_bert_layer_fwd": (I, [I] * 5 + [P] * 5 + [L, P, F, F, P]),
     "gcgcn_bert_layer_bwd": (I, [I] * 5 + [P] * 4 + [L, P, P, P, P, L, P, F, F, P]),
+    "gcgcn_bert_attn_fwd_len": (I, [I] * 4 + [P] * 6 + [c_uint64, F, P]),
+    "gcgcn_bert_attn_bwd_len": (I, [I] * 4 + [P] * 9 + [c_uint64, F, P]),
+    "gcgcn_res_ln_fwd_len": (I, [L, I] + [P] * 6 + [I] + [P] * 4 + [c_uint64, F, P]),
+    "gcgcn_res_ln_bwd_len": (I, [L, I] + [P] * 8 + [I] + [P] * 5 + [L, P, c_uint64, F, P]),
+    "gcgcn_bias_gelu_fwd_len": (I, [L, I, P, P, P, I, P, P]),
+    "gcgcn_bias_gelu_bwd_len": (I, [L, I, P, P, P, P, I, P, P]),
+    "gcgcn_bert_layer_fwd_len": (I, [I] * 5 + [P] * 7 + [L, P, F, F, P]),
+    "gcgcn_bert_layer_bwd_len": (I, [I] * 5 + [P] * 6 + [L, P, P, P, P, L, P, F, F, P]),
 }
 
 _lib = None

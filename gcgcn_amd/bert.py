@@ -131,6 +131,16 @@ class BertModel(nn.Module):
     ``pooled = tanh(pooler.dense(encoded_last[:, 0]))``.  ``attention_mask`` ``[B,T]`` (1 = a token, 0 = padding) becomes the additive
     penalty ``(1 - mask) * -10000`` on the scores: a row whose keys are all masked is a finite softmax.
 
+    ``lengths``: the documents' token counts ``[B]`` (integers, ``0 <= lengths[b] <= T``), or None.  Row ``(b, t)`` is live iff
+    ``t < lengths[b]``.  Live rows of every layer's output, and every gradient, are what the model computes for document ``b`` ALONE,
+    truncated to ``lengths[b]`` tokens, with no mask; padding rows of every layer's output are exactly zero whatever token ids sit
+    there, and a gradient arriving on them is ignored (NaN included).  ``attention_mask`` may still be given on top (holes inside
+    the prefix).  ``pooled`` is computed from row 0 as before: for a document of length 0 that row is zero and ``pooled`` is
+    ``tanh(pooler.dense.bias)``.  ``impl="hip"`` routes the lengths through the kernels (csrc/bert.hip: the attention core streams
+    the live keys only, the Linears run on the live 16-row blocks, nothing is read on the host, a captured step replays on new
+    lengths); ``impl="torch"`` implements the same contract as a prefix mask plus ``torch.where`` on the padding rows.  The dropout
+    indices are the padded tensors', so from one snapshot the length path and the prefix-mask path drop the same live elements.
+
     ``dropout_override``: None, or ``f(layer, site, t) -> t`` replacing the dropout of site "emb" (layer -1), "attn", "ao", "out" of
     the torch implementation -- how a test replays the masks the HIP kernels drew.  After a training forward of ``impl="hip"``,
     ``last_rng_snaps`` holds the snapshots it used: ``[0]`` for the embeddings, ``[1 + l]`` for layer ``l``."""
@@ -165,9 +175,11 @@ class BertModel(nn.Module):
             return self.dropout_override(layer, site, t)
         return F.dropout(t, p, self.training)
 
-    def forward(self, input_ids, token_type_ids=None, attention_mask=None, output_all_encoded_layers=True):
+    def forward(self, input_ids, token_type_ids=None, attention_mask=None, output_all_encoded_layers=True, lengths=None):
         c, e = self.config, self.embeddings
         B, T = input_ids.shape
+        if lengths is not None and tuple(lengths.shape) != (B,):
+            raise ValueError(f"BertModel: lengths {tuple(lengths.shape)}, expected ({B},)")
         if T > c.max_position_embeddings:
             raise ValueError(f"BertModel: {T} tokens exceed max_position_embeddings = {c.max_position_embeddings}")
         tt = torch.zeros_like(input_ids) if token_type_ids is None else token_type_ids
@@ -175,19 +187,27 @@ class BertModel(nn.Module):
         emb = e.word_embeddings(input_ids) + e.position_embeddings(pos)[None] + e.token_type_embeddings(tt)
         key_bias = None if attention_mask is None else (1.0 - attention_mask.to(emb.dtype)) * MASK_PENALTY
         if self.impl == "hip":
-            outs = self._encode_hip(emb, key_bias)
+            outs = self._encode_hip(emb, key_bias, lengths)
         else:
-            x = self._drop(-1, "emb", layer_norm(emb, e.LayerNorm.weight, e.LayerNorm.bias), c.hidden_dropout_prob)
+            live = None
+            if lengths is not None:     # the contract in plain PyTorch: a prefix mask on the keys, padding rows selected away
+                live = torch.arange(T, device=emb.device)[None, :] < lengths.to(emb.device)[:, None]
+                prefix = (~live).to(emb.dtype) * MASK_PENALTY      # exp(-10000 - max) is exactly 0 in float32 and in float64
+                key_bias = prefix if key_bias is None else key_bias + prefix
+                live = live[:, :, None]
+            # torch.where, not a product: its backward hands the unselected branch a zero whatever arrives, NaN included
+            zero_pad = (lambda t: t) if live is None else (lambda t: torch.where(live, t, torch.zeros((), dtype=t.dtype, device=t.device)))
+            x = zero_pad(self._drop(-1, "emb", layer_norm(emb, e.LayerNorm.weight, e.LayerNorm.bias), c.hidden_dropout_prob))
             outs = []
             for li, layer in enumerate(self.encoder.layer):
                 probs = {"attn": c.attention_probs_dropout_prob, "ao": c.hidden_dropout_prob, "out": c.hidden_dropout_prob}
-                x = torch_layer(x, key_bias, layer.tensors(), c.num_attention_heads, lambda s, t: self._drop(li, s, t, probs[s]))
+                x = zero_pad(torch_layer(x, key_bias, layer.tensors(), c.num_attention_heads, lambda s, t: self._drop(li, s, t, probs[s])))
                 outs.append(x)
         last = outs[-1] if outs else x
         pooled = torch.tanh(self.pooler.dense(last[:, 0]))
         return (outs if output_all_encoded_layers else last), pooled
 
-    def _encode_hip(self, emb, key_bias):
+    def _encode_hip(self, emb, key_bias, lengths=None):
         from . import _lib, functional as Fn
         c, e = self.config, self.embeddings
         if not emb.is_cuda:
@@ -195,10 +215,15 @@ class BertModel(nn.Module):
         training = self.training
         n = len(self.encoder.layer)
         snaps = []
+        tv = rowblk = None
+        if lengths is not None:      # one list of live 16-row blocks for every layer and its backward, built on the device
+            tv = lengths.to(device=emb.device, dtype=torch.int32).contiguous()
+            rowblk = Fn.row_blocks(tv, emb.shape[0], emb.shape[1])
         with Fn.rng_scope(emb.device, n + 1, enabled=training):
             snap = Fn.rng_snapshot(emb.device) if training and c.hidden_dropout_prob > 0 else None
             snaps.append(snap)
-            x = Fn.res_layer_norm(emb, e.LayerNorm.weight, e.LayerNorm.bias)      # the dropout follows the LayerNorm here
+            # the dropout follows the LayerNorm here; with lengths the LayerNorm zeroes the padding rows and the dropout keeps 0 at 0
+            x = Fn.res_layer_norm(emb, e.LayerNorm.weight, e.LayerNorm.bias, t_valid=tv)
             if snap is not None:
                 x = Fn.DropoutFn.apply(x, c.hidden_dropout_prob, snap, _lib.SALT_BERT_EMB)
             outs = []
@@ -207,7 +232,7 @@ class BertModel(nn.Module):
                 snap = Fn.rng_snapshot(emb.device) if training else None
                 snaps.append(snap)
                 x = Fn.bert_layer(x, kb, *layer.tensors(), p_attn=c.attention_probs_dropout_prob, p_hidden=c.hidden_dropout_prob,
-                                  training=training, snap=snap)
+                                  training=training, snap=snap, t_valid=tv, rowblk=rowblk)
                 outs.append(x)
         self.last_rng_snaps = snaps if training else None
         if not outs:

@@ -1306,4 +1306,103 @@ int gcgcn_bert_layer_bwd(int B, int T, int D, int H, int Dff, const float* x, co
                         p_attn, p_hidden, (hipStream_t)stream);
 }
 
+// ---- the same with per-document token lengths (t_valid int32 [B] on the device, row (b, t) live iff t < t_valid[b]; gcgcn.h) -----------
+static int bert_len_ok(const char* who, const int32_t* t_valid, int64_t rows, int T) {
+  GC_REQUIRE(t_valid, "%s: t_valid is null (the entry point without _len takes no lengths)", who);
+  GC_REQUIRE(T >= 1 && rows % T == 0, "%s: %lld rows are no whole documents of T = %d", who, (long long)rows, T);
+  return 0;
+}
+int gcgcn_bert_attn_fwd_len(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const int32_t* t_valid, float* ctx,
+                            float* lse, const void* rng_snap, uint64_t salt, float p, void* stream) {
+  GC_TRY(bert_attn_shape_ok("bert_attn_fwd_len", B, T, H, dh));
+  GC_TRY(bert_drop_ok("bert_attn_fwd_len", rng_snap, p));
+  GC_REQUIRE(qkv && ctx && lse && t_valid, "bert_attn_fwd_len: null pointer");
+  GC_REQUIRE(al16(qkv), "bert_attn_fwd_len: qkv must be 16-byte aligned");
+  return bert_attn_fwd(B, T, H, qkv, key_bias, ctx, lse, make_drop(rng_snap, salt, p), (hipStream_t)stream, t_valid);
+}
+int gcgcn_bert_attn_bwd_len(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const int32_t* t_valid, const float* ctx,
+                            const float* lse, const float* dctx, float* dqkv, float* delta, const void* rng_snap, uint64_t salt, float p,
+                            void* stream) {
+  GC_TRY(bert_attn_shape_ok("bert_attn_bwd_len", B, T, H, dh));
+  GC_TRY(bert_drop_ok("bert_attn_bwd_len", rng_snap, p));
+  GC_REQUIRE(qkv && ctx && lse && dctx && dqkv && delta && t_valid, "bert_attn_bwd_len: null pointer");
+  GC_REQUIRE(al16(qkv) && al16(dctx), "bert_attn_bwd_len: qkv and dctx must be 16-byte aligned");
+  return bert_attn_bwd(B, T, H, qkv, key_bias, ctx, lse, dctx, dqkv, delta, make_drop(rng_snap, salt, p), (hipStream_t)stream, t_valid);
+}
+int gcgcn_res_ln_fwd_len(int64_t rows, int D, const float* x, const float* bias, const float* res, const float* weight, const float* lnb,
+                         const int32_t* t_valid, int T, float* y, float* mean, float* rstd, const void* rng_snap, uint64_t salt, float p,
+                         void* stream) {
+  GC_TRY(res_ln_shape_ok("res_ln_fwd_len", rows, D));
+  GC_TRY(bert_len_ok("res_ln_fwd_len", t_valid, rows, T));
+  GC_TRY(bert_drop_ok("res_ln_fwd_len", rng_snap, p));
+  GC_REQUIRE(x && weight && lnb && y && (!mean == !rstd), "res_ln_fwd_len: null pointer");
+  return res_ln_fwd(rows, D, x, bias, res, weight, lnb, y, mean, rstd, make_drop(rng_snap, salt, p), (hipStream_t)stream, t_valid, T);
+}
+int gcgcn_res_ln_bwd_len(int64_t rows, int D, const float* dy, const float* x, const float* bias, const float* res, const float* weight,
+                         const float* mean, const float* rstd, const int32_t* t_valid, int T, float* dx, float* dres, float* dweight,
+                         float* dlnb, void* ws, int64_t ws_bytes, const void* rng_snap, uint64_t salt, float p, void* stream) {
+  GC_TRY(res_ln_shape_ok("res_ln_bwd_len", rows, D));
+  GC_TRY(bert_len_ok("res_ln_bwd_len", t_valid, rows, T));
+  GC_TRY(bert_drop_ok("res_ln_bwd_len", rng_snap, p));
+  GC_REQUIRE(dy && x && weight && mean && rstd && dx && dweight && dlnb && ws, "res_ln_bwd_len: null pointer");
+  GC_REQUIRE(ws_bytes >= gcgcn_res_ln_ws_bytes(D), "res_ln_bwd_len: workspace of %lld bytes needed (gcgcn_res_ln_ws_bytes)",
+             (long long)gcgcn_res_ln_ws_bytes(D));
+  return res_ln_bwd(rows, D, dy, x, bias, res, weight, mean, rstd, dx, dres, dweight, dlnb, (float*)ws, make_drop(rng_snap, salt, p),
+                    (hipStream_t)stream, t_valid, T);
+}
+int gcgcn_bias_gelu_fwd_len(int64_t rows, int C, const float* x, const float* bias, const int32_t* t_valid, int T, float* y, void* stream) {
+  GC_REQUIRE(x && y, "bias_gelu_fwd_len: null pointer");
+  GC_TRY(gelu_shape_ok("bias_gelu_fwd_len", rows, C, x, bias, y));
+  GC_TRY(bert_len_ok("bias_gelu_fwd_len", t_valid, rows, T));
+  return bias_gelu_fwd(rows, C, x, bias, y, (hipStream_t)stream, t_valid, T);
+}
+int gcgcn_bias_gelu_bwd_len(int64_t rows, int C, const float* dy, const float* x, const float* bias, const int32_t* t_valid, int T, float* dx,
+                            void* stream) {
+  GC_REQUIRE(dy && x && dx, "bias_gelu_bwd_len: null pointer");
+  GC_TRY(gelu_shape_ok("bias_gelu_bwd_len", rows, C, x, bias, dx));
+  GC_REQUIRE(al16(dy), "bias_gelu_bwd_len: buffers must be 16-byte aligned");
+  GC_TRY(bert_len_ok("bias_gelu_bwd_len", t_valid, rows, T));
+  return bias_gelu_bwd(rows, C, dy, x, bias, dx, (hipStream_t)stream, t_valid, T);
+}
+int gcgcn_bert_layer_fwd_len(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
+                             const int32_t* rowblk, const float* const* params, float* y, void* saved, int64_t saved_bytes,
+                             const void* rng_snap, float p_attn, float p_hidden, void* stream) {
+  GC_TRY(bert_layer_shape_ok("bert_layer_fwd_len", B, T, D, H, Dff));
+  GC_TRY(bert_drop_ok("bert_layer_fwd_len", rng_snap, p_attn));
+  GC_TRY(bert_drop_ok("bert_layer_fwd_len", rng_snap, p_hidden));
+  GC_TRY(bert_params_ok("bert_layer_fwd_len", params));
+  GC_REQUIRE(t_valid, "bert_layer_fwd_len: t_valid is null");
+  GC_REQUIRE(!rowblk || T % 16 == 0, "bert_layer_fwd_len: a row-block list needs T a multiple of 16 (T = %d)", T);
+  GC_REQUIRE(x && y && saved && al16(x) && al16(y) && al16(saved), "bert_layer_fwd_len: x, y, saved must be given and 16-byte aligned");
+  GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "bert_layer_fwd_len: %lld bytes of saved activations needed "
+             "(gcgcn_bert_layer_ws_bytes, which = 0)", (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
+  const BertLayerParams p = {params[0], params[1], params[2], params[3], params[4], params[5],
+                             params[6], params[7], params[8], params[9], params[10], params[11]};
+  return bert_layer_fwd(B, T, D, H, Dff, x, key_bias, p, y, (float*)saved, rng_snap, p_attn, p_hidden, (hipStream_t)stream, t_valid, rowblk);
+}
+int gcgcn_bert_layer_bwd_len(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
+                             const int32_t* rowblk, const float* const* params, const void* saved, int64_t saved_bytes, const float* dy,
+                             float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn, float p_hidden,
+                             void* stream) {
+  GC_TRY(bert_layer_shape_ok("bert_layer_bwd_len", B, T, D, H, Dff));
+  GC_TRY(bert_drop_ok("bert_layer_bwd_len", rng_snap, p_attn));
+  GC_TRY(bert_drop_ok("bert_layer_bwd_len", rng_snap, p_hidden));
+  GC_TRY(bert_params_ok("bert_layer_bwd_len", params));
+  GC_TRY(bert_params_ok("bert_layer_bwd_len", grads));
+  GC_REQUIRE(t_valid, "bert_layer_bwd_len: t_valid is null");
+  GC_REQUIRE(!rowblk || T % 16 == 0, "bert_layer_bwd_len: a row-block list needs T a multiple of 16 (T = %d)", T);
+  GC_REQUIRE(x && saved && dy && dx && ws && al16(x) && al16(saved) && al16(dy) && al16(dx) && al16(ws),
+             "bert_layer_bwd_len: x, saved, dy, dx, ws must be given and 16-byte aligned");
+  GC_REQUIRE(dx != dy, "bert_layer_bwd_len: dx aliases dy");
+  GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "bert_layer_bwd_len: %lld bytes of saved activations needed",
+             (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
+  GC_REQUIRE(ws_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1), "bert_layer_bwd_len: workspace of %lld bytes needed "
+             "(gcgcn_bert_layer_ws_bytes, which = 1)", (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1));
+  const BertLayerParams p = {params[0], params[1], params[2], params[3], params[4], params[5],
+                             params[6], params[7], params[8], params[9], params[10], params[11]};
+  const BertLayerGrads g = {grads[0], grads[1], grads[2], grads[3], grads[4], grads[5], grads[6], grads[7], grads[8], grads[9], grads[10], grads[11]};
+  return bert_layer_bwd(B, T, D, H, Dff, x, key_bias, p, (const float*)saved, dy, dx, g, (float*)ws, ws_bytes / (int64_t)sizeof(float), rng_snap,
+                        p_attn, p_hidden, (hipStream_t)stream, t_valid, rowblk);
+}
+
 }  // extern "C"

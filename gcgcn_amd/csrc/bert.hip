@@ -28,6 +28,7 @@
 // through a select, rows past T are not stored: what lies behind a buffer's end is never read and never reaches a result.
 #include "bert.hpp"
 #include "gemm.hpp"
+#include "rowops.hpp"
 
 namespace gc {
 
@@ -101,10 +102,20 @@ __device__ __forceinline__ float doc_bias_max(const float* __restrict__ kb, cons
   return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
 }
 
+// Token lengths (LEN instantiations; t_valid [B], row (b, t) is live iff t < t_valid[b]).  Tl = the document's length clamped to
+// [0, T] takes T's place in every predicate -- the rows that are loaded, the keys that get a probability, the streamed loop's end --
+// while T keeps the strides and the dropout index.  A workgroup whose 16 rows are all padding stores its zeros and leaves before
+// the first barrier; one that holds the document's last live rows stores zeros on the padding rows beside them.  Both decisions
+// are uniform per workgroup and made outside the matrix-instruction sequences.  Without LEN the code is what it was.
+__device__ __forceinline__ int live_len(const int* __restrict__ t_valid, const int b, const int T) {
+  return __builtin_amdgcn_readfirstlane(min(max(t_valid[b], 0), T));
+}
+
 // ---- forward -------------------------------------------------------------------------------------------------------------------
+template <bool LEN>
 __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const float* __restrict__ qkv, const float* __restrict__ key_bias,
                                                             float* __restrict__ ctx, float* __restrict__ lse, const int T, const int H,
-                                                            const float alpha, const Drop drop) {
+                                                            const float alpha, const Drop drop, const int* __restrict__ t_valid) {
   __shared__ __attribute__((aligned(16))) float Qs[AQ * AS];
   __shared__ __attribute__((aligned(16))) float Bs[AK * AS];
   __shared__ __attribute__((aligned(16))) float Ss[AQ * SS];
@@ -113,18 +124,27 @@ __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const float* __restr
   const long ld = 3L * D;
   const float* base = qkv + (long)b * T * ld + h * AD;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, c16 = l & 15, q = l >> 4;
-  const int nkb = (T + AK - 1) / AK;
+  const int Tl = LEN ? live_len(t_valid, b, T) : T;
+  if (LEN && q0 >= Tl) {   // padding rows only: ctx = 0 (the products behind it read these rows), lse = 0
+    for (int i = threadIdx.x; i < AQ * AD; i += 256) {
+      const int r = q0 + (i >> 6);
+      if (r < T) ctx[((long)b * T + r) * D + h * AD + (i & 63)] = 0.f;
+    }
+    if (threadIdx.x < AQ && q0 + threadIdx.x < T) lse[((long)b * H + h) * T + q0 + threadIdx.x] = 0.f;
+    return;
+  }
+  const int nkb = (Tl + AK - 1) / AK;
   __shared__ float shm[4];
-  const float cb = doc_bias_max(key_bias ? key_bias + (long)b * T : nullptr, T, shm);
+  const float cb = doc_bias_max(key_bias ? key_bias + (long)b * T : nullptr, Tl, shm);
 
-  load_rows<AQ>(Qs, base, ld, q0, T);
+  load_rows<AQ>(Qs, base, ld, q0, Tl);
   for (int kb = 0; kb < nkb; ++kb) {
     __syncthreads();   // the previous block's readers are done with Bs
-    load_rows<AK>(Bs, base + D, ld, kb * AK, T);
+    load_rows<AK>(Bs, base + D, ld, kb * AK, Tl);
     __syncthreads();
     const f32x4 s = tile_nt(Qs + c16 * AS, Bs + (16 * w + c16) * AS, q);
     const int key = kb * AK + 16 * w + c16;
-    const bool kin = key < T;
+    const bool kin = key < Tl;
     const float kbv = kin && key_bias ? key_bias[(long)b * T + key] - cb : 0.f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) Ss[(4 * q + r) * SS + key] = kin ? __builtin_fmaf(s[r], alpha, kbv) : -INFINITY;
@@ -143,7 +163,7 @@ __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const float* __restr
 #pragma unroll
     for (int o = 8; o; o >>= 1) sum += __shfl_xor(sum, o, 16);
     const float L = m + logf(sum);
-    if (sub == 0 && i < T) lse[((long)b * H + h) * T + i] = L;
+    if (sub == 0 && i < T) lse[((long)b * H + h) * T + i] = i < Tl ? L : 0.f;
     const bool dr = drop.snap != nullptr;
     const uint64_t dk = dr ? drop_key(drop) : 0;
     const uint64_t slice = ((uint64_t)b * H + h) * (uint64_t)T;
@@ -157,35 +177,40 @@ __global__ __launch_bounds__(256) void bert_attn_fwd_kernel(const float* __restr
   f32x4 o = {0.f, 0.f, 0.f, 0.f};
   for (int kb = 0; kb < nkb; ++kb) {
     __syncthreads();   // the probabilities are written; the previous block's readers are done with Bs
-    load_rows<AK>(Bs, base + 2 * D, ld, kb * AK, T);
+    load_rows<AK>(Bs, base + 2 * D, ld, kb * AK, Tl);
     __syncthreads();
     o += tile_nn(Ss + c16 * SS + kb * AK, Bs + 16 * w + c16, q);
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int i = q0 + 4 * q + r;
-    if (i < T) ctx[((long)b * T + i) * D + h * AD + 16 * w + c16] = o[r];
+    if (i < T) ctx[((long)b * T + i) * D + h * AD + 16 * w + c16] = i < Tl ? o[r] : 0.f;
   }
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------------------
 // delta [B][H][T] = sum_d dctx * ctx: one wave per (b, t, h)
+template <bool LEN>
 __global__ __launch_bounds__(256) void bert_attn_delta_kernel(const float* __restrict__ ctx, const float* __restrict__ dctx,
-                                                              float* __restrict__ delta, const long n, const int T, const int H) {
+                                                              float* __restrict__ delta, const long n, const int T, const int H,
+                                                              const int* __restrict__ t_valid) {
   const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);   // (b T + t) H + h
   if (i >= n) return;
   const int l = threadIdx.x & 63;
-  const float s = wave_sum(ctx[i * AD + l] * dctx[i * AD + l]);
   const int h = (int)(i % H);
   const long bt = i / H;
+  const bool pad = LEN && (int)(bt % T) >= live_len(t_valid, (int)(bt / T), T);   // wave-uniform; dctx of a padding row is not read
+  const float s = pad ? 0.f : wave_sum(ctx[i * AD + l] * dctx[i * AD + l]);
   if (l == 0) delta[((bt / T) * H + h) * T + bt % T] = s;
 }
 
 // dq of a query block: streams key blocks.  dS_ij = P_ij (keep_ij dP_ij - delta_i), dP = dO v^T, dq = alpha dS k.
+template <bool LEN>
 __global__ __launch_bounds__(256) void bert_attn_bwd_q_kernel(const float* __restrict__ qkv, const float* __restrict__ key_bias,
                                                               const float* __restrict__ lse, const float* __restrict__ delta,
                                                               const float* __restrict__ dctx, float* __restrict__ dqkv, const int T,
-                                                              const int H, const float alpha, const Drop drop) {
+                                                              const int H, const float alpha, const Drop drop,
+                                                              const int* __restrict__ t_valid) {
   __shared__ __attribute__((aligned(16))) float Qs[AQ * AS];
   __shared__ __attribute__((aligned(16))) float Gs[AQ * AS];    // dO
   __shared__ __attribute__((aligned(16))) float Ks[AK * AS];
@@ -197,36 +222,44 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_q_kernel(const float* __res
   const long ld = 3L * D;
   const float* base = qkv + (long)b * T * ld + h * AD;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, c16 = l & 15, q = l >> 4;
-  const int nkb = (T + AK - 1) / AK;
+  const int Tl = LEN ? live_len(t_valid, b, T) : T;
+  if (LEN && q0 >= Tl) {   // padding rows only: dq = 0 (the weight gradient and the bias' column sums read these rows)
+    for (int i = threadIdx.x; i < AQ * AD; i += 256) {
+      const int r = q0 + (i >> 6);
+      if (r < T) dqkv[((long)b * T + r) * ld + h * AD + (i & 63)] = 0.f;
+    }
+    return;
+  }
+  const int nkb = (Tl + AK - 1) / AK;
   const bool dr = drop.snap != nullptr;
   const uint64_t dk = dr ? drop_key(drop) : 0;
   const uint64_t slice = ((uint64_t)b * H + h) * (uint64_t)T;
   __shared__ float shm[4];
-  const float cb = doc_bias_max(key_bias ? key_bias + (long)b * T : nullptr, T, shm);
+  const float cb = doc_bias_max(key_bias ? key_bias + (long)b * T : nullptr, Tl, shm);
 
-  load_rows<AQ>(Qs, base, ld, q0, T);
-  load_rows<AQ>(Gs, dctx + (long)b * T * D + h * AD, D, q0, T);
+  load_rows<AQ>(Qs, base, ld, q0, Tl);
+  load_rows<AQ>(Gs, dctx + (long)b * T * D + h * AD, D, q0, Tl);
   if (threadIdx.x < AQ) {
     const int i = q0 + threadIdx.x;
     const long o = ((long)b * H + h) * T + i;
-    Ls[threadIdx.x] = i < T ? lse[o] : 0.f;
-    Dl[threadIdx.x] = i < T ? delta[o] : 0.f;
+    Ls[threadIdx.x] = i < Tl ? lse[o] : 0.f;
+    Dl[threadIdx.x] = i < Tl ? delta[o] : 0.f;
   }
   f32x4 dq = {0.f, 0.f, 0.f, 0.f};
   for (int kb = 0; kb < nkb; ++kb) {
     __syncthreads();   // the previous block's readers are done with Ks and Ds
-    load_rows<AK>(Ks, base + D, ld, kb * AK, T);
-    load_rows<AK>(Vs, base + 2 * D, ld, kb * AK, T);
+    load_rows<AK>(Ks, base + D, ld, kb * AK, Tl);
+    load_rows<AK>(Vs, base + 2 * D, ld, kb * AK, Tl);
     __syncthreads();
     const f32x4 s = tile_nt(Qs + c16 * AS, Ks + (16 * w + c16) * AS, q);
     const f32x4 dp = tile_nt(Gs + c16 * AS, Vs + (16 * w + c16) * AS, q);
     const int key = kb * AK + 16 * w + c16;
-    const bool kin = key < T;
+    const bool kin = key < Tl;
     const float kbv = kin && key_bias ? key_bias[(long)b * T + key] - cb : 0.f;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = 4 * q + r, i = q0 + row;
-      const float p = kin && i < T ? expf(__builtin_fmaf(s[r], alpha, kbv) - Ls[row]) : 0.f;
+      const float p = kin && i < Tl ? expf(__builtin_fmaf(s[r], alpha, kbv) - Ls[row]) : 0.f;
       const float dpv = dr ? dp[r] * attn_keep(drop, dk, slice, i, key, T) : dp[r];
       Ds[row * AS + 16 * w + c16] = p * (dpv - Dl[row]);
     }
@@ -236,16 +269,18 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_q_kernel(const float* __res
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int i = q0 + 4 * q + r;
-    if (i < T) dqkv[((long)b * T + i) * ld + h * AD + 16 * w + c16] = dq[r] * alpha;
+    if (i < T) dqkv[((long)b * T + i) * ld + h * AD + 16 * w + c16] = i < Tl ? dq[r] * alpha : 0.f;
   }
 }
 
 // dk and dv of a key block: streams query blocks.  The tiles are the transposes: S^T = k q^T, dP^T = v dO^T, rows = the block's keys.
 // dv = Pd^T dO (Pd = the dropped probabilities), dk = alpha dS^T q.
+template <bool LEN>
 __global__ __launch_bounds__(256) void bert_attn_bwd_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ key_bias,
                                                                const float* __restrict__ lse, const float* __restrict__ delta,
                                                                const float* __restrict__ dctx, float* __restrict__ dqkv, const int T,
-                                                               const int H, const float alpha, const Drop drop) {
+                                                               const int H, const float alpha, const Drop drop,
+                                                               const int* __restrict__ t_valid) {
   __shared__ __attribute__((aligned(16))) float Ks[AQ * AS];
   __shared__ __attribute__((aligned(16))) float Vs[AQ * AS];
   __shared__ __attribute__((aligned(16))) float Qs[AK * AS];
@@ -259,31 +294,42 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_kv_kernel(const float* __re
   const float* base = qkv + (long)b * T * ld + h * AD;
   const float* gbase = dctx + (long)b * T * D + h * AD;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, c16 = l & 15, q = l >> 4;
-  const int nqb = (T + AK - 1) / AK;
+  const int Tl = LEN ? live_len(t_valid, b, T) : T;
+  if (LEN && k0 >= Tl) {   // padding rows only: dk = dv = 0
+    for (int i = threadIdx.x; i < AQ * AD; i += 256) {
+      const int r = k0 + (i >> 6);
+      if (r < T) {
+        float* o = dqkv + ((long)b * T + r) * ld + h * AD + (i & 63);
+        o[D] = 0.f, o[2 * D] = 0.f;
+      }
+    }
+    return;
+  }
+  const int nqb = (Tl + AK - 1) / AK;
   const bool dr = drop.snap != nullptr;
   const uint64_t dk_ = dr ? drop_key(drop) : 0;
   const uint64_t slice = ((uint64_t)b * H + h) * (uint64_t)T;
 
   __shared__ float shm[4];
-  const float cb = doc_bias_max(key_bias ? key_bias + (long)b * T : nullptr, T, shm);
-  load_rows<AQ>(Ks, base + D, ld, k0, T);
-  load_rows<AQ>(Vs, base + 2 * D, ld, k0, T);
+  const float cb = doc_bias_max(key_bias ? key_bias + (long)b * T : nullptr, Tl, shm);
+  load_rows<AQ>(Ks, base + D, ld, k0, Tl);
+  load_rows<AQ>(Vs, base + 2 * D, ld, k0, Tl);
   float kbv[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int key = k0 + 4 * q + r;
-    kbv[r] = key < T && key_bias ? key_bias[(long)b * T + key] - cb : 0.f;
+    kbv[r] = key < Tl && key_bias ? key_bias[(long)b * T + key] - cb : 0.f;
   }
   f32x4 dk = {0.f, 0.f, 0.f, 0.f}, dv = {0.f, 0.f, 0.f, 0.f};
   for (int qb = 0; qb < nqb; ++qb) {
     __syncthreads();   // the previous block's readers are done with Qs, Gs, Ps, Ds, Ls, Dl
-    load_rows<AK>(Qs, base, ld, qb * AK, T);
-    load_rows<AK>(Gs, gbase, D, qb * AK, T);
+    load_rows<AK>(Qs, base, ld, qb * AK, Tl);
+    load_rows<AK>(Gs, gbase, D, qb * AK, Tl);
     if (threadIdx.x < AK) {
       const int i = qb * AK + threadIdx.x;
       const long o = ((long)b * H + h) * T + i;
-      Ls[threadIdx.x] = i < T ? lse[o] : 0.f;
-      Dl[threadIdx.x] = i < T ? delta[o] : 0.f;
+      Ls[threadIdx.x] = i < Tl ? lse[o] : 0.f;
+      Dl[threadIdx.x] = i < Tl ? delta[o] : 0.f;
     }
     __syncthreads();
     const f32x4 st = tile_nt(Ks + c16 * AS, Qs + (16 * w + c16) * AS, q);
@@ -293,7 +339,7 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_kv_kernel(const float* __re
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = 4 * q + r, key = k0 + row;
-      const float p = key < T && i < T ? expf(__builtin_fmaf(st[r], alpha, kbv[r]) - Li) : 0.f;
+      const float p = key < Tl && i < Tl ? expf(__builtin_fmaf(st[r], alpha, kbv[r]) - Li) : 0.f;
       const float keep = dr ? attn_keep(drop, dk_, slice, i, key, T) : 1.f;
       Ps[row * AS + qi] = p * keep;
       Ds[row * AS + qi] = p * (dpt[r] * keep - di);
@@ -307,33 +353,38 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_kv_kernel(const float* __re
     const int key = k0 + 4 * q + r;
     if (key < T) {
       float* o = dqkv + ((long)b * T + key) * ld + h * AD + 16 * w + c16;
-      o[D] = dk[r] * alpha;
-      o[2 * D] = dv[r];
+      o[D] = key < Tl ? dk[r] * alpha : 0.f;
+      o[2 * D] = key < Tl ? dv[r] : 0.f;
     }
   }
 }
 
-int bert_attn_fwd(int B, int T, int H, const float* qkv, const float* key_bias, float* ctx, float* lse, Drop drop, hipStream_t st) {
+int bert_attn_fwd(int B, int T, int H, const float* qkv, const float* key_bias, float* ctx, float* lse, Drop drop, hipStream_t st,
+                  const int* t_valid) {
   const float alpha = 1.f / sqrtf((float)AD);
-  GC_LAUNCH_TIMED("bert_attn_fwd", 4.0 * B * H * T * T * AD, bert_attn_fwd_kernel, dim3(cdiv(T, AQ), H, B), dim3(256), 0, st, qkv, key_bias,
-                  ctx, lse, T, H, alpha, drop);
+  const auto kernel = t_valid ? bert_attn_fwd_kernel<true> : bert_attn_fwd_kernel<false>;
+  GC_LAUNCH_TIMED("bert_attn_fwd", 4.0 * B * H * T * T * AD, kernel, dim3(cdiv(T, AQ), H, B), dim3(256), 0, st, qkv, key_bias, ctx, lse, T, H,
+                  alpha, drop, t_valid);
   return check_launch("bert_attn_fwd");
 }
 
 int bert_attn_bwd(int B, int T, int H, const float* qkv, const float* key_bias, const float* ctx, const float* lse, const float* dctx,
-                  float* dqkv, float* delta, Drop drop, hipStream_t st) {
+                  float* dqkv, float* delta, Drop drop, hipStream_t st, const int* t_valid) {
   const float alpha = 1.f / sqrtf((float)AD);
   const long n = (long)B * T * H;
   {
     ProfScope ps("bert_attn_delta", st);
-    hipLaunchKernelGGL(bert_attn_delta_kernel, dim3(cdiv(n, 4)), dim3(256), 0, st, ctx, dctx, delta, n, T, H);
+    const auto kd = t_valid ? bert_attn_delta_kernel<true> : bert_attn_delta_kernel<false>;
+    hipLaunchKernelGGL(kd, dim3(cdiv(n, 4)), dim3(256), 0, st, ctx, dctx, delta, n, T, H, t_valid);
     GC_TRY(check_launch("bert_attn_delta"));
   }
-  GC_LAUNCH_TIMED("bert_attn_bwd_q", 6.0 * B * H * T * T * AD, bert_attn_bwd_q_kernel, dim3(cdiv(T, AQ), H, B), dim3(256), 0, st, qkv,
-                  key_bias, lse, delta, dctx, dqkv, T, H, alpha, drop);
+  const auto kq = t_valid ? bert_attn_bwd_q_kernel<true> : bert_attn_bwd_q_kernel<false>;
+  GC_LAUNCH_TIMED("bert_attn_bwd_q", 6.0 * B * H * T * T * AD, kq, dim3(cdiv(T, AQ), H, B), dim3(256), 0, st, qkv, key_bias, lse, delta, dctx,
+                  dqkv, T, H, alpha, drop, t_valid);
   GC_TRY(check_launch("bert_attn_bwd_q"));
-  GC_LAUNCH_TIMED("bert_attn_bwd_kv", 8.0 * B * H * T * T * AD, bert_attn_bwd_kv_kernel, dim3(cdiv(T, AQ), H, B), dim3(256), 0, st, qkv,
-                  key_bias, lse, delta, dctx, dqkv, T, H, alpha, drop);
+  const auto kkv = t_valid ? bert_attn_bwd_kv_kernel<true> : bert_attn_bwd_kv_kernel<false>;
+  GC_LAUNCH_TIMED("bert_attn_bwd_kv", 8.0 * B * H * T * T * AD, kkv, dim3(cdiv(T, AQ), H, B), dim3(256), 0, st, qkv, key_bias, lse, delta, dctx,
+                  dqkv, T, H, alpha, drop, t_valid);
   return check_launch("bert_attn_bwd_kv");
 }
 
@@ -360,13 +411,22 @@ __device__ __forceinline__ void ln_input(float (&v)[LNV], const float* __restric
   }
 }
 
+// Token lengths (t_valid, T; rows = B T): the wave of a padding row stores zeros -- y, which the next product and the weight
+// gradient behind it read on every row, and mean / rstd -- and reads nothing: what x and res hold there (the rows a row-block
+// product left unwritten) never reaches a result.
 __global__ __launch_bounds__(256) void res_ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ bias,
                                                          const float* __restrict__ res, const float* __restrict__ weight,
                                                          const float* __restrict__ lnb, float* __restrict__ y, float* __restrict__ mean,
-                                                         float* __restrict__ rstd, const long rows, const int D, const Drop drop) {
+                                                         float* __restrict__ rstd, const long rows, const int D, const Drop drop,
+                                                         const int* __restrict__ t_valid, const int T) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;   // wave-uniform
   const int l = threadIdx.x & 63, n = D >> 6;
+  if (t_valid && (int)(row % T) >= live_len(t_valid, (int)(row / T), T)) {   // wave-uniform
+    for (int i = 0; i < n; ++i) y[row * D + l + 64 * i] = 0.f;
+    if (l == 0 && mean) mean[row] = 0.f, rstd[row] = 0.f;
+    return;
+  }
   const uint64_t dk = drop.snap ? drop_key(drop) : 0;
   float v[LNV];
   ln_input(v, x, bias, res, row, D, l, drop, dk);
@@ -394,7 +454,8 @@ __global__ __launch_bounds__(256) void res_ln_bwd_kernel(const float* __restrict
                                                          const float* __restrict__ res, const float* __restrict__ weight,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          float* __restrict__ dx, float* __restrict__ dres, float* __restrict__ part,
-                                                         const long rows, const int D, const Drop drop) {
+                                                         const long rows, const int D, const Drop drop, const int* __restrict__ t_valid,
+                                                         const int T) {
   __shared__ float sh[4][2][BERT_LN_MAX_D];
   const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, n = D >> 6;
   const uint64_t dk = drop.snap ? drop_key(drop) : 0;
@@ -402,6 +463,14 @@ __global__ __launch_bounds__(256) void res_ln_bwd_kernel(const float* __restrict
 #pragma unroll
   for (int i = 0; i < LNV; ++i) aw[i] = 0.f, ab[i] = 0.f;
   for (long row = (long)blockIdx.x * 4 + wv; row < rows; row += (long)gridDim.x * 4) {
+    if (t_valid && (int)(row % T) >= live_len(t_valid, (int)(row / T), T)) {   // a padding row (wave-uniform): dy there counts as zero and
+      for (int i = 0; i < n; ++i) {                                            // is not read; dx = dres = 0, nothing joins the column sums
+        const long o = row * D + l + 64 * i;
+        if (dres) dres[o] = 0.f;
+        dx[o] = 0.f;
+      }
+      continue;
+    }
     float v[LNV], g[LNV];
     ln_input(v, x, bias, res, row, D, l, drop, dk);
     const float m = mean[row], r = rstd[row];
@@ -449,18 +518,20 @@ __global__ __launch_bounds__(256) void res_ln_bwd_reduce_kernel(const float* __r
 }
 
 int res_ln_fwd(long rows, int D, const float* x, const float* bias, const float* res, const float* weight, const float* lnb, float* y,
-               float* mean, float* rstd, Drop drop, hipStream_t st) {
+               float* mean, float* rstd, Drop drop, hipStream_t st, const int* t_valid, int T) {
   ProfScope ps("bert_res_ln_fwd", st);
-  hipLaunchKernelGGL(res_ln_fwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, bias, res, weight, lnb, y, mean, rstd, rows, D, drop);
+  hipLaunchKernelGGL(res_ln_fwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, bias, res, weight, lnb, y, mean, rstd, rows, D, drop, t_valid,
+                     t_valid ? T : 1);
   return check_launch("res_ln_fwd");
 }
 
 int res_ln_bwd(long rows, int D, const float* dy, const float* x, const float* bias, const float* res, const float* weight,
                const float* mean, const float* rstd, float* dx, float* dres, float* dweight, float* dlnb, float* part, Drop drop,
-               hipStream_t st) {
+               hipStream_t st, const int* t_valid, int T) {
   const int G = (int)std::min<long>(BERT_LN_PARTS, cdiv(rows, 4));
   ProfScope ps("bert_res_ln_bwd", st);
-  hipLaunchKernelGGL(res_ln_bwd_kernel, dim3(G), dim3(256), 0, st, dy, x, bias, res, weight, mean, rstd, dx, dres, part, rows, D, drop);
+  hipLaunchKernelGGL(res_ln_bwd_kernel, dim3(G), dim3(256), 0, st, dy, x, bias, res, weight, mean, rstd, dx, dres, part, rows, D, drop,
+                     t_valid, t_valid ? T : 1);
   GC_TRY(check_launch("res_ln_bwd"));
   hipLaunchKernelGGL(res_ln_bwd_reduce_kernel, dim3(cdiv(2 * D, 256)), dim3(256), 0, st, part, G, D, dweight, dlnb);
   return check_launch("res_ln_bwd_reduce");
@@ -471,10 +542,20 @@ __device__ __forceinline__ float gelu_f(float z) { return z * 0.5f * (1.f + erff
 __device__ __forceinline__ float gelu_df(float z) {
   return 0.5f * (1.f + erff(z * 0.70710678118654752f)) + z * 0.39894228040143268f * expf(-0.5f * z * z);
 }
-template <bool BWD>
+// LEN (t_valid, T; rows = B T): an element of a padding row becomes zero -- g and dz are read on every row by the weight gradients
+// and the bias' column sum -- and neither x nor dy is read there.
+template <bool BWD, bool LEN>
 __global__ __launch_bounds__(256) void bias_gelu_kernel(const float* __restrict__ dy, const float* __restrict__ x, const float* __restrict__ bias,
-                                                        float* __restrict__ out, const long n4, const int C4) {
+                                                        float* __restrict__ out, const long n4, const int C4, const int* __restrict__ t_valid,
+                                                        const int T) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    if constexpr (LEN) {
+      const long row = i / C4;
+      if ((int)(row % T) >= min(max(t_valid[row / T], 0), T)) {
+        reinterpret_cast<float4*>(out)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        continue;
+      }
+    }
     float4 z = reinterpret_cast<const float4*>(x)[i];
     if (bias) {
       const float4 bv = reinterpret_cast<const float4*>(bias)[i % C4];
@@ -490,16 +571,19 @@ __global__ __launch_bounds__(256) void bias_gelu_kernel(const float* __restrict_
     reinterpret_cast<float4*>(out)[i] = o;
   }
 }
-int bias_gelu_fwd(long rows, int C, const float* x, const float* bias, float* y, hipStream_t st) {
+int bias_gelu_fwd(long rows, int C, const float* x, const float* bias, float* y, hipStream_t st, const int* t_valid, int T) {
   const long n4 = rows * C / 4;
   ProfScope ps("bert_gelu_fwd", st);
-  hipLaunchKernelGGL(bias_gelu_kernel<false>, dim3((int)std::min<long>(cdiv(n4, 256), 4096)), dim3(256), 0, st, nullptr, x, bias, y, n4, C / 4);
+  const auto kernel = t_valid ? bias_gelu_kernel<false, true> : bias_gelu_kernel<false, false>;
+  hipLaunchKernelGGL(kernel, dim3((int)std::min<long>(cdiv(n4, 256), 4096)), dim3(256), 0, st, (const float*)nullptr, x, bias, y, n4, C / 4,
+                     t_valid, T);
   return check_launch("bias_gelu_fwd");
 }
-int bias_gelu_bwd(long rows, int C, const float* dy, const float* x, const float* bias, float* dx, hipStream_t st) {
+int bias_gelu_bwd(long rows, int C, const float* dy, const float* x, const float* bias, float* dx, hipStream_t st, const int* t_valid, int T) {
   const long n4 = rows * C / 4;
   ProfScope ps("bert_gelu_bwd", st);
-  hipLaunchKernelGGL(bias_gelu_kernel<true>, dim3((int)std::min<long>(cdiv(n4, 256), 4096)), dim3(256), 0, st, dy, x, bias, dx, n4, C / 4);
+  const auto kernel = t_valid ? bias_gelu_kernel<true, true> : bias_gelu_kernel<true, false>;
+  hipLaunchKernelGGL(kernel, dim3((int)std::min<long>(cdiv(n4, 256), 4096)), dim3(256), 0, st, dy, x, bias, dx, n4, C / 4, t_valid, T);
   return check_launch("bias_gelu_bwd");
 }
 
@@ -551,61 +635,78 @@ Work work_views(float* base, int B, int T, int D, int H, int Dff) {
 long bert_layer_saved_elems(int B, int T, int D, int H, int Dff) { return saved_views(nullptr, B, T, D, H, Dff).total; }
 long bert_layer_ws_elems(int B, int T, int D, int H, int Dff) { return work_views(nullptr, B, T, D, H, Dff).total; }
 
+// Token lengths (t_valid; bert.hpp has the contract).  Every product runs on the live 16-row blocks where the launcher serves the
+// list (rowblk, gcgcn_row_blocks(B, T, t_valid); gemm_plan decides, per problem) and dense elsewhere.  Either way is correct because
+// no product's padding rows are read unguarded: the kernel BEHIND each product is length-aware and stores the zeros that the next
+// product, the weight gradients (which sum over the padding rows of a partly live block, or over all of them when dense) and the
+// bias' column sums read --
+//   forward :  qkv -> attention core (loads live rows only; ctx = 0),  ao -> LayerNorm (a = 0),  z -> GELU (g = 0),  o2 -> LayerNorm (y = 0)
+//   backward:  dy -> LayerNorm (d o2 = d a = 0),  dg -> GELU (dz = 0),  da -> LayerNorm (d ao = dx' = 0),  dctx -> attention core (dqkv = 0)
+// -- and dx, which leaves the layer, is zero-stored on the dead blocks by the product itself (rb_zero); on a partly live block and on
+// the dense route it is dqkv Wqkv + dx' = 0 W + 0.
+namespace {
+GemmArgs on_rows(GemmArgs g, const int* rowblk, int mode, int zero_dead = 0) {
+  if (rowblk) g.rb = rowblk + ROWBLK_HDR, g.rb_n = rowblk, g.rb_mode = mode, g.rb_zero = zero_dead;
+  return g;
+}
+}  // namespace
+
 int bert_layer_fwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const BertLayerParams& p, float* y,
-                   float* saved, const void* snap, float p_attn, float p_hidden, hipStream_t st) {
+                   float* saved, const void* snap, float p_attn, float p_hidden, hipStream_t st, const int* tv, const int* rowblk) {
   const long R = (long)B * T;
   const Saved s = saved_views(saved, B, T, D, H, Dff);
-  GemmArgs g = gemm_nt(x, D, p.wqkv, D, s.qkv, 3 * D, (int)R, 3 * D, D).tagged("bert_gemm");
+  const int* rb = tv && T % 16 == 0 ? rowblk : nullptr;
+  GemmArgs g = on_rows(gemm_nt(x, D, p.wqkv, D, s.qkv, 3 * D, (int)R, 3 * D, D).tagged("bert_gemm"), rb, 1);
   g.bias = p.bqkv;
   GC_TRY(gemm(g, st, 0, 1));
-  GC_TRY(bert_attn_fwd(B, T, H, s.qkv, key_bias, s.ctx, s.lse, make_drop(snap, SALT_BERT_ATTN, p_attn), st));
-  GC_TRY(gemm(gemm_nt(s.ctx, D, p.wo, D, s.ao, D, (int)R, D, D).tagged("bert_gemm"), st, 0, 1));
-  GC_TRY(res_ln_fwd(R, D, s.ao, p.bo, x, p.ln1w, p.ln1b, s.a, s.mean1, s.rstd1, make_drop(snap, SALT_BERT_AO, p_hidden), st));
-  GC_TRY(gemm(gemm_nt(s.a, D, p.wi, D, s.z, Dff, (int)R, Dff, D).tagged("bert_gemm"), st, 0, 1));
-  GC_TRY(bias_gelu_fwd(R, Dff, s.z, p.bi, s.g, st));
-  GC_TRY(gemm(gemm_nt(s.g, Dff, p.wo2, Dff, s.o2, D, (int)R, D, Dff).tagged("bert_gemm"), st, 0, 1));
-  return res_ln_fwd(R, D, s.o2, p.bo2, s.a, p.ln2w, p.ln2b, y, s.mean2, s.rstd2, make_drop(snap, SALT_BERT_OUT, p_hidden), st);
+  GC_TRY(bert_attn_fwd(B, T, H, s.qkv, key_bias, s.ctx, s.lse, make_drop(snap, SALT_BERT_ATTN, p_attn), st, tv));
+  GC_TRY(gemm(on_rows(gemm_nt(s.ctx, D, p.wo, D, s.ao, D, (int)R, D, D).tagged("bert_gemm"), rb, 1), st, 0, 1));
+  GC_TRY(res_ln_fwd(R, D, s.ao, p.bo, x, p.ln1w, p.ln1b, s.a, s.mean1, s.rstd1, make_drop(snap, SALT_BERT_AO, p_hidden), st, tv, T));
+  GC_TRY(gemm(on_rows(gemm_nt(s.a, D, p.wi, D, s.z, Dff, (int)R, Dff, D).tagged("bert_gemm"), rb, 1), st, 0, 1));
+  GC_TRY(bias_gelu_fwd(R, Dff, s.z, p.bi, s.g, st, tv, T));
+  GC_TRY(gemm(on_rows(gemm_nt(s.g, Dff, p.wo2, Dff, s.o2, D, (int)R, D, Dff).tagged("bert_gemm"), rb, 1), st, 0, 1));
+  return res_ln_fwd(R, D, s.o2, p.bo2, s.a, p.ln2w, p.ln2b, y, s.mean2, s.rstd2, make_drop(snap, SALT_BERT_OUT, p_hidden), st, tv, T);
 }
 
 int bert_layer_bwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const BertLayerParams& p,
                    const float* saved, const float* dy, float* dx, const BertLayerGrads& d, float* ws, long ws_elems, const void* snap,
-                   float p_attn, float p_hidden, hipStream_t st) {
+                   float p_attn, float p_hidden, hipStream_t st, const int* tv, const int* rowblk) {
   const long R = (long)B * T;
   const Saved s = saved_views(const_cast<float*>(saved), B, T, D, H, Dff);
   const Work w = work_views(ws, B, T, D, H, Dff);
   GC_REQUIRE(ws_elems >= w.total, "bert_layer_bwd: workspace of %ld floats needed", w.total);
   const int M = (int)R;
+  const int* rb = tv && T % 16 == 0 ? rowblk : nullptr;
+  // a weight gradient sums over the live row blocks (mode 2), a data gradient computes them (mode 1)
+  auto wgrad = [&](GemmArgs g) { return on_rows(g.split_ws(w.split, w.split_elems).tagged("bert_gemm"), rb, 2); };
+  auto dgrad = [&](GemmArgs g, int zero_dead = 0) { return on_rows(g.split_ws(w.split, w.split_elems).tagged("bert_gemm"), rb, 1, zero_dead); };
 
   // y = LN2(dropout(o2 + bo2) + a):  t1 = d o2, t2 = d a (the residual's share)
   GC_TRY(res_ln_bwd(R, D, dy, s.o2, p.bo2, s.a, p.ln2w, s.mean2, s.rstd2, w.t1, w.t2, d.ln2w, d.ln2b, w.lnpart,
-                    make_drop(snap, SALT_BERT_OUT, p_hidden), st));
+                    make_drop(snap, SALT_BERT_OUT, p_hidden), st, tv, T));
   {   // o2 = g Wo2^T:  dWo2 = t1^T g, big = dg = t1 Wo2, dbo2 = column sums of t1
-    GemmArgs gs[2] = {gemm_tn(w.t1, D, s.g, Dff, d.wo2, Dff, D, Dff, M).split_ws(w.split, w.split_elems).tagged("bert_gemm"),
-                      gemm_nn(w.t1, D, p.wo2, Dff, w.big, Dff, M, Dff, D).split_ws(w.split, w.split_elems).tagged("bert_gemm")};
+    GemmArgs gs[2] = {wgrad(gemm_tn(w.t1, D, s.g, Dff, d.wo2, Dff, D, Dff, M)), dgrad(gemm_nn(w.t1, D, p.wo2, Dff, w.big, Dff, M, Dff, D))};
     const ColRide cr = col_sum(w.t1, R, D, D, d.bo2, w.colpart);
     GC_TRY(gemm_group(gs, 2, st, &cr));
   }
-  GC_TRY(bias_gelu_bwd(R, Dff, w.big, s.z, p.bi, w.big, st));   // big = dz
+  GC_TRY(bias_gelu_bwd(R, Dff, w.big, s.z, p.bi, w.big, st, tv, T));   // big = dz
   {   // z = a Wi^T:  dWi = big^T a, t3 = da = big Wi + t2, dbi = column sums of big
-    GemmArgs gs[2] = {gemm_tn(w.big, Dff, s.a, D, d.wi, D, Dff, D, M).split_ws(w.split, w.split_elems).tagged("bert_gemm"),
-                      gemm_nn(w.big, Dff, p.wi, D, w.t3, D, M, D, Dff).split_ws(w.split, w.split_elems).tagged("bert_gemm")};
+    GemmArgs gs[2] = {wgrad(gemm_tn(w.big, Dff, s.a, D, d.wi, D, Dff, D, M)), dgrad(gemm_nn(w.big, Dff, p.wi, D, w.t3, D, M, D, Dff))};
     gs[1].add = w.t2, gs[1].ldadd = D;
     const ColRide cr = col_sum(w.big, R, Dff, Dff, d.bi, w.colpart);
     GC_TRY(gemm_group(gs, 2, st, &cr));
   }
   // a = LN1(dropout(ao + bo) + x):  t1 = d ao, t2 = dx (the residual's share)
   GC_TRY(res_ln_bwd(R, D, w.t3, s.ao, p.bo, x, p.ln1w, s.mean1, s.rstd1, w.t1, w.t2, d.ln1w, d.ln1b, w.lnpart,
-                    make_drop(snap, SALT_BERT_AO, p_hidden), st));
+                    make_drop(snap, SALT_BERT_AO, p_hidden), st, tv, T));
   {   // ao = ctx Wo^T:  dWo = t1^T ctx, t3 = dctx = t1 Wo, dbo = column sums of t1
-    GemmArgs gs[2] = {gemm_tn(w.t1, D, s.ctx, D, d.wo, D, D, D, M).split_ws(w.split, w.split_elems).tagged("bert_gemm"),
-                      gemm_nn(w.t1, D, p.wo, D, w.t3, D, M, D, D).split_ws(w.split, w.split_elems).tagged("bert_gemm")};
+    GemmArgs gs[2] = {wgrad(gemm_tn(w.t1, D, s.ctx, D, d.wo, D, D, D, M)), dgrad(gemm_nn(w.t1, D, p.wo, D, w.t3, D, M, D, D))};
     const ColRide cr = col_sum(w.t1, R, D, D, d.bo, w.colpart);
     GC_TRY(gemm_group(gs, 2, st, &cr));
   }
-  GC_TRY(bert_attn_bwd(B, T, H, s.qkv, key_bias, s.ctx, s.lse, w.t3, w.big, w.delta, make_drop(snap, SALT_BERT_ATTN, p_attn), st));   // big = dqkv
+  GC_TRY(bert_attn_bwd(B, T, H, s.qkv, key_bias, s.ctx, s.lse, w.t3, w.big, w.delta, make_drop(snap, SALT_BERT_ATTN, p_attn), st, tv));   // big = dqkv
   {   // qkv = x Wqkv^T + b:  dWqkv = big^T x, dx = big Wqkv + t2, dbqkv = column sums of big
-    GemmArgs gs[2] = {gemm_tn(w.big, 3 * D, x, D, d.wqkv, D, 3 * D, D, M).split_ws(w.split, w.split_elems).tagged("bert_gemm"),
-                      gemm_nn(w.big, 3 * D, p.wqkv, D, dx, D, M, D, 3 * D).split_ws(w.split, w.split_elems).tagged("bert_gemm")};
+    GemmArgs gs[2] = {wgrad(gemm_tn(w.big, 3 * D, x, D, d.wqkv, D, 3 * D, D, M)), dgrad(gemm_nn(w.big, 3 * D, p.wqkv, D, dx, D, M, D, 3 * D), 1)};
     gs[1].add = w.t2, gs[1].ldadd = D;
     const ColRide cr = col_sum(w.big, R, 3 * D, 3 * D, d.bqkv, w.colpart);
     return gemm_group(gs, 2, st, &cr);

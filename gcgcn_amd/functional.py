@@ -1439,15 +1439,19 @@ class ResLayerNormFn(torch.autograd.Function):
     """y = LayerNorm(dropout(x + bias) + res) over the last axis (eps = 1e-12, biased variance); bias, res, dropout optional."""
 
     @staticmethod
-    def forward(ctx, x, bias, res, weight, lnb, p, snap, salt):
+    def forward(ctx, x, bias, res, weight, lnb, p, snap, salt, t_valid=None):
         D = x.shape[-1]
         rows = x.numel() // D
         y = torch.empty_like(x)
         mean, rstd = torch.empty(rows, device=x.device), torch.empty(rows, device=x.device)
-        call("gcgcn_res_ln_fwd", rows, D, _p(x), _p(bias), _p(res), _p(weight), _p(lnb), _p(y), _p(mean), _p(rstd), _p(snap), salt, float(p),
-             _stream())
+        if t_valid is None:
+            call("gcgcn_res_ln_fwd", rows, D, _p(x), _p(bias), _p(res), _p(weight), _p(lnb), _p(y), _p(mean), _p(rstd), _p(snap), salt, float(p),
+                 _stream())
+        else:
+            call("gcgcn_res_ln_fwd_len", rows, D, _p(x), _p(bias), _p(res), _p(weight), _p(lnb), _p(t_valid), x.shape[-2], _p(y), _p(mean),
+                 _p(rstd), _p(snap), salt, float(p), _stream())
         torch.autograd.graph.increment_version((y, mean, rstd))
-        ctx.p, ctx.snap, ctx.salt, ctx.has = float(p), snap, salt, (bias is not None, res is not None)
+        ctx.p, ctx.snap, ctx.salt, ctx.has, ctx.t_valid = float(p), snap, salt, (bias is not None, res is not None), t_valid
         ctx.save_for_backward(x, weight, mean, rstd, *(t for t in (bias, res) if t is not None))
         return y
 
@@ -1465,18 +1469,30 @@ class ResLayerNormFn(torch.autograd.Function):
         dres = torch.empty_like(x) if res is not None else None
         dw, db = torch.empty_like(weight), torch.empty_like(weight)
         ws = _f32_buf(_bytes_or_raise("gcgcn_res_ln_ws_bytes", D), x.device)
-        call("gcgcn_res_ln_bwd", rows, D, _p(dy), _p(x), _p(bias), _p(res), _p(weight), _p(mean), _p(rstd), _p(dx), _p(dres), _p(dw), _p(db),
-             _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.salt, ctx.p, _stream())
+        if ctx.t_valid is None:
+            call("gcgcn_res_ln_bwd", rows, D, _p(dy), _p(x), _p(bias), _p(res), _p(weight), _p(mean), _p(rstd), _p(dx), _p(dres), _p(dw), _p(db),
+                 _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.salt, ctx.p, _stream())
+        else:
+            call("gcgcn_res_ln_bwd_len", rows, D, _p(dy), _p(x), _p(bias), _p(res), _p(weight), _p(mean), _p(rstd), _p(ctx.t_valid), x.shape[-2],
+                 _p(dx), _p(dres), _p(dw), _p(db), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.salt, ctx.p, _stream())
         torch.autograd.graph.increment_version((dx, dw, db) + (() if dres is None else (dres,)))
         dbias = dx.reshape(rows, D).sum(0) if bias is not None and ctx.needs_input_grad[1] else None
-        return dx, dbias, dres, dw, db, None, None, None
+        return dx, dbias, dres, dw, db, None, None, None, None
 
 
-def res_layer_norm(x, weight, bias, lin_bias=None, res=None, p=0.0, training=False, snap=None, salt=_lib.SALT_BERT_EMB):
+def res_layer_norm(x, weight, bias, lin_bias=None, res=None, p=0.0, training=False, snap=None, salt=_lib.SALT_BERT_EMB, t_valid=None):
     """``LayerNorm(dropout(x + lin_bias) + res)`` over the last axis in HIP, with the contract's LayerNorm: biased variance,
     ``weight * (v - mean) / sqrt(var + 1e-12) + bias``.  ``lin_bias`` ``[D]``, ``res`` (``x``'s shape) and the dropout are each
-    optional.  ``D`` a multiple of 64, at most 1024.  ``snap``: the rng snapshot of the dropout site (default: a fresh one)."""
+    optional.  ``D`` a multiple of 64, at most 1024.  ``snap``: the rng snapshot of the dropout site (default: a fresh one).
+
+    ``t_valid``: token counts ``[B]`` for ``x[B,T,D]`` (row ``(b, t)`` is live iff ``t < t_valid[b]``).  Padding rows of the output and
+    of the gradients of ``x`` and ``res`` are exactly zero, neither ``x``, ``res`` nor the arriving gradient is read there, and
+    the parameter gradients sum over the live rows.  ``None``: every row, the call as it was."""
     x = _chk(x, "x")
+    if t_valid is not None:
+        if x.dim() != 3:
+            raise ValueError(f"res_layer_norm: t_valid needs x[B,T,D], got shape {tuple(x.shape)}")
+        t_valid = _nv(t_valid, x.shape[0], x.shape[1], x.device)
     weight, bias = _chk(weight, "weight", 1), _chk(bias, "bias", 1)
     D = x.shape[-1]
     if weight.shape != (D,) or bias.shape != (D,):
@@ -1490,7 +1506,8 @@ def res_layer_norm(x, weight, bias, lin_bias=None, res=None, p=0.0, training=Fal
     p = float(p) if training else 0.0
     if p > 0 and snap is None:
         snap = rng_snapshot(x.device)
-    return ResLayerNormFn.apply(x, None if lin_bias is None else lin_bias.contiguous(), res, weight, bias, p, snap if p > 0 else None, salt)
+    return ResLayerNormFn.apply(x, None if lin_bias is None else lin_bias.contiguous(), res, weight, bias, p, snap if p > 0 else None, salt,
+                                t_valid)
 
 
 BERT_LAYER_TENSORS = ("query.weight", "query.bias", "key.weight", "key.bias", "value.weight", "value.bias", "attention.output.dense.weight",
@@ -1504,19 +1521,25 @@ def _ptr_array(tensors):
 
 
 class BertLayerFn(torch.autograd.Function):
-    """(x[B,T,D], key_bias[B,T] | None, the 12 tensors of gcgcn_bert_layer_fwd's parameter list) -> y[B,T,D]."""
+    """(x[B,T,D], key_bias[B,T] | None, t_valid[B] | None, rowblk | None, the 12 tensors of gcgcn_bert_layer_fwd's parameter list) ->
+    y[B,T,D].  With t_valid the _len entry points run (include/gcgcn.h)."""
 
     @staticmethod
-    def forward(ctx, x, key_bias, H, p_attn, p_hidden, snap, *params):
+    def forward(ctx, x, key_bias, H, p_attn, p_hidden, snap, t_valid, rowblk, *params):
         B, T, D = x.shape
         Dff = params[6].shape[0]
         dims = (B, T, D, H, Dff)
         saved = _f32_buf(_bytes_or_raise("gcgcn_bert_layer_ws_bytes", *dims, 0), x.device)
         y = torch.empty_like(x)
-        call("gcgcn_bert_layer_fwd", *dims, _p(x), _p(key_bias), _ptr_array(params), _p(y), _p(saved), saved.numel() * 4, _p(snap),
-             float(p_attn), float(p_hidden), _stream())
+        if t_valid is None:
+            call("gcgcn_bert_layer_fwd", *dims, _p(x), _p(key_bias), _ptr_array(params), _p(y), _p(saved), saved.numel() * 4, _p(snap),
+                 float(p_attn), float(p_hidden), _stream())
+        else:
+            call("gcgcn_bert_layer_fwd_len", *dims, _p(x), _p(key_bias), _p(t_valid), _p(rowblk), _ptr_array(params), _p(y), _p(saved),
+                 saved.numel() * 4, _p(snap), float(p_attn), float(p_hidden), _stream())
         torch.autograd.graph.increment_version((y, saved))
         ctx.dims, ctx.ps, ctx.snap, ctx.has_kb = dims, (float(p_attn), float(p_hidden)), snap, key_bias is not None
+        ctx.t_valid, ctx.rowblk = t_valid, rowblk
         if any(ctx.needs_input_grad):
             ctx.save_for_backward(x, saved, *params, *(() if key_bias is None else (key_bias,)))
         return y
@@ -1531,21 +1554,33 @@ class BertLayerFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         grads = tuple(torch.empty_like(t) for t in params)
         ws = _f32_buf(_bytes_or_raise("gcgcn_bert_layer_ws_bytes", *ctx.dims, 1), x.device)
-        call("gcgcn_bert_layer_bwd", *ctx.dims, _p(x), _p(key_bias), _ptr_array(params), _p(saved), saved.numel() * 4, _p(dy), _p(dx),
-             _ptr_array(grads), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.ps[0], ctx.ps[1], _stream())
+        if ctx.t_valid is None:
+            call("gcgcn_bert_layer_bwd", *ctx.dims, _p(x), _p(key_bias), _ptr_array(params), _p(saved), saved.numel() * 4, _p(dy), _p(dx),
+                 _ptr_array(grads), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.ps[0], ctx.ps[1], _stream())
+        else:
+            call("gcgcn_bert_layer_bwd_len", *ctx.dims, _p(x), _p(key_bias), _p(ctx.t_valid), _p(ctx.rowblk), _ptr_array(params), _p(saved),
+                 saved.numel() * 4, _p(dy), _p(dx), _ptr_array(grads), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.ps[0], ctx.ps[1], _stream())
         torch.autograd.graph.increment_version((dx,) + grads)
-        return (dx, None, None, None, None, None) + grads
+        return (dx, None, None, None, None, None, None, None) + grads
 
 
 def bert_layer(x, key_bias, wq, bq, wk, bk, wv, bv, wo, bo, ln1_w, ln1_b, wi, bi, wo2, bo2, ln2_w, ln2_b, p_attn=0.1, p_hidden=0.1,
-               training=False, snap=None):
+               training=False, snap=None, t_valid=None, rowblk=None):
     """One BERT encoder layer (``pytorch_pretrained_bert`` 0.6 ``BertLayer``) in HIP: ``x[B,T,D]`` -> ``[B,T,D]``.  ``key_bias``:
     ``[B,T]`` additive score penalty per key (``(1 - mask) * -10000``) or None.  The 16 parameter tensors in ``BERT_LAYER_TENSORS``'
     order, Linear weights ``[out, in]``; the number of heads is ``D / 64`` (the attention kernels serve a head width of 64) and
     ``T <= 512``.  In training mode three dropout sites draw from one rng snapshot (``snap``, default a fresh one, inside an
     ``rng_scope`` the scope's next): the attention probabilities (``p_attn``, salt ``SALT_BERT_ATTN``, index = offset in
     ``[B,H,T,T]``) and the two Linear outputs in front of the LayerNorms (``p_hidden``, ``SALT_BERT_AO`` / ``SALT_BERT_OUT``,
-    index = offset in ``[B,T,D]``).  Gradients reach ``x`` and all 16 tensors; two runs from one seed are bitwise equal."""
+    index = offset in ``[B,T,D]``).  Gradients reach ``x`` and all 16 tensors; two runs from one seed are bitwise equal.
+
+    ``t_valid``: the documents' token counts ``[B]`` (int, on the device, ``0 <= t_valid[b] <= T``).  Live rows ``t < t_valid[b]`` get what
+    the layer computes for document ``b`` alone at ``T = t_valid[b]`` with no mask (``key_bias`` may still punch holes inside the
+    prefix); the output and the gradient of ``x`` are exactly zero on padding rows, the gradient arriving there is ignored (NaN
+    included) and ``x`` must be zero there.  The dropout indices do not move.  ``rowblk``: ``row_blocks(t_valid, B, T)``, built once
+    per model forward and shared by the layers -- the Linears then run on the live 16-row blocks where the GEMM launcher serves the
+    list and dense elsewhere (always when ``T % 16 != 0``), with the same results contract; ``None`` with ``t_valid``: dense.
+    ``t_valid=None``: the call as it was."""
     x = _chk(x, "x", 3)
     names = ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo", "ln1_w", "ln1_b", "wi", "bi", "wo2", "bo2", "ln2_w", "ln2_b")
     ts = [_chk(t, n) for n, t in zip(names, (wq, bq, wk, bk, wv, bv, wo, bo, ln1_w, ln1_b, wi, bi, wo2, bo2, ln2_w, ln2_b))]
@@ -1566,4 +1601,12 @@ def bert_layer(x, key_bias, wq, bq, wk, bk, wv, bv, wo, bo, ln1_w, ln1_b, wi, bi
         snap = rng_snapshot(x.device)
     # query | key | value stacked: one product instead of three (autograd splits the gradients again), as lstm_layer stacks directions
     wqkv, bqkv = torch.cat([ts[0], ts[2], ts[4]], 0), torch.cat([ts[1], ts[3], ts[5]], 0)
-    return BertLayerFn.apply(x, key_bias, D // 64, p_attn, p_hidden, snap if (p_attn > 0 or p_hidden > 0) else None, wqkv, bqkv, *ts[6:])
+    if t_valid is not None:
+        t_valid = _nv(t_valid, B, T, x.device)
+        if rowblk is not None and (T % 16 or rowblk.dtype != torch.int32 or rowblk.device != x.device or
+                                   rowblk.numel() < int(_lib.lib().gcgcn_row_blocks_ints(B, T))):
+            raise ValueError(f"bert_layer: rowblk is not row_blocks(t_valid, {B}, {T})")
+    elif rowblk is not None:
+        raise ValueError("bert_layer: rowblk without t_valid")
+    return BertLayerFn.apply(x, key_bias, D // 64, p_attn, p_hidden, snap if (p_attn > 0 or p_hidden > 0) else None, t_valid, rowblk, wqkv,
+                             bqkv, *ts[6:])

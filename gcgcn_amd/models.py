@@ -27,6 +27,7 @@ import torch
 from torch import nn
 from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
 
+from .bert import BertModel as OwnBertModel
 from .functional import lstm_layer, token_context, token_embed
 from .modules import GraphModelTail
 
@@ -253,13 +254,18 @@ class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
 
     def forward(self, document, document_ner, document_pos, adj_matrix, sen_matrix, pos_matrix_h, pos_matrix_t, node_pos, node_type,
                 node_relative_pos, n_valid: Optional[Tensor] = None, t_valid: Optional[Tensor] = None, **caps):
-        """``t_valid``: the token count of every document of a batch, ``[B]``; the encoder is then called with
-        ``attention_mask = arange(T) < t_valid[:, None]``, so that real tokens do not attend to padding."""
+        """``t_valid``: the token count of every document of a batch, ``[B]``.  This library's own encoder (``config.bert_impl``) is
+        called with ``lengths=t_valid``: each document runs at its own token count and the token states of padding rows are exactly
+        zero -- ``impl="hip"`` in the kernels, on live tokens only; ``impl="torch"`` by the same contract in plain PyTorch, so the two
+        stay interchangeable on every row.  Any other encoder is called with ``attention_mask = arange(T) < t_valid[:, None]`` as
+        before, so that real tokens do not attend to padding."""
         batched = document.dim() == 2
         if not batched:
             document, document_ner, document_pos = (t.unsqueeze(0) for t in (document, document_ner, document_pos))
         if t_valid is None:
             doc, _ = self.bert(document, output_all_encoded_layers=False)                    # bert:275
+        elif isinstance(self.bert, OwnBertModel):
+            doc, _ = self.bert(document, output_all_encoded_layers=False, lengths=t_valid)
         else:
             mask = torch.arange(document.size(1), device=document.device) < t_valid.to(document.device)[:, None]
             doc, _ = self.bert(document, attention_mask=mask, output_all_encoded_layers=False)

@@ -650,6 +650,51 @@ int gcgcn_bert_layer_bwd(int B, int T, int D, int H, int Dff, const float* x, co
                          const void* saved, int64_t saved_bytes, const float* dy, float* dx, float* const* grads, void* ws, int64_t ws_bytes,
                          const void* rng_snap, float p_attn, float p_hidden, void* stream);
 
+/* ---- the same with per-document token lengths -----------------------------------------------------------------
+ * t_valid: int32 [B] on the device, 0 <= t_valid[b] <= T (values outside are clamped).  Row (b, t) is LIVE iff t < t_valid[b].  The layout
+ * stays padded; T keeps every stride and every dropout index (the offset in the virtual [B][H][T][T] and [B T][D] tensors), so the
+ * length path and the prefix-mask path draw the same keep decisions on live elements from one snapshot.
+ *  1. Live rows: outputs, saved state and gradients are what the entry point without _len computes for document b alone at T = t_valid[b]
+ *     with no mask.  Keys at or past t_valid[b] have probability exactly 0.  key_bias may still be given (holes inside the live prefix) and
+ *     keeps its meaning; c_b is then the largest penalty of the document's live keys.
+ *  2. Padding rows: every output row (ctx, lse, dqkv, y, mean, rstd, dx, dres, gelu's output; the layer's y and dx) is exactly 0.0f.
+ *     Gradients arriving there (dctx, dy) are not read: they may hold anything, NaN included.  The LAYER's input x must be zero on padding
+ *     rows; the caller owns this (gcgcn_amd.BertModel guarantees it whatever token ids sit there).  The stand-alone row functions read
+ *     nothing of a padding row.
+ *  3. t_valid[b] == 0: the document contributes nothing and produces zeros; no softmax over an empty key set is formed.
+ *  4. No host read, no allocation, capturable: a captured call replayed after t_valid was overwritten in place computes the new lengths.
+ *     No float atomics: bit-reproducible.
+ *  5. No result depends on memory the call did not write.  A weight gradient sums over the padding rows of a partly live 16-row block (on
+ *     the dense route: over all padding rows), so every kernel whose output such a sum reads stores zeros there.
+ * The grids do not depend on the lengths (fixed for capture): a workgroup of the attention kernels whose 16 rows are all padding stores
+ * its zeros and leaves, the others stream ceil(t_valid[b] / 64) blocks instead of ceil(T / 64).
+ * gcgcn_bert_layer_*_len: rowblk = the list gcgcn_row_blocks(B, T, t_valid) built (T a multiple of 16; build it once per model forward and
+ * hand it to every layer and its backward), or NULL.  With it the four forward products compute, the data gradients compute and the weight
+ * gradients sum over the live 16-row blocks only.  The GEMM launcher drops the list per problem on shapes it does not serve -- B T or a
+ * width that is no multiple of 64, more than 512 blocks for a weight gradient (B T > 8192), unaligned operands, launches too small to
+ * gain -- and T % 16 != 0 has no list at all: those products run dense and the results obey the same contract. */
+int gcgcn_bert_attn_fwd_len(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const int32_t* t_valid, float* ctx,
+                            float* lse, const void* rng_snap, uint64_t salt, float p, void* stream);
+int gcgcn_bert_attn_bwd_len(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const int32_t* t_valid, const float* ctx,
+                            const float* lse, const float* dctx, float* dqkv, float* delta, const void* rng_snap, uint64_t salt, float p,
+                            void* stream);
+int gcgcn_res_ln_fwd_len(int64_t rows, int D, const float* x, const float* bias, const float* res, const float* weight, const float* lnb,
+                         const int32_t* t_valid, int T, float* y, float* mean, float* rstd, const void* rng_snap, uint64_t salt, float p,
+                         void* stream);
+int gcgcn_res_ln_bwd_len(int64_t rows, int D, const float* dy, const float* x, const float* bias, const float* res, const float* weight,
+                         const float* mean, const float* rstd, const int32_t* t_valid, int T, float* dx, float* dres, float* dweight,
+                         float* dlnb, void* ws, int64_t ws_bytes, const void* rng_snap, uint64_t salt, float p, void* stream);
+int gcgcn_bias_gelu_fwd_len(int64_t rows, int C, const float* x, const float* bias, const int32_t* t_valid, int T, float* y, void* stream);
+int gcgcn_bias_gelu_bwd_len(int64_t rows, int C, const float* dy, const float* x, const float* bias, const int32_t* t_valid, int T, float* dx,
+                            void* stream);
+int gcgcn_bert_layer_fwd_len(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
+                             const int32_t* rowblk, const float* const* params, float* y, void* saved, int64_t saved_bytes,
+                             const void* rng_snap, float p_attn, float p_hidden, void* stream);
+int gcgcn_bert_layer_bwd_len(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
+                             const int32_t* rowblk, const float* const* params, const void* saved, int64_t saved_bytes, const float* dy,
+                             float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn, float p_hidden,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

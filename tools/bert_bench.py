@@ -5,8 +5,14 @@ gradients (dropout off: both implementations then compute the same function), ea
 layer's time split: each non-GEMM kernel timed on its own through the C ABI, the rest is the GEMM layer.
 
     python tools/bert_bench.py [--layers 12] [--iters 20] [--json out.json]
+    python tools/bert_bench.py --lengths {full,ragged} [--shape 4x512] [--layers 12] [--iters 20] [--json out.json]
 
-Prints one table and, with --json, writes the numbers.  DESIGN.md section 8.9 holds the table of record."""
+With --lengths only the HIP encoder runs, as one replayed hipGraph, twice on the same token counts in the same process: the
+prefix-mask path (attention_mask = arange(T) < t_valid, every row computed) and the length path (lengths = t_valid, live tokens
+only).  ``full``: every document at T -- the feature's overhead.  ``ragged``: a fixed seeded draw, uniform integers in [T/8, T];
+seed and mean are printed.  --shape restricts the run to one (B, T), so that a caller can give every run its own time limit.
+
+Prints one table and, with --json, writes the numbers.  DESIGN.md section 8.9 holds the tables of record."""
 import argparse
 import json
 import os
@@ -35,18 +41,35 @@ def timed(fn, iters, warmup=3):
     return statistics.median(ms)
 
 
-def model_step(layers, impl, B, T, dev):
+LENGTH_SEED = 2024
+
+
+def draw_lengths(kind, B, T):
+    """Token counts of the --lengths runs: every document at T, or the fixed seeded draw from [T/8, T]."""
+    if kind == "full":
+        return torch.full((B,), T, dtype=torch.int32)
+    g = torch.Generator().manual_seed(LENGTH_SEED + 1000 * B + T)
+    return torch.randint(T // 8, T + 1, (B,), generator=g).to(torch.int32)
+
+
+def model_step(layers, impl, B, T, dev, t_valid=None, by_lengths=False):
+    """t_valid None: the masks this tool has always used.  Otherwise the prefix mask of these counts, or (by_lengths) lengths=t_valid."""
     cfg = BertConfig(num_hidden_layers=layers, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
     torch.manual_seed(0)
     model = BertModel(cfg, impl=impl).to(dev).train()
     g = torch.Generator().manual_seed(1)
     ids = torch.randint(0, cfg.vocab_size, (B, T), generator=g).to(dev)
-    mask = (torch.arange(T)[None, :] < torch.tensor([T - 37 * (b % 3) for b in range(B)])[:, None]).float().to(dev)
+    counts = torch.tensor([T - 37 * (b % 3) for b in range(B)]) if t_valid is None else t_valid.cpu()
+    mask = (torch.arange(T)[None, :] < counts[:, None]).float().to(dev)
     dy = torch.randn(B, T, cfg.hidden_size, generator=g).to(dev)
+    tv = None if t_valid is None else t_valid.to(dev)
 
     def step():
         model.zero_grad(set_to_none=True)
-        out, pooled = model(ids, attention_mask=mask, output_all_encoded_layers=False)
+        if by_lengths:
+            out, pooled = model(ids, output_all_encoded_layers=False, lengths=tv)
+        else:
+            out, pooled = model(ids, attention_mask=mask, output_all_encoded_layers=False)
         ((out * dy).sum() + pooled.sum()).backward()
     return step
 
@@ -98,11 +121,30 @@ def main():
     ap.add_argument("--layers", type=int, default=12)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--json")
+    ap.add_argument("--lengths", choices=("full", "ragged"), help="the HIP encoder's prefix-mask path against its length path on these token counts")
+    ap.add_argument("--shape", help="BxT: this shape only (default: 4x512 and 8x256)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.backends.cuda.matmul.allow_tf32 = False
     rows = []
-    for B, T in ((4, 512), (8, 256)):
+    shapes = ((4, 512), (8, 256)) if not a.shape else (tuple(int(v) for v in a.shape.lower().split("x")),)
+    if a.lengths:
+        for B, T in shapes:
+            tv = draw_lengths(a.lengths, B, T)
+            print(f"B={B} T={T} lengths={a.lengths} seed={LENGTH_SEED} t_valid={tv.tolist()} mean={tv.float().mean().item():.1f} "
+                  f"({tv.float().mean().item() / T:.3f} of T)", flush=True)
+            for layers in sorted({1, a.layers}):
+                r = {"B": B, "T": T, "layers": layers, "lengths": a.lengths, "seed": LENGTH_SEED, "t_valid": tv.tolist()}
+                for name, by_lengths in (("mask", False), ("len", True)):
+                    step = model_step(layers, "hip", B, T, dev, tv, by_lengths)
+                    r[f"hip_{name}_graph_ms"] = timed(graphed(step), a.iters)
+                    del step
+                    torch.cuda.empty_cache()
+                rows.append(r)
+                print(f"B={B} T={T} layers={layers:2d} lengths={a.lengths}: " + "  ".join(f"{k}={v:.3f}" for k, v in r.items() if k.endswith("_ms"))
+                      + f"  len/mask={r['hip_len_graph_ms'] / r['hip_mask_graph_ms']:.3f}", flush=True)
+        shapes = ()
+    for B, T in shapes:
         for layers in (1, a.layers):
             r = {"B": B, "T": T, "layers": layers}
             for impl in ("torch", "hip"):
