@@ -139,6 +139,10 @@ SIGNATURES = {
     "gcgcn_bias_gelu_bwd_len": (I, [L, I, P, P, P, P, I, P, P]),
     "gcgcn_bert_layer_fwd_len": (I, [I] * 5 + [P] * 7 + [L, P, F, F, P]),
     "gcgcn_bert_layer_bwd_len": (I, [I] * 5 + [P] * 6 + [L, P, P, P, P, L, P, F, F, P]),
+    "gcgcn_gemm_bf16_ws_bytes": (L, [I, I, I]),
+    "gcgcn_gemm_bf16": (I, [I, I, P, L, P, L, P, L, I, I, I, P, P, L, P, L, P]),
+    "gcgcn_bert_layer_fwd_mm": (I, [I] * 5 + [P] * 7 + [L, P, F, F, P, I]),
+    "gcgcn_bert_layer_bwd_mm": (I, [I] * 5 + [P] * 6 + [L, P, P, P, P, L, P, F, F, P, I]),
 }
 
 _lib = None

@@ -2,7 +2,8 @@
 
 ``BertModel(config, impl="torch")`` is the contract in plain PyTorch (any device, any float dtype; the reference of the tests).
 ``BertModel(config, impl="hip")`` runs every encoder layer through ``functional.bert_layer`` (csrc/bert.hip: masked attention
-core, LayerNorm with residual and dropout, erf GELU, forward and backward, the Linears on the fp32-MFMA GEMM layer) and the
+core, LayerNorm with residual and dropout, erf GELU, forward and backward, the Linears on the fp32-MFMA GEMM layer or, with
+``matmul="bf16"``, on the bf16 matrix cores) and the
 embeddings' LayerNorm through ``functional.res_layer_norm`` (their dropout is the library's elementwise kernel); it raises on CPU tensors.  The three embedding gathers
 (word, position, token type) and the pooler (one ``[B, D] x [D, D]`` product and a tanh) stay PyTorch in both implementations:
 three gathers and one small product.  Parameters live in ordinary ``nn.Embedding`` / ``nn.Linear`` / ``nn.LayerNorm`` holders
@@ -107,22 +108,54 @@ class _Encoder(nn.Module):
         self.layer = nn.ModuleList(_Layer(c) for _ in range(c.num_hidden_layers))
 
 
-def torch_layer(x, key_bias, params, heads, drop: Callable):
+MATMULS = ("fp32", "bf16")
+
+
+def _bf16(t):
+    """Round every element to bfloat16 (to nearest even) and return it in the tensor's own dtype."""
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
+class Bf16LinearFn(torch.autograd.Function):
+    """``y = bf16(x) bf16(W)^T + b`` with ``dX = bf16(dY) bf16(W)``, ``dW = bf16(dY)^T bf16(X)`` and ``db`` = the sum of the UNROUNDED
+    ``dY``; the products run in the tensors' own dtype.  The definition of ``matmul="bf16"``: operands rounded once, accumulation,
+    bias and everything around the product at full precision."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        xr, wr = _bf16(x), _bf16(w)
+        ctx.save_for_backward(xr, wr)
+        return xr @ wr.t() + b
+
+    @staticmethod
+    def backward(ctx, dy):
+        xr, wr = ctx.saved_tensors
+        dr = _bf16(dy)
+        k, n = xr.shape[-1], dr.shape[-1]
+        return dr @ wr, dr.reshape(-1, n).t() @ xr.reshape(-1, k), dy.reshape(-1, n).sum(0)
+
+
+def bf16_linear(x, w, b):
+    return Bf16LinearFn.apply(x, w, b)
+
+
+def torch_layer(x, key_bias, params, heads, drop: Callable, linear: Callable = F.linear):
     """One encoder layer in plain PyTorch.  ``key_bias``: ``[B, T]`` additive penalty or None.  ``drop(site, t)``: the dropout of
-    site "attn" (on P ``[B, H, T, T]``), "ao" or "out" (on ``[B, T, D]``)."""
+    site "attn" (on P ``[B, H, T, T]``), "ao" or "out" (on ``[B, T, D]``).  ``linear(x, w, b)``: the six Linears (``bf16_linear`` for
+    ``matmul="bf16"``)."""
     wq, bq, wk, bk, wv, bv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2 = params
     B, T, D = x.shape
     dh = D // heads
     split = lambda t: t.view(B, T, heads, dh).permute(0, 2, 1, 3)
-    q, k, v = split(F.linear(x, wq, bq)), split(F.linear(x, wk, bk)), split(F.linear(x, wv, bv))
+    q, k, v = split(linear(x, wq, bq)), split(linear(x, wk, bk)), split(linear(x, wv, bv))
     s = q @ k.transpose(-1, -2) / math.sqrt(dh)
     if key_bias is not None:
         s = s + key_bias[:, None, None, :]
     p = drop("attn", torch.softmax(s, dim=-1))
     ctx = (p @ v).permute(0, 2, 1, 3).reshape(B, T, D)
-    a = layer_norm(drop("ao", F.linear(ctx, wo, bo)) + x, g1, b1)
-    i = gelu(F.linear(a, wi, bi))
-    return layer_norm(drop("out", F.linear(i, wo2, bo2)) + a, g2, b2)
+    a = layer_norm(drop("ao", linear(ctx, wo, bo)) + x, g1, b1)
+    i = gelu(linear(a, wi, bi))
+    return layer_norm(drop("out", linear(i, wo2, bo2)) + a, g2, b2)
 
 
 class BertModel(nn.Module):
@@ -142,20 +175,30 @@ class BertModel(nn.Module):
     indices are the padded tensors', so from one snapshot the length path and the prefix-mask path drop the same live elements.
 
     ``dropout_override``: None, or ``f(layer, site, t) -> t`` replacing the dropout of site "emb" (layer -1), "attn", "ao", "out" of
-    the torch implementation -- how a test replays the masks the HIP kernels drew.  After a training forward of ``impl="hip"``,
+    the torch implementation -- how a test replays the masks the HIP kernels drew.
+
+    ``matmul``: ``"fp32"`` (default; nothing changes) or ``"bf16"``: the six Linears of every encoder layer -- query, key, value,
+    attention.output.dense, intermediate.dense, output.dense -- take bf16 operands with full-precision accumulation, forward and
+    backward (``Bf16LinearFn`` is the definition: operands rounded once to nearest even, the bias gradient from the unrounded
+    gradient).  Parameters, activations, gradients and ``state_dict`` stay what they are: a checkpoint moves freely between the two
+    settings, and an optimizer sees fp32 master weights.  The embeddings, the attention core, LayerNorm, GELU and the pooler are
+    unchanged.  ``impl="hip"`` hands the selector to every layer (csrc/gemm_bf16.hip: the bf16 matrix cores); ``impl="torch"`` is the
+    same contract on any device and float dtype.  After a training forward of ``impl="hip"``,
     ``last_rng_snaps`` holds the snapshots it used: ``[0]`` for the embeddings, ``[1 + l]`` for layer ``l``."""
 
-    def __init__(self, config: Optional[BertConfig] = None, impl: str = "torch"):
+    def __init__(self, config: Optional[BertConfig] = None, impl: str = "torch", matmul: str = "fp32"):
         super().__init__()
         config = BertConfig() if config is None else config
         if impl not in ("torch", "hip"):
             raise ValueError(f"BertModel: impl must be 'torch' or 'hip', got {impl!r}")
+        if matmul not in MATMULS:
+            raise ValueError(f"BertModel: matmul must be 'fp32' or 'bf16', got {matmul!r}")
         if config.hidden_size % config.num_attention_heads:
             raise ValueError(f"BertModel: hidden size {config.hidden_size} is no multiple of {config.num_attention_heads} heads")
         if impl == "hip" and config.hidden_size != 64 * config.num_attention_heads:
             raise ValueError(f"BertModel(impl='hip'): the attention kernels serve a head width of 64, not "
                              f"{config.hidden_size // config.num_attention_heads}")
-        self.config, self.impl = config, impl
+        self.config, self.impl, self.matmul = config, impl, matmul
         self.embeddings = _Embeddings(config)
         self.encoder = _Encoder(config)
         self.pooler = _Dense(config.hidden_size, config.hidden_size)
@@ -199,9 +242,11 @@ class BertModel(nn.Module):
             zero_pad = (lambda t: t) if live is None else (lambda t: torch.where(live, t, torch.zeros((), dtype=t.dtype, device=t.device)))
             x = zero_pad(self._drop(-1, "emb", layer_norm(emb, e.LayerNorm.weight, e.LayerNorm.bias), c.hidden_dropout_prob))
             outs = []
+            linear = (bf16_linear,) if self.matmul == "bf16" else ()      # "fp32": the call as it was
             for li, layer in enumerate(self.encoder.layer):
                 probs = {"attn": c.attention_probs_dropout_prob, "ao": c.hidden_dropout_prob, "out": c.hidden_dropout_prob}
-                x = zero_pad(torch_layer(x, key_bias, layer.tensors(), c.num_attention_heads, lambda s, t: self._drop(li, s, t, probs[s])))
+                x = zero_pad(torch_layer(x, key_bias, layer.tensors(), c.num_attention_heads, lambda s, t: self._drop(li, s, t, probs[s]),
+                                         *linear))
                 outs.append(x)
         last = outs[-1] if outs else x
         pooled = torch.tanh(self.pooler.dense(last[:, 0]))
@@ -213,6 +258,7 @@ class BertModel(nn.Module):
         if not emb.is_cuda:
             raise RuntimeError(f"BertModel(impl='hip') runs on MI355X only; got {emb.device} tensors (impl='torch' runs anywhere)")
         training = self.training
+        mm = {"matmul": self.matmul} if self.matmul != "fp32" else {}      # "fp32": the call as it was
         n = len(self.encoder.layer)
         snaps = []
         tv = rowblk = None
@@ -232,7 +278,7 @@ class BertModel(nn.Module):
                 snap = Fn.rng_snapshot(emb.device) if training else None
                 snaps.append(snap)
                 x = Fn.bert_layer(x, kb, *layer.tensors(), p_attn=c.attention_probs_dropout_prob, p_hidden=c.hidden_dropout_prob,
-                                  training=training, snap=snap, t_valid=tv, rowblk=rowblk)
+                                  training=training, snap=snap, t_valid=tv, rowblk=rowblk, **mm)
                 outs.append(x)
         self.last_rng_snaps = snaps if training else None
         if not outs:

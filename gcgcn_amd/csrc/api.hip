@@ -17,6 +17,7 @@
 #include "lstm.hpp"
 #include "frontend.hpp"
 #include "bert.hpp"
+#include "gemm_bf16.hpp"
 #include "rowops.hpp"
 
 namespace gc {
@@ -1403,6 +1404,73 @@ int gcgcn_bert_layer_bwd_len(int B, int T, int D, int H, int Dff, const float* x
   const BertLayerGrads g = {grads[0], grads[1], grads[2], grads[3], grads[4], grads[5], grads[6], grads[7], grads[8], grads[9], grads[10], grads[11]};
   return bert_layer_bwd(B, T, D, H, Dff, x, key_bias, p, (const float*)saved, dy, dx, g, (float*)ws, ws_bytes / (int64_t)sizeof(float), rng_snap,
                         p_attn, p_hidden, (hipStream_t)stream, t_valid, rowblk);
+}
+
+// ---- opt-in bf16 matrix products (gemm_bf16.hip) -------------------------------------------------------------
+int64_t gcgcn_gemm_bf16_ws_bytes(int M, int N, int K) {
+  if (M < 1 || N < 1 || K < 1) {
+    set_error("gemm_bf16_ws_bytes: M = %d, N = %d, K = %d (each at least 1)", M, N, K);
+    return -1;
+  }
+  return (int64_t)sizeof(float) * gemm_bf16_ws_elems(M, N, K);
+}
+int gcgcn_gemm_bf16(int a_kc, int b_kc, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M, int N, int K,
+                    const float* bias, const float* add, int64_t ldadd, void* ws, int64_t ws_bytes, void* stream) {
+  GC_REQUIRE(M >= 1 && N >= 1 && K >= 1, "gemm_bf16: M = %d, N = %d, K = %d (each at least 1)", M, N, K);
+  const int64_t need = gcgcn_gemm_bf16_ws_bytes(M, N, K);
+  GC_REQUIRE(need == 0 || (ws && al16(ws) && ws_bytes >= need), "gemm_bf16: a 16-byte aligned workspace of %lld bytes needed "
+             "(gcgcn_gemm_bf16_ws_bytes)", (long long)need);
+  GemmBf16Args g = gemm_bf16_stored(a_kc != 0, b_kc != 0, A, lda, B, ldb, C, ldc, M, N, K);
+  g.bias = bias, g.add = add, g.ldadd = add ? ldadd : 0;
+  g.ws = (float*)ws, g.ws_elems = ws ? ws_bytes / (int64_t)sizeof(float) : 0;
+  return gemm_bf16(g, (hipStream_t)stream);
+}
+static int bert_matmul_ok(const char* who, int matmul) {
+  GC_REQUIRE(matmul == BERT_MM_FP32 || matmul == BERT_MM_BF16, "%s: matmul = %d (0: fp32, 1: bf16 operands)", who, matmul);
+  return 0;
+}
+int gcgcn_bert_layer_fwd_mm(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
+                            const int32_t* rowblk, const float* const* params, float* y, void* saved, int64_t saved_bytes,
+                            const void* rng_snap, float p_attn, float p_hidden, void* stream, int matmul) {
+  GC_TRY(bert_layer_shape_ok("bert_layer_fwd_mm", B, T, D, H, Dff));
+  GC_TRY(bert_matmul_ok("bert_layer_fwd_mm", matmul));
+  GC_TRY(bert_drop_ok("bert_layer_fwd_mm", rng_snap, p_attn));
+  GC_TRY(bert_drop_ok("bert_layer_fwd_mm", rng_snap, p_hidden));
+  GC_TRY(bert_params_ok("bert_layer_fwd_mm", params));
+  GC_REQUIRE(t_valid || !rowblk, "bert_layer_fwd_mm: a row-block list without t_valid");
+  GC_REQUIRE(!rowblk || T % 16 == 0, "bert_layer_fwd_mm: a row-block list needs T a multiple of 16 (T = %d)", T);
+  GC_REQUIRE(x && y && saved && al16(x) && al16(y) && al16(saved), "bert_layer_fwd_mm: x, y, saved must be given and 16-byte aligned");
+  GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "bert_layer_fwd_mm: %lld bytes of saved activations needed "
+             "(gcgcn_bert_layer_ws_bytes, which = 0)", (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
+  const BertLayerParams p = {params[0], params[1], params[2], params[3], params[4], params[5],
+                             params[6], params[7], params[8], params[9], params[10], params[11]};
+  return bert_layer_fwd(B, T, D, H, Dff, x, key_bias, p, y, (float*)saved, rng_snap, p_attn, p_hidden, (hipStream_t)stream, t_valid, rowblk,
+                        matmul);
+}
+int gcgcn_bert_layer_bwd_mm(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
+                            const int32_t* rowblk, const float* const* params, const void* saved, int64_t saved_bytes, const float* dy,
+                            float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn, float p_hidden,
+                            void* stream, int matmul) {
+  GC_TRY(bert_layer_shape_ok("bert_layer_bwd_mm", B, T, D, H, Dff));
+  GC_TRY(bert_matmul_ok("bert_layer_bwd_mm", matmul));
+  GC_TRY(bert_drop_ok("bert_layer_bwd_mm", rng_snap, p_attn));
+  GC_TRY(bert_drop_ok("bert_layer_bwd_mm", rng_snap, p_hidden));
+  GC_TRY(bert_params_ok("bert_layer_bwd_mm", params));
+  GC_TRY(bert_params_ok("bert_layer_bwd_mm", grads));
+  GC_REQUIRE(t_valid || !rowblk, "bert_layer_bwd_mm: a row-block list without t_valid");
+  GC_REQUIRE(!rowblk || T % 16 == 0, "bert_layer_bwd_mm: a row-block list needs T a multiple of 16 (T = %d)", T);
+  GC_REQUIRE(x && saved && dy && dx && ws && al16(x) && al16(saved) && al16(dy) && al16(dx) && al16(ws),
+             "bert_layer_bwd_mm: x, saved, dy, dx, ws must be given and 16-byte aligned");
+  GC_REQUIRE(dx != dy, "bert_layer_bwd_mm: dx aliases dy");
+  GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "bert_layer_bwd_mm: %lld bytes of saved activations needed",
+             (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
+  GC_REQUIRE(ws_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1), "bert_layer_bwd_mm: workspace of %lld bytes needed "
+             "(gcgcn_bert_layer_ws_bytes, which = 1)", (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1));
+  const BertLayerParams p = {params[0], params[1], params[2], params[3], params[4], params[5],
+                             params[6], params[7], params[8], params[9], params[10], params[11]};
+  const BertLayerGrads g = {grads[0], grads[1], grads[2], grads[3], grads[4], grads[5], grads[6], grads[7], grads[8], grads[9], grads[10], grads[11]};
+  return bert_layer_bwd(B, T, D, H, Dff, x, key_bias, p, (const float*)saved, dy, dx, g, (float*)ws, ws_bytes / (int64_t)sizeof(float), rng_snap,
+                        p_attn, p_hidden, (hipStream_t)stream, t_valid, rowblk, matmul);
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@
 // through a select, rows past T are not stored: what lies behind a buffer's end is never read and never reaches a result.
 #include "bert.hpp"
 #include "gemm.hpp"
+#include "gemm_bf16.hpp"
 #include "rowops.hpp"
 
 namespace gc {
@@ -651,10 +652,47 @@ GemmArgs on_rows(GemmArgs g, const int* rowblk, int mode, int zero_dead = 0) {
 }
 }  // namespace
 
+// ---- matmul = BERT_MM_BF16: the twelve products on the bf16 matrix cores (gemm_bf16.hpp) ---------------------------------------------
+// Everything between the products is the fp32 code above, the dropout sites and their indices included.  The products always run
+// DENSE: a row-block list is accepted and ignored.  The contract of the padding rows holds on the dense route by the argument in
+// front of on_rows() -- every buffer a product reads on padding rows is zero-stored by the length-aware kernel in front of it (x by
+// the caller, ctx by the attention core, a by LayerNorm, g by GELU; d o2 / d ao / dx' by LayerNorm's backward, dz by GELU's, dqkv by
+// the core's) -- and bf16(0) = 0, so dx = 0 W + 0 exactly.  A dense product also WRITES every row, so nothing the workspaces held
+// before the call survives.  The bias gradients are the exact fp32 column sums of the fp32 gradient tensors, launched stand-alone
+// (rowops' colsum through colpart: two launches per bias where the fp32 route has none of its own).
+namespace {
+int linear_bf16(float* y, const float* x, const float* w, const float* bias, int M, int N, int K, hipStream_t st) {   // y = x w^T + bias
+  GemmBf16Args g = gemm_bf16_stored(1, 1, x, K, w, K, y, N, M, N, K);
+  g.bias = bias;
+  return gemm_bf16(g, st);
+}
+// of y [M][N] = x [M][K] w[N][K]^T + b:  dw = dy^T x,  dx = dy w (+ add),  db = column sums of dy
+int linear_bf16_bwd(const float* dy, const float* x, const float* w, float* dw, float* dx, const float* add, float* db, int M, int N, int K,
+                    const Work& wk, hipStream_t st) {
+  GemmBf16Args gw = gemm_bf16_stored(0, 0, dy, N, x, K, dw, K, N, K, M);
+  gw.ws = wk.split, gw.ws_elems = wk.split_elems;
+  GC_TRY(gemm_bf16(gw, st));
+  GemmBf16Args gx = gemm_bf16_stored(1, 0, dy, N, w, K, dx, K, M, K, N);
+  gx.add = add, gx.ldadd = K, gx.ws = wk.split, gx.ws_elems = wk.split_elems;
+  GC_TRY(gemm_bf16(gx, st));
+  return colsum(dy, nullptr, db, M, N, N, 1, 0, 0, 0, 0, wk.colpart, st);
+}
+}  // namespace
+
 int bert_layer_fwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const BertLayerParams& p, float* y,
-                   float* saved, const void* snap, float p_attn, float p_hidden, hipStream_t st, const int* tv, const int* rowblk) {
+                   float* saved, const void* snap, float p_attn, float p_hidden, hipStream_t st, const int* tv, const int* rowblk, int matmul) {
   const long R = (long)B * T;
   const Saved s = saved_views(saved, B, T, D, H, Dff);
+  if (matmul == BERT_MM_BF16) {
+    GC_TRY(linear_bf16(s.qkv, x, p.wqkv, p.bqkv, (int)R, 3 * D, D, st));
+    GC_TRY(bert_attn_fwd(B, T, H, s.qkv, key_bias, s.ctx, s.lse, make_drop(snap, SALT_BERT_ATTN, p_attn), st, tv));
+    GC_TRY(linear_bf16(s.ao, s.ctx, p.wo, nullptr, (int)R, D, D, st));
+    GC_TRY(res_ln_fwd(R, D, s.ao, p.bo, x, p.ln1w, p.ln1b, s.a, s.mean1, s.rstd1, make_drop(snap, SALT_BERT_AO, p_hidden), st, tv, T));
+    GC_TRY(linear_bf16(s.z, s.a, p.wi, nullptr, (int)R, Dff, D, st));
+    GC_TRY(bias_gelu_fwd(R, Dff, s.z, p.bi, s.g, st, tv, T));
+    GC_TRY(linear_bf16(s.o2, s.g, p.wo2, nullptr, (int)R, D, Dff, st));
+    return res_ln_fwd(R, D, s.o2, p.bo2, s.a, p.ln2w, p.ln2b, y, s.mean2, s.rstd2, make_drop(snap, SALT_BERT_OUT, p_hidden), st, tv, T);
+  }
   const int* rb = tv && T % 16 == 0 ? rowblk : nullptr;
   GemmArgs g = on_rows(gemm_nt(x, D, p.wqkv, D, s.qkv, 3 * D, (int)R, 3 * D, D).tagged("bert_gemm"), rb, 1);
   g.bias = p.bqkv;
@@ -670,12 +708,24 @@ int bert_layer_fwd(int B, int T, int D, int H, int Dff, const float* x, const fl
 
 int bert_layer_bwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const BertLayerParams& p,
                    const float* saved, const float* dy, float* dx, const BertLayerGrads& d, float* ws, long ws_elems, const void* snap,
-                   float p_attn, float p_hidden, hipStream_t st, const int* tv, const int* rowblk) {
+                   float p_attn, float p_hidden, hipStream_t st, const int* tv, const int* rowblk, int matmul) {
   const long R = (long)B * T;
   const Saved s = saved_views(const_cast<float*>(saved), B, T, D, H, Dff);
   const Work w = work_views(ws, B, T, D, H, Dff);
   GC_REQUIRE(ws_elems >= w.total, "bert_layer_bwd: workspace of %ld floats needed", w.total);
   const int M = (int)R;
+  if (matmul == BERT_MM_BF16) {   // the chain below, product for product
+    GC_TRY(res_ln_bwd(R, D, dy, s.o2, p.bo2, s.a, p.ln2w, s.mean2, s.rstd2, w.t1, w.t2, d.ln2w, d.ln2b, w.lnpart,
+                      make_drop(snap, SALT_BERT_OUT, p_hidden), st, tv, T));
+    GC_TRY(linear_bf16_bwd(w.t1, s.g, p.wo2, d.wo2, w.big, nullptr, d.bo2, M, D, Dff, w, st));          // big = dg
+    GC_TRY(bias_gelu_bwd(R, Dff, w.big, s.z, p.bi, w.big, st, tv, T));                                   // big = dz
+    GC_TRY(linear_bf16_bwd(w.big, s.a, p.wi, d.wi, w.t3, w.t2, d.bi, M, Dff, D, w, st));                 // t3 = da
+    GC_TRY(res_ln_bwd(R, D, w.t3, s.ao, p.bo, x, p.ln1w, s.mean1, s.rstd1, w.t1, w.t2, d.ln1w, d.ln1b, w.lnpart,
+                      make_drop(snap, SALT_BERT_AO, p_hidden), st, tv, T));
+    GC_TRY(linear_bf16_bwd(w.t1, s.ctx, p.wo, d.wo, w.t3, nullptr, d.bo, M, D, D, w, st));               // t3 = dctx
+    GC_TRY(bert_attn_bwd(B, T, H, s.qkv, key_bias, s.ctx, s.lse, w.t3, w.big, w.delta, make_drop(snap, SALT_BERT_ATTN, p_attn), st, tv));
+    return linear_bf16_bwd(w.big, x, p.wqkv, d.wqkv, dx, w.t2, d.bqkv, M, 3 * D, D, w, st);              // big = dqkv
+  }
   const int* rb = tv && T % 16 == 0 ? rowblk : nullptr;
   // a weight gradient sums over the live row blocks (mode 2), a data gradient computes them (mode 1)
   auto wgrad = [&](GemmArgs g) { return on_rows(g.split_ws(w.split, w.split_elems).tagged("bert_gemm"), rb, 2); };

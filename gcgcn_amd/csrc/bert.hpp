@@ -67,11 +67,16 @@ long bert_layer_ws_elems(int B, int T, int D, int H, int Dff);   // the backward
 // t_valid: x must be zero on padding rows (the caller's, as for the graph blocks' X); y and dx are exactly zero there, dy there is
 // not read.  rowblk: gcgcn_row_blocks(B, T, t_valid) (T a multiple of 16) or nullptr -- the products then run on the live 16-row blocks
 // wherever the GEMM launcher serves the list, dense elsewhere; the results obey the same contract either way.
+// matmul: BERT_MM_FP32 = the fp32-MFMA GEMM layer, launch for launch what it was; BERT_MM_BF16 = the twelve Linear products with bf16
+// operands (gemm_bf16.hpp: fp32 in memory, rounded once on the way into LDS, fp32 accumulation), always dense (rowblk is ignored), the
+// bias gradients as stand-alone fp32 column sums.  The saved state and the workspace are the same either way.
+constexpr int BERT_MM_FP32 = 0, BERT_MM_BF16 = 1;
 int bert_layer_fwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const BertLayerParams& p, float* y,
                    float* saved, const void* snap, float p_attn, float p_hidden, hipStream_t st, const int* t_valid = nullptr,
-                   const int* rowblk = nullptr);
+                   const int* rowblk = nullptr, int matmul = BERT_MM_FP32);
 int bert_layer_bwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const BertLayerParams& p,
                    const float* saved, const float* dy, float* dx, const BertLayerGrads& g, float* ws, long ws_elems, const void* snap,
-                   float p_attn, float p_hidden, hipStream_t st, const int* t_valid = nullptr, const int* rowblk = nullptr);
+                   float p_attn, float p_hidden, hipStream_t st, const int* t_valid = nullptr, const int* rowblk = nullptr,
+                   int matmul = BERT_MM_FP32);
 
 }  // namespace gc

@@ -1521,17 +1521,21 @@ def _ptr_array(tensors):
 
 
 class BertLayerFn(torch.autograd.Function):
-    """(x[B,T,D], key_bias[B,T] | None, t_valid[B] | None, rowblk | None, the 12 tensors of gcgcn_bert_layer_fwd's parameter list) ->
-    y[B,T,D].  With t_valid the _len entry points run (include/gcgcn.h)."""
+    """(x[B,T,D], key_bias[B,T] | None, t_valid[B] | None, rowblk | None, matmul, the 12 tensors of gcgcn_bert_layer_fwd's parameter
+    list) -> y[B,T,D].  With t_valid the _len entry points run (include/gcgcn.h); matmul = 1 (bf16 operands) runs the _mm ones."""
 
     @staticmethod
-    def forward(ctx, x, key_bias, H, p_attn, p_hidden, snap, t_valid, rowblk, *params):
+    def forward(ctx, x, key_bias, H, p_attn, p_hidden, snap, t_valid, rowblk, matmul, *params):
         B, T, D = x.shape
         Dff = params[6].shape[0]
         dims = (B, T, D, H, Dff)
         saved = _f32_buf(_bytes_or_raise("gcgcn_bert_layer_ws_bytes", *dims, 0), x.device)
         y = torch.empty_like(x)
-        if t_valid is None:
+        ctx.matmul = matmul
+        if matmul:
+            call("gcgcn_bert_layer_fwd_mm", *dims, _p(x), _p(key_bias), _p(t_valid), _p(rowblk), _ptr_array(params), _p(y), _p(saved),
+                 saved.numel() * 4, _p(snap), float(p_attn), float(p_hidden), _stream(), matmul)
+        elif t_valid is None:
             call("gcgcn_bert_layer_fwd", *dims, _p(x), _p(key_bias), _ptr_array(params), _p(y), _p(saved), saved.numel() * 4, _p(snap),
                  float(p_attn), float(p_hidden), _stream())
         else:
@@ -1554,18 +1558,31 @@ class BertLayerFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         grads = tuple(torch.empty_like(t) for t in params)
         ws = _f32_buf(_bytes_or_raise("gcgcn_bert_layer_ws_bytes", *ctx.dims, 1), x.device)
-        if ctx.t_valid is None:
+        if ctx.matmul:
+            call("gcgcn_bert_layer_bwd_mm", *ctx.dims, _p(x), _p(key_bias), _p(ctx.t_valid), _p(ctx.rowblk), _ptr_array(params), _p(saved),
+                 saved.numel() * 4, _p(dy), _p(dx), _ptr_array(grads), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.ps[0], ctx.ps[1], _stream(),
+                 ctx.matmul)
+        elif ctx.t_valid is None:
             call("gcgcn_bert_layer_bwd", *ctx.dims, _p(x), _p(key_bias), _ptr_array(params), _p(saved), saved.numel() * 4, _p(dy), _p(dx),
                  _ptr_array(grads), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.ps[0], ctx.ps[1], _stream())
         else:
             call("gcgcn_bert_layer_bwd_len", *ctx.dims, _p(x), _p(key_bias), _p(ctx.t_valid), _p(ctx.rowblk), _ptr_array(params), _p(saved),
                  saved.numel() * 4, _p(dy), _p(dx), _ptr_array(grads), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.ps[0], ctx.ps[1], _stream())
         torch.autograd.graph.increment_version((dx,) + grads)
-        return (dx, None, None, None, None, None, None, None) + grads
+        return (dx, None, None, None, None, None, None, None, None) + grads
+
+
+BERT_MATMULS = ("fp32", "bf16")     # the value of gcgcn_bert_layer_*_mm's selector is the index
+
+
+def bert_matmul_index(matmul, who: str) -> int:
+    if matmul not in BERT_MATMULS:
+        raise ValueError(f"{who}: matmul must be 'fp32' or 'bf16', got {matmul!r}")
+    return BERT_MATMULS.index(matmul)
 
 
 def bert_layer(x, key_bias, wq, bq, wk, bk, wv, bv, wo, bo, ln1_w, ln1_b, wi, bi, wo2, bo2, ln2_w, ln2_b, p_attn=0.1, p_hidden=0.1,
-               training=False, snap=None, t_valid=None, rowblk=None):
+               training=False, snap=None, t_valid=None, rowblk=None, matmul="fp32"):
     """One BERT encoder layer (``pytorch_pretrained_bert`` 0.6 ``BertLayer``) in HIP: ``x[B,T,D]`` -> ``[B,T,D]``.  ``key_bias``:
     ``[B,T]`` additive score penalty per key (``(1 - mask) * -10000``) or None.  The 16 parameter tensors in ``BERT_LAYER_TENSORS``'
     order, Linear weights ``[out, in]``; the number of heads is ``D / 64`` (the attention kernels serve a head width of 64) and
@@ -1580,7 +1597,15 @@ def bert_layer(x, key_bias, wq, bq, wk, bk, wv, bv, wo, bo, ln1_w, ln1_b, wi, bi
     included) and ``x`` must be zero there.  The dropout indices do not move.  ``rowblk``: ``row_blocks(t_valid, B, T)``, built once
     per model forward and shared by the layers -- the Linears then run on the live 16-row blocks where the GEMM launcher serves the
     list and dense elsewhere (always when ``T % 16 != 0``), with the same results contract; ``None`` with ``t_valid``: dense.
-    ``t_valid=None``: the call as it was."""
+    ``t_valid=None``: the call as it was.
+
+    ``matmul``: ``"fp32"`` (default: exactly the calls made without the argument) or ``"bf16"``: the twelve Linear products of the
+    forward and the backward take bf16 operands -- every operand element rounded once, round to nearest even, what
+    ``t.to(torch.bfloat16)`` does -- on the bf16 matrix cores, with fp32 accumulation; activations, weights and gradients stay fp32
+    in memory, the bias gradients are fp32 sums of the unrounded gradients and everything between the products is unchanged.  The
+    products then always run dense (``rowblk`` is accepted and ignored); the contract of the padding rows holds.
+    ``BertModel(impl="torch", matmul="bf16")`` is the definition."""
+    mm = bert_matmul_index(matmul, "bert_layer")
     x = _chk(x, "x", 3)
     names = ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo", "ln1_w", "ln1_b", "wi", "bi", "wo2", "bo2", "ln2_w", "ln2_b")
     ts = [_chk(t, n) for n, t in zip(names, (wq, bq, wk, bk, wv, bv, wo, bo, ln1_w, ln1_b, wi, bi, wo2, bo2, ln2_w, ln2_b))]
@@ -1608,5 +1633,35 @@ def bert_layer(x, key_bias, wq, bq, wk, bk, wv, bv, wo, bo, ln1_w, ln1_b, wi, bi
             raise ValueError(f"bert_layer: rowblk is not row_blocks(t_valid, {B}, {T})")
     elif rowblk is not None:
         raise ValueError("bert_layer: rowblk without t_valid")
-    return BertLayerFn.apply(x, key_bias, D // 64, p_attn, p_hidden, snap if (p_attn > 0 or p_hidden > 0) else None, t_valid, rowblk, wqkv,
-                             bqkv, *ts[6:])
+    return BertLayerFn.apply(x, key_bias, D // 64, p_attn, p_hidden, snap if (p_attn > 0 or p_hidden > 0) else None, t_valid, rowblk, mm,
+                             wqkv, bqkv, *ts[6:])
+
+
+def gemm_bf16(a, b, form="nt", bias=None, add=None):
+    """``op(a) op(b) + bias[col] + add`` with bf16 operands and fp32 accumulation (csrc/gemm_bf16.hip through ``gcgcn_gemm_bf16``): fp32
+    in, fp32 out, every operand element rounded once to bf16.  ``form`` names how the operands are STORED: ``"nn"``: ``a[M,K] @
+    b[K,N]``; ``"nt"``: ``a[M,K] @ b[N,K].T``; ``"tn"``: ``a[K,M].T @ b[K,N]``.  ``a``, ``b`` and ``add`` may be row-strided views
+    (unit stride in the last axis).  ``bias`` ``[N]``, ``add`` ``[M,N]``.  No autograd: a binding for tests and tools."""
+    if form not in ("nn", "nt", "tn"):
+        raise ValueError(f"gemm_bf16: form must be 'nn', 'nt' or 'tn', got {form!r}")
+    for n, t in (("a", a), ("b", b), ("bias", bias), ("add", add)):
+        if t is None:
+            continue
+        if not t.is_cuda or t.dtype != torch.float32:
+            raise RuntimeError(f"gemm_bf16: {n} must be a float32 tensor on the GPU (there is no CPU fallback)")
+        if t.dim() != (1 if n == "bias" else 2) or t.stride(-1) != 1:
+            raise ValueError(f"gemm_bf16: {n} has shape {tuple(t.shape)} and strides {t.stride()}")
+    a_kc, b_kc = form != "tn", form == "nt"
+    M, K = a.shape if a_kc else a.shape[::-1]
+    N, Kb = b.shape if b_kc else b.shape[::-1]
+    if K != Kb or min(M, N, K) < 1:
+        raise ValueError(f"gemm_bf16: a {tuple(a.shape)} and b {tuple(b.shape)} do not form a '{form}' product")
+    if bias is not None and bias.shape != (N,):
+        raise ValueError(f"gemm_bf16: bias {tuple(bias.shape)}, expected ({N},)")
+    if add is not None and add.shape != (M, N):
+        raise ValueError(f"gemm_bf16: add {tuple(add.shape)}, expected ({M}, {N})")
+    c = torch.empty(M, N, device=a.device)
+    ws = _f32_buf(_bytes_or_raise("gcgcn_gemm_bf16_ws_bytes", M, N, K), a.device)
+    call("gcgcn_gemm_bf16", int(a_kc), int(b_kc), _p(a), a.stride(0), _p(b), b.stride(0), _p(c), N, M, N, K, _p(bias), _p(add),
+         0 if add is None else add.stride(0), _p(ws) if ws.numel() else None, ws.numel() * 4, _stream())
+    return c

@@ -218,7 +218,11 @@ class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
 
     ``config.bert_impl = "torch" | "hip"`` builds this library's own encoder instead: ``gcgcn_amd.BertModel(config.bert_config or
     BertConfig(), impl=...)``, its weights loaded from the LOCAL file ``config.bert_weights`` when that is set; the token width
-    follows ``bert_config.hidden_size``.  Without ``bert_impl`` nothing changes."""
+    follows ``bert_config.hidden_size``.  Without ``bert_impl`` nothing changes.
+
+    ``config.bert_matmul = "fp32" | "bf16"`` (needs ``bert_impl``; a ``ValueError`` without it) is that encoder's ``matmul``: with
+    ``"bf16"`` the encoder layers' Linears take bf16 operands with fp32 accumulation while parameters, gradients and the
+    ``state_dict`` stay fp32 (``gcgcn_amd.BertModel``).  Without ``bert_matmul`` nothing changes."""
 
     WORD_VEC_SIZE = 768
     _KEY_ORDER = ("bert", "ner_emb", "entity_embed", "get_weighted_adj_matrix", "get_adj_matrix", "graphcnn", "linear_re",
@@ -228,11 +232,17 @@ class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
     def __init__(self, config, bert: Optional[nn.Module] = None):
         super().__init__(config, layer_num=4, head_num=4)                                   # bert:247-248
         impl = getattr(config, "bert_impl", None)
+        matmul = getattr(config, "bert_matmul", None)
+        if matmul is not None:
+            if matmul not in ("fp32", "bf16"):
+                raise ValueError(f"config.bert_matmul must be 'fp32' or 'bf16', got {matmul!r}")
+            if impl is None:
+                raise ValueError("config.bert_matmul selects the Linears of this library's own encoder: set config.bert_impl too")
         if bert is None and impl is not None:                                                # this library's own encoder (bert.py)
             from .bert import BertConfig, BertModel as OwnBert, load_pretrained_state_dict
             if impl not in ("torch", "hip"):
                 raise ValueError(f"config.bert_impl must be 'torch' or 'hip', got {impl!r}")
-            bert = OwnBert(getattr(config, "bert_config", None) or BertConfig(), impl=impl)
+            bert = OwnBert(getattr(config, "bert_config", None) or BertConfig(), impl=impl, **({} if matmul is None else {"matmul": matmul}))
             if getattr(config, "bert_weights", None):
                 load_pretrained_state_dict(bert, config.bert_weights)
             if bert.config.hidden_size != self.WORD_VEC_SIZE:

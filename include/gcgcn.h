@@ -695,6 +695,31 @@ int gcgcn_bert_layer_bwd_len(int B, int T, int D, int H, int Dff, const float* x
                              float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn, float p_hidden,
                              void* stream);
 
+/* ---- opt-in bf16 matrix products (gemm_bf16.hip) --------------------------------------------------------------
+ * gcgcn_gemm_bf16: C [M][N] = op(A) op(B) + bias[col] + add[row][col] (bias [N], add [M][ldadd], each or both NULL) for the storage
+ * forms of gcgcn_gemm: a_kc = 1: A is stored [M][K], else [K][M]; b_kc = 1: B is stored [N][K], else [K][N]; NN (1, 0), NT (1, 1) and
+ * TN (0, 0) are served.  Operands and result are fp32 in memory.  Every operand element is rounded once to bf16, round to nearest even
+ * (what tensor.to(torch.bfloat16) does), on its way into the workgroup's LDS; the products run on v_mfma_f32_16x16x32_bf16, the
+ * accumulation, the epilogue (bias, then add) and the store are fp32.  Every M, N, K >= 1 is served; nothing outside the [M][K], [K][N],
+ * [M][N] views is read or written, the ld padding included.  Long K on few tiles is cut into runs whose partial tiles go through ws
+ * (gcgcn_gemm_bf16_ws_bytes(M, N, K) bytes, 16-byte aligned; 0: ws may be NULL) and are added in a fixed order: no float atomics, two
+ * runs are bitwise equal.  Capturable: no host read, no allocation, no synchronisation.
+ * gcgcn_bert_layer_fwd_mm / gcgcn_bert_layer_bwd_mm: the _len entry points (t_valid and rowblk may both be NULL: every row is live)
+ * with a selector for the twelve Linear products.  matmul = 0: the fp32 GEMM layer, launch for launch what the entry points above
+ * run.  matmul = 1: bf16 operands as above -- everything else (attention core, LayerNorms, GELU, dropout sites and indices, saved
+ * state, workspace sizes) is unchanged, the bias gradients are exact fp32 column sums, and the products always run dense (rowblk is
+ * accepted and ignored; the padding-row contract of the _len entry points holds).  Both calls of a pair take the same matmul. */
+int64_t gcgcn_gemm_bf16_ws_bytes(int M, int N, int K);
+int gcgcn_gemm_bf16(int a_kc, int b_kc, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M, int N, int K,
+                    const float* bias, const float* add, int64_t ldadd, void* ws, int64_t ws_bytes, void* stream);
+int gcgcn_bert_layer_fwd_mm(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
+                            const int32_t* rowblk, const float* const* params, float* y, void* saved, int64_t saved_bytes,
+                            const void* rng_snap, float p_attn, float p_hidden, void* stream, int matmul);
+int gcgcn_bert_layer_bwd_mm(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
+                            const int32_t* rowblk, const float* const* params, const void* saved, int64_t saved_bytes, const float* dy,
+                            float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn, float p_hidden,
+                            void* stream, int matmul);
+
 #ifdef __cplusplus
 }
 #endif

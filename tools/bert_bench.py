@@ -6,11 +6,17 @@ layer's time split: each non-GEMM kernel timed on its own through the C ABI, the
 
     python tools/bert_bench.py [--layers 12] [--iters 20] [--json out.json]
     python tools/bert_bench.py --lengths {full,ragged} [--shape 4x512] [--layers 12] [--iters 20] [--json out.json]
+    python tools/bert_bench.py --matmul fp32 bf16 [--lengths ragged] [--shape 4x512] [--layers 12] [--iters 10] [--json out.json]
 
 With --lengths only the HIP encoder runs, as one replayed hipGraph, twice on the same token counts in the same process: the
 prefix-mask path (attention_mask = arange(T) < t_valid, every row computed) and the length path (lengths = t_valid, live tokens
 only).  ``full``: every document at T -- the feature's overhead.  ``ragged``: a fixed seeded draw, uniform integers in [T/8, T];
 seed and mean are printed.  --shape restricts the run to one (B, T), so that a caller can give every run its own time limit.
+
+With --matmul only the HIP encoder runs, as one replayed hipGraph, once per listed setting of BertModel(matmul=...), back to back in
+the same process on the same inputs (median, min and max of --iters samples; with --lengths on those token counts through
+lengths=), followed by one layer's twelve Linear products timed alone through the C ABI: the fp32 GEMM layer's launch against the
+bf16 kernel's, with the achieved TF/s.
 
 Prints one table and, with --json, writes the numbers.  DESIGN.md section 8.9 holds the tables of record."""
 import argparse
@@ -41,6 +47,22 @@ def timed(fn, iters, warmup=3):
     return statistics.median(ms)
 
 
+def timed_stats(fn, iters, warmup=3):
+    """(median, min, max) ms of `iters` samples."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(iters):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms), min(ms), max(ms)
+
+
 LENGTH_SEED = 2024
 
 
@@ -52,11 +74,11 @@ def draw_lengths(kind, B, T):
     return torch.randint(T // 8, T + 1, (B,), generator=g).to(torch.int32)
 
 
-def model_step(layers, impl, B, T, dev, t_valid=None, by_lengths=False):
+def model_step(layers, impl, B, T, dev, t_valid=None, by_lengths=False, matmul="fp32"):
     """t_valid None: the masks this tool has always used.  Otherwise the prefix mask of these counts, or (by_lengths) lengths=t_valid."""
     cfg = BertConfig(num_hidden_layers=layers, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
     torch.manual_seed(0)
-    model = BertModel(cfg, impl=impl).to(dev).train()
+    model = BertModel(cfg, impl=impl, matmul=matmul).to(dev).train()
     g = torch.Generator().manual_seed(1)
     ids = torch.randint(0, cfg.vocab_size, (B, T), generator=g).to(dev)
     counts = torch.tensor([T - 37 * (b % 3) for b in range(B)]) if t_valid is None else t_valid.cpu()
@@ -116,6 +138,29 @@ def kernel_split(B, T, dev, iters):
     return out
 
 
+def product_split(B, T, dev, iters):
+    """One base-size layer's twelve Linear products alone, random data: (name, M, N, K, fp32 ms, bf16 ms).  The fp32 launch is the GEMM
+    layer's stand-alone one with its own split choice (in the layer the backward's pairs share a group launch)."""
+    D, I, R = 768, 3072, B * T
+    st = torch.cuda.current_stream().cuda_stream
+    p = lambda t: t.data_ptr()
+    ws = torch.empty(16 << 20, device=dev)
+    out = []
+    for lin, (N, K) in (("qkv", (3 * D, D)), ("attn.out", (D, D)), ("intermediate", (I, D)), ("output", (D, I))):
+        x, w, dy = torch.randn(R, K, device=dev), torch.randn(N, K, device=dev), torch.randn(R, N, device=dev)
+        y, dx, dw = torch.empty(R, N, device=dev), torch.empty(R, K, device=dev), torch.empty(N, K, device=dev)
+        # (form, a_kc, b_kc, A, lda, B, ldb, C, ldc, M, N, K)
+        probs = (("fwd  nt", 1, 1, x, K, w, K, y, N, R, N, K), ("dx   nn", 1, 0, dy, N, w, K, dx, K, R, K, N), ("dw   tn", 0, 0, dy, N, x, K, dw, K, N, K, R))
+        for name, akc, bkc, A, lda, Bm, ldb, C, ldc, m, n, k in probs:
+            f32 = timed(lambda: _lib.call("gcgcn_gemm", m, n, k, p(A), lda, akc, p(Bm), ldb, bkc, p(C), ldc, 1, 0, 0, 0, 1.0, None, 0, 0, 0, 0, p(ws),
+                                          ws.numel(), st), iters)
+            b16 = timed(lambda: _lib.call("gcgcn_gemm_bf16", akc, bkc, p(A), lda, p(Bm), ldb, p(C), ldc, m, n, k, None, None, 0, p(ws), ws.numel() * 4,
+                                          st), iters)
+            out.append({"product": f"{lin} {name}", "M": m, "N": n, "K": k, "fp32_ms": f32, "bf16_ms": b16,
+                        "fp32_tflops": 2e-9 * m * n * k / f32, "bf16_tflops": 2e-9 * m * n * k / b16})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=12)
@@ -123,12 +168,35 @@ def main():
     ap.add_argument("--json")
     ap.add_argument("--lengths", choices=("full", "ragged"), help="the HIP encoder's prefix-mask path against its length path on these token counts")
     ap.add_argument("--shape", help="BxT: this shape only (default: 4x512 and 8x256)")
+    ap.add_argument("--matmul", nargs="+", choices=("fp32", "bf16"), help="the HIP encoder with these matmul settings, back to back")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.backends.cuda.matmul.allow_tf32 = False
     rows = []
     shapes = ((4, 512), (8, 256)) if not a.shape else (tuple(int(v) for v in a.shape.lower().split("x")),)
-    if a.lengths:
+    if a.matmul:
+        for B, T in shapes:
+            tv = draw_lengths(a.lengths, B, T) if a.lengths else None
+            if tv is not None:
+                print(f"B={B} T={T} lengths={a.lengths} seed={LENGTH_SEED} t_valid={tv.tolist()} mean={tv.float().mean().item():.1f}", flush=True)
+            for layers in sorted({1, a.layers}):
+                r = {"B": B, "T": T, "layers": layers, "lengths": a.lengths, "t_valid": None if tv is None else tv.tolist()}
+                for mm in a.matmul:
+                    step = model_step(layers, "hip", B, T, dev, tv, tv is not None, matmul=mm)
+                    r[f"{mm}_graph_ms"], r[f"{mm}_min_ms"], r[f"{mm}_max_ms"] = timed_stats(graphed(step), a.iters)
+                    del step
+                    torch.cuda.empty_cache()
+                rows.append(r)
+                print(f"B={B} T={T} layers={layers:2d} lengths={a.lengths}: " + "  ".join(f"{k}={v:.3f}" for k, v in r.items() if k.endswith("_ms")),
+                      flush=True)
+            if not a.lengths:
+                split = product_split(B, T, dev, a.iters)
+                rows.append({"B": B, "T": T, "products": split})
+                for q in split:
+                    print(f"B={B} T={T} {q['product']:22s} ({q['M']:5d},{q['N']:5d},{q['K']:5d})  fp32 {q['fp32_ms']:.4f} ms {q['fp32_tflops']:6.1f} TF/s   "
+                          f"bf16 {q['bf16_ms']:.4f} ms {q['bf16_tflops']:6.1f} TF/s", flush=True)
+        shapes = ()
+    elif a.lengths:
         for B, T in shapes:
             tv = draw_lengths(a.lengths, B, T)
             print(f"B={B} T={T} lengths={a.lengths} seed={LENGTH_SEED} t_valid={tv.tolist()} mean={tv.float().mean().item():.1f} "
