@@ -18,6 +18,8 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
+from .functional import bert_matmul_index
+
 LN_EPS = 1e-12
 MASK_PENALTY = -10000.0
 
@@ -108,9 +110,6 @@ class _Encoder(nn.Module):
         self.layer = nn.ModuleList(_Layer(c) for _ in range(c.num_hidden_layers))
 
 
-MATMULS = ("fp32", "bf16")
-
-
 def _bf16(t):
     """Round every element to bfloat16 (to nearest even) and return it in the tensor's own dtype."""
     return t.to(torch.bfloat16).to(t.dtype)
@@ -191,8 +190,7 @@ class BertModel(nn.Module):
         config = BertConfig() if config is None else config
         if impl not in ("torch", "hip"):
             raise ValueError(f"BertModel: impl must be 'torch' or 'hip', got {impl!r}")
-        if matmul not in MATMULS:
-            raise ValueError(f"BertModel: matmul must be 'fp32' or 'bf16', got {matmul!r}")
+        bert_matmul_index(matmul, "BertModel")      # raises on anything but the allowed names
         if config.hidden_size % config.num_attention_heads:
             raise ValueError(f"BertModel: hidden size {config.hidden_size} is no multiple of {config.num_attention_heads} heads")
         if impl == "hip" and config.hidden_size != 64 * config.num_attention_heads:
@@ -258,7 +256,6 @@ class BertModel(nn.Module):
         if not emb.is_cuda:
             raise RuntimeError(f"BertModel(impl='hip') runs on MI355X only; got {emb.device} tensors (impl='torch' runs anywhere)")
         training = self.training
-        mm = {"matmul": self.matmul} if self.matmul != "fp32" else {}      # "fp32": the call as it was
         n = len(self.encoder.layer)
         snaps = []
         tv = rowblk = None
@@ -278,7 +275,7 @@ class BertModel(nn.Module):
                 snap = Fn.rng_snapshot(emb.device) if training else None
                 snaps.append(snap)
                 x = Fn.bert_layer(x, kb, *layer.tensors(), p_attn=c.attention_probs_dropout_prob, p_hidden=c.hidden_dropout_prob,
-                                  training=training, snap=snap, t_valid=tv, rowblk=rowblk, **mm)
+                                  training=training, snap=snap, t_valid=tv, rowblk=rowblk, matmul=self.matmul)
                 outs.append(x)
         self.last_rng_snaps = snaps if training else None
         if not outs:

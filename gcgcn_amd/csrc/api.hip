@@ -1197,21 +1197,49 @@ static int bert_layer_shape_ok(const char* who, int B, int T, int D, int H, int 
   return 0;
 }
 
+// Token lengths: t_valid int32 [B] on the device, row (b, t) live iff t < t_valid[b] (gcgcn.h).  Each operation below has ONE body
+// that checks, unpacks and calls into gc::.  It takes the most general argument list, the name of the symbol that was called (who)
+// and need_len, whether that symbol requires t_valid.  The exported symbols only forward: the plain ones pass no lengths (and
+// BERT_MM_FP32), the _len ones set need_len, _mm passes everything through.
+static int bert_len_ok(const char* who, const int32_t* t_valid, int64_t rows, int T) {
+  GC_REQUIRE(t_valid, "%s: t_valid is null (the entry point without _len takes no lengths)", who);
+  GC_REQUIRE(T >= 1 && rows % T == 0, "%s: %lld rows are no whole documents of T = %d", who, (long long)rows, T);
+  return 0;
+}
+
+static int attn_fwd(const char* who, bool need_len, int B, int T, int H, int dh, const float* qkv, const float* key_bias,
+                    const int32_t* t_valid, float* ctx, float* lse, const void* rng_snap, uint64_t salt, float p, void* stream) {
+  GC_TRY(bert_attn_shape_ok(who, B, T, H, dh));
+  GC_TRY(bert_drop_ok(who, rng_snap, p));
+  GC_REQUIRE(qkv && ctx && lse && (t_valid || !need_len), "%s: null pointer", who);
+  GC_REQUIRE(al16(qkv), "%s: qkv must be 16-byte aligned", who);
+  return bert_attn_fwd(B, T, H, qkv, key_bias, ctx, lse, make_drop(rng_snap, salt, p), (hipStream_t)stream, t_valid);
+}
+static int attn_bwd(const char* who, bool need_len, int B, int T, int H, int dh, const float* qkv, const float* key_bias,
+                    const int32_t* t_valid, const float* ctx, const float* lse, const float* dctx, float* dqkv, float* delta,
+                    const void* rng_snap, uint64_t salt, float p, void* stream) {
+  GC_TRY(bert_attn_shape_ok(who, B, T, H, dh));
+  GC_TRY(bert_drop_ok(who, rng_snap, p));
+  GC_REQUIRE(qkv && ctx && lse && dctx && dqkv && delta && (t_valid || !need_len), "%s: null pointer", who);
+  GC_REQUIRE(al16(qkv) && al16(dctx), "%s: qkv and dctx must be 16-byte aligned", who);
+  return bert_attn_bwd(B, T, H, qkv, key_bias, ctx, lse, dctx, dqkv, delta, make_drop(rng_snap, salt, p), (hipStream_t)stream, t_valid);
+}
 int gcgcn_bert_attn_fwd(int B, int T, int H, int dh, const float* qkv, const float* key_bias, float* ctx, float* lse, const void* rng_snap,
                         uint64_t salt, float p, void* stream) {
-  GC_TRY(bert_attn_shape_ok("bert_attn_fwd", B, T, H, dh));
-  GC_TRY(bert_drop_ok("bert_attn_fwd", rng_snap, p));
-  GC_REQUIRE(qkv && ctx && lse, "bert_attn_fwd: null pointer");
-  GC_REQUIRE(al16(qkv), "bert_attn_fwd: qkv must be 16-byte aligned");
-  return bert_attn_fwd(B, T, H, qkv, key_bias, ctx, lse, make_drop(rng_snap, salt, p), (hipStream_t)stream);
+  return attn_fwd("bert_attn_fwd", false, B, T, H, dh, qkv, key_bias, nullptr, ctx, lse, rng_snap, salt, p, stream);
+}
+int gcgcn_bert_attn_fwd_len(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const int32_t* t_valid, float* ctx,
+                            float* lse, const void* rng_snap, uint64_t salt, float p, void* stream) {
+  return attn_fwd("bert_attn_fwd_len", true, B, T, H, dh, qkv, key_bias, t_valid, ctx, lse, rng_snap, salt, p, stream);
 }
 int gcgcn_bert_attn_bwd(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const float* ctx, const float* lse,
                         const float* dctx, float* dqkv, float* delta, const void* rng_snap, uint64_t salt, float p, void* stream) {
-  GC_TRY(bert_attn_shape_ok("bert_attn_bwd", B, T, H, dh));
-  GC_TRY(bert_drop_ok("bert_attn_bwd", rng_snap, p));
-  GC_REQUIRE(qkv && ctx && lse && dctx && dqkv && delta, "bert_attn_bwd: null pointer");
-  GC_REQUIRE(al16(qkv) && al16(dctx), "bert_attn_bwd: qkv and dctx must be 16-byte aligned");
-  return bert_attn_bwd(B, T, H, qkv, key_bias, ctx, lse, dctx, dqkv, delta, make_drop(rng_snap, salt, p), (hipStream_t)stream);
+  return attn_bwd("bert_attn_bwd", false, B, T, H, dh, qkv, key_bias, nullptr, ctx, lse, dctx, dqkv, delta, rng_snap, salt, p, stream);
+}
+int gcgcn_bert_attn_bwd_len(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const int32_t* t_valid, const float* ctx,
+                            const float* lse, const float* dctx, float* dqkv, float* delta, const void* rng_snap, uint64_t salt, float p,
+                            void* stream) {
+  return attn_bwd("bert_attn_bwd_len", true, B, T, H, dh, qkv, key_bias, t_valid, ctx, lse, dctx, dqkv, delta, rng_snap, salt, p, stream);
 }
 
 static int res_ln_shape_ok(const char* who, int64_t rows, int D) {
@@ -1223,23 +1251,47 @@ int64_t gcgcn_res_ln_ws_bytes(int D) {
   if (res_ln_shape_ok("res_ln_ws_bytes", 1, D)) return -1;
   return (int64_t)sizeof(float) * res_ln_ws_elems(D);
 }
+static int ln_fwd(const char* who, bool need_len, int64_t rows, int D, const float* x, const float* bias, const float* res,
+                  const float* weight, const float* lnb, const int32_t* t_valid, int T, float* y, float* mean, float* rstd,
+                  const void* rng_snap, uint64_t salt, float p, void* stream) {
+  GC_TRY(res_ln_shape_ok(who, rows, D));
+  if (need_len) GC_TRY(bert_len_ok(who, t_valid, rows, T));
+  GC_TRY(bert_drop_ok(who, rng_snap, p));
+  GC_REQUIRE(x && weight && lnb && y && (!mean == !rstd), "%s: null pointer", who);
+  return res_ln_fwd(rows, D, x, bias, res, weight, lnb, y, mean, rstd, make_drop(rng_snap, salt, p), (hipStream_t)stream, t_valid, T);
+}
+static int ln_bwd(const char* who, bool need_len, int64_t rows, int D, const float* dy, const float* x, const float* bias, const float* res,
+                  const float* weight, const float* mean, const float* rstd, const int32_t* t_valid, int T, float* dx, float* dres,
+                  float* dweight, float* dlnb, void* ws, int64_t ws_bytes, const void* rng_snap, uint64_t salt, float p, void* stream) {
+  GC_TRY(res_ln_shape_ok(who, rows, D));
+  if (need_len) GC_TRY(bert_len_ok(who, t_valid, rows, T));
+  GC_TRY(bert_drop_ok(who, rng_snap, p));
+  GC_REQUIRE(dy && x && weight && mean && rstd && dx && dweight && dlnb && ws, "%s: null pointer", who);
+  GC_REQUIRE(ws_bytes >= gcgcn_res_ln_ws_bytes(D), "%s: workspace of %lld bytes needed (gcgcn_res_ln_ws_bytes)", who,
+             (long long)gcgcn_res_ln_ws_bytes(D));
+  return res_ln_bwd(rows, D, dy, x, bias, res, weight, mean, rstd, dx, dres, dweight, dlnb, (float*)ws, make_drop(rng_snap, salt, p),
+                    (hipStream_t)stream, t_valid, T);
+}
 int gcgcn_res_ln_fwd(int64_t rows, int D, const float* x, const float* bias, const float* res, const float* weight, const float* lnb,
                      float* y, float* mean, float* rstd, const void* rng_snap, uint64_t salt, float p, void* stream) {
-  GC_TRY(res_ln_shape_ok("res_ln_fwd", rows, D));
-  GC_TRY(bert_drop_ok("res_ln_fwd", rng_snap, p));
-  GC_REQUIRE(x && weight && lnb && y && (!mean == !rstd), "res_ln_fwd: null pointer");
-  return res_ln_fwd(rows, D, x, bias, res, weight, lnb, y, mean, rstd, make_drop(rng_snap, salt, p), (hipStream_t)stream);
+  return ln_fwd("res_ln_fwd", false, rows, D, x, bias, res, weight, lnb, nullptr, 0, y, mean, rstd, rng_snap, salt, p, stream);
+}
+int gcgcn_res_ln_fwd_len(int64_t rows, int D, const float* x, const float* bias, const float* res, const float* weight, const float* lnb,
+                         const int32_t* t_valid, int T, float* y, float* mean, float* rstd, const void* rng_snap, uint64_t salt, float p,
+                         void* stream) {
+  return ln_fwd("res_ln_fwd_len", true, rows, D, x, bias, res, weight, lnb, t_valid, T, y, mean, rstd, rng_snap, salt, p, stream);
 }
 int gcgcn_res_ln_bwd(int64_t rows, int D, const float* dy, const float* x, const float* bias, const float* res, const float* weight,
                      const float* mean, const float* rstd, float* dx, float* dres, float* dweight, float* dlnb, void* ws, int64_t ws_bytes,
                      const void* rng_snap, uint64_t salt, float p, void* stream) {
-  GC_TRY(res_ln_shape_ok("res_ln_bwd", rows, D));
-  GC_TRY(bert_drop_ok("res_ln_bwd", rng_snap, p));
-  GC_REQUIRE(dy && x && weight && mean && rstd && dx && dweight && dlnb && ws, "res_ln_bwd: null pointer");
-  GC_REQUIRE(ws_bytes >= gcgcn_res_ln_ws_bytes(D), "res_ln_bwd: workspace of %lld bytes needed (gcgcn_res_ln_ws_bytes)",
-             (long long)gcgcn_res_ln_ws_bytes(D));
-  return res_ln_bwd(rows, D, dy, x, bias, res, weight, mean, rstd, dx, dres, dweight, dlnb, (float*)ws, make_drop(rng_snap, salt, p),
-                    (hipStream_t)stream);
+  return ln_bwd("res_ln_bwd", false, rows, D, dy, x, bias, res, weight, mean, rstd, nullptr, 0, dx, dres, dweight, dlnb, ws, ws_bytes,
+                rng_snap, salt, p, stream);
+}
+int gcgcn_res_ln_bwd_len(int64_t rows, int D, const float* dy, const float* x, const float* bias, const float* res, const float* weight,
+                         const float* mean, const float* rstd, const int32_t* t_valid, int T, float* dx, float* dres, float* dweight,
+                         float* dlnb, void* ws, int64_t ws_bytes, const void* rng_snap, uint64_t salt, float p, void* stream) {
+  return ln_bwd("res_ln_bwd_len", true, rows, D, dy, x, bias, res, weight, mean, rstd, t_valid, T, dx, dres, dweight, dlnb, ws, ws_bytes,
+                rng_snap, salt, p, stream);
 }
 
 static int gelu_shape_ok(const char* who, int64_t rows, int C, const void* a, const void* b, const void* c) {
@@ -1247,18 +1299,37 @@ static int gelu_shape_ok(const char* who, int64_t rows, int C, const void* a, co
   GC_REQUIRE(al16(a) && al16(b) && al16(c), "%s: buffers must be 16-byte aligned", who);
   return 0;
 }
+static int gelu_fwd(const char* who, bool need_len, int64_t rows, int C, const float* x, const float* bias, const int32_t* t_valid, int T,
+                    float* y, void* stream) {
+  GC_REQUIRE(x && y, "%s: null pointer", who);
+  GC_TRY(gelu_shape_ok(who, rows, C, x, bias, y));
+  if (need_len) GC_TRY(bert_len_ok(who, t_valid, rows, T));
+  return bias_gelu_fwd(rows, C, x, bias, y, (hipStream_t)stream, t_valid, T);
+}
+static int gelu_bwd(const char* who, bool need_len, int64_t rows, int C, const float* dy, const float* x, const float* bias,
+                    const int32_t* t_valid, int T, float* dx, void* stream) {
+  GC_REQUIRE(dy && x && dx, "%s: null pointer", who);
+  GC_TRY(gelu_shape_ok(who, rows, C, x, bias, dx));
+  GC_REQUIRE(al16(dy), "%s: buffers must be 16-byte aligned", who);
+  if (need_len) GC_TRY(bert_len_ok(who, t_valid, rows, T));
+  return bias_gelu_bwd(rows, C, dy, x, bias, dx, (hipStream_t)stream, t_valid, T);
+}
 int gcgcn_bias_gelu_fwd(int64_t rows, int C, const float* x, const float* bias, float* y, void* stream) {
-  GC_REQUIRE(x && y, "bias_gelu_fwd: null pointer");
-  GC_TRY(gelu_shape_ok("bias_gelu_fwd", rows, C, x, bias, y));
-  return bias_gelu_fwd(rows, C, x, bias, y, (hipStream_t)stream);
+  return gelu_fwd("bias_gelu_fwd", false, rows, C, x, bias, nullptr, 0, y, stream);
+}
+int gcgcn_bias_gelu_fwd_len(int64_t rows, int C, const float* x, const float* bias, const int32_t* t_valid, int T, float* y, void* stream) {
+  return gelu_fwd("bias_gelu_fwd_len", true, rows, C, x, bias, t_valid, T, y, stream);
 }
 int gcgcn_bias_gelu_bwd(int64_t rows, int C, const float* dy, const float* x, const float* bias, float* dx, void* stream) {
-  GC_REQUIRE(dy && x && dx, "bias_gelu_bwd: null pointer");
-  GC_TRY(gelu_shape_ok("bias_gelu_bwd", rows, C, x, bias, dx));
-  GC_REQUIRE(al16(dy), "bias_gelu_bwd: buffers must be 16-byte aligned");
-  return bias_gelu_bwd(rows, C, dy, x, bias, dx, (hipStream_t)stream);
+  return gelu_bwd("bias_gelu_bwd", false, rows, C, dy, x, bias, nullptr, 0, dx, stream);
+}
+int gcgcn_bias_gelu_bwd_len(int64_t rows, int C, const float* dy, const float* x, const float* bias, const int32_t* t_valid, int T, float* dx,
+                            void* stream) {
+  return gelu_bwd("bias_gelu_bwd_len", true, rows, C, dy, x, bias, t_valid, T, dx, stream);
 }
 
+// The layer.  rowblk: gcgcn_row_blocks(B, T, t_valid) or null.  matmul: 0 = the fp32 GEMM layer, 1 = the twelve Linear products with
+// bf16 operands (gemm_bf16.hip).
 int64_t gcgcn_bert_layer_ws_bytes(int B, int T, int D, int H, int Dff, int which) {
   if (bert_layer_shape_ok("bert_layer_ws_bytes", B, T, D, H, Dff)) return -1;
   if (which != 0 && which != 1) {
@@ -1272,138 +1343,87 @@ static int bert_params_ok(const char* who, const float* const* p) {
   for (int i = 0; i < GCGCN_BERT_LAYER_PARAMS; ++i) GC_REQUIRE(p[i] && al16(p[i]), "%s: parameter %d is null or not 16-byte aligned", who, i);
   return 0;
 }
-int gcgcn_bert_layer_fwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const float* const* params, float* y,
-                         void* saved, int64_t saved_bytes, const void* rng_snap, float p_attn, float p_hidden, void* stream) {
-  GC_TRY(bert_layer_shape_ok("bert_layer_fwd", B, T, D, H, Dff));
-  GC_TRY(bert_drop_ok("bert_layer_fwd", rng_snap, p_attn));
-  GC_TRY(bert_drop_ok("bert_layer_fwd", rng_snap, p_hidden));
-  GC_TRY(bert_params_ok("bert_layer_fwd", params));
-  GC_REQUIRE(x && y && saved && al16(x) && al16(y) && al16(saved), "bert_layer_fwd: x, y, saved must be given and 16-byte aligned");
-  GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "bert_layer_fwd: %lld bytes of saved activations needed "
-             "(gcgcn_bert_layer_ws_bytes, which = 0)", (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
-  const BertLayerParams p = {params[0], params[1], params[2], params[3], params[4], params[5],
-                             params[6], params[7], params[8], params[9], params[10], params[11]};
-  return bert_layer_fwd(B, T, D, H, Dff, x, key_bias, p, y, (float*)saved, rng_snap, p_attn, p_hidden, (hipStream_t)stream);
+static_assert(GCGCN_BERT_LAYER_PARAMS == 12, "bert_unpack names every tensor of the layer");
+extern "C++" template <class S, class P>   // BertLayerParams from the parameters' list, BertLayerGrads from the gradients'
+static S bert_unpack(P* const* p) {
+  return {p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10], p[11]};
 }
-int gcgcn_bert_layer_bwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const float* const* params,
-                         const void* saved, int64_t saved_bytes, const float* dy, float* dx, float* const* grads, void* ws, int64_t ws_bytes,
-                         const void* rng_snap, float p_attn, float p_hidden, void* stream) {
-  GC_TRY(bert_layer_shape_ok("bert_layer_bwd", B, T, D, H, Dff));
-  GC_TRY(bert_drop_ok("bert_layer_bwd", rng_snap, p_attn));
-  GC_TRY(bert_drop_ok("bert_layer_bwd", rng_snap, p_hidden));
-  GC_TRY(bert_params_ok("bert_layer_bwd", params));
-  GC_TRY(bert_params_ok("bert_layer_bwd", grads));
-  GC_REQUIRE(x && saved && dy && dx && ws && al16(x) && al16(saved) && al16(dy) && al16(dx) && al16(ws),
-             "bert_layer_bwd: x, saved, dy, dx, ws must be given and 16-byte aligned");
-  GC_REQUIRE(dx != dy, "bert_layer_bwd: dx aliases dy");
-  GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "bert_layer_bwd: %lld bytes of saved activations needed",
-             (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
-  GC_REQUIRE(ws_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1), "bert_layer_bwd: workspace of %lld bytes needed "
-             "(gcgcn_bert_layer_ws_bytes, which = 1)", (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1));
-  const BertLayerParams p = {params[0], params[1], params[2], params[3], params[4], params[5],
-                             params[6], params[7], params[8], params[9], params[10], params[11]};
-  const BertLayerGrads g = {grads[0], grads[1], grads[2], grads[3], grads[4], grads[5], grads[6], grads[7], grads[8], grads[9], grads[10], grads[11]};
-  return bert_layer_bwd(B, T, D, H, Dff, x, key_bias, p, (const float*)saved, dy, dx, g, (float*)ws, ws_bytes / (int64_t)sizeof(float), rng_snap,
-                        p_attn, p_hidden, (hipStream_t)stream);
-}
-
-// ---- the same with per-document token lengths (t_valid int32 [B] on the device, row (b, t) live iff t < t_valid[b]; gcgcn.h) -----------
-static int bert_len_ok(const char* who, const int32_t* t_valid, int64_t rows, int T) {
-  GC_REQUIRE(t_valid, "%s: t_valid is null (the entry point without _len takes no lengths)", who);
-  GC_REQUIRE(T >= 1 && rows % T == 0, "%s: %lld rows are no whole documents of T = %d", who, (long long)rows, T);
+// what the forward and the backward check alike, in front of their own buffers
+static int bert_layer_ok(const char* who, bool need_len, int B, int T, int D, int H, int Dff, const int32_t* t_valid, const int32_t* rowblk,
+                         const float* const* params, const void* rng_snap, float p_attn, float p_hidden, int matmul) {
+  GC_TRY(bert_layer_shape_ok(who, B, T, D, H, Dff));
+  GC_REQUIRE(matmul == BERT_MM_FP32 || matmul == BERT_MM_BF16, "%s: matmul = %d (0: fp32, 1: bf16 operands)", who, matmul);
+  GC_TRY(bert_drop_ok(who, rng_snap, p_attn));
+  GC_TRY(bert_drop_ok(who, rng_snap, p_hidden));
+  GC_TRY(bert_params_ok(who, params));
+  GC_REQUIRE(t_valid || !need_len, "%s: t_valid is null", who);
+  GC_REQUIRE(t_valid || !rowblk, "%s: a row-block list without t_valid", who);
+  GC_REQUIRE(!rowblk || T % 16 == 0, "%s: a row-block list needs T a multiple of 16 (T = %d)", who, T);
   return 0;
 }
-int gcgcn_bert_attn_fwd_len(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const int32_t* t_valid, float* ctx,
-                            float* lse, const void* rng_snap, uint64_t salt, float p, void* stream) {
-  GC_TRY(bert_attn_shape_ok("bert_attn_fwd_len", B, T, H, dh));
-  GC_TRY(bert_drop_ok("bert_attn_fwd_len", rng_snap, p));
-  GC_REQUIRE(qkv && ctx && lse && t_valid, "bert_attn_fwd_len: null pointer");
-  GC_REQUIRE(al16(qkv), "bert_attn_fwd_len: qkv must be 16-byte aligned");
-  return bert_attn_fwd(B, T, H, qkv, key_bias, ctx, lse, make_drop(rng_snap, salt, p), (hipStream_t)stream, t_valid);
+static int layer_fwd(const char* who, bool need_len, int B, int T, int D, int H, int Dff, const float* x, const float* key_bias,
+                     const int32_t* t_valid, const int32_t* rowblk, const float* const* params, float* y, void* saved, int64_t saved_bytes,
+                     const void* rng_snap, float p_attn, float p_hidden, void* stream, int matmul) {
+  GC_TRY(bert_layer_ok(who, need_len, B, T, D, H, Dff, t_valid, rowblk, params, rng_snap, p_attn, p_hidden, matmul));
+  GC_REQUIRE(x && y && saved && al16(x) && al16(y) && al16(saved), "%s: x, y, saved must be given and 16-byte aligned", who);
+  GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "%s: %lld bytes of saved activations needed "
+             "(gcgcn_bert_layer_ws_bytes, which = 0)", who, (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
+  return bert_layer_fwd(B, T, D, H, Dff, x, key_bias, bert_unpack<BertLayerParams>(params), y, (float*)saved, rng_snap, p_attn, p_hidden,
+                        (hipStream_t)stream, t_valid, rowblk, matmul);
 }
-int gcgcn_bert_attn_bwd_len(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const int32_t* t_valid, const float* ctx,
-                            const float* lse, const float* dctx, float* dqkv, float* delta, const void* rng_snap, uint64_t salt, float p,
-                            void* stream) {
-  GC_TRY(bert_attn_shape_ok("bert_attn_bwd_len", B, T, H, dh));
-  GC_TRY(bert_drop_ok("bert_attn_bwd_len", rng_snap, p));
-  GC_REQUIRE(qkv && ctx && lse && dctx && dqkv && delta && t_valid, "bert_attn_bwd_len: null pointer");
-  GC_REQUIRE(al16(qkv) && al16(dctx), "bert_attn_bwd_len: qkv and dctx must be 16-byte aligned");
-  return bert_attn_bwd(B, T, H, qkv, key_bias, ctx, lse, dctx, dqkv, delta, make_drop(rng_snap, salt, p), (hipStream_t)stream, t_valid);
+static int layer_bwd(const char* who, bool need_len, int B, int T, int D, int H, int Dff, const float* x, const float* key_bias,
+                     const int32_t* t_valid, const int32_t* rowblk, const float* const* params, const void* saved, int64_t saved_bytes,
+                     const float* dy, float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn,
+                     float p_hidden, void* stream, int matmul) {
+  GC_TRY(bert_layer_ok(who, need_len, B, T, D, H, Dff, t_valid, rowblk, params, rng_snap, p_attn, p_hidden, matmul));
+  GC_TRY(bert_params_ok(who, grads));
+  GC_REQUIRE(x && saved && dy && dx && ws && al16(x) && al16(saved) && al16(dy) && al16(dx) && al16(ws),
+             "%s: x, saved, dy, dx, ws must be given and 16-byte aligned", who);
+  GC_REQUIRE(dx != dy, "%s: dx aliases dy", who);
+  GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "%s: %lld bytes of saved activations needed "
+             "(gcgcn_bert_layer_ws_bytes, which = 0)", who, (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
+  GC_REQUIRE(ws_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1), "%s: workspace of %lld bytes needed "
+             "(gcgcn_bert_layer_ws_bytes, which = 1)", who, (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1));
+  return bert_layer_bwd(B, T, D, H, Dff, x, key_bias, bert_unpack<BertLayerParams>(params), (const float*)saved, dy, dx,
+                        bert_unpack<BertLayerGrads>(grads), (float*)ws, ws_bytes / (int64_t)sizeof(float), rng_snap, p_attn, p_hidden,
+                        (hipStream_t)stream, t_valid, rowblk, matmul);
 }
-int gcgcn_res_ln_fwd_len(int64_t rows, int D, const float* x, const float* bias, const float* res, const float* weight, const float* lnb,
-                         const int32_t* t_valid, int T, float* y, float* mean, float* rstd, const void* rng_snap, uint64_t salt, float p,
-                         void* stream) {
-  GC_TRY(res_ln_shape_ok("res_ln_fwd_len", rows, D));
-  GC_TRY(bert_len_ok("res_ln_fwd_len", t_valid, rows, T));
-  GC_TRY(bert_drop_ok("res_ln_fwd_len", rng_snap, p));
-  GC_REQUIRE(x && weight && lnb && y && (!mean == !rstd), "res_ln_fwd_len: null pointer");
-  return res_ln_fwd(rows, D, x, bias, res, weight, lnb, y, mean, rstd, make_drop(rng_snap, salt, p), (hipStream_t)stream, t_valid, T);
-}
-int gcgcn_res_ln_bwd_len(int64_t rows, int D, const float* dy, const float* x, const float* bias, const float* res, const float* weight,
-                         const float* mean, const float* rstd, const int32_t* t_valid, int T, float* dx, float* dres, float* dweight,
-                         float* dlnb, void* ws, int64_t ws_bytes, const void* rng_snap, uint64_t salt, float p, void* stream) {
-  GC_TRY(res_ln_shape_ok("res_ln_bwd_len", rows, D));
-  GC_TRY(bert_len_ok("res_ln_bwd_len", t_valid, rows, T));
-  GC_TRY(bert_drop_ok("res_ln_bwd_len", rng_snap, p));
-  GC_REQUIRE(dy && x && weight && mean && rstd && dx && dweight && dlnb && ws, "res_ln_bwd_len: null pointer");
-  GC_REQUIRE(ws_bytes >= gcgcn_res_ln_ws_bytes(D), "res_ln_bwd_len: workspace of %lld bytes needed (gcgcn_res_ln_ws_bytes)",
-             (long long)gcgcn_res_ln_ws_bytes(D));
-  return res_ln_bwd(rows, D, dy, x, bias, res, weight, mean, rstd, dx, dres, dweight, dlnb, (float*)ws, make_drop(rng_snap, salt, p),
-                    (hipStream_t)stream, t_valid, T);
-}
-int gcgcn_bias_gelu_fwd_len(int64_t rows, int C, const float* x, const float* bias, const int32_t* t_valid, int T, float* y, void* stream) {
-  GC_REQUIRE(x && y, "bias_gelu_fwd_len: null pointer");
-  GC_TRY(gelu_shape_ok("bias_gelu_fwd_len", rows, C, x, bias, y));
-  GC_TRY(bert_len_ok("bias_gelu_fwd_len", t_valid, rows, T));
-  return bias_gelu_fwd(rows, C, x, bias, y, (hipStream_t)stream, t_valid, T);
-}
-int gcgcn_bias_gelu_bwd_len(int64_t rows, int C, const float* dy, const float* x, const float* bias, const int32_t* t_valid, int T, float* dx,
-                            void* stream) {
-  GC_REQUIRE(dy && x && dx, "bias_gelu_bwd_len: null pointer");
-  GC_TRY(gelu_shape_ok("bias_gelu_bwd_len", rows, C, x, bias, dx));
-  GC_REQUIRE(al16(dy), "bias_gelu_bwd_len: buffers must be 16-byte aligned");
-  GC_TRY(bert_len_ok("bias_gelu_bwd_len", t_valid, rows, T));
-  return bias_gelu_bwd(rows, C, dy, x, bias, dx, (hipStream_t)stream, t_valid, T);
+int gcgcn_bert_layer_fwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const float* const* params, float* y,
+                         void* saved, int64_t saved_bytes, const void* rng_snap, float p_attn, float p_hidden, void* stream) {
+  return layer_fwd("bert_layer_fwd", false, B, T, D, H, Dff, x, key_bias, nullptr, nullptr, params, y, saved, saved_bytes, rng_snap, p_attn,
+                   p_hidden, stream, BERT_MM_FP32);
 }
 int gcgcn_bert_layer_fwd_len(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
                              const int32_t* rowblk, const float* const* params, float* y, void* saved, int64_t saved_bytes,
                              const void* rng_snap, float p_attn, float p_hidden, void* stream) {
-  GC_TRY(bert_layer_shape_ok("bert_layer_fwd_len", B, T, D, H, Dff));
-  GC_TRY(bert_drop_ok("bert_layer_fwd_len", rng_snap, p_attn));
-  GC_TRY(bert_drop_ok("bert_layer_fwd_len", rng_snap, p_hidden));
-  GC_TRY(bert_params_ok("bert_layer_fwd_len", params));
-  GC_REQUIRE(t_valid, "bert_layer_fwd_len: t_valid is null");
-  GC_REQUIRE(!rowblk || T % 16 == 0, "bert_layer_fwd_len: a row-block list needs T a multiple of 16 (T = %d)", T);
-  GC_REQUIRE(x && y && saved && al16(x) && al16(y) && al16(saved), "bert_layer_fwd_len: x, y, saved must be given and 16-byte aligned");
-  GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "bert_layer_fwd_len: %lld bytes of saved activations needed "
-             "(gcgcn_bert_layer_ws_bytes, which = 0)", (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
-  const BertLayerParams p = {params[0], params[1], params[2], params[3], params[4], params[5],
-                             params[6], params[7], params[8], params[9], params[10], params[11]};
-  return bert_layer_fwd(B, T, D, H, Dff, x, key_bias, p, y, (float*)saved, rng_snap, p_attn, p_hidden, (hipStream_t)stream, t_valid, rowblk);
+  return layer_fwd("bert_layer_fwd_len", true, B, T, D, H, Dff, x, key_bias, t_valid, rowblk, params, y, saved, saved_bytes, rng_snap,
+                   p_attn, p_hidden, stream, BERT_MM_FP32);
+}
+int gcgcn_bert_layer_fwd_mm(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
+                            const int32_t* rowblk, const float* const* params, float* y, void* saved, int64_t saved_bytes,
+                            const void* rng_snap, float p_attn, float p_hidden, void* stream, int matmul) {
+  return layer_fwd("bert_layer_fwd_mm", false, B, T, D, H, Dff, x, key_bias, t_valid, rowblk, params, y, saved, saved_bytes, rng_snap,
+                   p_attn, p_hidden, stream, matmul);
+}
+int gcgcn_bert_layer_bwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const float* const* params,
+                         const void* saved, int64_t saved_bytes, const float* dy, float* dx, float* const* grads, void* ws, int64_t ws_bytes,
+                         const void* rng_snap, float p_attn, float p_hidden, void* stream) {
+  return layer_bwd("bert_layer_bwd", false, B, T, D, H, Dff, x, key_bias, nullptr, nullptr, params, saved, saved_bytes, dy, dx, grads, ws,
+                   ws_bytes, rng_snap, p_attn, p_hidden, stream, BERT_MM_FP32);
 }
 int gcgcn_bert_layer_bwd_len(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
                              const int32_t* rowblk, const float* const* params, const void* saved, int64_t saved_bytes, const float* dy,
                              float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn, float p_hidden,
                              void* stream) {
-  GC_TRY(bert_layer_shape_ok("bert_layer_bwd_len", B, T, D, H, Dff));
-  GC_TRY(bert_drop_ok("bert_layer_bwd_len", rng_snap, p_attn));
-  GC_TRY(bert_drop_ok("bert_layer_bwd_len", rng_snap, p_hidden));
-  GC_TRY(bert_params_ok("bert_layer_bwd_len", params));
-  GC_TRY(bert_params_ok("bert_layer_bwd_len", grads));
-  GC_REQUIRE(t_valid, "bert_layer_bwd_len: t_valid is null");
-  GC_REQUIRE(!rowblk || T % 16 == 0, "bert_layer_bwd_len: a row-block list needs T a multiple of 16 (T = %d)", T);
-  GC_REQUIRE(x && saved && dy && dx && ws && al16(x) && al16(saved) && al16(dy) && al16(dx) && al16(ws),
-             "bert_layer_bwd_len: x, saved, dy, dx, ws must be given and 16-byte aligned");
-  GC_REQUIRE(dx != dy, "bert_layer_bwd_len: dx aliases dy");
-  GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "bert_layer_bwd_len: %lld bytes of saved activations needed",
-             (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
-  GC_REQUIRE(ws_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1), "bert_layer_bwd_len: workspace of %lld bytes needed "
-             "(gcgcn_bert_layer_ws_bytes, which = 1)", (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1));
-  const BertLayerParams p = {params[0], params[1], params[2], params[3], params[4], params[5],
-                             params[6], params[7], params[8], params[9], params[10], params[11]};
-  const BertLayerGrads g = {grads[0], grads[1], grads[2], grads[3], grads[4], grads[5], grads[6], grads[7], grads[8], grads[9], grads[10], grads[11]};
-  return bert_layer_bwd(B, T, D, H, Dff, x, key_bias, p, (const float*)saved, dy, dx, g, (float*)ws, ws_bytes / (int64_t)sizeof(float), rng_snap,
-                        p_attn, p_hidden, (hipStream_t)stream, t_valid, rowblk);
+  return layer_bwd("bert_layer_bwd_len", true, B, T, D, H, Dff, x, key_bias, t_valid, rowblk, params, saved, saved_bytes, dy, dx, grads, ws,
+                   ws_bytes, rng_snap, p_attn, p_hidden, stream, BERT_MM_FP32);
+}
+int gcgcn_bert_layer_bwd_mm(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
+                            const int32_t* rowblk, const float* const* params, const void* saved, int64_t saved_bytes, const float* dy,
+                            float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn, float p_hidden,
+                            void* stream, int matmul) {
+  return layer_bwd("bert_layer_bwd_mm", false, B, T, D, H, Dff, x, key_bias, t_valid, rowblk, params, saved, saved_bytes, dy, dx, grads, ws,
+                   ws_bytes, rng_snap, p_attn, p_hidden, stream, matmul);
 }
 
 // ---- opt-in bf16 matrix products (gemm_bf16.hip) -------------------------------------------------------------
@@ -1425,52 +1445,4 @@ int gcgcn_gemm_bf16(int a_kc, int b_kc, const float* A, int64_t lda, const float
   g.ws = (float*)ws, g.ws_elems = ws ? ws_bytes / (int64_t)sizeof(float) : 0;
   return gemm_bf16(g, (hipStream_t)stream);
 }
-static int bert_matmul_ok(const char* who, int matmul) {
-  GC_REQUIRE(matmul == BERT_MM_FP32 || matmul == BERT_MM_BF16, "%s: matmul = %d (0: fp32, 1: bf16 operands)", who, matmul);
-  return 0;
-}
-int gcgcn_bert_layer_fwd_mm(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
-                            const int32_t* rowblk, const float* const* params, float* y, void* saved, int64_t saved_bytes,
-                            const void* rng_snap, float p_attn, float p_hidden, void* stream, int matmul) {
-  GC_TRY(bert_layer_shape_ok("bert_layer_fwd_mm", B, T, D, H, Dff));
-  GC_TRY(bert_matmul_ok("bert_layer_fwd_mm", matmul));
-  GC_TRY(bert_drop_ok("bert_layer_fwd_mm", rng_snap, p_attn));
-  GC_TRY(bert_drop_ok("bert_layer_fwd_mm", rng_snap, p_hidden));
-  GC_TRY(bert_params_ok("bert_layer_fwd_mm", params));
-  GC_REQUIRE(t_valid || !rowblk, "bert_layer_fwd_mm: a row-block list without t_valid");
-  GC_REQUIRE(!rowblk || T % 16 == 0, "bert_layer_fwd_mm: a row-block list needs T a multiple of 16 (T = %d)", T);
-  GC_REQUIRE(x && y && saved && al16(x) && al16(y) && al16(saved), "bert_layer_fwd_mm: x, y, saved must be given and 16-byte aligned");
-  GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "bert_layer_fwd_mm: %lld bytes of saved activations needed "
-             "(gcgcn_bert_layer_ws_bytes, which = 0)", (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
-  const BertLayerParams p = {params[0], params[1], params[2], params[3], params[4], params[5],
-                             params[6], params[7], params[8], params[9], params[10], params[11]};
-  return bert_layer_fwd(B, T, D, H, Dff, x, key_bias, p, y, (float*)saved, rng_snap, p_attn, p_hidden, (hipStream_t)stream, t_valid, rowblk,
-                        matmul);
-}
-int gcgcn_bert_layer_bwd_mm(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
-                            const int32_t* rowblk, const float* const* params, const void* saved, int64_t saved_bytes, const float* dy,
-                            float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn, float p_hidden,
-                            void* stream, int matmul) {
-  GC_TRY(bert_layer_shape_ok("bert_layer_bwd_mm", B, T, D, H, Dff));
-  GC_TRY(bert_matmul_ok("bert_layer_bwd_mm", matmul));
-  GC_TRY(bert_drop_ok("bert_layer_bwd_mm", rng_snap, p_attn));
-  GC_TRY(bert_drop_ok("bert_layer_bwd_mm", rng_snap, p_hidden));
-  GC_TRY(bert_params_ok("bert_layer_bwd_mm", params));
-  GC_TRY(bert_params_ok("bert_layer_bwd_mm", grads));
-  GC_REQUIRE(t_valid || !rowblk, "bert_layer_bwd_mm: a row-block list without t_valid");
-  GC_REQUIRE(!rowblk || T % 16 == 0, "bert_layer_bwd_mm: a row-block list needs T a multiple of 16 (T = %d)", T);
-  GC_REQUIRE(x && saved && dy && dx && ws && al16(x) && al16(saved) && al16(dy) && al16(dx) && al16(ws),
-             "bert_layer_bwd_mm: x, saved, dy, dx, ws must be given and 16-byte aligned");
-  GC_REQUIRE(dx != dy, "bert_layer_bwd_mm: dx aliases dy");
-  GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "bert_layer_bwd_mm: %lld bytes of saved activations needed",
-             (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
-  GC_REQUIRE(ws_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1), "bert_layer_bwd_mm: workspace of %lld bytes needed "
-             "(gcgcn_bert_layer_ws_bytes, which = 1)", (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1));
-  const BertLayerParams p = {params[0], params[1], params[2], params[3], params[4], params[5],
-                             params[6], params[7], params[8], params[9], params[10], params[11]};
-  const BertLayerGrads g = {grads[0], grads[1], grads[2], grads[3], grads[4], grads[5], grads[6], grads[7], grads[8], grads[9], grads[10], grads[11]};
-  return bert_layer_bwd(B, T, D, H, Dff, x, key_bias, p, (const float*)saved, dy, dx, g, (float*)ws, ws_bytes / (int64_t)sizeof(float), rng_snap,
-                        p_attn, p_hidden, (hipStream_t)stream, t_valid, rowblk, matmul);
-}
-
 }  // extern "C"

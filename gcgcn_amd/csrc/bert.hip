@@ -636,11 +636,11 @@ Work work_views(float* base, int B, int T, int D, int H, int Dff) {
 long bert_layer_saved_elems(int B, int T, int D, int H, int Dff) { return saved_views(nullptr, B, T, D, H, Dff).total; }
 long bert_layer_ws_elems(int B, int T, int D, int H, int Dff) { return work_views(nullptr, B, T, D, H, Dff).total; }
 
-// Token lengths (t_valid; bert.hpp has the contract).  Every product runs on the live 16-row blocks where the launcher serves the
-// list (rowblk, gcgcn_row_blocks(B, T, t_valid); gemm_plan decides, per problem) and dense elsewhere.  Either way is correct because
-// no product's padding rows are read unguarded: the kernel BEHIND each product is length-aware and stores the zeros that the next
-// product, the weight gradients (which sum over the padding rows of a partly live block, or over all of them when dense) and the
-// bias' column sums read --
+// Token lengths (t_valid; bert.hpp has the contract).  On the fp32 route every product runs on the live 16-row blocks where the
+// launcher serves the list (rowblk, gcgcn_row_blocks(B, T, t_valid); gemm_plan decides, per problem) and dense elsewhere.  Either way
+// is correct because no product's padding rows are read unguarded: the kernel BEHIND each product is length-aware and stores the
+// zeros that the next product, the weight gradients (which sum over the padding rows of a partly live block, or over all of them
+// when dense) and the bias' column sums read --
 //   forward :  qkv -> attention core (loads live rows only; ctx = 0),  ao -> LayerNorm (a = 0),  z -> GELU (g = 0),  o2 -> LayerNorm (y = 0)
 //   backward:  dy -> LayerNorm (d o2 = d a = 0),  dg -> GELU (dz = 0),  da -> LayerNorm (d ao = dx' = 0),  dctx -> attention core (dqkv = 0)
 // -- and dx, which leaves the layer, is zero-stored on the dead blocks by the product itself (rb_zero); on a partly live block and on
@@ -650,59 +650,67 @@ GemmArgs on_rows(GemmArgs g, const int* rowblk, int mode, int zero_dead = 0) {
   if (rowblk) g.rb = rowblk + ROWBLK_HDR, g.rb_n = rowblk, g.rb_mode = mode, g.rb_zero = zero_dead;
   return g;
 }
-}  // namespace
 
-// ---- matmul = BERT_MM_BF16: the twelve products on the bf16 matrix cores (gemm_bf16.hpp) ---------------------------------------------
-// Everything between the products is the fp32 code above, the dropout sites and their indices included.  The products always run
-// DENSE: a row-block list is accepted and ignored.  The contract of the padding rows holds on the dense route by the argument in
-// front of on_rows() -- every buffer a product reads on padding rows is zero-stored by the length-aware kernel in front of it (x by
-// the caller, ctx by the attention core, a by LayerNorm, g by GELU; d o2 / d ao / dx' by LayerNorm's backward, dz by GELU's, dqkv by
-// the core's) -- and bf16(0) = 0, so dx = 0 W + 0 exactly.  A dense product also WRITES every row, so nothing the workspaces held
-// before the call survives.  The bias gradients are the exact fp32 column sums of the fp32 gradient tensors, launched stand-alone
-// (rowops' colsum through colpart: two launches per bias where the fp32 route has none of its own).
-namespace {
-int linear_bf16(float* y, const float* x, const float* w, const float* bias, int M, int N, int K, hipStream_t st) {   // y = x w^T + bias
-  GemmBf16Args g = gemm_bf16_stored(1, 1, x, K, w, K, y, N, M, N, K);
-  g.bias = bias;
-  return gemm_bf16(g, st);
-}
-// of y [M][N] = x [M][K] w[N][K]^T + b:  dw = dy^T x,  dx = dy w (+ add),  db = column sums of dy
-int linear_bf16_bwd(const float* dy, const float* x, const float* w, float* dw, float* dx, const float* add, float* db, int M, int N, int K,
-                    const Work& wk, hipStream_t st) {
-  GemmBf16Args gw = gemm_bf16_stored(0, 0, dy, N, x, K, dw, K, N, K, M);
-  gw.ws = wk.split, gw.ws_elems = wk.split_elems;
-  GC_TRY(gemm_bf16(gw, st));
-  GemmBf16Args gx = gemm_bf16_stored(1, 0, dy, N, w, K, dx, K, M, K, N);
-  gx.add = add, gx.ldadd = K, gx.ws = wk.split, gx.ws_elems = wk.split_elems;
-  GC_TRY(gemm_bf16(gx, st));
-  return colsum(dy, nullptr, db, M, N, N, 1, 0, 0, 0, 0, wk.colpart, st);
-}
+// One Linear of the layer, y [M][N] = x [M][K] w[N][K]^T + b, on the route that matmul names; the chains below are written once.
+// BERT_MM_FP32: the GEMM layer.  BERT_MM_BF16: the same products on the bf16 matrix cores (gemm_bf16.hpp); everything between the
+// products is the same fp32 code, the dropout sites and their indices included.  The bf16 products always run DENSE: a row-block list
+// is accepted and ignored.  The contract of the padding rows holds there by the argument above (x is zero-stored by the caller, every
+// other operand by the length-aware kernel in front of the product) and bf16(0) = 0, so dx = 0 W + 0 exactly.  A dense product also
+// WRITES every row, so nothing the workspaces held before the call survives.  The bf16 route's bias gradients are the exact fp32
+// column sums of the fp32 gradient tensors, launched stand-alone (rowops' colsum through colpart: two launches per bias where the
+// fp32 route has none of its own).
+struct Linear {
+  int matmul, M;
+  const int* rb;    // fp32 route: the live row blocks, or nullptr = dense
+  const Work* wk;   // the backward's split-K and column-sum slices (the forward has none)
+  hipStream_t st;
+
+  int fwd(float* y, const float* x, const float* w, const float* bias, int N, int K) const {
+    if (matmul == BERT_MM_BF16) {
+      GemmBf16Args g = gemm_bf16_stored(1, 1, x, K, w, K, y, N, M, N, K);
+      g.bias = bias;
+      return gemm_bf16(g, st);
+    }
+    GemmArgs g = on_rows(gemm_nt(x, K, w, K, y, N, M, N, K).tagged("bert_gemm"), rb, 1);
+    g.bias = bias;
+    return gemm(g, st, 0, 1);
+  }
+  // dw = dy^T x,  dx = dy w (+ add),  db = column sums of dy.  zero_dead: dx leaves the layer, the product zero-stores its dead blocks.
+  int bwd(const float* dy, const float* x, const float* w, float* dw, float* dx, const float* add, float* db, int N, int K,
+          int zero_dead = 0) const {
+    if (matmul == BERT_MM_BF16) {
+      GemmBf16Args gw = gemm_bf16_stored(0, 0, dy, N, x, K, dw, K, N, K, M);
+      gw.ws = wk->split, gw.ws_elems = wk->split_elems;
+      GC_TRY(gemm_bf16(gw, st));
+      GemmBf16Args gx = gemm_bf16_stored(1, 0, dy, N, w, K, dx, K, M, K, N);
+      gx.add = add, gx.ldadd = K, gx.ws = wk->split, gx.ws_elems = wk->split_elems;
+      GC_TRY(gemm_bf16(gx, st));
+      return colsum(dy, nullptr, db, M, N, N, 1, 0, 0, 0, 0, wk->colpart, st);
+    }
+    // one group launch: a weight gradient sums over the live row blocks (mode 2), a data gradient computes them (mode 1), the bias
+    // gradient rides along as a column sum
+    GemmArgs gs[2] = {on_rows(gemm_tn(dy, N, x, K, dw, K, N, K, M).split_ws(wk->split, wk->split_elems).tagged("bert_gemm"), rb, 2),
+                      on_rows(gemm_nn(dy, N, w, K, dx, K, M, K, N).split_ws(wk->split, wk->split_elems).tagged("bert_gemm"), rb, 1, zero_dead)};
+    if (add) gs[1].add = add, gs[1].ldadd = K;
+    const ColRide cr = col_sum(dy, M, N, N, db, wk->colpart);
+    return gemm_group(gs, 2, st, &cr);
+  }
+};
+const int* live_blocks(const int* tv, int T, const int* rowblk) { return tv && T % 16 == 0 ? rowblk : nullptr; }
 }  // namespace
 
 int bert_layer_fwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const BertLayerParams& p, float* y,
                    float* saved, const void* snap, float p_attn, float p_hidden, hipStream_t st, const int* tv, const int* rowblk, int matmul) {
   const long R = (long)B * T;
   const Saved s = saved_views(saved, B, T, D, H, Dff);
-  if (matmul == BERT_MM_BF16) {
-    GC_TRY(linear_bf16(s.qkv, x, p.wqkv, p.bqkv, (int)R, 3 * D, D, st));
-    GC_TRY(bert_attn_fwd(B, T, H, s.qkv, key_bias, s.ctx, s.lse, make_drop(snap, SALT_BERT_ATTN, p_attn), st, tv));
-    GC_TRY(linear_bf16(s.ao, s.ctx, p.wo, nullptr, (int)R, D, D, st));
-    GC_TRY(res_ln_fwd(R, D, s.ao, p.bo, x, p.ln1w, p.ln1b, s.a, s.mean1, s.rstd1, make_drop(snap, SALT_BERT_AO, p_hidden), st, tv, T));
-    GC_TRY(linear_bf16(s.z, s.a, p.wi, nullptr, (int)R, Dff, D, st));
-    GC_TRY(bias_gelu_fwd(R, Dff, s.z, p.bi, s.g, st, tv, T));
-    GC_TRY(linear_bf16(s.o2, s.g, p.wo2, nullptr, (int)R, D, Dff, st));
-    return res_ln_fwd(R, D, s.o2, p.bo2, s.a, p.ln2w, p.ln2b, y, s.mean2, s.rstd2, make_drop(snap, SALT_BERT_OUT, p_hidden), st, tv, T);
-  }
-  const int* rb = tv && T % 16 == 0 ? rowblk : nullptr;
-  GemmArgs g = on_rows(gemm_nt(x, D, p.wqkv, D, s.qkv, 3 * D, (int)R, 3 * D, D).tagged("bert_gemm"), rb, 1);
-  g.bias = p.bqkv;
-  GC_TRY(gemm(g, st, 0, 1));
+  const Linear lin = {matmul, (int)R, live_blocks(tv, T, rowblk), nullptr, st};
+  GC_TRY(lin.fwd(s.qkv, x, p.wqkv, p.bqkv, 3 * D, D));
   GC_TRY(bert_attn_fwd(B, T, H, s.qkv, key_bias, s.ctx, s.lse, make_drop(snap, SALT_BERT_ATTN, p_attn), st, tv));
-  GC_TRY(gemm(on_rows(gemm_nt(s.ctx, D, p.wo, D, s.ao, D, (int)R, D, D).tagged("bert_gemm"), rb, 1), st, 0, 1));
+  GC_TRY(lin.fwd(s.ao, s.ctx, p.wo, nullptr, D, D));
   GC_TRY(res_ln_fwd(R, D, s.ao, p.bo, x, p.ln1w, p.ln1b, s.a, s.mean1, s.rstd1, make_drop(snap, SALT_BERT_AO, p_hidden), st, tv, T));
-  GC_TRY(gemm(on_rows(gemm_nt(s.a, D, p.wi, D, s.z, Dff, (int)R, Dff, D).tagged("bert_gemm"), rb, 1), st, 0, 1));
+  GC_TRY(lin.fwd(s.z, s.a, p.wi, nullptr, Dff, D));
   GC_TRY(bias_gelu_fwd(R, Dff, s.z, p.bi, s.g, st, tv, T));
-  GC_TRY(gemm(on_rows(gemm_nt(s.g, Dff, p.wo2, Dff, s.o2, D, (int)R, D, Dff).tagged("bert_gemm"), rb, 1), st, 0, 1));
+  GC_TRY(lin.fwd(s.o2, s.g, p.wo2, nullptr, D, Dff));
   return res_ln_fwd(R, D, s.o2, p.bo2, s.a, p.ln2w, p.ln2b, y, s.mean2, s.rstd2, make_drop(snap, SALT_BERT_OUT, p_hidden), st, tv, T);
 }
 
@@ -713,54 +721,24 @@ int bert_layer_bwd(int B, int T, int D, int H, int Dff, const float* x, const fl
   const Saved s = saved_views(const_cast<float*>(saved), B, T, D, H, Dff);
   const Work w = work_views(ws, B, T, D, H, Dff);
   GC_REQUIRE(ws_elems >= w.total, "bert_layer_bwd: workspace of %ld floats needed", w.total);
-  const int M = (int)R;
-  if (matmul == BERT_MM_BF16) {   // the chain below, product for product
-    GC_TRY(res_ln_bwd(R, D, dy, s.o2, p.bo2, s.a, p.ln2w, s.mean2, s.rstd2, w.t1, w.t2, d.ln2w, d.ln2b, w.lnpart,
-                      make_drop(snap, SALT_BERT_OUT, p_hidden), st, tv, T));
-    GC_TRY(linear_bf16_bwd(w.t1, s.g, p.wo2, d.wo2, w.big, nullptr, d.bo2, M, D, Dff, w, st));          // big = dg
-    GC_TRY(bias_gelu_bwd(R, Dff, w.big, s.z, p.bi, w.big, st, tv, T));                                   // big = dz
-    GC_TRY(linear_bf16_bwd(w.big, s.a, p.wi, d.wi, w.t3, w.t2, d.bi, M, Dff, D, w, st));                 // t3 = da
-    GC_TRY(res_ln_bwd(R, D, w.t3, s.ao, p.bo, x, p.ln1w, s.mean1, s.rstd1, w.t1, w.t2, d.ln1w, d.ln1b, w.lnpart,
-                      make_drop(snap, SALT_BERT_AO, p_hidden), st, tv, T));
-    GC_TRY(linear_bf16_bwd(w.t1, s.ctx, p.wo, d.wo, w.t3, nullptr, d.bo, M, D, D, w, st));               // t3 = dctx
-    GC_TRY(bert_attn_bwd(B, T, H, s.qkv, key_bias, s.ctx, s.lse, w.t3, w.big, w.delta, make_drop(snap, SALT_BERT_ATTN, p_attn), st, tv));
-    return linear_bf16_bwd(w.big, x, p.wqkv, d.wqkv, dx, w.t2, d.bqkv, M, 3 * D, D, w, st);              // big = dqkv
-  }
-  const int* rb = tv && T % 16 == 0 ? rowblk : nullptr;
-  // a weight gradient sums over the live row blocks (mode 2), a data gradient computes them (mode 1)
-  auto wgrad = [&](GemmArgs g) { return on_rows(g.split_ws(w.split, w.split_elems).tagged("bert_gemm"), rb, 2); };
-  auto dgrad = [&](GemmArgs g, int zero_dead = 0) { return on_rows(g.split_ws(w.split, w.split_elems).tagged("bert_gemm"), rb, 1, zero_dead); };
+  const Linear lin = {matmul, (int)R, live_blocks(tv, T, rowblk), &w, st};
 
   // y = LN2(dropout(o2 + bo2) + a):  t1 = d o2, t2 = d a (the residual's share)
   GC_TRY(res_ln_bwd(R, D, dy, s.o2, p.bo2, s.a, p.ln2w, s.mean2, s.rstd2, w.t1, w.t2, d.ln2w, d.ln2b, w.lnpart,
                     make_drop(snap, SALT_BERT_OUT, p_hidden), st, tv, T));
-  {   // o2 = g Wo2^T:  dWo2 = t1^T g, big = dg = t1 Wo2, dbo2 = column sums of t1
-    GemmArgs gs[2] = {wgrad(gemm_tn(w.t1, D, s.g, Dff, d.wo2, Dff, D, Dff, M)), dgrad(gemm_nn(w.t1, D, p.wo2, Dff, w.big, Dff, M, Dff, D))};
-    const ColRide cr = col_sum(w.t1, R, D, D, d.bo2, w.colpart);
-    GC_TRY(gemm_group(gs, 2, st, &cr));
-  }
+  // o2 = g Wo2^T:  dWo2 = t1^T g, big = dg = t1 Wo2, dbo2 = column sums of t1
+  GC_TRY(lin.bwd(w.t1, s.g, p.wo2, d.wo2, w.big, nullptr, d.bo2, D, Dff));
   GC_TRY(bias_gelu_bwd(R, Dff, w.big, s.z, p.bi, w.big, st, tv, T));   // big = dz
-  {   // z = a Wi^T:  dWi = big^T a, t3 = da = big Wi + t2, dbi = column sums of big
-    GemmArgs gs[2] = {wgrad(gemm_tn(w.big, Dff, s.a, D, d.wi, D, Dff, D, M)), dgrad(gemm_nn(w.big, Dff, p.wi, D, w.t3, D, M, D, Dff))};
-    gs[1].add = w.t2, gs[1].ldadd = D;
-    const ColRide cr = col_sum(w.big, R, Dff, Dff, d.bi, w.colpart);
-    GC_TRY(gemm_group(gs, 2, st, &cr));
-  }
+  // z = a Wi^T:  dWi = big^T a, t3 = da = big Wi + t2, dbi = column sums of big
+  GC_TRY(lin.bwd(w.big, s.a, p.wi, d.wi, w.t3, w.t2, d.bi, Dff, D));
   // a = LN1(dropout(ao + bo) + x):  t1 = d ao, t2 = dx (the residual's share)
   GC_TRY(res_ln_bwd(R, D, w.t3, s.ao, p.bo, x, p.ln1w, s.mean1, s.rstd1, w.t1, w.t2, d.ln1w, d.ln1b, w.lnpart,
                     make_drop(snap, SALT_BERT_AO, p_hidden), st, tv, T));
-  {   // ao = ctx Wo^T:  dWo = t1^T ctx, t3 = dctx = t1 Wo, dbo = column sums of t1
-    GemmArgs gs[2] = {wgrad(gemm_tn(w.t1, D, s.ctx, D, d.wo, D, D, D, M)), dgrad(gemm_nn(w.t1, D, p.wo, D, w.t3, D, M, D, D))};
-    const ColRide cr = col_sum(w.t1, R, D, D, d.bo, w.colpart);
-    GC_TRY(gemm_group(gs, 2, st, &cr));
-  }
+  // ao = ctx Wo^T:  dWo = t1^T ctx, t3 = dctx = t1 Wo, dbo = column sums of t1
+  GC_TRY(lin.bwd(w.t1, s.ctx, p.wo, d.wo, w.t3, nullptr, d.bo, D, D));
   GC_TRY(bert_attn_bwd(B, T, H, s.qkv, key_bias, s.ctx, s.lse, w.t3, w.big, w.delta, make_drop(snap, SALT_BERT_ATTN, p_attn), st, tv));   // big = dqkv
-  {   // qkv = x Wqkv^T + b:  dWqkv = big^T x, dx = big Wqkv + t2, dbqkv = column sums of big
-    GemmArgs gs[2] = {wgrad(gemm_tn(w.big, 3 * D, x, D, d.wqkv, D, 3 * D, D, M)), dgrad(gemm_nn(w.big, 3 * D, p.wqkv, D, dx, D, M, D, 3 * D), 1)};
-    gs[1].add = w.t2, gs[1].ldadd = D;
-    const ColRide cr = col_sum(w.big, R, 3 * D, 3 * D, d.bqkv, w.colpart);
-    return gemm_group(gs, 2, st, &cr);
-  }
+  // qkv = x Wqkv^T + b:  dWqkv = big^T x, dx = big Wqkv + t2 (it leaves the layer), dbqkv = column sums of big
+  return lin.bwd(w.big, x, p.wqkv, d.wqkv, dx, w.t2, d.bqkv, 3 * D, D, 1);
 }
 
 }  // namespace gc

@@ -1224,11 +1224,8 @@ class LstmFn(torch.autograd.Function):
         out = torch.empty(B, T, nd * H, device=x.device)
         gates = torch.empty(B * T, nd * 4 * H, device=x.device)
         csave = torch.empty(B, T, nd * H, device=x.device) if need_grad else None
-        if lens is None:
-            call("gcgcn_lstm_fwd", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(bias), _p(h0), _p(c0), _p(out), _p(gates), _p(csave), _stream())
-        else:
-            call("gcgcn_lstm_fwd_len", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(bias), _p(h0), _p(c0), _p(out), _p(gates), _p(csave),
-                 _p(lens), _stream())
+        call("gcgcn_lstm_fwd_len", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(bias), _p(h0), _p(c0), _p(out), _p(gates), _p(csave),
+             _p(lens), _stream())     # null lengths: every step of every row
         written = (out, gates) if csave is None else (out, gates, csave)
         torch.autograd.graph.increment_version(written)     # raw-pointer writes, as in optim._written
         ctx.has_lens = lens is not None
@@ -1251,12 +1248,8 @@ class LstmFn(torch.autograd.Function):
         db = torch.empty(nd * 4 * H, device=x.device)
         dh0, dc0 = torch.empty_like(h0), torch.empty_like(c0)
         ws = _lstm_ws(B, T, I, H, nd, x.device)
-        args = (B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(h0), _p(c0), _p(out), _p(gates), _p(csave), _p(dout), _p(dgates),
-                _p(dx), _p(dw_ih), _p(dw_hh), _p(db), _p(dh0), _p(dc0), _p(ws), ws.numel() * 4)
-        if lens is None:
-            call("gcgcn_lstm_bwd", *args, _stream())
-        else:
-            call("gcgcn_lstm_bwd_len", *args, _p(lens), _stream())
+        call("gcgcn_lstm_bwd_len", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(h0), _p(c0), _p(out), _p(gates), _p(csave), _p(dout),
+             _p(dgates), _p(dx), _p(dw_ih), _p(dw_hh), _p(db), _p(dh0), _p(dc0), _p(ws), ws.numel() * 4, _p(lens), _stream())
         torch.autograd.graph.increment_version((dx, dw_ih, dw_hh, db, dh0, dc0))
         return dx, dw_ih, dw_hh, db, dh0, dc0, None
 
@@ -1444,12 +1437,9 @@ class ResLayerNormFn(torch.autograd.Function):
         rows = x.numel() // D
         y = torch.empty_like(x)
         mean, rstd = torch.empty(rows, device=x.device), torch.empty(rows, device=x.device)
-        if t_valid is None:
-            call("gcgcn_res_ln_fwd", rows, D, _p(x), _p(bias), _p(res), _p(weight), _p(lnb), _p(y), _p(mean), _p(rstd), _p(snap), salt, float(p),
-                 _stream())
-        else:
-            call("gcgcn_res_ln_fwd_len", rows, D, _p(x), _p(bias), _p(res), _p(weight), _p(lnb), _p(t_valid), x.shape[-2], _p(y), _p(mean),
-                 _p(rstd), _p(snap), salt, float(p), _stream())
+        # the _len symbols take the lengths in the middle of the plain ones' list, and refuse a null t_valid
+        name, lens = ("gcgcn_res_ln_fwd", ()) if t_valid is None else ("gcgcn_res_ln_fwd_len", (_p(t_valid), x.shape[-2]))
+        call(name, rows, D, _p(x), _p(bias), _p(res), _p(weight), _p(lnb), *lens, _p(y), _p(mean), _p(rstd), _p(snap), salt, float(p), _stream())
         torch.autograd.graph.increment_version((y, mean, rstd))
         ctx.p, ctx.snap, ctx.salt, ctx.has, ctx.t_valid = float(p), snap, salt, (bias is not None, res is not None), t_valid
         ctx.save_for_backward(x, weight, mean, rstd, *(t for t in (bias, res) if t is not None))
@@ -1469,12 +1459,9 @@ class ResLayerNormFn(torch.autograd.Function):
         dres = torch.empty_like(x) if res is not None else None
         dw, db = torch.empty_like(weight), torch.empty_like(weight)
         ws = _f32_buf(_bytes_or_raise("gcgcn_res_ln_ws_bytes", D), x.device)
-        if ctx.t_valid is None:
-            call("gcgcn_res_ln_bwd", rows, D, _p(dy), _p(x), _p(bias), _p(res), _p(weight), _p(mean), _p(rstd), _p(dx), _p(dres), _p(dw), _p(db),
-                 _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.salt, ctx.p, _stream())
-        else:
-            call("gcgcn_res_ln_bwd_len", rows, D, _p(dy), _p(x), _p(bias), _p(res), _p(weight), _p(mean), _p(rstd), _p(ctx.t_valid), x.shape[-2],
-                 _p(dx), _p(dres), _p(dw), _p(db), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.salt, ctx.p, _stream())
+        name, lens = ("gcgcn_res_ln_bwd", ()) if ctx.t_valid is None else ("gcgcn_res_ln_bwd_len", (_p(ctx.t_valid), x.shape[-2]))
+        call(name, rows, D, _p(dy), _p(x), _p(bias), _p(res), _p(weight), _p(mean), _p(rstd), *lens, _p(dx), _p(dres), _p(dw), _p(db),
+             _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.salt, ctx.p, _stream())
         torch.autograd.graph.increment_version((dx, dw, db) + (() if dres is None else (dres,)))
         dbias = dx.reshape(rows, D).sum(0) if bias is not None and ctx.needs_input_grad[1] else None
         return dx, dbias, dres, dw, db, None, None, None, None
@@ -1522,7 +1509,8 @@ def _ptr_array(tensors):
 
 class BertLayerFn(torch.autograd.Function):
     """(x[B,T,D], key_bias[B,T] | None, t_valid[B] | None, rowblk | None, matmul, the 12 tensors of gcgcn_bert_layer_fwd's parameter
-    list) -> y[B,T,D].  With t_valid the _len entry points run (include/gcgcn.h); matmul = 1 (bf16 operands) runs the _mm ones."""
+    list) -> y[B,T,D].  Every route is one call of the _mm entry points (include/gcgcn.h): null t_valid / rowblk = no lengths / dense
+    products, matmul = 0 / 1 = fp32 / bf16 operands."""
 
     @staticmethod
     def forward(ctx, x, key_bias, H, p_attn, p_hidden, snap, t_valid, rowblk, matmul, *params):
@@ -1532,15 +1520,8 @@ class BertLayerFn(torch.autograd.Function):
         saved = _f32_buf(_bytes_or_raise("gcgcn_bert_layer_ws_bytes", *dims, 0), x.device)
         y = torch.empty_like(x)
         ctx.matmul = matmul
-        if matmul:
-            call("gcgcn_bert_layer_fwd_mm", *dims, _p(x), _p(key_bias), _p(t_valid), _p(rowblk), _ptr_array(params), _p(y), _p(saved),
-                 saved.numel() * 4, _p(snap), float(p_attn), float(p_hidden), _stream(), matmul)
-        elif t_valid is None:
-            call("gcgcn_bert_layer_fwd", *dims, _p(x), _p(key_bias), _ptr_array(params), _p(y), _p(saved), saved.numel() * 4, _p(snap),
-                 float(p_attn), float(p_hidden), _stream())
-        else:
-            call("gcgcn_bert_layer_fwd_len", *dims, _p(x), _p(key_bias), _p(t_valid), _p(rowblk), _ptr_array(params), _p(y), _p(saved),
-                 saved.numel() * 4, _p(snap), float(p_attn), float(p_hidden), _stream())
+        call("gcgcn_bert_layer_fwd_mm", *dims, _p(x), _p(key_bias), _p(t_valid), _p(rowblk), _ptr_array(params), _p(y), _p(saved),
+             saved.numel() * 4, _p(snap), float(p_attn), float(p_hidden), _stream(), matmul)
         torch.autograd.graph.increment_version((y, saved))
         ctx.dims, ctx.ps, ctx.snap, ctx.has_kb = dims, (float(p_attn), float(p_hidden)), snap, key_bias is not None
         ctx.t_valid, ctx.rowblk = t_valid, rowblk
@@ -1558,16 +1539,9 @@ class BertLayerFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         grads = tuple(torch.empty_like(t) for t in params)
         ws = _f32_buf(_bytes_or_raise("gcgcn_bert_layer_ws_bytes", *ctx.dims, 1), x.device)
-        if ctx.matmul:
-            call("gcgcn_bert_layer_bwd_mm", *ctx.dims, _p(x), _p(key_bias), _p(ctx.t_valid), _p(ctx.rowblk), _ptr_array(params), _p(saved),
-                 saved.numel() * 4, _p(dy), _p(dx), _ptr_array(grads), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.ps[0], ctx.ps[1], _stream(),
-                 ctx.matmul)
-        elif ctx.t_valid is None:
-            call("gcgcn_bert_layer_bwd", *ctx.dims, _p(x), _p(key_bias), _ptr_array(params), _p(saved), saved.numel() * 4, _p(dy), _p(dx),
-                 _ptr_array(grads), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.ps[0], ctx.ps[1], _stream())
-        else:
-            call("gcgcn_bert_layer_bwd_len", *ctx.dims, _p(x), _p(key_bias), _p(ctx.t_valid), _p(ctx.rowblk), _ptr_array(params), _p(saved),
-                 saved.numel() * 4, _p(dy), _p(dx), _ptr_array(grads), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.ps[0], ctx.ps[1], _stream())
+        call("gcgcn_bert_layer_bwd_mm", *ctx.dims, _p(x), _p(key_bias), _p(ctx.t_valid), _p(ctx.rowblk), _ptr_array(params), _p(saved),
+             saved.numel() * 4, _p(dy), _p(dx), _ptr_array(grads), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.ps[0], ctx.ps[1], _stream(),
+             ctx.matmul)
         torch.autograd.graph.increment_version((dx,) + grads)
         return (dx, None, None, None, None, None, None, None, None) + grads
 
