@@ -143,6 +143,10 @@ SIGNATURES = {
     "gcgcn_gemm_bf16": (I, [I, I, P, L, P, L, P, L, I, I, I, P, P, L, P, L, P]),
     "gcgcn_bert_layer_fwd_mm": (I, [I] * 5 + [P] * 7 + [L, P, F, F, P, I]),
     "gcgcn_bert_layer_bwd_mm": (I, [I] * 5 + [P] * 6 + [L, P, P, P, P, L, P, F, F, P, I]),
+    "gcgcn_bert_attn_fwd_mx": (I, [I] * 4 + [P] * 6 + [c_uint64, F, P, I]),
+    "gcgcn_bert_attn_bwd_mx": (I, [I] * 4 + [P] * 9 + [c_uint64, F, P, I]),
+    "gcgcn_bert_layer_fwd_mx": (I, [I] * 5 + [P] * 7 + [L, P, F, F, P, I, I]),
+    "gcgcn_bert_layer_bwd_mx": (I, [I] * 5 + [P] * 6 + [L, P, P, P, P, L, P, F, F, P, I, I]),
 }
 
 _lib = None

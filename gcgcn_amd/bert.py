@@ -3,7 +3,7 @@
 ``BertModel(config, impl="torch")`` is the contract in plain PyTorch (any device, any float dtype; the reference of the tests).
 ``BertModel(config, impl="hip")`` runs every encoder layer through ``functional.bert_layer`` (csrc/bert.hip: masked attention
 core, LayerNorm with residual and dropout, erf GELU, forward and backward, the Linears on the fp32-MFMA GEMM layer or, with
-``matmul="bf16"``, on the bf16 matrix cores) and the
+``matmul="bf16"``, on the bf16 matrix cores; the attention core's products there too with ``attention="bf16"``) and the
 embeddings' LayerNorm through ``functional.res_layer_norm`` (their dropout is the library's elementwise kernel); it raises on CPU tensors.  The three embedding gathers
 (word, position, token type) and the pooler (one ``[B, D] x [D, D]`` product and a tanh) stay PyTorch in both implementations:
 three gathers and one small product.  Parameters live in ordinary ``nn.Embedding`` / ``nn.Linear`` / ``nn.LayerNorm`` holders
@@ -18,7 +18,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
-from .functional import bert_matmul_index
+from .functional import bert_attention_index, bert_matmul_index
 
 LN_EPS = 1e-12
 MASK_PENALTY = -10000.0
@@ -138,20 +138,81 @@ def bf16_linear(x, w, b):
     return Bf16LinearFn.apply(x, w, b)
 
 
-def torch_layer(x, key_bias, params, heads, drop: Callable, linear: Callable = F.linear):
+class Bf16AttentionFn(torch.autograd.Function):
+    """The attention core with bf16 operands, per (document, head): ``q, k, v`` ``[.., T, dh]``, ``penalty`` (additive, broadcastable
+    to ``[.., T, T]``, or None), ``m`` (the multiplicative dropout mask ``keep / (1 - p)`` ``[.., T, T]``, all ones in eval mode, or
+    None = ones) -> ``(ctx [.., T, dh], lse [.., T])``.  With ``r(.)`` one rounding to bfloat16 (nearest even) and ``alpha = 1 /
+    sqrt(dh)``::
+
+        S = alpha r(q) r(k)^T + penalty      P = softmax(S) over the keys, unrounded      Pd = m o P      ctx = r(Pd) r(v)
+        delta_i = sum_d dctx_id ctx_id       dPd = r(dctx) r(v)^T                         dS = P o (m o dPd - delta)
+        dv = r(Pd)^T r(dctx)                 dq = alpha r(dS) r(k)                        dk = alpha r(dS)^T r(q)
+
+    The backward is stated, not derived by autograd.  Every accumulation, the softmax, ``lse``, ``delta`` and ``dS`` stay in the
+    tensors' own dtype.  The definition of ``attention="bf16"``; ``lse`` takes no gradient."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, penalty, m):
+        alpha = 1.0 / math.sqrt(q.shape[-1])
+        qr, kr, vr = _bf16(q), _bf16(k), _bf16(v)
+        s = alpha * (qr @ kr.transpose(-1, -2))
+        lse_shift = 0.0
+        if penalty is not None:
+            # a softmax does not see a shift common to its keys: the penalty enters relative to its row maximum (what the kernels do
+            # with c_b), so a row whose keys are all at -10000 keeps the scores' low bits in float32; lse gets the shift back
+            c = penalty.amax(-1, keepdim=True)
+            s = s + (penalty - c)
+            lse_shift = c.expand(s.shape[:-1] + (1,)).squeeze(-1)
+        p = torch.softmax(s, dim=-1)
+        lse = torch.logsumexp(s, dim=-1) + lse_shift
+        pdr = _bf16(p if m is None else m * p)
+        out = pdr @ vr
+        ctx.alpha, ctx.has_m = alpha, m is not None
+        ctx.save_for_backward(qr, kr, vr, p, pdr, out, *(() if m is None else (m,)))
+        ctx.mark_non_differentiable(lse)
+        return out, lse
+
+    @staticmethod
+    def backward(ctx, dctx, _dlse):
+        qr, kr, vr, p, pdr, out = ctx.saved_tensors[:6]
+        delta = (dctx * out).sum(-1, keepdim=True)
+        dr = _bf16(dctx)
+        dpd = dr @ vr.transpose(-1, -2)
+        if ctx.has_m:
+            dpd = ctx.saved_tensors[6] * dpd
+        dsr = _bf16(p * (dpd - delta))
+        dv = pdr.transpose(-1, -2) @ dr
+        dq = ctx.alpha * (dsr @ kr)
+        dk = ctx.alpha * (dsr.transpose(-1, -2) @ qr)
+        return dq, dk, dv, None, None
+
+
+def bf16_attention(q, k, v, penalty, m):
+    """``ctx`` of ``Bf16AttentionFn``."""
+    return Bf16AttentionFn.apply(q, k, v, penalty, m)[0]
+
+
+def torch_layer(x, key_bias, params, heads, drop: Callable, linear: Callable = F.linear, attention: Optional[Callable] = None):
     """One encoder layer in plain PyTorch.  ``key_bias``: ``[B, T]`` additive penalty or None.  ``drop(site, t)``: the dropout of
     site "attn" (on P ``[B, H, T, T]``), "ao" or "out" (on ``[B, T, D]``).  ``linear(x, w, b)``: the six Linears (``bf16_linear`` for
-    ``matmul="bf16"``)."""
+    ``matmul="bf16"``).  ``attention(q, k, v, penalty, m) -> ctx [B, H, T, dh]``: None = the fp32 core written out below;
+    ``bf16_attention`` for ``attention="bf16"``.  The mask is then obtained as ``m = drop("attn", ones)``, so ``drop`` must be
+    MULTIPLICATIVE at that site (``drop("attn", t) == t * drop("attn", ones)``), as ``F.dropout`` and a replayed keep mask are."""
     wq, bq, wk, bk, wv, bv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2 = params
     B, T, D = x.shape
     dh = D // heads
     split = lambda t: t.view(B, T, heads, dh).permute(0, 2, 1, 3)
     q, k, v = split(linear(x, wq, bq)), split(linear(x, wk, bk)), split(linear(x, wv, bv))
-    s = q @ k.transpose(-1, -2) / math.sqrt(dh)
-    if key_bias is not None:
-        s = s + key_bias[:, None, None, :]
-    p = drop("attn", torch.softmax(s, dim=-1))
-    ctx = (p @ v).permute(0, 2, 1, 3).reshape(B, T, D)
+    if attention is not None:
+        m = drop("attn", torch.ones(B, heads, T, T, dtype=x.dtype, device=x.device))
+        ctx = attention(q, k, v, None if key_bias is None else key_bias[:, None, None, :], m)
+    else:
+        s = q @ k.transpose(-1, -2) / math.sqrt(dh)
+        if key_bias is not None:
+            s = s + key_bias[:, None, None, :]
+        p = drop("attn", torch.softmax(s, dim=-1))
+        ctx = p @ v
+    ctx = ctx.permute(0, 2, 1, 3).reshape(B, T, D)
     a = layer_norm(drop("ao", linear(ctx, wo, bo)) + x, g1, b1)
     i = gelu(linear(a, wi, bi))
     return layer_norm(drop("out", linear(i, wo2, bo2)) + a, g2, b2)
@@ -174,7 +235,8 @@ class BertModel(nn.Module):
     indices are the padded tensors', so from one snapshot the length path and the prefix-mask path drop the same live elements.
 
     ``dropout_override``: None, or ``f(layer, site, t) -> t`` replacing the dropout of site "emb" (layer -1), "attn", "ao", "out" of
-    the torch implementation -- how a test replays the masks the HIP kernels drew.
+    the torch implementation -- how a test replays the masks the HIP kernels drew.  With ``attention="bf16"`` the override of site
+    "attn" is called on a tensor of ones and must be multiplicative (``f(l, "attn", t) == t * f(l, "attn", ones)``).
 
     ``matmul``: ``"fp32"`` (default; nothing changes) or ``"bf16"``: the six Linears of every encoder layer -- query, key, value,
     attention.output.dense, intermediate.dense, output.dense -- take bf16 operands with full-precision accumulation, forward and
@@ -182,21 +244,28 @@ class BertModel(nn.Module):
     gradient).  Parameters, activations, gradients and ``state_dict`` stay what they are: a checkpoint moves freely between the two
     settings, and an optimizer sees fp32 master weights.  The embeddings, the attention core, LayerNorm, GELU and the pooler are
     unchanged.  ``impl="hip"`` hands the selector to every layer (csrc/gemm_bf16.hip: the bf16 matrix cores); ``impl="torch"`` is the
-    same contract on any device and float dtype.  After a training forward of ``impl="hip"``,
+    same contract on any device and float dtype.
+
+    ``attention``: ``"fp32"`` (default; nothing changes) or ``"bf16"``: the attention core's four matrix products -- ``q k^T``,
+    ``P v`` and in the backward ``dctx v^T``, ``dS k`` / ``dS^T q`` / ``P^T dctx`` -- take bf16 operands with full-precision
+    accumulation; softmax, ``lse``, ``delta`` and ``dS`` stay at full precision and the dropout mask is the one the fp32 core draws
+    (``Bf16AttentionFn`` is the definition).  Independent of ``matmul``: all four combinations are valid, and a checkpoint moves
+    freely between them.  ``impl="hip"``: csrc/bert_attn_bf16.hip.  After a training forward of ``impl="hip"``,
     ``last_rng_snaps`` holds the snapshots it used: ``[0]`` for the embeddings, ``[1 + l]`` for layer ``l``."""
 
-    def __init__(self, config: Optional[BertConfig] = None, impl: str = "torch", matmul: str = "fp32"):
+    def __init__(self, config: Optional[BertConfig] = None, impl: str = "torch", matmul: str = "fp32", attention: str = "fp32"):
         super().__init__()
         config = BertConfig() if config is None else config
         if impl not in ("torch", "hip"):
             raise ValueError(f"BertModel: impl must be 'torch' or 'hip', got {impl!r}")
         bert_matmul_index(matmul, "BertModel")      # raises on anything but the allowed names
+        bert_attention_index(attention, "BertModel")
         if config.hidden_size % config.num_attention_heads:
             raise ValueError(f"BertModel: hidden size {config.hidden_size} is no multiple of {config.num_attention_heads} heads")
         if impl == "hip" and config.hidden_size != 64 * config.num_attention_heads:
             raise ValueError(f"BertModel(impl='hip'): the attention kernels serve a head width of 64, not "
                              f"{config.hidden_size // config.num_attention_heads}")
-        self.config, self.impl, self.matmul = config, impl, matmul
+        self.config, self.impl, self.matmul, self.attention = config, impl, matmul, attention
         self.embeddings = _Embeddings(config)
         self.encoder = _Encoder(config)
         self.pooler = _Dense(config.hidden_size, config.hidden_size)
@@ -240,11 +309,13 @@ class BertModel(nn.Module):
             zero_pad = (lambda t: t) if live is None else (lambda t: torch.where(live, t, torch.zeros((), dtype=t.dtype, device=t.device)))
             x = zero_pad(self._drop(-1, "emb", layer_norm(emb, e.LayerNorm.weight, e.LayerNorm.bias), c.hidden_dropout_prob))
             outs = []
-            linear = (bf16_linear,) if self.matmul == "bf16" else ()      # "fp32": the call as it was
+            linear = {"linear": bf16_linear} if self.matmul == "bf16" else {}      # "fp32": the call as it was
+            if self.attention == "bf16":
+                linear["attention"] = bf16_attention
             for li, layer in enumerate(self.encoder.layer):
                 probs = {"attn": c.attention_probs_dropout_prob, "ao": c.hidden_dropout_prob, "out": c.hidden_dropout_prob}
                 x = zero_pad(torch_layer(x, key_bias, layer.tensors(), c.num_attention_heads, lambda s, t: self._drop(li, s, t, probs[s]),
-                                         *linear))
+                                         **linear))
                 outs.append(x)
         last = outs[-1] if outs else x
         pooled = torch.tanh(self.pooler.dense(last[:, 0]))
@@ -275,7 +346,7 @@ class BertModel(nn.Module):
                 snap = Fn.rng_snapshot(emb.device) if training else None
                 snaps.append(snap)
                 x = Fn.bert_layer(x, kb, *layer.tensors(), p_attn=c.attention_probs_dropout_prob, p_hidden=c.hidden_dropout_prob,
-                                  training=training, snap=snap, t_valid=tv, rowblk=rowblk, matmul=self.matmul)
+                                  training=training, snap=snap, t_valid=tv, rowblk=rowblk, matmul=self.matmul, attention=self.attention)
                 outs.append(x)
         self.last_rng_snaps = snaps if training else None
         if not outs:

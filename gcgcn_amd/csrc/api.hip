@@ -1200,7 +1200,11 @@ static int bert_layer_shape_ok(const char* who, int B, int T, int D, int H, int 
 // Token lengths: t_valid int32 [B] on the device, row (b, t) live iff t < t_valid[b] (gcgcn.h).  Each operation below has ONE body
 // that checks, unpacks and calls into gc::.  It takes the most general argument list, the name of the symbol that was called (who)
 // and need_len, whether that symbol requires t_valid.  The exported symbols only forward: the plain ones pass no lengths (and
-// BERT_MM_FP32), the _len ones set need_len, _mm passes everything through.
+// BERT_MM_FP32), the _len ones set need_len, _mm passes everything but the attention selector through, _mx everything.
+static int bert_attn_sel_ok(const char* who, int attn) {
+  GC_REQUIRE(attn == BERT_ATTN_FP32 || attn == BERT_ATTN_BF16, "%s: attn = %d (0: fp32, 1: bf16 operands)", who, attn);
+  return 0;
+}
 static int bert_len_ok(const char* who, const int32_t* t_valid, int64_t rows, int T) {
   GC_REQUIRE(t_valid, "%s: t_valid is null (the entry point without _len takes no lengths)", who);
   GC_REQUIRE(T >= 1 && rows % T == 0, "%s: %lld rows are no whole documents of T = %d", who, (long long)rows, T);
@@ -1208,38 +1212,55 @@ static int bert_len_ok(const char* who, const int32_t* t_valid, int64_t rows, in
 }
 
 static int attn_fwd(const char* who, bool need_len, int B, int T, int H, int dh, const float* qkv, const float* key_bias,
-                    const int32_t* t_valid, float* ctx, float* lse, const void* rng_snap, uint64_t salt, float p, void* stream) {
+                    const int32_t* t_valid, float* ctx, float* lse, const void* rng_snap, uint64_t salt, float p, void* stream, int attn) {
   GC_TRY(bert_attn_shape_ok(who, B, T, H, dh));
+  GC_TRY(bert_attn_sel_ok(who, attn));
   GC_TRY(bert_drop_ok(who, rng_snap, p));
   GC_REQUIRE(qkv && ctx && lse && (t_valid || !need_len), "%s: null pointer", who);
   GC_REQUIRE(al16(qkv), "%s: qkv must be 16-byte aligned", who);
-  return bert_attn_fwd(B, T, H, qkv, key_bias, ctx, lse, make_drop(rng_snap, salt, p), (hipStream_t)stream, t_valid);
+  GC_REQUIRE(attn == BERT_ATTN_FP32 || al16(ctx), "%s: ctx must be 16-byte aligned with attn = 1", who);
+  return bert_attn_fwd(B, T, H, qkv, key_bias, ctx, lse, make_drop(rng_snap, salt, p), (hipStream_t)stream, t_valid, attn);
 }
 static int attn_bwd(const char* who, bool need_len, int B, int T, int H, int dh, const float* qkv, const float* key_bias,
                     const int32_t* t_valid, const float* ctx, const float* lse, const float* dctx, float* dqkv, float* delta,
-                    const void* rng_snap, uint64_t salt, float p, void* stream) {
+                    const void* rng_snap, uint64_t salt, float p, void* stream, int attn) {
   GC_TRY(bert_attn_shape_ok(who, B, T, H, dh));
+  GC_TRY(bert_attn_sel_ok(who, attn));
   GC_TRY(bert_drop_ok(who, rng_snap, p));
   GC_REQUIRE(qkv && ctx && lse && dctx && dqkv && delta && (t_valid || !need_len), "%s: null pointer", who);
   GC_REQUIRE(al16(qkv) && al16(dctx), "%s: qkv and dctx must be 16-byte aligned", who);
-  return bert_attn_bwd(B, T, H, qkv, key_bias, ctx, lse, dctx, dqkv, delta, make_drop(rng_snap, salt, p), (hipStream_t)stream, t_valid);
+  GC_REQUIRE(attn == BERT_ATTN_FP32 || al16(dqkv), "%s: dqkv must be 16-byte aligned with attn = 1", who);
+  return bert_attn_bwd(B, T, H, qkv, key_bias, ctx, lse, dctx, dqkv, delta, make_drop(rng_snap, salt, p), (hipStream_t)stream, t_valid,
+                       attn);
 }
 int gcgcn_bert_attn_fwd(int B, int T, int H, int dh, const float* qkv, const float* key_bias, float* ctx, float* lse, const void* rng_snap,
                         uint64_t salt, float p, void* stream) {
-  return attn_fwd("bert_attn_fwd", false, B, T, H, dh, qkv, key_bias, nullptr, ctx, lse, rng_snap, salt, p, stream);
+  return attn_fwd("bert_attn_fwd", false, B, T, H, dh, qkv, key_bias, nullptr, ctx, lse, rng_snap, salt, p, stream, BERT_ATTN_FP32);
 }
 int gcgcn_bert_attn_fwd_len(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const int32_t* t_valid, float* ctx,
                             float* lse, const void* rng_snap, uint64_t salt, float p, void* stream) {
-  return attn_fwd("bert_attn_fwd_len", true, B, T, H, dh, qkv, key_bias, t_valid, ctx, lse, rng_snap, salt, p, stream);
+  return attn_fwd("bert_attn_fwd_len", true, B, T, H, dh, qkv, key_bias, t_valid, ctx, lse, rng_snap, salt, p, stream, BERT_ATTN_FP32);
+}
+int gcgcn_bert_attn_fwd_mx(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const int32_t* t_valid, float* ctx,
+                           float* lse, const void* rng_snap, uint64_t salt, float p, void* stream, int attn) {
+  return attn_fwd("bert_attn_fwd_mx", false, B, T, H, dh, qkv, key_bias, t_valid, ctx, lse, rng_snap, salt, p, stream, attn);
 }
 int gcgcn_bert_attn_bwd(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const float* ctx, const float* lse,
                         const float* dctx, float* dqkv, float* delta, const void* rng_snap, uint64_t salt, float p, void* stream) {
-  return attn_bwd("bert_attn_bwd", false, B, T, H, dh, qkv, key_bias, nullptr, ctx, lse, dctx, dqkv, delta, rng_snap, salt, p, stream);
+  return attn_bwd("bert_attn_bwd", false, B, T, H, dh, qkv, key_bias, nullptr, ctx, lse, dctx, dqkv, delta, rng_snap, salt, p, stream,
+                  BERT_ATTN_FP32);
 }
 int gcgcn_bert_attn_bwd_len(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const int32_t* t_valid, const float* ctx,
                             const float* lse, const float* dctx, float* dqkv, float* delta, const void* rng_snap, uint64_t salt, float p,
                             void* stream) {
-  return attn_bwd("bert_attn_bwd_len", true, B, T, H, dh, qkv, key_bias, t_valid, ctx, lse, dctx, dqkv, delta, rng_snap, salt, p, stream);
+  return attn_bwd("bert_attn_bwd_len", true, B, T, H, dh, qkv, key_bias, t_valid, ctx, lse, dctx, dqkv, delta, rng_snap, salt, p, stream,
+                  BERT_ATTN_FP32);
+}
+int gcgcn_bert_attn_bwd_mx(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const int32_t* t_valid, const float* ctx,
+                           const float* lse, const float* dctx, float* dqkv, float* delta, const void* rng_snap, uint64_t salt, float p,
+                           void* stream, int attn) {
+  return attn_bwd("bert_attn_bwd_mx", false, B, T, H, dh, qkv, key_bias, t_valid, ctx, lse, dctx, dqkv, delta, rng_snap, salt, p, stream,
+                  attn);
 }
 
 static int res_ln_shape_ok(const char* who, int64_t rows, int D) {
@@ -1329,7 +1350,7 @@ int gcgcn_bias_gelu_bwd_len(int64_t rows, int C, const float* dy, const float* x
 }
 
 // The layer.  rowblk: gcgcn_row_blocks(B, T, t_valid) or null.  matmul: 0 = the fp32 GEMM layer, 1 = the twelve Linear products with
-// bf16 operands (gemm_bf16.hip).
+// bf16 operands (gemm_bf16.hip).  attn: 0 = the fp32 attention core, 1 = the bf16 one (bert_attn_bf16.hip).
 int64_t gcgcn_bert_layer_ws_bytes(int B, int T, int D, int H, int Dff, int which) {
   if (bert_layer_shape_ok("bert_layer_ws_bytes", B, T, D, H, Dff)) return -1;
   if (which != 0 && which != 1) {
@@ -1350,9 +1371,10 @@ static S bert_unpack(P* const* p) {
 }
 // what the forward and the backward check alike, in front of their own buffers
 static int bert_layer_ok(const char* who, bool need_len, int B, int T, int D, int H, int Dff, const int32_t* t_valid, const int32_t* rowblk,
-                         const float* const* params, const void* rng_snap, float p_attn, float p_hidden, int matmul) {
+                         const float* const* params, const void* rng_snap, float p_attn, float p_hidden, int matmul, int attn) {
   GC_TRY(bert_layer_shape_ok(who, B, T, D, H, Dff));
   GC_REQUIRE(matmul == BERT_MM_FP32 || matmul == BERT_MM_BF16, "%s: matmul = %d (0: fp32, 1: bf16 operands)", who, matmul);
+  GC_TRY(bert_attn_sel_ok(who, attn));
   GC_TRY(bert_drop_ok(who, rng_snap, p_attn));
   GC_TRY(bert_drop_ok(who, rng_snap, p_hidden));
   GC_TRY(bert_params_ok(who, params));
@@ -1363,19 +1385,19 @@ static int bert_layer_ok(const char* who, bool need_len, int B, int T, int D, in
 }
 static int layer_fwd(const char* who, bool need_len, int B, int T, int D, int H, int Dff, const float* x, const float* key_bias,
                      const int32_t* t_valid, const int32_t* rowblk, const float* const* params, float* y, void* saved, int64_t saved_bytes,
-                     const void* rng_snap, float p_attn, float p_hidden, void* stream, int matmul) {
-  GC_TRY(bert_layer_ok(who, need_len, B, T, D, H, Dff, t_valid, rowblk, params, rng_snap, p_attn, p_hidden, matmul));
+                     const void* rng_snap, float p_attn, float p_hidden, void* stream, int matmul, int attn) {
+  GC_TRY(bert_layer_ok(who, need_len, B, T, D, H, Dff, t_valid, rowblk, params, rng_snap, p_attn, p_hidden, matmul, attn));
   GC_REQUIRE(x && y && saved && al16(x) && al16(y) && al16(saved), "%s: x, y, saved must be given and 16-byte aligned", who);
   GC_REQUIRE(saved_bytes >= gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0), "%s: %lld bytes of saved activations needed "
              "(gcgcn_bert_layer_ws_bytes, which = 0)", who, (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 0));
   return bert_layer_fwd(B, T, D, H, Dff, x, key_bias, bert_unpack<BertLayerParams>(params), y, (float*)saved, rng_snap, p_attn, p_hidden,
-                        (hipStream_t)stream, t_valid, rowblk, matmul);
+                        (hipStream_t)stream, t_valid, rowblk, matmul, attn);
 }
 static int layer_bwd(const char* who, bool need_len, int B, int T, int D, int H, int Dff, const float* x, const float* key_bias,
                      const int32_t* t_valid, const int32_t* rowblk, const float* const* params, const void* saved, int64_t saved_bytes,
                      const float* dy, float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn,
-                     float p_hidden, void* stream, int matmul) {
-  GC_TRY(bert_layer_ok(who, need_len, B, T, D, H, Dff, t_valid, rowblk, params, rng_snap, p_attn, p_hidden, matmul));
+                     float p_hidden, void* stream, int matmul, int attn) {
+  GC_TRY(bert_layer_ok(who, need_len, B, T, D, H, Dff, t_valid, rowblk, params, rng_snap, p_attn, p_hidden, matmul, attn));
   GC_TRY(bert_params_ok(who, grads));
   GC_REQUIRE(x && saved && dy && dx && ws && al16(x) && al16(saved) && al16(dy) && al16(dx) && al16(ws),
              "%s: x, saved, dy, dx, ws must be given and 16-byte aligned", who);
@@ -1386,44 +1408,57 @@ static int layer_bwd(const char* who, bool need_len, int B, int T, int D, int H,
              "(gcgcn_bert_layer_ws_bytes, which = 1)", who, (long long)gcgcn_bert_layer_ws_bytes(B, T, D, H, Dff, 1));
   return bert_layer_bwd(B, T, D, H, Dff, x, key_bias, bert_unpack<BertLayerParams>(params), (const float*)saved, dy, dx,
                         bert_unpack<BertLayerGrads>(grads), (float*)ws, ws_bytes / (int64_t)sizeof(float), rng_snap, p_attn, p_hidden,
-                        (hipStream_t)stream, t_valid, rowblk, matmul);
+                        (hipStream_t)stream, t_valid, rowblk, matmul, attn);
 }
 int gcgcn_bert_layer_fwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const float* const* params, float* y,
                          void* saved, int64_t saved_bytes, const void* rng_snap, float p_attn, float p_hidden, void* stream) {
   return layer_fwd("bert_layer_fwd", false, B, T, D, H, Dff, x, key_bias, nullptr, nullptr, params, y, saved, saved_bytes, rng_snap, p_attn,
-                   p_hidden, stream, BERT_MM_FP32);
+                   p_hidden, stream, BERT_MM_FP32, BERT_ATTN_FP32);
 }
 int gcgcn_bert_layer_fwd_len(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
                              const int32_t* rowblk, const float* const* params, float* y, void* saved, int64_t saved_bytes,
                              const void* rng_snap, float p_attn, float p_hidden, void* stream) {
   return layer_fwd("bert_layer_fwd_len", true, B, T, D, H, Dff, x, key_bias, t_valid, rowblk, params, y, saved, saved_bytes, rng_snap,
-                   p_attn, p_hidden, stream, BERT_MM_FP32);
+                   p_attn, p_hidden, stream, BERT_MM_FP32, BERT_ATTN_FP32);
 }
 int gcgcn_bert_layer_fwd_mm(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
                             const int32_t* rowblk, const float* const* params, float* y, void* saved, int64_t saved_bytes,
                             const void* rng_snap, float p_attn, float p_hidden, void* stream, int matmul) {
   return layer_fwd("bert_layer_fwd_mm", false, B, T, D, H, Dff, x, key_bias, t_valid, rowblk, params, y, saved, saved_bytes, rng_snap,
-                   p_attn, p_hidden, stream, matmul);
+                   p_attn, p_hidden, stream, matmul, BERT_ATTN_FP32);
+}
+int gcgcn_bert_layer_fwd_mx(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
+                            const int32_t* rowblk, const float* const* params, float* y, void* saved, int64_t saved_bytes,
+                            const void* rng_snap, float p_attn, float p_hidden, void* stream, int matmul, int attn) {
+  return layer_fwd("bert_layer_fwd_mx", false, B, T, D, H, Dff, x, key_bias, t_valid, rowblk, params, y, saved, saved_bytes, rng_snap,
+                   p_attn, p_hidden, stream, matmul, attn);
 }
 int gcgcn_bert_layer_bwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const float* const* params,
                          const void* saved, int64_t saved_bytes, const float* dy, float* dx, float* const* grads, void* ws, int64_t ws_bytes,
                          const void* rng_snap, float p_attn, float p_hidden, void* stream) {
   return layer_bwd("bert_layer_bwd", false, B, T, D, H, Dff, x, key_bias, nullptr, nullptr, params, saved, saved_bytes, dy, dx, grads, ws,
-                   ws_bytes, rng_snap, p_attn, p_hidden, stream, BERT_MM_FP32);
+                   ws_bytes, rng_snap, p_attn, p_hidden, stream, BERT_MM_FP32, BERT_ATTN_FP32);
 }
 int gcgcn_bert_layer_bwd_len(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
                              const int32_t* rowblk, const float* const* params, const void* saved, int64_t saved_bytes, const float* dy,
                              float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn, float p_hidden,
                              void* stream) {
   return layer_bwd("bert_layer_bwd_len", true, B, T, D, H, Dff, x, key_bias, t_valid, rowblk, params, saved, saved_bytes, dy, dx, grads, ws,
-                   ws_bytes, rng_snap, p_attn, p_hidden, stream, BERT_MM_FP32);
+                   ws_bytes, rng_snap, p_attn, p_hidden, stream, BERT_MM_FP32, BERT_ATTN_FP32);
 }
 int gcgcn_bert_layer_bwd_mm(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
                             const int32_t* rowblk, const float* const* params, const void* saved, int64_t saved_bytes, const float* dy,
                             float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn, float p_hidden,
                             void* stream, int matmul) {
   return layer_bwd("bert_layer_bwd_mm", false, B, T, D, H, Dff, x, key_bias, t_valid, rowblk, params, saved, saved_bytes, dy, dx, grads, ws,
-                   ws_bytes, rng_snap, p_attn, p_hidden, stream, matmul);
+                   ws_bytes, rng_snap, p_attn, p_hidden, stream, matmul, BERT_ATTN_FP32);
+}
+int gcgcn_bert_layer_bwd_mx(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
+                            const int32_t* rowblk, const float* const* params, const void* saved, int64_t saved_bytes, const float* dy,
+                            float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn, float p_hidden,
+                            void* stream, int matmul, int attn) {
+  return layer_bwd("bert_layer_bwd_mx", false, B, T, D, H, Dff, x, key_bias, t_valid, rowblk, params, saved, saved_bytes, dy, dx, grads, ws,
+                   ws_bytes, rng_snap, p_attn, p_hidden, stream, matmul, attn);
 }
 
 // ---- opt-in bf16 matrix products (gemm_bf16.hip) -------------------------------------------------------------

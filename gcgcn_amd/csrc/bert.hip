@@ -27,6 +27,7 @@
 // Padding.  Rows of a block past T are loaded as zeros through a predicate (never multiplied by 0), keys past T get probability 0
 // through a select, rows past T are not stored: what lies behind a buffer's end is never read and never reaches a result.
 #include "bert.hpp"
+#include "bert_attn.hpp"
 #include "gemm.hpp"
 #include "gemm_bf16.hpp"
 #include "rowops.hpp"
@@ -84,33 +85,12 @@ __device__ __forceinline__ f32x4 tile_nn(const float* xrow, const float* zcol, c
   return a0 + a1;
 }
 
-// keep-scale of element (i, j) of the (b, h) slice of the virtual [B][H][T][T] probability tensor: 1 / (1 - p) or 0
-__device__ __forceinline__ float attn_keep(const Drop& d, const uint64_t key, const uint64_t slice_row0, const int i, const int j, const int T) {
-  const uint64_t idx = (slice_row0 + (uint64_t)i) * (uint64_t)T + (uint64_t)j;
-  return rng_u32(key, idx) >= d.thresh ? d.scale : 0.f;
-}
-
-// c_b = the largest penalty of document b's keys (0 without key_bias), the same value in every thread.  The kernels work with
-// key_bias - c_b: a softmax does not see a shift common to its keys, and a document whose keys are ALL masked (every penalty -10000)
-// would otherwise lose the scores' low bits to the penalty's magnitude (one ulp of 1e4 is 1e-3).  lse is stored relative to c_b.
-__device__ __forceinline__ float doc_bias_max(const float* __restrict__ kb, const int T, float* sh) {
-  if (!kb) return 0.f;
-  float m = -INFINITY;
-  for (int j = threadIdx.x; j < T; j += 256) m = fmaxf(m, kb[j]);
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
-  __syncthreads();
-  return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-
 // Token lengths (LEN instantiations; t_valid [B], row (b, t) is live iff t < t_valid[b]).  Tl = the document's length clamped to
 // [0, T] takes T's place in every predicate -- the rows that are loaded, the keys that get a probability, the streamed loop's end --
 // while T keeps the strides and the dropout index.  A workgroup whose 16 rows are all padding stores its zeros and leaves before
 // the first barrier; one that holds the document's last live rows stores zeros on the padding rows beside them.  Both decisions
 // are uniform per workgroup and made outside the matrix-instruction sequences.  Without LEN the code is what it was.
-__device__ __forceinline__ int live_len(const int* __restrict__ t_valid, const int b, const int T) {
-  return __builtin_amdgcn_readfirstlane(min(max(t_valid[b], 0), T));
-}
+// (live_len, the penalty shift c_b and the dropout decision: bert_attn.hpp, shared with the bf16 core.)
 
 // ---- forward -------------------------------------------------------------------------------------------------------------------
 template <bool LEN>
@@ -361,7 +341,8 @@ __global__ __launch_bounds__(256) void bert_attn_bwd_kv_kernel(const float* __re
 }
 
 int bert_attn_fwd(int B, int T, int H, const float* qkv, const float* key_bias, float* ctx, float* lse, Drop drop, hipStream_t st,
-                  const int* t_valid) {
+                  const int* t_valid, int attn) {
+  if (attn == BERT_ATTN_BF16) return bert_attn_bf16_fwd(B, T, H, qkv, key_bias, ctx, lse, drop, st, t_valid);
   const float alpha = 1.f / sqrtf((float)AD);
   const auto kernel = t_valid ? bert_attn_fwd_kernel<true> : bert_attn_fwd_kernel<false>;
   GC_LAUNCH_TIMED("bert_attn_fwd", 4.0 * B * H * T * T * AD, kernel, dim3(cdiv(T, AQ), H, B), dim3(256), 0, st, qkv, key_bias, ctx, lse, T, H,
@@ -370,15 +351,16 @@ int bert_attn_fwd(int B, int T, int H, const float* qkv, const float* key_bias, 
 }
 
 int bert_attn_bwd(int B, int T, int H, const float* qkv, const float* key_bias, const float* ctx, const float* lse, const float* dctx,
-                  float* dqkv, float* delta, Drop drop, hipStream_t st, const int* t_valid) {
+                  float* dqkv, float* delta, Drop drop, hipStream_t st, const int* t_valid, int attn) {
   const float alpha = 1.f / sqrtf((float)AD);
   const long n = (long)B * T * H;
-  {
+  {   // delta comes from the stored fp32 ctx, unrounded, at either setting of attn
     ProfScope ps("bert_attn_delta", st);
     const auto kd = t_valid ? bert_attn_delta_kernel<true> : bert_attn_delta_kernel<false>;
     hipLaunchKernelGGL(kd, dim3(cdiv(n, 4)), dim3(256), 0, st, ctx, dctx, delta, n, T, H, t_valid);
     GC_TRY(check_launch("bert_attn_delta"));
   }
+  if (attn == BERT_ATTN_BF16) return bert_attn_bf16_bwd(B, T, H, qkv, key_bias, lse, delta, dctx, dqkv, drop, st, t_valid);
   const auto kq = t_valid ? bert_attn_bwd_q_kernel<true> : bert_attn_bwd_q_kernel<false>;
   GC_LAUNCH_TIMED("bert_attn_bwd_q", 6.0 * B * H * T * T * AD, kq, dim3(cdiv(T, AQ), H, B), dim3(256), 0, st, qkv, key_bias, lse, delta, dctx,
                   dqkv, T, H, alpha, drop, t_valid);
@@ -700,12 +682,13 @@ const int* live_blocks(const int* tv, int T, const int* rowblk) { return tv && T
 }  // namespace
 
 int bert_layer_fwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const BertLayerParams& p, float* y,
-                   float* saved, const void* snap, float p_attn, float p_hidden, hipStream_t st, const int* tv, const int* rowblk, int matmul) {
+                   float* saved, const void* snap, float p_attn, float p_hidden, hipStream_t st, const int* tv, const int* rowblk, int matmul,
+                   int attn) {
   const long R = (long)B * T;
   const Saved s = saved_views(saved, B, T, D, H, Dff);
   const Linear lin = {matmul, (int)R, live_blocks(tv, T, rowblk), nullptr, st};
   GC_TRY(lin.fwd(s.qkv, x, p.wqkv, p.bqkv, 3 * D, D));
-  GC_TRY(bert_attn_fwd(B, T, H, s.qkv, key_bias, s.ctx, s.lse, make_drop(snap, SALT_BERT_ATTN, p_attn), st, tv));
+  GC_TRY(bert_attn_fwd(B, T, H, s.qkv, key_bias, s.ctx, s.lse, make_drop(snap, SALT_BERT_ATTN, p_attn), st, tv, attn));
   GC_TRY(lin.fwd(s.ao, s.ctx, p.wo, nullptr, D, D));
   GC_TRY(res_ln_fwd(R, D, s.ao, p.bo, x, p.ln1w, p.ln1b, s.a, s.mean1, s.rstd1, make_drop(snap, SALT_BERT_AO, p_hidden), st, tv, T));
   GC_TRY(lin.fwd(s.z, s.a, p.wi, nullptr, Dff, D));
@@ -716,7 +699,7 @@ int bert_layer_fwd(int B, int T, int D, int H, int Dff, const float* x, const fl
 
 int bert_layer_bwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const BertLayerParams& p,
                    const float* saved, const float* dy, float* dx, const BertLayerGrads& d, float* ws, long ws_elems, const void* snap,
-                   float p_attn, float p_hidden, hipStream_t st, const int* tv, const int* rowblk, int matmul) {
+                   float p_attn, float p_hidden, hipStream_t st, const int* tv, const int* rowblk, int matmul, int attn) {
   const long R = (long)B * T;
   const Saved s = saved_views(const_cast<float*>(saved), B, T, D, H, Dff);
   const Work w = work_views(ws, B, T, D, H, Dff);
@@ -736,7 +719,8 @@ int bert_layer_bwd(int B, int T, int D, int H, int Dff, const float* x, const fl
                     make_drop(snap, SALT_BERT_AO, p_hidden), st, tv, T));
   // ao = ctx Wo^T:  dWo = t1^T ctx, t3 = dctx = t1 Wo, dbo = column sums of t1
   GC_TRY(lin.bwd(w.t1, s.ctx, p.wo, d.wo, w.t3, nullptr, d.bo, D, D));
-  GC_TRY(bert_attn_bwd(B, T, H, s.qkv, key_bias, s.ctx, s.lse, w.t3, w.big, w.delta, make_drop(snap, SALT_BERT_ATTN, p_attn), st, tv));   // big = dqkv
+  GC_TRY(bert_attn_bwd(B, T, H, s.qkv, key_bias, s.ctx, s.lse, w.t3, w.big, w.delta, make_drop(snap, SALT_BERT_ATTN, p_attn), st, tv,
+                       attn));   // big = dqkv
   // qkv = x Wqkv^T + b:  dWqkv = big^T x, dx = big Wqkv + t2 (it leaves the layer), dbqkv = column sums of big
   return lin.bwd(w.big, x, p.wqkv, d.wqkv, dx, w.t2, d.bqkv, 3 * D, D, 1);
 }

@@ -26,12 +26,22 @@ constexpr uint64_t SALT_BERT_OUT = 0x424f5531ull;    // on output.dense(i) + bia
 // document's largest penalty, which keeps a document whose keys are all masked at full precision.  Nothing of size [T][T] is written
 // to memory.
 // With t_valid: keys at or past t_valid[b] have probability exactly 0, c_b is the largest penalty of the document's LIVE keys.
+// attn: BERT_ATTN_FP32 = the kernels of bert.hip, launch for launch what they were; BERT_ATTN_BF16 = the same contract with the four
+// matrix products on bf16 operands (bert_attn_bf16.hip): q, k, v and dctx rounded once on their way into LDS or registers, P and dS
+// when they become operands, fp32 accumulation, softmax, lse, delta and dS in fp32; the dropout mask is bit for bit the same.
+constexpr int BERT_ATTN_FP32 = 0, BERT_ATTN_BF16 = 1;
 int bert_attn_fwd(int B, int T, int H, const float* qkv, const float* key_bias, float* ctx, float* lse, Drop drop, hipStream_t st,
-                  const int* t_valid = nullptr);
+                  const int* t_valid = nullptr, int attn = BERT_ATTN_FP32);
 // dqkv [B][T][3 D] = dq | dk | dv.  delta: [B][H][T] floats of scratch (sum_d dctx * ctx).  P is recomputed from q, k and lse and
 // the dropout mask from the same Drop; one workgroup writes each element of dq (per query block) and of dk / dv (per key block).
 int bert_attn_bwd(int B, int T, int H, const float* qkv, const float* key_bias, const float* ctx, const float* lse, const float* dctx,
-                  float* dqkv, float* delta, Drop drop, hipStream_t st, const int* t_valid = nullptr);
+                  float* dqkv, float* delta, Drop drop, hipStream_t st, const int* t_valid = nullptr, int attn = BERT_ATTN_FP32);
+// the bf16 core's launches (bert_attn_bf16.hip); bert_attn_fwd / bert_attn_bwd dispatch to them, the backward after the delta kernel.
+// ctx and dqkv must be 16-byte aligned.
+int bert_attn_bf16_fwd(int B, int T, int H, const float* qkv, const float* key_bias, float* ctx, float* lse, Drop drop, hipStream_t st,
+                       const int* t_valid);
+int bert_attn_bf16_bwd(int B, int T, int H, const float* qkv, const float* key_bias, const float* lse, const float* delta,
+                       const float* dctx, float* dqkv, Drop drop, hipStream_t st, const int* t_valid);
 
 // ---- y [rows][D] = weight * (v - mean) / sqrt(var + 1e-12) + lnb,  v = dropout(x + bias) + res; bias, res, dropout each optional.
 // D a multiple of 64, <= 1024.  mean / rstd [rows]: written when given (the backward reads them).  Dropout index = row * D + col.
@@ -70,13 +80,14 @@ long bert_layer_ws_elems(int B, int T, int D, int H, int Dff);   // the backward
 // matmul: BERT_MM_FP32 = the fp32-MFMA GEMM layer, launch for launch what it was; BERT_MM_BF16 = the twelve Linear products with bf16
 // operands (gemm_bf16.hpp: fp32 in memory, rounded once on the way into LDS, fp32 accumulation), always dense (rowblk is ignored), the
 // bias gradients as stand-alone fp32 column sums.  The saved state and the workspace are the same either way.
+// attn: the attention core's selector (above), independent of matmul.
 constexpr int BERT_MM_FP32 = 0, BERT_MM_BF16 = 1;
 int bert_layer_fwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const BertLayerParams& p, float* y,
                    float* saved, const void* snap, float p_attn, float p_hidden, hipStream_t st, const int* t_valid = nullptr,
-                   const int* rowblk = nullptr, int matmul = BERT_MM_FP32);
+                   const int* rowblk = nullptr, int matmul = BERT_MM_FP32, int attn = BERT_ATTN_FP32);
 int bert_layer_bwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const BertLayerParams& p,
                    const float* saved, const float* dy, float* dx, const BertLayerGrads& g, float* ws, long ws_elems, const void* snap,
                    float p_attn, float p_hidden, hipStream_t st, const int* t_valid = nullptr, const int* rowblk = nullptr,
-                   int matmul = BERT_MM_FP32);
+                   int matmul = BERT_MM_FP32, int attn = BERT_ATTN_FP32);
 
 }  // namespace gc

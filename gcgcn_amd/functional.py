@@ -1508,20 +1508,20 @@ def _ptr_array(tensors):
 
 
 class BertLayerFn(torch.autograd.Function):
-    """(x[B,T,D], key_bias[B,T] | None, t_valid[B] | None, rowblk | None, matmul, the 12 tensors of gcgcn_bert_layer_fwd's parameter
-    list) -> y[B,T,D].  Every route is one call of the _mm entry points (include/gcgcn.h): null t_valid / rowblk = no lengths / dense
-    products, matmul = 0 / 1 = fp32 / bf16 operands."""
+    """(x[B,T,D], key_bias[B,T] | None, t_valid[B] | None, rowblk | None, matmul, attn, the 12 tensors of gcgcn_bert_layer_fwd's
+    parameter list) -> y[B,T,D].  Every route is one call of the _mx entry points (include/gcgcn.h): null t_valid / rowblk = no lengths /
+    dense products, matmul = 0 / 1 = fp32 / bf16 operands of the Linears, attn = 0 / 1 = the same for the attention core."""
 
     @staticmethod
-    def forward(ctx, x, key_bias, H, p_attn, p_hidden, snap, t_valid, rowblk, matmul, *params):
+    def forward(ctx, x, key_bias, H, p_attn, p_hidden, snap, t_valid, rowblk, matmul, attn, *params):
         B, T, D = x.shape
         Dff = params[6].shape[0]
         dims = (B, T, D, H, Dff)
         saved = _f32_buf(_bytes_or_raise("gcgcn_bert_layer_ws_bytes", *dims, 0), x.device)
         y = torch.empty_like(x)
-        ctx.matmul = matmul
-        call("gcgcn_bert_layer_fwd_mm", *dims, _p(x), _p(key_bias), _p(t_valid), _p(rowblk), _ptr_array(params), _p(y), _p(saved),
-             saved.numel() * 4, _p(snap), float(p_attn), float(p_hidden), _stream(), matmul)
+        ctx.matmul, ctx.attn = matmul, attn
+        call("gcgcn_bert_layer_fwd_mx", *dims, _p(x), _p(key_bias), _p(t_valid), _p(rowblk), _ptr_array(params), _p(y), _p(saved),
+             saved.numel() * 4, _p(snap), float(p_attn), float(p_hidden), _stream(), matmul, attn)
         torch.autograd.graph.increment_version((y, saved))
         ctx.dims, ctx.ps, ctx.snap, ctx.has_kb = dims, (float(p_attn), float(p_hidden)), snap, key_bias is not None
         ctx.t_valid, ctx.rowblk = t_valid, rowblk
@@ -1539,11 +1539,11 @@ class BertLayerFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         grads = tuple(torch.empty_like(t) for t in params)
         ws = _f32_buf(_bytes_or_raise("gcgcn_bert_layer_ws_bytes", *ctx.dims, 1), x.device)
-        call("gcgcn_bert_layer_bwd_mm", *ctx.dims, _p(x), _p(key_bias), _p(ctx.t_valid), _p(ctx.rowblk), _ptr_array(params), _p(saved),
+        call("gcgcn_bert_layer_bwd_mx", *ctx.dims, _p(x), _p(key_bias), _p(ctx.t_valid), _p(ctx.rowblk), _ptr_array(params), _p(saved),
              saved.numel() * 4, _p(dy), _p(dx), _ptr_array(grads), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.ps[0], ctx.ps[1], _stream(),
-             ctx.matmul)
+             ctx.matmul, ctx.attn)
         torch.autograd.graph.increment_version((dx,) + grads)
-        return (dx, None, None, None, None, None, None, None, None) + grads
+        return (dx, None, None, None, None, None, None, None, None, None) + grads
 
 
 BERT_MATMULS = ("fp32", "bf16")     # the value of gcgcn_bert_layer_*_mm's selector is the index
@@ -1555,8 +1555,72 @@ def bert_matmul_index(matmul, who: str) -> int:
     return BERT_MATMULS.index(matmul)
 
 
+BERT_ATTENTIONS = ("fp32", "bf16")  # the value of the _mx entry points' attn selector is the index
+
+
+def bert_attention_index(attention, who: str) -> int:
+    if not isinstance(attention, str) or attention not in BERT_ATTENTIONS:
+        raise ValueError(f"{who}: attention must be 'fp32' or 'bf16', got {attention!r}")
+    return BERT_ATTENTIONS.index(attention)
+
+
+class BertAttentionFn(torch.autograd.Function):
+    """(qkv[B,T,3D], key_bias[B,T] | None, t_valid[B] | None) -> ctx[B,T,D] through gcgcn_bert_attn_fwd_mx / _bwd_mx."""
+
+    @staticmethod
+    def forward(ctx, qkv, key_bias, H, p, snap, t_valid, attn):
+        B, T, D3 = qkv.shape
+        out = torch.empty(B, T, D3 // 3, device=qkv.device)
+        lse = torch.empty(B, H, T, device=qkv.device)
+        call("gcgcn_bert_attn_fwd_mx", B, T, H, 64, _p(qkv), _p(key_bias), _p(t_valid), _p(out), _p(lse), _p(snap), _lib.SALT_BERT_ATTN,
+             float(p), _stream(), attn)
+        torch.autograd.graph.increment_version((out, lse))
+        ctx.H, ctx.p, ctx.snap, ctx.t_valid, ctx.attn, ctx.has_kb = H, float(p), snap, t_valid, attn, key_bias is not None
+        ctx.save_for_backward(qkv, out, lse, *(() if key_bias is None else (key_bias,)))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dctx):
+        qkv, out, lse = ctx.saved_tensors[:3]
+        key_bias = ctx.saved_tensors[3] if ctx.has_kb else None
+        B, T, _ = qkv.shape
+        dctx = dctx.contiguous()
+        dqkv, delta = torch.empty_like(qkv), torch.empty_like(lse)
+        call("gcgcn_bert_attn_bwd_mx", B, T, ctx.H, 64, _p(qkv), _p(key_bias), _p(ctx.t_valid), _p(out), _p(lse), _p(dctx), _p(dqkv),
+             _p(delta), _p(ctx.snap), _lib.SALT_BERT_ATTN, ctx.p, _stream(), ctx.attn)
+        torch.autograd.graph.increment_version((dqkv, delta))
+        return dqkv, None, None, None, None, None, None
+
+
+def bert_attention(qkv, key_bias, H, p=0.0, training=False, snap=None, t_valid=None, attention="fp32"):
+    """The BERT attention core in HIP on packed ``qkv[B,T,3D]``, ``D = 64 H``: row ``(b, t)`` holds ``q | k | v``, head ``h`` in
+    columns ``[64 h, 64 h + 64)`` of each.  Returns ``ctx[B,T,D] = dropout(softmax(q k^T / 8 + key_bias[b, key])) v``; the gradient
+    reaches ``qkv``.  ``key_bias``: ``[B,T]`` additive penalty per key or None.  ``T <= 512``.  In training mode with ``p > 0`` the
+    probabilities are dropped with the mask of ``dropout_keep_mask(snap, SALT_BERT_ATTN, p, B * H * T * T)`` (``snap``: default a
+    fresh snapshot), regenerated in the backward.  ``t_valid``: token counts ``[B]``: rows at or past ``t_valid[b]`` are no keys, their
+    ``ctx`` and gradient are exactly zero and the gradient arriving there is not read.  ``attention``: ``"fp32"`` (csrc/bert.hip) or
+    ``"bf16"`` (csrc/bert_attn_bf16.hip: the four products on bf16 operands, ``gcgcn_amd.bert.Bf16AttentionFn`` is the definition;
+    the mask drawn is the same).  Nothing of size ``[T,T]`` reaches memory; two runs from one seed are bitwise equal."""
+    attn = bert_attention_index(attention, "bert_attention")
+    qkv = _chk(qkv, "qkv", 3)
+    B, T, D3 = qkv.shape
+    if H < 1 or D3 != 3 * 64 * H:
+        raise ValueError(f"bert_attention: qkv {tuple(qkv.shape)} is not [B, T, 3 * 64 * {H}] (the kernels serve a head width of 64)")
+    if key_bias is not None:
+        key_bias = _chk(key_bias, "key_bias", 2)
+        if key_bias.shape != (B, T):
+            raise ValueError(f"bert_attention: key_bias {tuple(key_bias.shape)}, expected ({B}, {T})")
+    p = float(p) if training else 0.0
+    if p > 0 and snap is None:
+        snap = rng_snapshot(qkv.device)
+    if t_valid is not None:
+        t_valid = _nv(t_valid, B, T, qkv.device)
+    return BertAttentionFn.apply(qkv, key_bias, H, p, snap if p > 0 else None, t_valid, attn)
+
+
 def bert_layer(x, key_bias, wq, bq, wk, bk, wv, bv, wo, bo, ln1_w, ln1_b, wi, bi, wo2, bo2, ln2_w, ln2_b, p_attn=0.1, p_hidden=0.1,
-               training=False, snap=None, t_valid=None, rowblk=None, matmul="fp32"):
+               training=False, snap=None, t_valid=None, rowblk=None, matmul="fp32", attention="fp32"):
     """One BERT encoder layer (``pytorch_pretrained_bert`` 0.6 ``BertLayer``) in HIP: ``x[B,T,D]`` -> ``[B,T,D]``.  ``key_bias``:
     ``[B,T]`` additive score penalty per key (``(1 - mask) * -10000``) or None.  The 16 parameter tensors in ``BERT_LAYER_TENSORS``'
     order, Linear weights ``[out, in]``; the number of heads is ``D / 64`` (the attention kernels serve a head width of 64) and
@@ -1578,8 +1642,14 @@ def bert_layer(x, key_bias, wq, bq, wk, bk, wv, bv, wo, bo, ln1_w, ln1_b, wi, bi
     ``t.to(torch.bfloat16)`` does -- on the bf16 matrix cores, with fp32 accumulation; activations, weights and gradients stay fp32
     in memory, the bias gradients are fp32 sums of the unrounded gradients and everything between the products is unchanged.  The
     products then always run dense (``rowblk`` is accepted and ignored); the contract of the padding rows holds.
-    ``BertModel(impl="torch", matmul="bf16")`` is the definition."""
+    ``BertModel(impl="torch", matmul="bf16")`` is the definition.
+
+    ``attention``: ``"fp32"`` (default: the attention kernels as they were) or ``"bf16"``: the core's four matrix products take bf16
+    operands on the bf16 matrix cores (csrc/bert_attn_bf16.hip) -- ``q``, ``k``, ``v`` and the arriving gradient rounded once, ``P``
+    and ``dS`` when they become operands, fp32 accumulation, softmax, ``lse`` and ``delta`` in fp32; masks, token lengths and the
+    dropout mask are the fp32 core's.  Independent of ``matmul``.  ``gcgcn_amd.bert.Bf16AttentionFn`` is the definition."""
     mm = bert_matmul_index(matmul, "bert_layer")
+    attn = bert_attention_index(attention, "bert_layer")
     x = _chk(x, "x", 3)
     names = ("wq", "bq", "wk", "bk", "wv", "bv", "wo", "bo", "ln1_w", "ln1_b", "wi", "bi", "wo2", "bo2", "ln2_w", "ln2_b")
     ts = [_chk(t, n) for n, t in zip(names, (wq, bq, wk, bk, wv, bv, wo, bo, ln1_w, ln1_b, wi, bi, wo2, bo2, ln2_w, ln2_b))]
@@ -1608,7 +1678,7 @@ def bert_layer(x, key_bias, wq, bq, wk, bk, wv, bv, wo, bo, ln1_w, ln1_b, wi, bi
     elif rowblk is not None:
         raise ValueError("bert_layer: rowblk without t_valid")
     return BertLayerFn.apply(x, key_bias, D // 64, p_attn, p_hidden, snap if (p_attn > 0 or p_hidden > 0) else None, t_valid, rowblk, mm,
-                             wqkv, bqkv, *ts[6:])
+                             attn, wqkv, bqkv, *ts[6:])
 
 
 def gemm_bf16(a, b, form="nt", bias=None, add=None):

@@ -222,7 +222,11 @@ class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
 
     ``config.bert_matmul = "fp32" | "bf16"`` (needs ``bert_impl``; a ``ValueError`` without it) is that encoder's ``matmul``: with
     ``"bf16"`` the encoder layers' Linears take bf16 operands with fp32 accumulation while parameters, gradients and the
-    ``state_dict`` stay fp32 (``gcgcn_amd.BertModel``).  Without ``bert_matmul`` nothing changes."""
+    ``state_dict`` stay fp32 (``gcgcn_amd.BertModel``).  Without ``bert_matmul`` nothing changes.
+
+    ``config.bert_attention = "fp32" | "bf16"`` (needs ``bert_impl``; a ``ValueError`` without it) is that encoder's ``attention``:
+    with ``"bf16"`` the attention core's four matrix products take bf16 operands as well (``gcgcn_amd.bert.Bf16AttentionFn`` is the
+    definition).  Independent of ``bert_matmul``.  Without ``bert_attention`` nothing changes."""
 
     WORD_VEC_SIZE = 768
     _KEY_ORDER = ("bert", "ner_emb", "entity_embed", "get_weighted_adj_matrix", "get_adj_matrix", "graphcnn", "linear_re",
@@ -238,11 +242,18 @@ class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
                 raise ValueError(f"config.bert_matmul must be 'fp32' or 'bf16', got {matmul!r}")
             if impl is None:
                 raise ValueError("config.bert_matmul selects the Linears of this library's own encoder: set config.bert_impl too")
+        attention = getattr(config, "bert_attention", None)
+        if attention is not None:
+            if attention not in ("fp32", "bf16"):
+                raise ValueError(f"config.bert_attention must be 'fp32' or 'bf16', got {attention!r}")
+            if impl is None:
+                raise ValueError("config.bert_attention selects the attention core of this library's own encoder: set config.bert_impl too")
         if bert is None and impl is not None:                                                # this library's own encoder (bert.py)
             from .bert import BertConfig, BertModel as OwnBert, load_pretrained_state_dict
             if impl not in ("torch", "hip"):
                 raise ValueError(f"config.bert_impl must be 'torch' or 'hip', got {impl!r}")
-            bert = OwnBert(getattr(config, "bert_config", None) or BertConfig(), impl=impl, **({} if matmul is None else {"matmul": matmul}))
+            bert = OwnBert(getattr(config, "bert_config", None) or BertConfig(), impl=impl, **({} if matmul is None else {"matmul": matmul}),
+                           **({} if attention is None else {"attention": attention}))
             if getattr(config, "bert_weights", None):
                 load_pretrained_state_dict(bert, config.bert_weights)
             if bert.config.hidden_size != self.WORD_VEC_SIZE:

@@ -720,6 +720,35 @@ int gcgcn_bert_layer_bwd_mm(int B, int T, int D, int H, int Dff, const float* x,
                             float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn, float p_hidden,
                             void* stream, int matmul);
 
+/* ---- opt-in bf16 attention core (bert_attn_bf16.hip) -----------------------------------------------------------
+ * gcgcn_bert_attn_fwd_mx / gcgcn_bert_attn_bwd_mx: the argument lists of gcgcn_bert_attn_*_len (t_valid may be NULL: every row is
+ * live) plus a selector.  attn = 0: the fp32 core, launch for launch and bit for bit what the entry points above run.  attn = 1: the
+ * four matrix products of the core take bf16 operands on v_mfma_f32_16x16x32_bf16, with r(.) one rounding to bf16, nearest even:
+ *     S = r(q) r(k)^T / 8 + key_bias,  P = softmax(S) (fp32, unrounded),  Pd = keep / (1 - p) o P,  ctx = r(Pd) r(v),  lse as above;
+ *     delta = sum_d dctx ctx (fp32, from the stored ctx),  dPd = r(dctx) r(v)^T,  dS = P o (keep / (1 - p) o dPd - delta),
+ *     dv = r(Pd)^T r(dctx),  dq = r(dS) r(k) / 8,  dk = r(dS)^T r(q) / 8.
+ * q, k, v and dctx are rounded once on their way into LDS or registers, P and dS when they become operands; every accumulation, the
+ * softmax, lse, delta and dS are fp32; qkv, ctx, lse, dctx and dqkv stay fp32 in memory in the layouts above.  Everything else of the
+ * contract holds unchanged: dh = 64, T <= 512, key_bias and the c_b shift (a document whose keys are all masked keeps a finite
+ * softmax), the five points of the token lengths (grids independent of the lengths; a workgroup whose 64 rows are all padding stores
+ * its zeros and leaves), the dropout index in the virtual [B][H][T][T] tensor -- from one snapshot and salt attn = 1 draws bit for bit
+ * the mask attn = 0 draws --, nothing of size [T][T] in memory, one writer per output element, no float atomics, capturable.
+ * With attn = 1, ctx (forward) and dqkv (backward) must be 16-byte aligned as well.  Any other attn is refused.
+ * gcgcn_bert_layer_fwd_mx / gcgcn_bert_layer_bwd_mx: the _mm argument lists plus attn behind matmul; the two selectors are
+ * independent, the saved state and the workspace sizes do not depend on either.  Both calls of a pair take the same selectors. */
+int gcgcn_bert_attn_fwd_mx(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const int32_t* t_valid, float* ctx,
+                           float* lse, const void* rng_snap, uint64_t salt, float p, void* stream, int attn);
+int gcgcn_bert_attn_bwd_mx(int B, int T, int H, int dh, const float* qkv, const float* key_bias, const int32_t* t_valid, const float* ctx,
+                           const float* lse, const float* dctx, float* dqkv, float* delta, const void* rng_snap, uint64_t salt, float p,
+                           void* stream, int attn);
+int gcgcn_bert_layer_fwd_mx(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
+                            const int32_t* rowblk, const float* const* params, float* y, void* saved, int64_t saved_bytes,
+                            const void* rng_snap, float p_attn, float p_hidden, void* stream, int matmul, int attn);
+int gcgcn_bert_layer_bwd_mx(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const int32_t* t_valid,
+                            const int32_t* rowblk, const float* const* params, const void* saved, int64_t saved_bytes, const float* dy,
+                            float* dx, float* const* grads, void* ws, int64_t ws_bytes, const void* rng_snap, float p_attn, float p_hidden,
+                            void* stream, int matmul, int attn);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ layer's time split: each non-GEMM kernel timed on its own through the C ABI, the
     python tools/bert_bench.py [--layers 12] [--iters 20] [--json out.json]
     python tools/bert_bench.py --lengths {full,ragged} [--shape 4x512] [--layers 12] [--iters 20] [--json out.json]
     python tools/bert_bench.py --matmul fp32 bf16 [--lengths ragged] [--shape 4x512] [--layers 12] [--iters 10] [--json out.json]
+    python tools/bert_bench.py --attention fp32 bf16 [--matmul fp32 bf16] [--shape 4x512] [--layers 12] [--iters 10] [--json out.json]
 
 With --lengths only the HIP encoder runs, as one replayed hipGraph, twice on the same token counts in the same process: the
 prefix-mask path (attention_mask = arange(T) < t_valid, every row computed) and the length path (lengths = t_valid, live tokens
@@ -17,6 +18,10 @@ With --matmul only the HIP encoder runs, as one replayed hipGraph, once per list
 the same process on the same inputs (median, min and max of --iters samples; with --lengths on those token counts through
 lengths=), followed by one layer's twelve Linear products timed alone through the C ABI: the fp32 GEMM layer's launch against the
 bf16 kernel's, with the achieved TF/s.
+
+With --attention the same graph-replay runs go over every listed combination of BertModel(matmul=..., attention=...) (--matmul
+defaults to fp32 alone), and the kernel-alone section times the attention core through gcgcn_bert_attn_fwd_mx / _bwd_mx at each
+listed setting, back to back in the same process on the same data, with the achieved TF/s (4 and 10 B H T^2 64 flop).
 
 Prints one table and, with --json, writes the numbers.  DESIGN.md section 8.9 holds the tables of record."""
 import argparse
@@ -74,11 +79,11 @@ def draw_lengths(kind, B, T):
     return torch.randint(T // 8, T + 1, (B,), generator=g).to(torch.int32)
 
 
-def model_step(layers, impl, B, T, dev, t_valid=None, by_lengths=False, matmul="fp32"):
+def model_step(layers, impl, B, T, dev, t_valid=None, by_lengths=False, matmul="fp32", attention="fp32"):
     """t_valid None: the masks this tool has always used.  Otherwise the prefix mask of these counts, or (by_lengths) lengths=t_valid."""
     cfg = BertConfig(num_hidden_layers=layers, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
     torch.manual_seed(0)
-    model = BertModel(cfg, impl=impl, matmul=matmul).to(dev).train()
+    model = BertModel(cfg, impl=impl, matmul=matmul, attention=attention).to(dev).train()
     g = torch.Generator().manual_seed(1)
     ids = torch.randint(0, cfg.vocab_size, (B, T), generator=g).to(dev)
     counts = torch.tensor([T - 37 * (b % 3) for b in range(B)]) if t_valid is None else t_valid.cpu()
@@ -138,6 +143,27 @@ def kernel_split(B, T, dev, iters):
     return out
 
 
+def core_split(B, T, dev, iters, settings):
+    """The attention core alone at base size through the _mx entry points, random data, dropout off: one row per setting."""
+    D, H = 768, 12
+    st = torch.cuda.current_stream().cuda_stream
+    p = lambda t: t.data_ptr()
+    qkv, dqkv = torch.randn(B, T, 3 * D, device=dev), torch.empty(B, T, 3 * D, device=dev)
+    kb = torch.zeros(B, T, device=dev)
+    ctx, dctx = torch.empty(B, T, D, device=dev), torch.randn(B, T, D, device=dev)
+    lse, delta = torch.empty(B, H, T, device=dev), torch.empty(B, H, T, device=dev)
+    out = []
+    for name in settings:
+        attn = ("fp32", "bf16").index(name)
+        f = timed_stats(lambda: _lib.call("gcgcn_bert_attn_fwd_mx", B, T, H, 64, p(qkv), p(kb), None, p(ctx), p(lse), None, 0, 0.0, st, attn), iters)
+        b = timed_stats(lambda: _lib.call("gcgcn_bert_attn_bwd_mx", B, T, H, 64, p(qkv), p(kb), None, p(ctx), p(lse), p(dctx), p(dqkv), p(delta),
+                                          None, 0, 0.0, st, attn), iters)
+        flop = 1e-9 * B * H * T * T * 64
+        out.append({"attention": name, "fwd_ms": f[0], "fwd_min_ms": f[1], "fwd_max_ms": f[2], "bwd_ms": b[0], "bwd_min_ms": b[1],
+                    "bwd_max_ms": b[2], "fwd_tflops": 4 * flop / f[0], "bwd_tflops": 10 * flop / b[0]})
+    return out
+
+
 def product_split(B, T, dev, iters):
     """One base-size layer's twelve Linear products alone, random data: (name, M, N, K, fp32 ms, bf16 ms).  The fp32 launch is the GEMM
     layer's stand-alone one with its own split choice (in the layer the backward's pairs share a group launch)."""
@@ -169,27 +195,37 @@ def main():
     ap.add_argument("--lengths", choices=("full", "ragged"), help="the HIP encoder's prefix-mask path against its length path on these token counts")
     ap.add_argument("--shape", help="BxT: this shape only (default: 4x512 and 8x256)")
     ap.add_argument("--matmul", nargs="+", choices=("fp32", "bf16"), help="the HIP encoder with these matmul settings, back to back")
+    ap.add_argument("--attention", nargs="+", choices=("fp32", "bf16"), help="the HIP encoder with these attention settings (times --matmul)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.backends.cuda.matmul.allow_tf32 = False
     rows = []
     shapes = ((4, 512), (8, 256)) if not a.shape else (tuple(int(v) for v in a.shape.lower().split("x")),)
-    if a.matmul:
+    if a.matmul or a.attention:
+        combos = [(mm, at) for mm in (a.matmul or ["fp32"]) for at in (a.attention or ["fp32"])]
         for B, T in shapes:
             tv = draw_lengths(a.lengths, B, T) if a.lengths else None
             if tv is not None:
                 print(f"B={B} T={T} lengths={a.lengths} seed={LENGTH_SEED} t_valid={tv.tolist()} mean={tv.float().mean().item():.1f}", flush=True)
             for layers in sorted({1, a.layers}):
                 r = {"B": B, "T": T, "layers": layers, "lengths": a.lengths, "t_valid": None if tv is None else tv.tolist()}
-                for mm in a.matmul:
-                    step = model_step(layers, "hip", B, T, dev, tv, tv is not None, matmul=mm)
-                    r[f"{mm}_graph_ms"], r[f"{mm}_min_ms"], r[f"{mm}_max_ms"] = timed_stats(graphed(step), a.iters)
+                for mm, at in combos:
+                    step = model_step(layers, "hip", B, T, dev, tv, tv is not None, matmul=mm, attention=at)
+                    key = mm if not a.attention else f"mm_{mm}_attn_{at}"
+                    r[f"{key}_graph_ms"], r[f"{key}_min_ms"], r[f"{key}_max_ms"] = timed_stats(graphed(step), a.iters)
                     del step
                     torch.cuda.empty_cache()
                 rows.append(r)
                 print(f"B={B} T={T} layers={layers:2d} lengths={a.lengths}: " + "  ".join(f"{k}={v:.3f}" for k, v in r.items() if k.endswith("_ms")),
                       flush=True)
-            if not a.lengths:
+            if a.attention and not a.lengths:
+                cs = core_split(B, T, dev, a.iters, a.attention)
+                rows.append({"B": B, "T": T, "core": cs})
+                for q in cs:
+                    print(f"B={B} T={T} attention core alone, attention={q['attention']}: fwd {q['fwd_ms']:.4f} ms ({q['fwd_min_ms']:.4f}-"
+                          f"{q['fwd_max_ms']:.4f}) {q['fwd_tflops']:5.1f} TF/s   bwd {q['bwd_ms']:.4f} ms ({q['bwd_min_ms']:.4f}-{q['bwd_max_ms']:.4f}) "
+                          f"{q['bwd_tflops']:5.1f} TF/s", flush=True)
+            if a.matmul and not a.lengths:
                 split = product_split(B, T, dev, a.iters)
                 rows.append({"B": B, "T": T, "products": split})
                 for q in split:
