@@ -1,17 +1,20 @@
 """ctypes binding of libgcgcn_hip.so (the C ABI declared in include/gcgcn.h).
 
-There is no CPU or eager-PyTorch fallback: if the shared library is missing this module
-raises, and every op raises when handed a non-GPU tensor.
+The header is the single source of the binding: SIGNATURES is parsed from it at import, so a new entry point is bound by declaring it
+there.  There is no CPU or eager-PyTorch fallback: if the shared library is missing this module raises, and every op raises when
+handed a non-GPU tensor.
 """
 from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_uint64, c_void_p
+import re
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GCGCN_LIB=<path> loads another build of the same ABI (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("GCGCN_LIB") or os.path.join(_HERE, "lib", "libgcgcn_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcgcn.h")
 
 ABI_VERSION = 7
 
@@ -24,10 +27,8 @@ SALT_BERT_AO = 0x42414F31
 SALT_BERT_OUT = 0x424F5531
 SALT_BERT_EMB = 0x42454D31
 
-P = c_void_p  # every device pointer crosses the ABI as void*
-I = c_int
-F = c_float
-L = c_int64
+P, I, F, L = c_void_p, c_int, c_float, c_int64  # short names for tests and tools; every device pointer crosses the ABI as void*
+
 
 class MhaHook(ctypes.Structure):
     """gcgcn_mha_hook: MultiHeadAttention's work riding inside the MultiGraphConvolution calls of the same hop (include/gcgcn.h)."""
@@ -41,113 +42,66 @@ class EdgeRide(ctypes.Structure):
                 ("inp", c_void_p), ("n_valid", c_void_p), ("out", c_void_p)]
 
 
-# name -> (restype, argtypes); kept in the order of include/gcgcn.h
-SIGNATURES = {
-    "gcgcn_version": (I, []),
-    "gcgcn_last_error": (c_char_p, []),
-    "gcgcn_set_option": (I, [c_char_p, I]),
-    "gcgcn_debug_spread": (I, [L, L, L, L, P, P]),
-    "gcgcn_debug_chain_plan": (I, [I] * 11 + [P]),
-    "gcgcn_debug_head_plan": (I, [I, I, I, I, P]),
-    "gcgcn_debug_gemm_plan": (I, [I, P, P, I, L, L, P]),
-    "gcgcn_debug_edge_plan": (I, [I] * 13 + [P]),
-    "gcgcn_debug_attn_plan": (I, [I] * 8 + [P]),
-    "gcgcn_debug_out_bwd_plan": (I, [I] * 12 + [P]),
-    "gcgcn_prof_start": (I, [c_char_p, I]),
-    "gcgcn_prof_enable": (I, [I]),
-    "gcgcn_prof_stop": (I, [P, P, P]),
-    "gcgcn_rng_next": (I, [P, P, I, P]),
-    "gcgcn_dropout_keep": (I, [P, L, P, c_uint64, F, P]),
-    "gcgcn_dropout": (I, [P, P, L, P, c_uint64, F, P]),
-    "gcgcn_gat_layout": (I, [I, I, P]),
-    "gcgcn_gat_fwd": (I, [I, I, I, I, P, P, P, P, P, F, P, P, P, P, P, P, P, I, P, I, P]),
-    "gcgcn_gat_bwd_scratch": (L, [I, I, I]),
-    "gcgcn_gat_bwd": (I, [I, I, I, I, P, P, P, P, P, F, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "gcgcn_edge_mean_fwd": (I, [I, I, I, P, P, P, P]),
-    "gcgcn_edge_mean_bwd": (I, [I, I, I, P, P, P, P]),
-    "gcgcn_mha_layout": (I, [I, P]),
-    "gcgcn_mha_scratch": (L, [I, I, I]),
-    "gcgcn_row_blocks_ints": (L, [I, I]),
-    "gcgcn_row_blocks": (I, [I, I, P, P, P]),
-    "gcgcn_mha_fwd": (I, [I, I, I, I, P, P, P, P, F, P, P, P, P, P, P]),
-    "gcgcn_mha_bwd": (I, [I, I, I, I, P, P, P, F, P, P, P, P, P, P, P, P, P, P, I, P, P]),
-    "gcgcn_maggc_fusable": (I, [I, I, I]),
-    "gcgcn_gcn_layout": (I, [I, I, I, P]),
-    "gcgcn_gcn_scratch": (L, [I, I, I, I]),
-    "gcgcn_gcn_fwd": (I, [I, I, I, I, I, P, P, P, P, P, P, F, P, F, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "gcgcn_gcn_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, F, P, F, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "gcgcn_defer_create": (P, []),
-    "gcgcn_defer_destroy": (None, [P]),
-    "gcgcn_defer_count": (I, [P]),
-    "gcgcn_defer_flush": (I, [P, P]),
-    "gcgcn_graphconv_fwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P]),
-    "gcgcn_graphconv_bwd": (I, [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "gcgcn_pair_bce_fwd": (I, [I, I, I, P, P, P, P, P, P]),
-    "gcgcn_pair_bce_bwd": (I, [I, I, I, P, P, P, P, P, P]),
-    "gcgcn_pair_stats": (I, [I, I, I, P, P, P, P, P]),
-    "gcgcn_eval_ws_bytes": (L, [L, L]),
-    "gcgcn_eval_scan": (I, [I, I, I, P, P, P, P, P, P, L, P, P]),
-    "gcgcn_eval_rank": (I, [P, L, P, L, P, P]),
-    "gcgcn_eval_curve": (I, [P, L, L, P, ctypes.c_double, P, P, P, P, P, L, P]),
-    "gcgcn_producer_layout": (I, [I, I, P]),
-    "gcgcn_producer_count": (I, [I, I, I, I, P, P, P, P]),
-    "gcgcn_producer_sizes": (I, [I, I, I, I, I, I, I, L, L, P]),
-    "gcgcn_producer_fwd": (I, [I, I, I, I, I, I, I, P, P, P, P, I, P, P, P, P, L, L, P, P, P, L, P, P]),
-    "gcgcn_producer_bwd": (I, [I, I, I, I, I, I, I, P, P, P, P, I, P, P, P, P, L, L, P, P, P, P, P, P, P, P, P, P]),
-    "gcgcn_producer_det_elems": (I, [I, I, I, L, P]),
-    "gcgcn_producer_bwd_det": (I, [I, I, I, I, I, I, I, P, P, P, P, I, P, P, P, P, L, L, P, P, P, P, P, P, P, P, P, P, L, P]),
-    "gcgcn_edge_mean_fwd_compact": (I, [I, I, I, P, P, P, P, P, P]),
-    "gcgcn_edge_mean_bwd_compact": (I, [I, I, I, P, P, P, P, P, P, P]),
-    "gcgcn_gat_fwd_compact": (I, [I, I, I, I, P, P, P, P, P, P, P, F, P, P, P, P, P, P, P, I, I, P]),
-    "gcgcn_gat_bwd_compact_scratch": (L, [I, I, I]),
-    "gcgcn_gat_bwd_compact": (I, [I, I, I, I, P, P, P, P, P, P, P, F, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "gcgcn_head_layout": (I, [I, I, I, I, I, P]),
-    "gcgcn_head_sizes": (I, [I, I, I, I, P]),
-    "gcgcn_head_fwd": (I, [I, I, I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P]),
-    "gcgcn_head_bwd": (I, [I, I, I, I, I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "gcgcn_tensorise": (I, [I, I, I, I, I, I, I, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "gcgcn_adam_step": (I, [I, P, L, ctypes.c_double, ctypes.c_double, ctypes.c_double, P]),
-    "gcgcn_adam_ws_bytes": (L, [I, L]),
-    "gcgcn_adam_step_dev": (I, [I, P, L, ctypes.c_double, ctypes.c_double, ctypes.c_double, P, ctypes.c_double, P, L, P, P]),
-    "gcgcn_gemm": (I, [I, I, I, P, L, I, P, L, I, P, L, I, L, L, L, F, P, I, I, I, I, P, L, P]),
-    "gcgcn_gemm_dyn": (I, [I, I, I, P, L, I, P, L, I, P, L, P, I, P, I, L, P, L, P]),
-    "gcgcn_lstm_ws_bytes": (L, [I] * 5),
-    "gcgcn_lstm_fwd": (I, [I] * 5 + [P] * 10),
-    "gcgcn_lstm_bwd": (I, [I] * 5 + [P] * 17 + [L, P]),
-    "gcgcn_lstm_fwd_len": (I, [I] * 5 + [P] * 11),
-    "gcgcn_lstm_bwd_len": (I, [I] * 5 + [P] * 17 + [L, P, P]),
-    "gcgcn_frontend_ws_bytes": (L, [I] * 9),
-    "gcgcn_embed_fwd": (I, [I] * 8 + [P] * 9),
-    "gcgcn_embed_bwd": (I, [I] * 8 + [P] * 5 + [I, I] + [P] * 4 + [L, P]),
-    "gcgcn_context_fwd": (I, [I] * 5 + [P] * 8),
-    "gcgcn_context_bwd": (I, [I] * 5 + [P] * 11 + [L, P]),
-    "gcgcn_bert_attn_fwd": (I, [I] * 4 + [P] * 5 + [c_uint64, F, P]),
-    "gcgcn_bert_attn_bwd": (I, [I] * 4 + [P] * 8 + [c_uint64, F, P]),
-    "gcgcn_res_ln_ws_bytes": (L, [I]),
-    "gcgcn_res_ln_fwd": (I, [L, I] + [P] * 9 + [c_uint64, F, P]),
-    "gcgcn_res_ln_bwd": (I, [L, I] + [P] * 12 + [L, P, c_uint64, F, P]),
-    "gcgcn_bias_gelu_fwd": (I, [L, I, P, P, P, P]),
-    "gcgcn_bias_gelu_bwd": (I, [L, I, P, P, P, P, P]),
-    "gcgcn_bert_layer_ws_bytes": (L, [I] * 6),
-    "gcgcn_bert_layer_fwd": (I, [I] * 5 + [P] * 5 + [L, P, F, F, P]),
-    "gcgcn_bert_layer_bwd": (I, [I] * 5 + [P] * 4 + [L, P, P, P, P, L, P, F, F, P]),
-    "gcgcn_bert_attn_fwd_len": (I, [I] * 4 + [P] * 6 + [c_uint64, F, P]),
-    "gcgcn_bert_attn_bwd_len": (I, [I] * 4 + [P] * 9 + [c_uint64, F, P]),
-    "gcgcn_res_ln_fwd_len": (I, [L, I] + [P] * 6 + [I] + [P] * 4 + [c_uint64, F, P]),
-    "gcgcn_res_ln_bwd_len": (I, [L, I] + [P] * 8 + [I] + [P] * 5 + [L, P, c_uint64, F, P]),
-    "gcgcn_bias_gelu_fwd_len": (I, [L, I, P, P, P, I, P, P]),
-    "gcgcn_bias_gelu_bwd_len": (I, [L, I, P, P, P, P, I, P, P]),
-    "gcgcn_bert_layer_fwd_len": (I, [I] * 5 + [P] * 7 + [L, P, F, F, P]),
-    "gcgcn_bert_layer_bwd_len": (I, [I] * 5 + [P] * 6 + [L, P, P, P, P, L, P, F, F, P]),
-    "gcgcn_gemm_bf16_ws_bytes": (L, [I, I, I]),
-    "gcgcn_gemm_bf16": (I, [I, I, P, L, P, L, P, L, I, I, I, P, P, L, P, L, P]),
-    "gcgcn_bert_layer_fwd_mm": (I, [I] * 5 + [P] * 7 + [L, P, F, F, P, I]),
-    "gcgcn_bert_layer_bwd_mm": (I, [I] * 5 + [P] * 6 + [L, P, P, P, P, L, P, F, F, P, I]),
-    "gcgcn_bert_attn_fwd_mx": (I, [I] * 4 + [P] * 6 + [c_uint64, F, P, I]),
-    "gcgcn_bert_attn_bwd_mx": (I, [I] * 4 + [P] * 9 + [c_uint64, F, P, I]),
-    "gcgcn_bert_layer_fwd_mx": (I, [I] * 5 + [P] * 7 + [L, P, F, F, P, I, I]),
-    "gcgcn_bert_layer_bwd_mx": (I, [I] * 5 + [P] * 6 + [L, P, P, P, P, L, P, F, F, P, I, I]),
-}
+# ---- the header's declarations as ctypes ---------------------------------------------------------------------------------------
+_SCALARS = {"int": c_int, "int32_t": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "float": c_float, "double": c_double}
+_DECL = re.compile(r"([\w\s*]+?)\b(gcgcn_\w+)\s*\(([^()]*)\)")                     # <ret> gcgcn_<name>(<args>)
+_STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;")
+
+
+def _ctype(text: str, symbol: str, named: bool = True):
+    """One parameter or field ("const float* x", "int B"), or with named=False one return type ("int64_t", "void"), as ctypes.
+    const char* is c_char_p, every other pointer c_void_p, a scalar what _SCALARS says; anything else raises."""
+    toks = text.replace("*", " * ").split()
+    if "*" in toks:
+        return c_char_p if toks[:3] == ["const", "char", "*"] and toks.count("*") == 1 else c_void_p
+    toks = [t for t in toks if t != "const"]
+    if toks == ["void"] and not named:
+        return None
+    if toks and toks[0] in _SCALARS and len(toks) <= 1 + named:
+        return _SCALARS[toks[0]]
+    bad = toks[0] if toks and toks[0] not in _SCALARS else " ".join(toks[1:]) or "an empty declaration"
+    raise RuntimeError(f"gcgcn_amd: cannot bind {symbol}: no ctypes type for {bad!r} in {text.strip()!r} (include/gcgcn.h)")
+
+
+def _parse_header(text: str):
+    """The text of gcgcn.h -> (name -> (restype, argtypes), struct -> [(field, type)]), both in the header's order.  Comments,
+    preprocessor lines and the extern "C" braces are dropped; every statement left must be a typedef struct or a gcgcn_* declaration."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    structs = {}
+    for name, body in _STRUCT.findall(text):
+        structs[name] = []
+        for decl in filter(str.strip, body.split(";")):
+            first, *more = decl.split(",")                                          # "int32_t B, N, D": one type, several names
+            ctype = _ctype(first, name)
+            if more and "*" in first:
+                raise RuntimeError(f"gcgcn_amd: cannot bind {name}: several names behind a pointer in {decl.strip()!r} (include/gcgcn.h)")
+            structs[name] += [(n.replace("*", " ").split()[-1], ctype) for n in (first, *more)]
+    sigs = {}
+    for stmt in filter(str.strip, re.sub(r'extern\s+"C"\s*\{|\}', " ", _STRUCT.sub(" ", text)).split(";")):
+        m = _DECL.fullmatch(stmt.strip())
+        if not m or m.group(2) in sigs:
+            raise RuntimeError(f"gcgcn_amd: cannot bind {m.group(2) if m else 'include/gcgcn.h'}: "
+                               f"{'declared twice' if m else 'not a declaration'}: {' '.join(stmt.split())[:100]!r}")
+        ret, name, args = m.groups()
+        sigs[name] = (_ctype(ret, name, named=False), [] if args.strip() == "void" else [_ctype(a, name) for a in args.split(",")])
+    return sigs, structs
+
+
+def _load_header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f"gcgcn_amd: {HEADER_PATH} not found. The binding is derived from the C header of the source tree; "
+                           "there is no recorded copy to fall back to.")
+    with open(HEADER_PATH) as f:
+        sigs, structs = _parse_header(f.read())
+    for cls, name in ((MhaHook, "gcgcn_mha_hook"), (EdgeRide, "gcgcn_edge_ride")):
+        declared = [("inp" if n == "in" else n, t) for n, t in structs.get(name, [])]  # `in` is a Python keyword
+        if cls._fields_ != declared:
+            raise RuntimeError(f"gcgcn_amd: {cls.__name__}._fields_ {cls._fields_} differ from {name} in include/gcgcn.h: {declared}")
+    return sigs
+
+
+SIGNATURES = _load_header()  # name -> (restype, argtypes), in the order of include/gcgcn.h
 
 _lib = None
 

@@ -37,6 +37,18 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _bytes_or_raise(name: str, *dims) -> int:
+    """What a ``*_ws_bytes`` symbol answers for these dimensions; a refusal (negative) raises with the library's message."""
+    need = getattr(_lib.lib(), name)(*dims)
+    if need < 0:
+        raise RuntimeError(f"{name} failed: {_lib.lib().gcgcn_last_error().decode()}")
+    return need
+
+
+def _f32_buf(nbytes: int, dev) -> Tensor:
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+
+
 def _chk(t: Tensor, name: str, ndim: Optional[int] = None) -> Tensor:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name}: expected a tensor, got {type(t).__name__}")
@@ -1204,13 +1216,6 @@ def pair_bce_loss(logits, labels, n_valid=None, stats=None):
 
 
 # ---- the token encoder's LSTM layer (csrc/lstm.hip) ----------------------------------------------------------------------------
-def _lstm_ws(B: int, T: int, I: int, H: int, nd: int, dev) -> Tensor:
-    need = _lib.lib().gcgcn_lstm_ws_bytes(B, T, I, H, nd)
-    if need < 0:
-        raise RuntimeError(f"gcgcn_lstm_ws_bytes failed: {_lib.lib().gcgcn_last_error().decode()}")
-    return torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
-
-
 class LstmFn(torch.autograd.Function):
     """(x[B,T,I], w_ih[nd*4H,I], w_hh[nd*4H,H], bias[nd*4H], h0[nd,B,H], c0[nd,B,H]) -> out[B,T,nd*H]: one ``nn.LSTM`` layer over
     all T steps with the directions' parameters stacked and ``bias = b_ih + b_hh`` (``lstm_layer`` stacks and splits them).
@@ -1247,7 +1252,7 @@ class LstmFn(torch.autograd.Function):
         dx, dw_ih, dw_hh = torch.empty_like(x), torch.empty_like(w_ih), torch.empty_like(w_hh)
         db = torch.empty(nd * 4 * H, device=x.device)
         dh0, dc0 = torch.empty_like(h0), torch.empty_like(c0)
-        ws = _lstm_ws(B, T, I, H, nd, x.device)
+        ws = _f32_buf(_bytes_or_raise("gcgcn_lstm_ws_bytes", B, T, I, H, nd), x.device)
         call("gcgcn_lstm_bwd_len", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(h0), _p(c0), _p(out), _p(gates), _p(csave), _p(dout),
              _p(dgates), _p(dx), _p(dw_ih), _p(dw_hh), _p(db), _p(dh0), _p(dc0), _p(ws), ws.numel() * 4, _p(lens), _stream())
         torch.autograd.graph.increment_version((dx, dw_ih, dw_hh, db, dh0, dc0))
@@ -1309,13 +1314,6 @@ def lstm_layer(x, w_ih, w_hh, b_ih, b_hh, h0, c0, w_ih_r=None, w_hh_r=None, b_ih
 
 
 # ---- the token front end either side of the BiLSTM (csrc/frontend.hip) -----------------------------------------------------------
-def _frontend_ws(dev, B, T, V=0, P=0, R=0, Dw=0, Dc=0, Dn=0, K=0) -> Tensor:
-    need = _lib.lib().gcgcn_frontend_ws_bytes(B, T, V, P, R, Dw, Dc, Dn, K)
-    if need < 0:
-        raise RuntimeError(f"gcgcn_frontend_ws_bytes failed: {_lib.lib().gcgcn_last_error().decode()}")
-    return torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
-
-
 class TokenEmbedFn(torch.autograd.Function):
     """(word_w[V,Dw], coref_w[P,Dc], ner_w[R,Dn], document, document_pos, document_ner int64 [B,T], scale[B,I] or None) ->
     x[B,T,I]: the three gathers side by side, times the locked-dropout factor."""
@@ -1341,7 +1339,7 @@ class TokenEmbedFn(torch.autograd.Function):
         dx = dx.contiguous()
         dev = dx.device
         dword, dcoref, dner = torch.empty(V, Dw, device=dev), torch.empty(P, Dc, device=dev), torch.empty(R, Dn, device=dev)
-        ws = _frontend_ws(dev, B, T, V, P, R, Dw, Dc, Dn)
+        ws = _f32_buf(_bytes_or_raise("gcgcn_frontend_ws_bytes", *ctx.dims, 0), dev)                      # K = 0: the embeddings alone
         call("gcgcn_embed_bwd", *ctx.dims, _p(document), _p(document_pos), _p(document_ner), _p(dx), _p(scale), ctx.pads[0], ctx.pads[1],
              _p(dword), _p(dcoref), _p(dner), _p(ws), ws.numel() * 4, _stream())
         torch.autograd.graph.increment_version((dword, dcoref, dner))
@@ -1395,7 +1393,7 @@ class TokenContextFn(torch.autograd.Function):
         dctx, dnode = dctx.contiguous(), dnode.contiguous()
         dpre, dh, dw = torch.empty_like(out), torch.empty_like(h), torch.empty_like(weight)
         db = torch.empty(Hd, device=h.device)
-        ws = _frontend_ws(h.device, B, T, K=K)
+        ws = _f32_buf(_bytes_or_raise("gcgcn_frontend_ws_bytes", B, T, 0, 0, 0, 0, 0, 0, K), h.device)    # no tables: the context alone
         call("gcgcn_context_bwd", B, T, N, K, Hd, _p(h), _p(weight), _p(node_pos), _p(out), _p(dctx), _p(dnode), _p(dpre), _p(dh), _p(dw),
              _p(db), _p(ws), ws.numel() * 4, _stream())
         torch.autograd.graph.increment_version((dh, dw, db))
@@ -1417,17 +1415,6 @@ def token_context(h, weight, bias, node_pos):
 
 
 # ---- the BERT encoder layer (csrc/bert.hip) --------------------------------------------------------------------------------------
-def _bytes_or_raise(name: str, *dims) -> int:
-    need = getattr(_lib.lib(), name)(*dims)
-    if need < 0:
-        raise RuntimeError(f"{name} failed: {_lib.lib().gcgcn_last_error().decode()}")
-    return need
-
-
-def _f32_buf(nbytes: int, dev) -> Tensor:
-    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
-
-
 class ResLayerNormFn(torch.autograd.Function):
     """y = LayerNorm(dropout(x + bias) + res) over the last axis (eps = 1e-12, biased variance); bias, res, dropout optional."""
 

@@ -1,14 +1,11 @@
 """matmul="bf16" without a GPU: the plain-PyTorch definition against a hand-written restatement, the selector's defaults and refusals,
 the new symbols, and the two facts about chosen seeds and constants that the GPU tests rely on."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
 from gcgcn_amd import _lib, functional as Fn, models as M
 from gcgcn_amd import bert as bert_mod
 from gcgcn_amd.bert import BertModel
@@ -161,13 +158,8 @@ def test_model_config_selector():
 
 
 def test_new_symbols_are_declared_bound_and_exported():
-    hdr = open(os.path.join(ROOT, "include", "gcgcn.h")).read()
+    """The four symbols against the header and the library: tests/test_abi_cpu.py.  Here: how their lists relate, and the sizes."""
     h = _lib.lib()
-    for name in ("gcgcn_gemm_bf16", "gcgcn_gemm_bf16_ws_bytes", "gcgcn_bert_layer_fwd_mm", "gcgcn_bert_layer_bwd_mm"):
-        decl = re.search(r"\b%s\(([^;]*)\);" % name, hdr)
-        assert decl, f"{name} is not declared in include/gcgcn.h"
-        assert name in _lib.SIGNATURES and hasattr(h, name), name
-        assert len(_lib.SIGNATURES[name][1]) == decl.group(1).count(",") + 1, f"{name}: argument count differs from the header's"
     for name in ("gcgcn_bert_layer_fwd", "gcgcn_bert_layer_bwd"):          # the _len argument list plus the selector
         assert _lib.SIGNATURES[name + "_mm"][1] == _lib.SIGNATURES[name + "_len"][1] + [_lib.I]
     assert h.gcgcn_version() == 7

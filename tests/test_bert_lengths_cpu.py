@@ -5,9 +5,6 @@ Reference: the float64 ``impl="torch"`` model on each document ALONE, truncated 
 gradients summed over the documents.  Both sides are float64 on the CPU and differ only in the order of a few sums (a softmax over T
 keys of which T - lengths[b] are exactly 0, against one over lengths[b] keys), so the bound is round-off: 1e-12 relative and
 absolute on values of order 1 to 10."""
-import os
-import re
-
 import pytest
 import torch
 
@@ -18,9 +15,6 @@ from gcgcn_amd.bert import BertModel
 from bert_cases import config, model_case
 from bert_length_cases import fresh_model, model_len_reference, pad_mask, run_with_lengths
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ["gcgcn_bert_attn_fwd_len", "gcgcn_bert_attn_bwd_len", "gcgcn_res_ln_fwd_len", "gcgcn_res_ln_bwd_len", "gcgcn_bias_gelu_fwd_len",
-       "gcgcn_bias_gelu_bwd_len", "gcgcn_bert_layer_fwd_len", "gcgcn_bert_layer_bwd_len"]
 
 def _model(D, H, dtype=torch.float64):
     return fresh_model(D, H, dtype=dtype).eval()
@@ -99,11 +93,9 @@ def test_hip_impl_still_refuses_cpu_tensors():
 
 
 def test_symbols_declared_bound_exported():
-    header = open(os.path.join(ROOT, "include", "gcgcn.h")).read()
-    h = _lib.lib()                      # loading checks every SIGNATURES entry against the library and the ABI version
-    for name in NEW:
-        assert re.search(r"\b%s\(" % name, header), name
-        assert name in _lib.SIGNATURES and hasattr(h, name), name
+    """The eight _len symbols against the header and the library: tests/test_abi_cpu.py.  Here: the ABI version and the Python
+    signatures that carry the lengths."""
+    h = _lib.lib()                      # loading binds every declaration of the header and checks the ABI version
     assert _lib.ABI_VERSION == 7 and h.gcgcn_version() == 7
     import inspect
     assert "lengths" in inspect.signature(BertModel.forward).parameters

@@ -1,10 +1,7 @@
-"""The HIP LSTM layer (csrc/lstm.hip, functional.lstm_layer, EncoderLSTM(impl="hip")): what holds without a GPU.  The ABI's three
-symbols are declared and bound; the default encoder is the one it was; CPU tensors are refused; and the bound of
+"""The HIP LSTM layer (csrc/lstm.hip, functional.lstm_layer, EncoderLSTM(impl="hip")): what holds without a GPU.  (The ABI's three
+symbols against the header: tests/test_abi_cpu.py.)  The default encoder is the one it was; CPU tensors are refused; and the bound of
 tests/test_lstm_gpu.py is one that float32 arithmetic can meet: torch's own float32 CPU LSTM meets it against float64 at every
 shape of the GPU sweep."""
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
@@ -13,20 +10,6 @@ from torch import nn
 import gcgcn_amd
 from gcgcn_amd import _lib, models as M
 from lstm_cases import H, SWEEP, TABLE, case, reference, run_torch, worst
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = ("gcgcn_lstm_ws_bytes", "gcgcn_lstm_fwd", "gcgcn_lstm_bwd")
-
-
-def test_symbols_are_declared_and_bound():
-    header = open(os.path.join(ROOT, "include", "gcgcn.h")).read()
-    for name in SYMBOLS:
-        decl = re.search(r"^(?:int|int64_t)\s+" + name + r"\s*\(([^;]*)\)\s*;", header, re.M)
-        assert decl, f"{name} is not declared in gcgcn.h"
-        assert name in _lib.SIGNATURES, f"{name} is not bound in _lib.SIGNATURES"
-        assert len(_lib.SIGNATURES[name][1]) == decl.group(1).count(",") + 1, f"{name}: argument count differs from the header's"
-    assert _lib.ABI_VERSION == 7                       # additive
-
 
 def test_width_not_served_is_refused_on_the_host():
     h = _lib.lib()
