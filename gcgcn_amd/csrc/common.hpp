@@ -56,6 +56,10 @@ __device__ __forceinline__ float wave_max(float v) {
   return fmaxf(fmaxf(lane_value(v, 0), lane_value(v, 16)), fmaxf(lane_value(v, 32), lane_value(v, 48)));
 }
 
+// v_mfma_f32_32x32x2_f32 operand / result mapping (wave of 64 lanes): A[row = lane & 31][k = lane >> 5],
+// B[k = lane >> 5][col = lane & 31], D[row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)][col = lane & 31].
+__device__ __forceinline__ int mfma_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
+
 // ---- counter-based dropout RNG ------------------------------------------------------------
 // A dropout site is identified by (seed, counter) -- snapshotted on the device at forward time
 // by gcgcn_rng_next, so a hipGraph replay draws fresh masks -- plus a per-site salt.  Element

@@ -112,18 +112,13 @@ __global__ __launch_bounds__(256, 4) void head_gemm_kernel(const GemmArgs g, con
 }
 
 // ---- second generation of the three passes whose A operand is an outer product (MODE 1..3) -------------------------
-// The operand never touches LDS at all: with K ordered (b-chunk of 32, then a), the MFMA A operand of lane (row i, k-half)
-// is P[i, a] * Q[i, b]: the 16 Q values a lane needs for a whole b-chunk sit in registers (reloaded 4 times per tile),
-// P[i, a] is one prefetched dword per k-step, and the operand is ONE v_mul per MFMA pair.  Only the weight panel is staged
-// through LDS (k-major image, register double buffering as in gemm_body).  Workgroup tile 64 pairs x 128 columns, four
-// waves of 32 x 64 (two accumulators: each generated A value feeds two MFMAs).
 //   MODE 1: C[p, r]  = sum_(a,b) eh[p,a] et[p,b] W_b[r,a,b] + sum_k [eh | et][p,k] W_c[r,k] + bias    (P = eh, Q = et)
 //   MODE 2: C[p, a]  = sum_(r,b) dout[p,r] et[p,b] W_b[r,a,b]                                         (P = doutp, Q = et)
 //   MODE 3: C[p, b]  = sum_(r,a) dout[p,r] eh[p,a] W_b[r,a,b]                                         (P = doutp, Q = eh)
 struct Bil2 {
   const float* P; const float* Q; const float* W; const float* W2; const float* bias;
   float* C;
-  int rows, nA, ncol, ldc, accumulate_unused;
+  int rows, nA, ncol, ldc;
   // compacted pair rows (ragged batches, head_fwd / head_bwd): the number of rows lives on the device (workgroups past it exit
   // at once), and output row r goes to row crow[r] of C (the pair's slot in the padded [B, N, N, .] tensor); NULL = dense
   const int* rows_dev; const int* crow;
@@ -144,168 +139,45 @@ struct BilPos {
   }
 };
 
-template <int MODE>
-__global__ __launch_bounds__(256, 3) void head_bil2_kernel(const Bil2 a) {
-  constexpr int BN = 128, LDB = (MODE == 3) ? BN : BN + 1, SB = BK * LDB;
-  __shared__ __attribute__((aligned(16))) float lds[2 * SB];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wr = wave >> 1, wc = wave & 1, l31 = lane & 31, lh = lane >> 5;
-  const int m0 = blockIdx.x * 64;
-  const int nrows = a.rows_dev ? *a.rows_dev : a.rows;
-  if (m0 >= nrows || (a.rows_dev && (nrows < a.sel_lo || nrows >= a.sel_hi))) return;
-  const long row = min(m0 + wr * 32 + l31, nrows - 1);   // this lane's A row (clamped: rows past the end are never stored)
-  const float* __restrict__ prow = a.P + row * HW;
-  const float* __restrict__ qrow = a.Q + row * HW;
-  const int per_bc = a.nA + (MODE == 1 ? 1 : 0), nsteps = 4 * per_bc + (MODE == 1 ? 4 : 0);
-  // per-thread offsets of its four 16-byte pieces of a weight tile (32-bit: the weights are < 2^31 floats), the step adds
-  // a uniform offset
-  unsigned offW[4], offW2[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int f = t + 256 * q;
-    if (MODE == 1) {
-      const unsigned nn = (unsigned)min(f >> 3, a.ncol - 1);
-      offW[q] = nn * (HW * HW) + ((f & 7) << 2), offW2[q] = nn * (2 * HW) + ((f & 7) << 2);
-    } else if (MODE == 2) {
-      offW[q] = (unsigned)(f >> 3) * HW + ((f & 7) << 2), offW2[q] = 0;
-    } else {
-      offW[q] = (unsigned)(f >> 5) * HW + ((f & 31) << 2), offW2[q] = 0;
-    }
-  }
-  auto loadB = [&](float (&r)[4][4], const BilPos& p) {   // uniform: which array, which offset
-    const float* base = a.W;
-    unsigned so;
-    bool second = false;
-    if (MODE == 1) {
-      if (p.bc >= 4) second = true, so = (unsigned)min(p.aa, 3) * BK;                 // W_c[r][32 j ..]        (tail, clamped)
-      else if (p.aa == a.nA) second = true, so = HW + p.bc * BK;                      // W_c[r][128 + 32 bc ..]
-      else so = (unsigned)p.aa * HW + p.bc * BK;                                      // W_b[r][a][32 bc ..]
-      if (second) base = a.W2;
-    } else if (MODE == 2) {
-      so = (unsigned)min(p.aa, a.nA - 1) * (HW * HW) + min(p.bc, 3) * BK;             // W_b[r][a = n][32 bc ..]
-    } else {
-      so = ((unsigned)min(p.aa, a.nA - 1) * HW + min(p.bc, 3) * BK) * HW;             // W_b[r][a = 32 bc + k][b = n]
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 v = ld4(base + so + (second ? offW2[q] : offW[q]));
-      r[q][0] = v.x, r[q][1] = v.y, r[q][2] = v.z, r[q][3] = v.w;
-    }
-  };
-  auto storeB = [&](const float (&r)[4][4], float* __restrict__ dst) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int f = t + 256 * q;
-      if (MODE == 3) {
-        *reinterpret_cast<float4*>(dst + (f >> 5) * LDB + ((f & 31) << 2)) = make_float4(r[q][0], r[q][1], r[q][2], r[q][3]);
-      } else {
-        float* d = dst + ((f & 7) << 2) * LDB + (f >> 3);
-        d[0] = r[q][0], d[LDB] = r[q][1], d[2 * LDB] = r[q][2], d[3 * LDB] = r[q][3];
-      }
-    }
-  };
-  f32x16 acc0, acc1;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc0[r] = 0.f, acc1[r] = 0.f;
-  float qv[16];
-  auto loadQ = [&](int bc) {   // the lane's 16 Q values of this b-chunk: Q[row, 32 bc + 2 kk + lh]
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float4 v = ld4(qrow + bc * BK + 4 * j);
-      qv[2 * j] = lh ? v.y : v.x, qv[2 * j + 1] = lh ? v.w : v.z;
-    }
-  };
-  auto pval = [&](const BilPos& p) -> float {  // the step's P factor, requested one step ahead
-    if (p.bc >= 4) return 0.f;
-    return (MODE == 1 && p.aa == a.nA) ? 1.f : prow[min(p.aa, a.nA - 1)];
-  };
-  const float* bl0 = lds + lh * LDB + wc * 64 + l31;
-  auto compute = [&](const float* __restrict__ bl, const BilPos& p, float pa) {
-    if (MODE == 1 && p.bc >= 4) {   // Linear, eh half: A = P[row, 32 j + k]
-      const float* ph = prow + min(p.aa, 3) * BK;
-#pragma unroll
-      for (int kk = 0; kk < 16; ++kk) {
-        const float av = ph[2 * kk + lh];
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bl[2 * kk * LDB], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bl[2 * kk * LDB + 32], acc1, 0, 0, 0);
-      }
-      return;
-    }
-#pragma unroll
-    for (int kk = 0; kk < 16; ++kk) {
-      const float av = pa * qv[kk];
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bl[2 * kk * LDB], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bl[2 * kk * LDB + 32], acc1, 0, 0, 0);
-    }
-  };
-  float rb0[4][4], rb1[4][4];
-  BilPos pc = {0, 0}, pl = {0, 0};   // compute position, load position (two steps ahead)
-  loadB(rb0, pl);
-  storeB(rb0, lds);
-  pl.next(per_bc);
-  loadB(rb0, pl);
-  pl.next(per_bc);
-  BilPos pp = pc;
-  float pa = pval(pp);
-  pp.next(per_bc);
-  float pn = pval(pp);
-  loadQ(0);
-  __syncthreads();
-  for (int s = 0; s < nsteps; s += 2) {
-    loadB(rb1, pl);
-    pl.next(per_bc);
-    if (pc.aa == 0 && pc.bc > 0 && pc.bc < 4) loadQ(pc.bc);
-    compute(bl0, pc, pa);
-    pc.next(per_bc), pp.next(per_bc);
-    pa = pn, pn = pval(pp);
-    storeB(rb0, lds + SB);
-    __syncthreads();
-    if (s + 1 >= nsteps) break;
-    loadB(rb0, pl);
-    pl.next(per_bc);
-    if (pc.aa == 0 && pc.bc > 0 && pc.bc < 4) loadQ(pc.bc);
-    compute(bl0 + SB, pc, pa);
-    pc.next(per_bc), pp.next(per_bc);
-    pa = pn, pn = pval(pp);
-    storeB(rb1, lds);
-    __syncthreads();
-  }
-  // epilogue: lane holds column wc*64 + {0, 32} + l31 of rows m0 + wr*32 + (r & 3) + 8 (r >> 2) + 4 lh
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int col = wc * 64 + j * 32 + l31;
-    if (col >= a.ncol) continue;
-    const float bias = a.bias ? a.bias[col] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const long rw = m0 + wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      if (rw < nrows) a.C[(a.crow ? (long)a.crow[rw] : rw) * a.ldc + col] = (j ? acc1[r] : acc0[r]) + bias;
-    }
-  }
-}
+// The weight image in LDS: two stages of a 32-deep k-step by 128 columns, k-major (MODE 3's natural layout needs no padding)
+constexpr int bil_ldb(int mode) { return mode == 3 ? 128 : 129; }
+constexpr int bil_lds_floats(int mode) { return 2 * BK * bil_ldb(mode); }
 
-// MODE 1 with the relation count just past a multiple of 32 (R = 97 = 3 x 32 + 1): workgroup tile 128 pairs x 97 columns, a wave
-// owns 32 pairs and ALL columns -- three accumulators for columns 0-95 (each generated A value feeds three MFMAs) and column 96
-// on the vector ALU: the A values are in registers anyway, the column's weights are one broadcast LDS read per k, so the
-// 97th relation costs one v_fma per generated value instead of a fourth 32-column MFMA block (a quarter of the pass).
-// MODE 2 / 3 (128 exact columns): the same 128-pair tile with four accumulators per wave -- each generated value feeds four
-// MFMAs instead of two.
-template <int MODE>
-__global__ __launch_bounds__(256, 2) void head_bil3_kernel(const Bil2 a) {
-  constexpr int NACC = (MODE == 1) ? 3 : 4;
-  constexpr int BN = 128, LDB = (MODE == 3) ? BN : BN + 1, SB = BK * LDB;
-  __shared__ __attribute__((aligned(16))) float lds[2 * SB];
+// One body for both tile sizes, PAIRS = 64 or 128 pair rows per workgroup (head_bil2_kernel / head_bil3_kernel below).
+// The operand never touches LDS at all: with K ordered (b-chunk of 32, then a), the MFMA A operand of lane (row i, k-half)
+// is P[i, a] * Q[i, b]: the 16 Q values a lane needs for a whole b-chunk sit in registers (reloaded 4 times per tile),
+// P[i, a] is one prefetched dword per k-step, and the operand is ONE v_mul per NACC MFMAs.  Only the weight panel is staged
+// through LDS (k-major image, register double buffering as in gemm_body).
+template <int MODE, int PAIRS>
+__device__ __forceinline__ void head_bil_body(const Bil2& a, float* lds) {
+  static_assert(PAIRS == 64 || PAIRS == 128, "64 or 128 pair rows per workgroup");
+  // PAIRS == 64: workgroup tile 64 pairs x 128 columns, four waves of 32 x 64 (two accumulators: each generated A value feeds
+  // two MFMAs).
+  // PAIRS == 128: a wave owns 32 pairs and ALL columns.  MODE 1 with the relation count just past a multiple of 32 (R = 97 =
+  // 3 x 32 + 1): three accumulators for columns 0-95 (each generated A value feeds three MFMAs) and column 96 on the vector ALU:
+  // the A values are in registers anyway, the column's weights are one broadcast LDS read per k, so the 97th relation costs one
+  // v_fma per generated value instead of a fourth 32-column MFMA block (a quarter of the pass).  MODE 2 / 3 (128 exact columns):
+  // four accumulators per wave -- each generated value feeds four MFMAs instead of two.  Only this tile knows the K split
+  // (Bil2::part).
+  constexpr int NACC = PAIRS == 64 ? 2 : MODE == 1 ? 3 : 4;
+  constexpr bool COL96 = PAIRS == 128 && MODE == 1;
+  constexpr bool SPLIT = PAIRS == 128;
+  constexpr int LDB = bil_ldb(MODE), SB = BK * LDB;
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, l31 = lane & 31, lh = lane >> 5;
-  const int m0 = blockIdx.x * 128;
+  const int wr = PAIRS == 64 ? wave >> 1 : wave;         // the wave's 32 rows of the tile
+  const int c0 = PAIRS == 64 ? (wave & 1) * 64 : 0;      // and its first column
+  const int m0 = blockIdx.x * PAIRS, row0 = m0 + wr * 32;   // the workgroup's and the wave's first row
   const int nrows = a.rows_dev ? *a.rows_dev : a.rows;
   if (m0 >= nrows || (a.rows_dev && (nrows < a.sel_lo || nrows >= a.sel_hi))) return;
-  const long row = min(m0 + wave * 32 + l31, nrows - 1);   // this lane's A row (clamped: rows past the end are never stored)
+  const long row = min(row0 + l31, nrows - 1);   // this lane's A row (clamped: rows past the end are never stored)
   const float* __restrict__ prow = a.P + row * HW;
   const float* __restrict__ qrow = a.Q + row * HW;
   const int per_bc = a.nA + (MODE == 1 ? 1 : 0);
   // the k sequence: four b-chunks of per_bc steps, then (MODE 1) four tail steps.  Unsplit: all of it; split (a.part): chunk
   // blockIdx.y, the last one with the tail
-  const int ysp = a.part ? (int)blockIdx.y : 0;
-  const int nsteps = a.part ? per_bc + ((MODE == 1 && ysp == 3) ? 4 : 0) : 4 * per_bc + (MODE == 1 ? 4 : 0);
+  const bool split = SPLIT && a.part;
+  const int ysp = split ? (int)blockIdx.y : 0;
+  const int nsteps = split ? per_bc + ((MODE == 1 && ysp == 3) ? 4 : 0) : 4 * per_bc + (MODE == 1 ? 4 : 0);
   // per-thread offsets of its four 16-byte pieces of a weight tile (32-bit: the weights are < 2^31 floats), the step adds
   // a uniform offset
   unsigned offW[4], offW2[4];
@@ -353,10 +225,12 @@ __global__ __launch_bounds__(256, 2) void head_bil3_kernel(const Bil2 a) {
       }
     }
   };
-  f32x16 acc0, acc1, acc2, acc3;
+  f32x16 acc[NACC];   // columns c0 + 32 j + l31; indexed by unrolled constants only (registers)
 #pragma unroll
-  for (int r = 0; r < 16; ++r) acc0[r] = 0.f, acc1[r] = 0.f, acc2[r] = 0.f, acc3[r] = 0.f;
-  float a96 = 0.f;   // column 96: this lane's k half of its row's dot product
+  for (int r = 0; r < 16; ++r)
+#pragma unroll
+    for (int j = 0; j < NACC; ++j) acc[j][r] = 0.f;
+  float a96 = 0.f;   // COL96: this lane's k half of its row's dot product with column 96
   float qv[16];
   auto loadQ = [&](int bc) {   // the lane's 16 Q values of this b-chunk: Q[row, 32 bc + 2 kk + lh]
 #pragma unroll
@@ -369,28 +243,27 @@ __global__ __launch_bounds__(256, 2) void head_bil3_kernel(const Bil2 a) {
     if (p.bc >= 4) return 0.f;
     return (MODE == 1 && p.aa == a.nA) ? 1.f : prow[min(p.aa, a.nA - 1)];
   };
-  const float* bl0 = lds + lh * LDB + l31;
+  const float* bl0 = lds + lh * LDB + c0 + l31;
+  // (the MFMA sequence stands in both loops: behind a shared lambda the compiler moves the step's last column-96 fmaf past the
+  // join of the two branches, where it waits for its LDS read with no MFMA to cover it)
   auto compute = [&](const float* __restrict__ bl, const BilPos& p, float pa) {
     if (MODE == 1 && p.bc >= 4) {   // Linear, eh half: A = P[row, 32 j + k]
       const float* ph = prow + min(p.aa, 3) * BK;
 #pragma unroll
       for (int kk = 0; kk < 16; ++kk) {
         const float av = ph[2 * kk + lh];
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bl[2 * kk * LDB], acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bl[2 * kk * LDB + 32], acc1, 0, 0, 0);
-        acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bl[2 * kk * LDB + 64], acc2, 0, 0, 0);
-        a96 = fmaf(av, bl[2 * kk * LDB + 96 - l31], a96);   // (MODE 1 only reaches this branch)
+#pragma unroll
+        for (int j = 0; j < NACC; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bl[2 * kk * LDB + 32 * j], acc[j], 0, 0, 0);
+        if constexpr (COL96) a96 = fmaf(av, bl[2 * kk * LDB + 96 - l31], a96);
       }
       return;
     }
 #pragma unroll
     for (int kk = 0; kk < 16; ++kk) {
       const float av = pa * qv[kk];
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bl[2 * kk * LDB], acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bl[2 * kk * LDB + 32], acc1, 0, 0, 0);
-      acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bl[2 * kk * LDB + 64], acc2, 0, 0, 0);
-      if (NACC == 4) acc3 = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bl[2 * kk * LDB + 96], acc3, 0, 0, 0);
-      else a96 = fmaf(av, bl[2 * kk * LDB + 96 - l31], a96);
+#pragma unroll
+      for (int j = 0; j < NACC; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bl[2 * kk * LDB + 32 * j], acc[j], 0, 0, 0);
+      if constexpr (COL96) a96 = fmaf(av, bl[2 * kk * LDB + 96 - l31], a96);
     }
   };
   float rb0[4][4], rb1[4][4];
@@ -425,40 +298,51 @@ __global__ __launch_bounds__(256, 2) void head_bil3_kernel(const Bil2 a) {
     storeB(rb1, lds);
     __syncthreads();
   }
-  // epilogue: lane holds columns {0, 32, 64} + l31 of rows m0 + wave*32 + (r & 3) + 8 (r >> 2) + 4 lh, and its k half of column 96
-  a96 += __shfl_xor(a96, 32);
-  if (a.part) {   // K split: raw partial sums of this chunk, [y][row][128]; the combine kernel adds the bias and stores
+  // epilogue: lane holds columns c0 + 32 j + l31 of rows row0 + mfma_row(r, lane), and (COL96) its k half of column 96 of row
+  // row0 + l31
+  if constexpr (COL96) a96 += __shfl_xor(a96, 32);
+  if (split) {   // K split: raw partial sums of this chunk, [y][row][128]; the combine kernel adds the bias and stores
     float* __restrict__ wp = a.part + (long)ysp * a.part_rows * 128;
 #pragma unroll
     for (int j = 0; j < NACC; ++j) {
-      const int col = j * 32 + l31;
+      const int col = c0 + j * 32 + l31;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const long rw = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-        if (rw < nrows) wp[rw * 128 + col] = (j == 0 ? acc0[r] : j == 1 ? acc1[r] : j == 2 ? acc2[r] : acc3[r]);
+        const long rw = row0 + mfma_row(r, lane);
+        if (rw < nrows) wp[rw * 128 + col] = acc[j][r];
       }
     }
-    if (MODE == 1 && lh == 0) {
-      const long rw = m0 + wave * 32 + l31;
-      if (rw < nrows) wp[rw * 128 + 96] = a96;
+    if constexpr (COL96) {
+      const long rw = row0 + l31;
+      if (lh == 0 && rw < nrows) wp[rw * 128 + 96] = a96;
     }
     return;
   }
 #pragma unroll
   for (int j = 0; j < NACC; ++j) {
-    const int col = j * 32 + l31;
+    const int col = c0 + j * 32 + l31;
     if (col >= a.ncol) continue;
     const float bias = a.bias ? a.bias[col] : 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const long rw = m0 + wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-      if (rw < nrows) a.C[(a.crow ? (long)a.crow[rw] : rw) * a.ldc + col] = (j == 0 ? acc0[r] : j == 1 ? acc1[r] : j == 2 ? acc2[r] : acc3[r]) + bias;
+      const long rw = row0 + mfma_row(r, lane);
+      if (rw < nrows) a.C[(a.crow ? (long)a.crow[rw] : rw) * a.ldc + col] = acc[j][r] + bias;
     }
   }
-  if (MODE == 1 && a.ncol > 96 && lh == 0) {
-    const long rw = m0 + wave * 32 + l31;
-    if (rw < nrows) a.C[(a.crow ? (long)a.crow[rw] : rw) * a.ldc + 96] = a96 + (a.bias ? a.bias[96] : 0.f);
+  if constexpr (COL96) {
+    const long rw = row0 + l31;
+    if (a.ncol > 96 && lh == 0 && rw < nrows) a.C[(a.crow ? (long)a.crow[rw] : rw) * a.ldc + 96] = a96 + (a.bias ? a.bias[96] : 0.f);
   }
+}
+template <int MODE>
+__global__ __launch_bounds__(256, 3) void head_bil2_kernel(const Bil2 a) {   // 64 pairs per workgroup, three workgroups per CU
+  __shared__ __attribute__((aligned(16))) float lds[bil_lds_floats(MODE)];
+  head_bil_body<MODE, 64>(a, lds);
+}
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void head_bil3_kernel(const Bil2 a) {   // 128 pairs per workgroup, two per CU
+  __shared__ __attribute__((aligned(16))) float lds[bil_lds_floats(MODE)];
+  head_bil_body<MODE, 128>(a, lds);
 }
 
 // ---- d W_b[r, (a, b)] = sum_p dout[p, r] eh[p, a] et[p, b]  for R just past a multiple of 32 (R = 97) ---------------------
@@ -552,7 +436,7 @@ __global__ __launch_bounds__(256, 3) void head_dw_kernel(const HeadDw a) {
   for (int j = 0; j < 3; ++j)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = 32 * j + (r & 3) + 8 * (r >> 2) + 4 * lh;
+      const int row = 32 * j + mfma_row(r, lane);
       if (row < a.R) o[(long)row * (HW * HW)] = (j == 0 ? acc0[r] : j == 1 ? acc1[r] : acc2[r]);
     }
   if (a.R > 96 && lh == 0) o[96L * (HW * HW)] = a96;
@@ -621,7 +505,7 @@ static HeadPlan head_plan(long pairs, int R, bool ragged) {
 // W2 / bias (mode 1) and, for compacted rows, rows_dev / crow / the slab of the four-way split (part, part_rows).
 static Bil2 bil_pass(int mode, const float* P, const float* Q, const float* W, float* C, long rows, int R) {
   Bil2 a;
-  a.P = P, a.Q = Q, a.W = W, a.W2 = nullptr, a.bias = nullptr, a.C = C, a.rows = (int)rows, a.accumulate_unused = 0;
+  a.P = P, a.Q = Q, a.W = W, a.W2 = nullptr, a.bias = nullptr, a.C = C, a.rows = (int)rows;
   a.nA = mode == 1 ? HW : R, a.ncol = a.ldc = mode == 1 ? R : HW;
   a.rows_dev = nullptr, a.crow = nullptr, a.sel_lo = 0, a.sel_hi = 0x7fffffff, a.part = nullptr, a.part_rows = 0;
   return a;
@@ -644,6 +528,9 @@ static Gen1 gen1_pass(int mode, const Bil2& a) {
   p.o.W2 = a.W2, p.o.ldw2 = mode == 1 ? 2 * HW : 0;
   return p;
 }
+using Gen1Kernel = void (*)(GemmArgs, HeadOps);   // by mode (1..4): which operands are k-contiguous
+static const Gen1Kernel gen1_kernels[4] = {head_gemm_kernel<1, true, true>, head_gemm_kernel<2, true, true>, head_gemm_kernel<3, true, false>,
+                                           head_gemm_kernel<4, false, false>};
 static int head_gemm(int mode, const Gen1& p, hipStream_t st) {
   GemmArgs g = p.g;
   const long tiles = (long)cdiv(g.M, 64) * cdiv(g.N, 64);
@@ -658,12 +545,7 @@ static int head_gemm(int mode, const Gen1& p, hipStream_t st) {
   g.batch1 = g.batch2 = 1;
   const dim3 grid((unsigned)(tiles * splits)), block(256);
   const double flops = 2.0 * g.M * g.N * g.K;
-  switch (mode) {
-    case 1: GC_LAUNCH_TIMED("head_bilinear", flops, (head_gemm_kernel<1, true, true>), grid, block, 0, st, g, p.o); break;
-    case 2: GC_LAUNCH_TIMED("head_bilinear", flops, (head_gemm_kernel<2, true, true>), grid, block, 0, st, g, p.o); break;
-    case 3: GC_LAUNCH_TIMED("head_bilinear", flops, (head_gemm_kernel<3, true, false>), grid, block, 0, st, g, p.o); break;
-    default: GC_LAUNCH_TIMED("head_bilinear", flops, (head_gemm_kernel<4, false, false>), grid, block, 0, st, g, p.o); break;
-  }
+  GC_LAUNCH_TIMED("head_bilinear", flops, gen1_kernels[mode - 1], grid, block, 0, st, g, p.o);
   if (int e = check_launch("head_gemm")) return e;
   return splits > 1 ? splitk_reduce(g, st) : 0;
 }

@@ -43,10 +43,6 @@ __device__ __forceinline__ void load_q_chunk(float* qs, const float* __restrict_
   }
 }
 
-// v_mfma_f32_32x32x2_f32 operand / result mapping (wave of 64 lanes): A[row = lane & 31][k = lane >> 5],
-// B[k = lane >> 5][col = lane & 31], D[row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)][col = lane & 31].
-__device__ __forceinline__ int mfma_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
-
 // P = softmax(alpha Q_h Q_h^T) over the valid columns, A = dropout(P) for one (document, head) pair z (glove:136-140).
 // sm: MT * MS + MT * (kchunk + 1) floats of LDS.  The first 256 threads of the workgroup do the work (`t` their index, `on`
 // false for any further waves, which only keep the barriers company): a launch of its own runs it with 256 threads
