@@ -114,7 +114,8 @@ struct Opt {
 };
 static Opt g_opts[] = {{"head_v1", 0, false},      {"head_bil3", 0, false}, {"head_bil3_bwd", 0, false}, {"head_dw3", 0, false},
                        {"head_compact", 0, false}, {"chain_t", 0, false},   {"chain_big", 0, false},     {"split_widen", 0, false},
-                       {"chain", 0, false},        {"mha_core", 0, false},  {"group_dump", 0, false}};
+                       {"chain", 0, false},        {"mha_core", 0, false},  {"group_dump", 0, false},
+                       {"bf16_rows", 0, false}};   // 0: the BERT layer's bf16 products ignore the row-block list (bert.hip's on_rows reads it)
 int option(const char* name, int dflt) {
   for (Opt& o : g_opts) {
     if (strcmp(o.name, name) != 0) continue;

@@ -635,21 +635,27 @@ GemmArgs on_rows(GemmArgs g, const int* rowblk, int mode, int zero_dead = 0) {
 
 // One Linear of the layer, y [M][N] = x [M][K] w[N][K]^T + b, on the route that matmul names; the chains below are written once.
 // BERT_MM_FP32: the GEMM layer.  BERT_MM_BF16: the same products on the bf16 matrix cores (gemm_bf16.hpp); everything between the
-// products is the same fp32 code, the dropout sites and their indices included.  The bf16 products always run DENSE: a row-block list
-// is accepted and ignored.  The contract of the padding rows holds there by the argument above (x is zero-stored by the caller, every
-// other operand by the length-aware kernel in front of the product) and bf16(0) = 0, so dx = 0 W + 0 exactly.  A dense product also
-// WRITES every row, so nothing the workspaces held before the call survives.  The bf16 route's bias gradients are the exact fp32
-// column sums of the fp32 gradient tensors, launched stand-alone (rowops' colsum through colpart: two launches per bias where the
-// fp32 route has none of its own).
+// products is the same fp32 code, the dropout sites and their indices included.  The bf16 products take the row-block list the way
+// the fp32 ones do -- mode 1 forward and on the data gradients (rb_zero where dx leaves the layer), mode 2 on the weight gradients,
+// which SKIP the 64-deep steps without a live block and otherwise sum in the dense order -- where their launcher serves it
+// (gemm_bf16.hpp has the rule) and run dense elsewhere, and everywhere when option bf16_rows (GCGCN_BF16_ROWS, default 1) is 0.
+// Either way gives the same bits: x is zero-stored by the caller and every other operand by the length-aware kernel in front of the
+// product, bf16(0) = 0, so a dense dx is 0 W + 0 exactly and a skipped step would have added zeros.  The bf16 route's bias gradients
+// are the exact fp32 column sums of the fp32 gradient tensors, launched stand-alone and dense (rowops' colsum through colpart: two
+// launches per bias where the fp32 route has none of its own).
+GemmBf16Args on_rows(GemmBf16Args g, const int* rowblk, int mode, int zero_dead = 0) {
+  if (rowblk && option("bf16_rows", 1) != 0) g.rb = rowblk + ROWBLK_HDR, g.rb_n = rowblk, g.rb_mode = mode, g.rb_zero = zero_dead;
+  return g;
+}
 struct Linear {
   int matmul, M;
-  const int* rb;    // fp32 route: the live row blocks, or nullptr = dense
+  const int* rb;    // the live row blocks, or nullptr = dense
   const Work* wk;   // the backward's split-K and column-sum slices (the forward has none)
   hipStream_t st;
 
   int fwd(float* y, const float* x, const float* w, const float* bias, int N, int K) const {
     if (matmul == BERT_MM_BF16) {
-      GemmBf16Args g = gemm_bf16_stored(1, 1, x, K, w, K, y, N, M, N, K);
+      GemmBf16Args g = on_rows(gemm_bf16_stored(1, 1, x, K, w, K, y, N, M, N, K), rb, 1);
       g.bias = bias;
       return gemm_bf16(g, st);
     }
@@ -661,10 +667,10 @@ struct Linear {
   int bwd(const float* dy, const float* x, const float* w, float* dw, float* dx, const float* add, float* db, int N, int K,
           int zero_dead = 0) const {
     if (matmul == BERT_MM_BF16) {
-      GemmBf16Args gw = gemm_bf16_stored(0, 0, dy, N, x, K, dw, K, N, K, M);
+      GemmBf16Args gw = on_rows(gemm_bf16_stored(0, 0, dy, N, x, K, dw, K, N, K, M), rb, 2);
       gw.ws = wk->split, gw.ws_elems = wk->split_elems;
       GC_TRY(gemm_bf16(gw, st));
-      GemmBf16Args gx = gemm_bf16_stored(1, 0, dy, N, w, K, dx, K, M, K, N);
+      GemmBf16Args gx = on_rows(gemm_bf16_stored(1, 0, dy, N, w, K, dx, K, M, K, N), rb, 1, zero_dead);
       gx.add = add, gx.ldadd = K, gx.ws = wk->split, gx.ws_elems = wk->split_elems;
       GC_TRY(gemm_bf16(gx, st));
       return colsum(dy, nullptr, db, M, N, N, 1, 0, 0, 0, 0, wk->colpart, st);

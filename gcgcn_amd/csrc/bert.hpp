@@ -78,8 +78,9 @@ long bert_layer_ws_elems(int B, int T, int D, int H, int Dff);   // the backward
 // not read.  rowblk: gcgcn_row_blocks(B, T, t_valid) (T a multiple of 16) or nullptr -- the products then run on the live 16-row blocks
 // wherever the GEMM launcher serves the list, dense elsewhere; the results obey the same contract either way.
 // matmul: BERT_MM_FP32 = the fp32-MFMA GEMM layer, launch for launch what it was; BERT_MM_BF16 = the twelve Linear products with bf16
-// operands (gemm_bf16.hpp: fp32 in memory, rounded once on the way into LDS, fp32 accumulation), always dense (rowblk is ignored), the
-// bias gradients as stand-alone fp32 column sums.  The saved state and the workspace are the same either way.
+// operands (gemm_bf16.hpp: fp32 in memory, rounded once on the way into LDS, fp32 accumulation), on the live row blocks of rowblk where
+// that launcher serves the list (bit for bit the dense products; option bf16_rows = 0 runs them dense), the bias gradients as
+// stand-alone fp32 column sums.  The saved state and the workspace are the same either way.
 // attn: the attention core's selector (above), independent of matmul.
 constexpr int BERT_MM_FP32 = 0, BERT_MM_BF16 = 1;
 int bert_layer_fwd(int B, int T, int D, int H, int Dff, const float* x, const float* key_bias, const BertLayerParams& p, float* y,

@@ -1627,8 +1627,9 @@ def bert_layer(x, key_bias, wq, bq, wk, bk, wv, bv, wo, bo, ln1_w, ln1_b, wi, bi
     ``matmul``: ``"fp32"`` (default: exactly the calls made without the argument) or ``"bf16"``: the twelve Linear products of the
     forward and the backward take bf16 operands -- every operand element rounded once, round to nearest even, what
     ``t.to(torch.bfloat16)`` does -- on the bf16 matrix cores, with fp32 accumulation; activations, weights and gradients stay fp32
-    in memory, the bias gradients are fp32 sums of the unrounded gradients and everything between the products is unchanged.  The
-    products then always run dense (``rowblk`` is accepted and ignored); the contract of the padding rows holds.
+    in memory, the bias gradients are fp32 sums of the unrounded gradients and everything between the products is unchanged.  With
+    ``rowblk`` these products, too, run on the live 16-row blocks where their launcher serves the list (weight gradients skip the
+    64-deep steps without a live block), bit for bit what the dense products give; the contract of the padding rows holds.
     ``BertModel(impl="torch", matmul="bf16")`` is the definition.
 
     ``attention``: ``"fp32"`` (default: the attention kernels as they were) or ``"bf16"``: the core's four matrix products take bf16

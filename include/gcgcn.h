@@ -707,8 +707,11 @@ int gcgcn_bert_layer_bwd_len(int B, int T, int D, int H, int Dff, const float* x
  * gcgcn_bert_layer_fwd_mm / gcgcn_bert_layer_bwd_mm: the _len entry points (t_valid and rowblk may both be NULL: every row is live)
  * with a selector for the twelve Linear products.  matmul = 0: the fp32 GEMM layer, launch for launch what the entry points above
  * run.  matmul = 1: bf16 operands as above -- everything else (attention core, LayerNorms, GELU, dropout sites and indices, saved
- * state, workspace sizes) is unchanged, the bias gradients are exact fp32 column sums, and the products always run dense (rowblk is
- * accepted and ignored; the padding-row contract of the _len entry points holds).  Both calls of a pair take the same matmul. */
+ * state, workspace sizes) is unchanged, the bias gradients are exact fp32 column sums, and with rowblk the products run on the live
+ * 16-row blocks where their launcher serves the list (whole 64-row tiles of 16-byte aligned operands; dense elsewhere): forward
+ * products and data gradients compute the live blocks, weight gradients skip the 64-deep steps without a live block.  The results are
+ * bit for bit those of the dense products (gcgcn_set_option("bf16_rows", 0) / GCGCN_BF16_ROWS=0 runs those), and the padding-row
+ * contract of the _len entry points holds.  Both calls of a pair take the same matmul. */
 int64_t gcgcn_gemm_bf16_ws_bytes(int M, int N, int K);
 int gcgcn_gemm_bf16(int a_kc, int b_kc, const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int M, int N, int K,
                     const float* bias, const float* add, int64_t ldadd, void* ws, int64_t ws_bytes, void* stream);

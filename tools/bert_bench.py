@@ -17,7 +17,8 @@ seed and mean are printed.  --shape restricts the run to one (B, T), so that a c
 With --matmul only the HIP encoder runs, as one replayed hipGraph, once per listed setting of BertModel(matmul=...), back to back in
 the same process on the same inputs (median, min and max of --iters samples; with --lengths on those token counts through
 lengths=), followed by one layer's twelve Linear products timed alone through the C ABI: the fp32 GEMM layer's launch against the
-bf16 kernel's, with the achieved TF/s.
+bf16 kernel's, with the achieved TF/s.  With --lengths the bf16 setting runs twice, back to back on the same data: option bf16_rows = 0
+(its products ignore the row-block list: dense launches) and 1 (live row blocks), columns ``..._rows0`` / ``..._rows1``.
 
 With --attention the same graph-replay runs go over every listed combination of BertModel(matmul=..., attention=...) (--matmul
 defaults to fp32 alone), and the kernel-alone section times the attention core through gcgcn_bert_attn_fwd_mx / _bwd_mx at each
@@ -69,6 +70,7 @@ def timed_stats(fn, iters, warmup=3):
 
 
 LENGTH_SEED = 2024
+ROWS_OPTION = b"bf16_rows"      # 0: the bf16 products ignore the row-block list
 
 
 def draw_lengths(kind, B, T):
@@ -212,7 +214,14 @@ def main():
                 for mm, at in combos:
                     step = model_step(layers, "hip", B, T, dev, tv, tv is not None, matmul=mm, attention=at)
                     key = mm if not a.attention else f"mm_{mm}_attn_{at}"
-                    r[f"{key}_graph_ms"], r[f"{key}_min_ms"], r[f"{key}_max_ms"] = timed_stats(graphed(step), a.iters)
+                    # bf16 products with lengths: the dense launches (bf16_rows = 0) and the row-block ones (1) back to back on this data;
+                    # the option is read at launch, so each side captures its own graph
+                    for on in ((0, 1) if (mm == "bf16" and tv is not None) else (None,)):
+                        k = key if on is None else f"{key}_rows{on}"
+                        if on is not None:
+                            _lib.call("gcgcn_set_option", ROWS_OPTION, on)
+                        r[f"{k}_graph_ms"], r[f"{k}_min_ms"], r[f"{k}_max_ms"] = timed_stats(graphed(step), a.iters)
+                    _lib.call("gcgcn_set_option", ROWS_OPTION, 1)
                     del step
                     torch.cuda.empty_cache()
                 rows.append(r)
