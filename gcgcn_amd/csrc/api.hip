@@ -132,7 +132,21 @@ int option(const char* name, int dflt) {
   }
   return dflt;
 }
+// "head_matmul" is not one of the switches above: it is an ARGUMENT of the next head call, handed over beside the call's list.
+// gcgcn_set_option("head_matmul", v) stores v for the calling THREAD; the next gcgcn_head_fwd / gcgcn_head_bwd / gcgcn_debug_head_plan
+// on that thread takes it and leaves 0 behind.  Nothing process-wide and nothing lasting selects the arithmetic: no environment
+// variable is read, another thread never sees the value, and a call that nobody announced runs fp32.
+static thread_local int g_head_matmul_next = 0;
+int head_matmul_take() {
+  const int v = g_head_matmul_next;
+  g_head_matmul_next = 0;
+  return v;
+}
 static bool set_opt(const char* name, int value) {
+  if (strcmp(name, "head_matmul") == 0) {
+    g_head_matmul_next = value;
+    return true;
+  }
   for (Opt& o : g_opts)
     if (strcmp(o.name, name) == 0) {
       o.value = value, o.resolved = true;

@@ -113,6 +113,9 @@ inline Drop make_drop(const void* snap, uint64_t salt, float p) {
 
 // run-time A/B switch `name` (gcgcn_set_option > environment variable GCGCN_<NAME> > dflt); api.hip
 int option(const char* name, int dflt);
+// the matmul argument of the calling thread's next classifier-head call (gcgcn_set_option("head_matmul", v); api.hip): returned
+// and reset to 0
+int head_matmul_take();
 
 // Two kinds of workgroup in one launch: `na` long-running ones (matrix tiles) and short ones (rows of a streaming pass).
 // The tiles go out in COHORTS of `cohort` consecutive workgroups, one cohort every `stride` indices (stride >= cohort;

@@ -17,6 +17,7 @@
 #include <string.h>
 
 #include "gemm_body.hpp"
+#include "head_bf16.hpp"
 #include "rowops.hpp"
 
 namespace gc {
@@ -467,6 +468,7 @@ __global__ __launch_bounds__(256) void head_bil_combine_kernel(const float* __re
 }
 
 // ---- which kernel serves which pass: decided once per call, here and nowhere else (gcgcn_debug_head_plan shows the result) ----
+constexpr int HEAD_MM_FP32 = 0, HEAD_MM_BF16 = 1;   // the matmul argument of a head call (head_matmul_take)
 constexpr int HEAD_TILE128_MIN_ROWS = 32768;   // one 128-pair tile per compute unit (the rule head_plan applies to host-side counts)
 struct HeadPlan {
   enum Pass { GEMM, TILE64, TILE128 };   // head_gemm_kernel<mode> | head_bil2_kernel<mode> | head_bil3_kernel<mode>
@@ -474,9 +476,10 @@ struct HeadPlan {
   bool compact;      // the pair passes run on the pairs that exist (compacted rows); their count is on the device
   Pass fwd, bwd_e;   // the forward pass (mode 1); the d eh / d et passes (modes 2 and 3)
   Dw dw;             // d W_b
-  bool by_count(Pass p) const { return compact && p == TILE128; }   // both launch shapes, the device-side count selects one (head_pass)
+  bool bf16;         // matmul = 1: the four bilinear passes (the Linear's products folded in) run on head_bf16.hip's kernels
+  bool by_count(Pass p) const { return compact && p == TILE128 && !bf16; }   // both launch shapes, the device-side count selects one (head_pass)
 };
-static HeadPlan head_plan(long pairs, int R, bool ragged) {
+static HeadPlan head_plan(long pairs, int R, bool ragged, int matmul) {
   // Which generation runs the outer-product passes.  The register-generated one (head_bil2 / head_bil3: 128-pair tiles, two
   // workgroups per compute unit) wins once there is a tile per compute unit (B = 32: N = 64 15.8 vs 19.2 ms per step, N = 42 8.1
   // vs 8.3); below that the first one's finer tiles (64 x 64, four per compute unit) fill the chip better.  GCGCN_HEAD_V1=1 / =0
@@ -498,6 +501,13 @@ static HeadPlan head_plan(long pairs, int R, bool ragged) {
   p.bwd_e = (p.compact || !gen1) ? (bwd128 ? HeadPlan::TILE128 : HeadPlan::TILE64) : HeadPlan::GEMM;
   // d W_b: all R rows per workgroup, row 96 on the vector ALU (head_dw_kernel); the GEMM form pads R to 128 rows
   p.dw = (p.compact || (option("head_dw3", 1) != 0 && past96 && !gen1)) ? HeadPlan::DW_ROWS : HeadPlan::DW_GEMM;
+  // matmul = 1 (an argument of the call, handed over by gcgcn_set_option("head_matmul", 1) on the calling thread right before it; the
+  // entry points refuse anything but 0 / 1): bf16 operands, opt-in.  Every pass on head_bf16.hip's kernels -- 128-pair tiles, unsplit, one launch per pass for
+  // every row count and every R; all rows of d W_b / d W_c per workgroup.  No route is kept on fp32: at the two measured shapes
+  // ("bf16 bilinear passes") the bf16 passes are the faster ones.  Which rows are compacted is the fp32 rule
+  // above, so the padding slots of a ragged batch hold exactly what they hold with matmul = 0.
+  p.bf16 = matmul == HEAD_MM_BF16;
+  if (p.bf16) p.fwd = p.bwd_e = HeadPlan::TILE128, p.dw = HeadPlan::DW_ROWS;
   return p;
 }
 
@@ -581,6 +591,14 @@ static int head_pass(int mode, const Bil2& pass, const HeadPlan& plan, hipStream
   hipLaunchKernelGGL(head_bil_combine_kernel, dim3((unsigned)cdiv(prow * 32, 256)), dim3(256), 0, st, small.part, small.part_rows, small.rows_dev,
                      small.sel_lo, small.sel_hi, small.bias, small.crow, small.C, small.ncol, small.ldc);
   return check_launch("head_bil_combine");
+}
+
+// The same pass on bf16 operands (head_bf16.hip; plan.bf16).  W2: classification_layer_01.weight, whose product rides in every mode.
+static int head_pass_bf16(int mode, const Bil2& a, hipStream_t st) {
+  HeadBf16Pass p;
+  p.mode = mode, p.P = a.P, p.Q = a.Q, p.Wb = a.W, p.Wc = a.W2, p.bias = a.bias, p.C = a.C, p.rows = a.rows, p.R = mode == 1 ? a.ncol : a.nA;
+  p.rows_dev = a.rows_dev, p.crow = a.crow, p.sel_lo = a.sel_lo, p.sel_hi = a.sel_hi;
+  return head_bf16_pass(p, st);
 }
 
 // ---- per-entity term + type table:  UT[b, n, :] = U[b, n, :] + Tt[type[b, n], :];  bsum = b_bilinear + b_linear -------
@@ -954,9 +972,11 @@ int head_fwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int di
   Bil2 a = bil_pass(1, w.EH, w.ET, flat + y.Wb, logits, pairs, R);
   a.W2 = flat + y.Wc, a.bias = w.bsum;
   if (compact) {   // the pairs that exist, scattered into the padded tensor; every other slot is zero
-    GC_REQUIRE(hipMemsetAsync(logits, 0, sizeof(float) * pairs * R, st) == hipSuccess, "head: memset failed");
+    if (plan.bf16) GC_TRY(head_bf16_zero(logits, pairs * R, st));
+    else GC_REQUIRE(hipMemsetAsync(logits, 0, sizeof(float) * pairs * R, st) == hipSuccess, "head: memset failed");
     a.rows_dev = idx_cnt(w), a.crow = idx_prow(w, B), a.part = w.partF, a.part_rows = (int)w.part_rows;
   }
+  if (plan.bf16) return head_pass_bf16(1, a, st);
   return head_pass(1, a, plan, st);
 }
 
@@ -999,43 +1019,54 @@ int head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int di
   auto d_e = [&](int mode, const float* Q, float* C) {   // the bilinear part of d eh (mode 2, Q = et) / d et (mode 3, Q = eh)
     Bil2 a = bil_pass(mode, w.doutp, Q, flat + y.Wb, C, pairs, R);
     if (compact) a.rows_dev = cnt, a.part = w.partB, a.part_rows = (int)w.part_rows;   // (dEH / dET rows are compacted like the operands)
+    if (plan.bf16) {   // + dout W_c's half in the same accumulators
+      a.W2 = flat + y.Wc;
+      return head_pass_bf16(mode, a, st);
+    }
     return head_pass(mode, a, plan, st);
   };
   // d eh = sum_(r,b) dout[p,r] et[p,b] W_b[r,a,b]  + dout W_c[:, :128]
   GC_TRY(d_e(2, w.ET, w.dEH));
-  if (!compact) GC_TRY(gemm(dE_c[0], st));   // (compacted: with d et's, below)
+  if (!plan.bf16 && !compact) GC_TRY(gemm(dE_c[0], st));   // (compacted: with d et's, below; bf16: inside the pass)
   // d et = sum_(r,a) dout[p,r] eh[p,a] W_b[r,a,b]  + dout W_c[:, 128:]
   GC_TRY(d_e(3, w.EH, w.dET));
-  if (compact) GC_TRY(gemm_dyn_pair_xx(dE_c[0], dE_c[1], cnt, pairs, st));   // + dout W_c on both sides: one launch for the two halves
-  else GC_TRY(gemm(dE_c[1], st));
-  {  // d W_b[r, (a, b)] = sum_p dout[p, r] eh[p, a] et[p, b]: dout^T against the generated [pairs, 16384] operand
-    GemmArgs g = gemm_tn(w.doutp, HW, w.EH, HW, dflat + y.Wb, HW * HW, R, HW * HW, (int)pairs).split_ws(ws, wse);
-    if (plan.dw == HeadPlan::DW_ROWS) {
-      const long ksteps = cdiv(pairs, 32);
-      int splits = 1;
-      while (splits < 16 && (long)HW * splits < 2048 && ksteps / (splits * 2) >= 64 && (long)(splits * 2) * R * HW * HW <= wse) splits *= 2;
-      HeadDw d;
-      d.doutp = w.doutp, d.EH = w.EH, d.ET = w.ET, d.pairs = pairs, d.R = R, d.ksteps_per_split = (int)cdiv(ksteps, splits);
-      d.pairs_dev = cnt;   // compacted: K = the device-side count (the split factor stays the capacity's)
-      d.out = splits > 1 ? ws : dflat + y.Wb;
-      GC_LAUNCH_TIMED("head_bilinear", 2.0 * R * HW * HW * (double)pairs, head_dw_kernel, dim3(HW, splits), dim3(256), 0, st, d);
-      GC_TRY(check_launch("head_dw"));
-      if (splits > 1) {
-        g.splits = splits, g.batch1 = g.batch2 = 1;
-        GC_TRY(splitk_reduce(g, st));
-      }
-    } else {
-      GC_TRY(head_gemm(4, {g, head_ops(w.EH, w.ET, 0, pairs, R)}, st));
-    }
-  }
-  // d W_c = dout^T [eh | et]    (computed 128 rows deep into a workspace, the R real rows copied out)
-  if (compact) {   // the two halves over the same device-side pair count: one launch, one reduce
-    GC_TRY(gemm_dyn_pair_ww(dW_c[0], dW_c[1], cnt, pairs, st));
+  if (plan.bf16) {   // d W_b and d W_c from one launch, straight into dflat; the rest of this function is the fp32 code it was
+    HeadBf16Dw d;
+    d.doutp = w.doutp, d.EH = w.EH, d.ET = w.ET, d.dWb = dflat + y.Wb, d.dWc = dflat + y.Wc, d.ws = ws, d.ws_elems = wse, d.pairs = pairs, d.R = R;
+    d.pairs_dev = cnt;   // compacted: K = the device-side count
+    GC_TRY(head_bf16_dw(d, st));
   } else {
-    GC_TRY(gemm(dW_c[0], st));
-    GC_TRY(gemm(dW_c[1], st));
+    if (compact) GC_TRY(gemm_dyn_pair_xx(dE_c[0], dE_c[1], cnt, pairs, st));   // + dout W_c on both sides: one launch for the two halves
+    else GC_TRY(gemm(dE_c[1], st));
+    {  // d W_b[r, (a, b)] = sum_p dout[p, r] eh[p, a] et[p, b]: dout^T against the generated [pairs, 16384] operand
+      GemmArgs g = gemm_tn(w.doutp, HW, w.EH, HW, dflat + y.Wb, HW * HW, R, HW * HW, (int)pairs).split_ws(ws, wse);
+      if (plan.dw == HeadPlan::DW_ROWS) {
+        const long ksteps = cdiv(pairs, 32);
+        int splits = 1;
+        while (splits < 16 && (long)HW * splits < 2048 && ksteps / (splits * 2) >= 64 && (long)(splits * 2) * R * HW * HW <= wse) splits *= 2;
+        HeadDw d;
+        d.doutp = w.doutp, d.EH = w.EH, d.ET = w.ET, d.pairs = pairs, d.R = R, d.ksteps_per_split = (int)cdiv(ksteps, splits);
+        d.pairs_dev = cnt;   // compacted: K = the device-side count (the split factor stays the capacity's)
+        d.out = splits > 1 ? ws : dflat + y.Wb;
+        GC_LAUNCH_TIMED("head_bilinear", 2.0 * R * HW * HW * (double)pairs, head_dw_kernel, dim3(HW, splits), dim3(256), 0, st, d);
+        GC_TRY(check_launch("head_dw"));
+        if (splits > 1) {
+          g.splits = splits, g.batch1 = g.batch2 = 1;
+          GC_TRY(splitk_reduce(g, st));
+        }
+      } else {
+        GC_TRY(head_gemm(4, {g, head_ops(w.EH, w.ET, 0, pairs, R)}, st));
+      }
+    }
+    // d W_c = dout^T [eh | et]    (computed 128 rows deep into a workspace, the R real rows copied out)
+    if (compact) {   // the two halves over the same device-side pair count: one launch, one reduce
+      GC_TRY(gemm_dyn_pair_ww(dW_c[0], dW_c[1], cnt, pairs, st));
+    } else {
+      GC_TRY(gemm(dW_c[0], st));
+      GC_TRY(gemm(dW_c[1], st));
+    }
+    GC_REQUIRE(hipMemcpyAsync(dflat + y.Wc, w.dW, sizeof(float) * R * 2 * HW, hipMemcpyDeviceToDevice, st) == hipSuccess, "head: copy failed");
   }
-  GC_REQUIRE(hipMemcpyAsync(dflat + y.Wc, w.dW, sizeof(float) * R * 2 * HW, hipMemcpyDeviceToDevice, st) == hipSuccess, "head: copy failed");
   {
     ProfScope ps("head_feat", st);
     hipLaunchKernelGGL(head_tanh_bwd_kernel, dim3(cdiv(pairs * HW / 4, 256)), dim3(256), 0, st, w.EH, w.ET, w.dEH, w.dET, pairs * HW / 4, cnt);
@@ -1137,44 +1168,53 @@ int gcgcn_head_sizes(int B, int N, int R, int ND, int64_t* out3) {
 
 // The kernels a head call of this shape gets under the current options, by the very plan function gcgcn_head_fwd / _bwd call:
 // out[0..5] = compact, forward pass, d eh / d et passes (0 first-generation GEMM, 1 64-pair tile, 2 128-pair tile), d W_b (0 GEMM,
-// 1 all rows per workgroup), then whether the forward / the d e passes launch both shapes for the device-side count.  Exposed for
-// tests (no GPU needed).
+// 1 all rows per workgroup), then whether the forward / the d e passes launch both shapes for the device-side count.  Announced
+// with matmul = 1 (gcgcn_set_option("head_matmul", 1) on this thread right before) the three kernel answers are 3, 3, 2:
+// head_bf16.hip's pass kernel and its weight-gradient kernel.  Exposed for tests (no GPU needed).
 int gcgcn_debug_head_plan(int B, int N, int R, int ragged, int32_t* out) {
+  const int matmul = head_matmul_take();   // first: whatever this call returns, the announcement was for it
   GC_REQUIRE(B > 0 && N > 0 && (long)B * N * N < (1L << 31) / 2 && R >= 1 && R <= HW && out, "debug_head_plan: bad arguments");
-  const HeadPlan p = head_plan((long)B * N * N, R, ragged != 0);
-  out[0] = p.compact, out[1] = p.fwd, out[2] = p.bwd_e, out[3] = p.dw, out[4] = p.by_count(p.fwd), out[5] = p.by_count(p.bwd_e);
+  GC_REQUIRE(matmul == HEAD_MM_FP32 || matmul == HEAD_MM_BF16, "debug_head_plan: head_matmul = %d (0 = fp32, 1 = bf16)", matmul);
+  const HeadPlan p = head_plan((long)B * N * N, R, ragged != 0, matmul);
+  out[0] = p.compact, out[1] = p.bf16 ? 3 : p.fwd, out[2] = p.bf16 ? 3 : p.bwd_e, out[3] = p.bf16 ? 2 : p.dw;
+  out[4] = p.by_count(p.fwd), out[5] = p.by_count(p.bwd_e);
   return 0;
 }
 
 int gcgcn_head_fwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int dis_plus, const float* const* feats,
                    const int64_t* node_type, const int64_t* node_relative_pos, const float* ner_emb, const float* dis_table,
                    const int32_t* n_valid, const float* flat, float* fbuf, int32_t* ibuf, float* logits, void* stream) {
+  const int matmul = head_matmul_take();   // first: whatever this call returns, the announcement was for it
   GC_REQUIRE(B > 0 && N > 0 && Hd > 0 && nf > 0 && nf <= 8 && Pt > 0 && Pr > 0 && R > 0 && ND > 0, "head_fwd: bad shape");
   GC_REQUIRE(ND <= HT_IDS, "head_fwd: the distance table has %d rows, the head handles at most %d (gcgcn_head_bwd's per-id sums)", ND, HT_IDS);
   GC_REQUIRE(Hd % 4 == 0 && Pt % 4 == 0 && Pr % 4 == 0, "head_fwd: feature widths must be multiples of 4 (16-byte rows)");
   GC_REQUIRE(feats && node_type && node_relative_pos && ner_emb && dis_table && flat && fbuf && logits, "head_fwd: null pointer");
   GC_REQUIRE(!n_valid || ibuf, "head_fwd: n_valid given without ibuf");
+  GC_REQUIRE(matmul == HEAD_MM_FP32 || matmul == HEAD_MM_BF16, "head_fwd: head_matmul = %d (0 = fp32, 1 = bf16)", matmul);
+  const HeadPlan plan = head_plan((long)B * N * N, R, n_valid != nullptr, matmul);
   HeadBufs w = head_bind(fbuf, nullptr, B, N, R, ND, nullptr, nullptr);
   w.idx = ibuf;
   return head_fwd(B, N, Hd, nf, Pt, Pr, R, ND, dis_plus, feats, (const long long*)node_type, (const long long*)node_relative_pos, ner_emb,
-                  dis_table, n_valid, flat, w, logits, head_plan((long)B * N * N, R, n_valid != nullptr), (hipStream_t)stream);
+                  dis_table, n_valid, flat, w, logits, plan, (hipStream_t)stream);
 }
 
 int gcgcn_head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, int dis_plus, const float* const* feats,
                    const int64_t* node_type, const int64_t* node_relative_pos, const float* ner_emb, const float* dis_table,
                    const int32_t* n_valid, const float* flat, float* fbuf, int32_t* ibuf, float* bbuf, const float* dlogits,
                    float* const* dfeats, float* dner_emb, float* ddis_table, float* dflat, void* stream) {
+  const int matmul = head_matmul_take();   // first: whatever this call returns, the announcement was for it
   GC_REQUIRE(B > 0 && N > 0 && Hd > 0 && nf > 0 && nf <= 8 && Pt > 0 && Pr > 0 && R > 0 && ND > 0, "head_bwd: bad shape");
   GC_REQUIRE(ND <= HT_IDS, "head_bwd: the distance table has %d rows, the head handles at most %d (the per-id sums in LDS)", ND, HT_IDS);
   GC_REQUIRE(feats && node_type && node_relative_pos && ner_emb && dis_table && flat && fbuf && bbuf && dlogits && dfeats && dner_emb &&
                  ddis_table && dflat,
              "head_bwd: null pointer");
   GC_REQUIRE(!n_valid || ibuf, "head_bwd: n_valid given without ibuf");
+  GC_REQUIRE(matmul == HEAD_MM_FP32 || matmul == HEAD_MM_BF16, "head_bwd: head_matmul = %d (0 = fp32, 1 = bf16)", matmul);
+  const HeadPlan plan = head_plan((long)B * N * N, R, n_valid != nullptr, matmul);
   HeadBufs w = head_bind(fbuf, bbuf, B, N, R, ND, nullptr, nullptr);
   w.idx = ibuf;
   return head_bwd(B, N, Hd, nf, Pt, Pr, R, ND, dis_plus, feats, (const long long*)node_type, (const long long*)node_relative_pos, ner_emb,
-                  dis_table, n_valid, flat, w, dlogits, dfeats, dner_emb, ddis_table, dflat, head_plan((long)B * N * N, R, n_valid != nullptr),
-                  (hipStream_t)stream);
+                  dis_table, n_valid, flat, w, dlogits, dfeats, dner_emb, ddis_table, dflat, plan, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -797,12 +797,26 @@ class EdgeMeanCompactFn(torch.autograd.Function):
         return dEc, dbias, None, None
 
 
+def _head_call(matmul: int, name: str, *args):
+    """One head entry point with the argument matmul.  0: the call alone, as always.  1: announced to the library on this thread
+    right before the call, which takes the announcement (include/gcgcn.h, gcgcn_head_fwd) -- per thread and per call: a head on
+    another thread, or the next call on this one, is not affected."""
+    if matmul:
+        call("gcgcn_set_option", b"head_matmul", matmul)
+    call(name, *args)
+
+
 class HeadFn(torch.autograd.Function):
     """(flat, ner_emb[7,Pt], dis_table[ND,Pr], feats_0 .. feats_{nf-1} [B,N,Hd]; node_type, node_relative_pos) ->
     logits[B,N,N,R].  The classifier head, GCGCN_glove.py:306-307, 344-358."""
 
     @staticmethod
     def forward(ctx, flat, ner_emb, dis_table, node_type, rel, n_valid, R, dis_plus, *feats):
+        return HeadFn._forward(ctx, 0, flat, ner_emb, dis_table, node_type, rel, n_valid, R, dis_plus, *feats)
+
+    @staticmethod
+    def _forward(ctx, matmul, flat, ner_emb, dis_table, node_type, rel, n_valid, R, dis_plus, *feats):
+        """matmul: the argument of the forward and of the backward call (_head_call)."""
         B, N, Hd = feats[0].shape
         nf, Pt, (ND, Pr) = len(feats), ner_emb.shape[1], dis_table.shape
         dev = flat.device
@@ -813,10 +827,11 @@ class HeadFn(torch.autograd.Function):
         ibuf = torch.empty(sizes[2], dtype=torch.int32, device=dev) if n_valid is not None else None
         logits = torch.empty(B, N, N, R, device=dev)
         fp = (ctypes.c_void_p * nf)(*[f.data_ptr() for f in feats])
-        call("gcgcn_head_fwd", B, N, Hd, nf, Pt, Pr, R, ND, dis_plus, ctypes.cast(fp, ctypes.c_void_p), _p(node_type), _p(rel),
-             _p(ner_emb), _p(dis_table), _p(n_valid), _p(flat), _p(fbuf), _p(ibuf), _p(logits), _stream())
+        args = (B, N, Hd, nf, Pt, Pr, R, ND, dis_plus, ctypes.cast(fp, ctypes.c_void_p), _p(node_type), _p(rel), _p(ner_emb), _p(dis_table),
+                _p(n_valid), _p(flat), _p(fbuf), _p(ibuf), _p(logits), _stream())
+        _head_call(matmul, "gcgcn_head_fwd", *args)
         ctx.save_for_backward(flat, ner_emb, dis_table, node_type, rel, fbuf, *feats)
-        ctx.n_valid, ctx.R, ctx.dis_plus, ctx.nbwd, ctx.ibuf = n_valid, R, dis_plus, int(sizes[1]), ibuf
+        ctx.n_valid, ctx.R, ctx.dis_plus, ctx.nbwd, ctx.ibuf, ctx.matmul = n_valid, R, dis_plus, int(sizes[1]), ibuf, matmul
         return logits
 
     @staticmethod
@@ -831,10 +846,74 @@ class HeadFn(torch.autograd.Function):
         dner, dtab, dflat = torch.empty_like(ner_emb), torch.empty_like(dis_table), torch.zeros_like(flat)   # (gaps stay zero)
         fp = (ctypes.c_void_p * nf)(*[f.data_ptr() for f in feats])
         dp = (ctypes.c_void_p * nf)(*[f.data_ptr() for f in dfeats])
-        call("gcgcn_head_bwd", B, N, Hd, nf, Pt, Pr, ctx.R, ND, ctx.dis_plus, ctypes.cast(fp, ctypes.c_void_p), _p(node_type),
-             _p(rel), _p(ner_emb), _p(dis_table), _p(ctx.n_valid), _p(flat), _p(fbuf), _p(ctx.ibuf), _p(bbuf), _p(dlogits),
-             ctypes.cast(dp, ctypes.c_void_p), _p(dner), _p(dtab), _p(dflat), _stream())
+        args = (B, N, Hd, nf, Pt, Pr, ctx.R, ND, ctx.dis_plus, ctypes.cast(fp, ctypes.c_void_p), _p(node_type), _p(rel), _p(ner_emb),
+                _p(dis_table), _p(ctx.n_valid), _p(flat), _p(fbuf), _p(ctx.ibuf), _p(bbuf), _p(dlogits), ctypes.cast(dp, ctypes.c_void_p),
+                _p(dner), _p(dtab), _p(dflat), _stream())
+        _head_call(ctx.matmul, "gcgcn_head_bwd", *args)
         return (dflat, dner, dtab, None, None, None, None, None, *dfeats)
+
+
+class HeadBf16Fn(HeadFn):
+    """HeadFn with the four bilinear passes on bf16 operands (csrc/head_bf16.hip; Bf16HeadBilinearFn below is their definition)."""
+
+    @staticmethod
+    def forward(ctx, flat, ner_emb, dis_table, node_type, rel, n_valid, R, dis_plus, *feats):
+        return HeadFn._forward(ctx, 1, flat, ner_emb, dis_table, node_type, rel, n_valid, R, dis_plus, *feats)
+
+
+HEAD_MATMUL = {"fp32": HeadFn, "bf16": HeadBf16Fn}   # classifier_head's matmul -> the autograd node
+
+
+def _round_bf16(t: Tensor) -> Tensor:
+    """Round once to bf16 (nearest even) through float32, back in the dtype of ``t``."""
+    return t.to(torch.float32).to(torch.bfloat16).to(t.dtype)
+
+
+class Bf16HeadBilinearFn(torch.autograd.Function):
+    """The DEFINITION of ``classifier_head(..., matmul="bf16")``'s bilinear passes, in plain PyTorch on any device and dtype (its
+    float64 run is the reference of the tests): ``(eh[P,128], et[P,128], W_b[R,128,128], W_c[R,256], bias[R]) -> out[P,R]``, where
+    ``eh`` / ``et`` are the fp32 results of the unchanged gather + tanh and ``bias = bili_layer_01.bias +
+    classification_layer_01.bias``.  ``bf16(.)`` rounds once to nearest even; every sum is exact in the dtype it runs in (fp32 on the
+    device)::
+
+        out[p,r]    = sum_ab bf16(eh[p,a] et[p,b]) bf16(W_b[r,a,b]) + sum_k bf16(cat(eh, et)[p,k]) bf16(W_c[r,k]) + bias[r]
+        d eh[p,a]   = sum_rb bf16(dout[p,r] et[p,b]) bf16(W_b[r,a,b]) + sum_r bf16(dout[p,r]) bf16(W_c[r,a])
+        d et[p,b]   = sum_ra bf16(dout[p,r] eh[p,a]) bf16(W_b[r,a,b]) + sum_r bf16(dout[p,r]) bf16(W_c[r,128 + b])
+        dW_b[r,a,b] = sum_p bf16(dout[p,r]) bf16(eh[p,a] et[p,b])
+        dW_c        = bf16(dout)^T bf16(cat(eh, et)),        d bias = column sums of the UNROUNDED dout
+
+    The generated operands are formed as FLOAT32 products (whatever the dtype of the run) and rounded once; the bias never passes
+    through a rounding.  ``rnd`` replaces the rounding (the identity turns the function into the exact head)."""
+
+    @staticmethod
+    def forward(ctx, eh, et, Wb, Wc, bias, rnd=None):
+        rnd = rnd or _round_bf16
+        ctx.rnd = rnd
+        ctx.save_for_backward(eh, et, Wb, Wc)
+        Pn, R = eh.shape[0], Wb.shape[0]
+        outer = rnd(Bf16HeadBilinearFn._prod(eh, et, rnd)).reshape(Pn, -1)                    # [P, (a, b)]
+        return outer @ rnd(Wb).reshape(R, -1).t() + rnd(torch.cat([eh, et], 1)) @ rnd(Wc).t() + bias
+
+    @staticmethod
+    def _prod(x, y, rnd):
+        """x[p,i] y[p,j] as the kernel forms it: a float32 product (exact dtype when the rounding is switched off)."""
+        if rnd is _round_bf16:
+            return (x.to(torch.float32).unsqueeze(2) * y.to(torch.float32).unsqueeze(1)).to(x.dtype)
+        return x.unsqueeze(2) * y.unsqueeze(1)
+
+    @staticmethod
+    def backward(ctx, dout):
+        eh, et, Wb, Wc = ctx.saved_tensors
+        rnd, H = ctx.rnd, eh.shape[1]
+        Wbr, Wcr, dr = rnd(Wb), rnd(Wc), rnd(dout)
+        de = rnd(Bf16HeadBilinearFn._prod(dout, et, rnd))                                      # [P, r, b]
+        deh = torch.einsum("prb,rab->pa", de, Wbr) + dr @ Wcr[:, :H]
+        dt = rnd(Bf16HeadBilinearFn._prod(dout, eh, rnd))                                      # [P, r, a]
+        det = torch.einsum("pra,rab->pb", dt, Wbr) + dr @ Wcr[:, H:]
+        outer = rnd(Bf16HeadBilinearFn._prod(eh, et, rnd))                                     # [P, a, b]
+        dWb = torch.einsum("pr,pab->rab", dr, outer)
+        dWc = dr.t() @ rnd(torch.cat([eh, et], 1))
+        return deh, det, dWb, dWc, dout.sum(0), None
 
 
 # Range-check the integer ids handed to the head / the producer before the kernels index with them.  The reference's
@@ -858,9 +937,15 @@ def _check_id_range(checks):
         raise IndexError(f"{name}: ids must lie in [{lo}, {hi}], got min {int(t.min())} / max {int(t.max())}")
 
 
-def classifier_head(feats, node_type, node_relative_pos, ner_emb, dis_table, flat, relation_num, n_valid=None, dis_plus=10):
+def classifier_head(feats, node_type, node_relative_pos, ner_emb, dis_table, flat, relation_num, n_valid=None, dis_plus=10, matmul="fp32"):
     """logits[B,N,N,R] from the model's node_feats list (each [B,N,Hd]), node_type int64[B,N], node_relative_pos
-    int64[B,N,N], the two embedding tables and the head's flat parameters."""
+    int64[B,N,N], the two embedding tables and the head's flat parameters.
+
+    ``matmul="bf16"`` (opt-in): the forward pass, ``d eh``, ``d et`` and the weight gradients of the bilinear and the Linear layer take
+    bf16 operands with fp32 accumulation (csrc/head_bf16.hip; :class:`Bf16HeadBilinearFn` is the definition); everything else, and
+    every tensor in memory, stays fp32.  ``"fp32"`` (default) issues the calls it always issued."""
+    if matmul not in HEAD_MATMUL:
+        raise ValueError(f"classifier_head: matmul must be 'fp32' or 'bf16', got {matmul!r}")
     feats = [_chk(f, f"node_feats[{i}]", 3) for i, f in enumerate(feats)]
     B, N, Hd = feats[0].shape
     if any(tuple(f.shape) != (B, N, Hd) for f in feats):
@@ -877,9 +962,9 @@ def classifier_head(feats, node_type, node_relative_pos, ner_emb, dis_table, fla
                          f"pass keeps one sum per id in LDS), got {tuple(dis_table.shape)}")
     _check_id_range([("node_type", node_type, 0, NER_ROWS - 1),
                      ("node_relative_pos", node_relative_pos, -int(dis_plus), int(dis_plus))])
-    return HeadFn.apply(_chk(flat, "flat"), _chk(ner_emb, "ner_emb.weight", 2), _chk(dis_table, "dis_embed.weight", 2),
-                        node_type.contiguous(), node_relative_pos.contiguous(), _nv(n_valid, B, N, flat.device),
-                        int(relation_num), int(dis_plus), *feats)
+    return HEAD_MATMUL[matmul].apply(_chk(flat, "flat"), _chk(ner_emb, "ner_emb.weight", 2), _chk(dis_table, "dis_embed.weight", 2),
+                                     node_type.contiguous(), node_relative_pos.contiguous(), _nv(n_valid, B, N, flat.device),
+                                     int(relation_num), int(dis_plus), *feats)
 
 
 def producer_live_counts(sen: Tensor, n_valid=None):

@@ -113,7 +113,8 @@ class _GraphRelationModel(GraphModelTail):
     def __init__(self, config, layer_num: int, head_num: int):
         super().__init__(hidden_size=self.HIDDEN, layer_num=layer_num, head_num=head_num, graph_hop=config.graph_hop,
                          alpha=config.alpha, dis_size=config.dis_size, entity_type_size=config.entity_type_size,
-                         relation_num=config.relation_num, dis_plus=config.dis_plus, dropout=0.2)
+                         relation_num=config.relation_num, dis_plus=config.dis_plus, dropout=0.2,
+                         head_matmul=getattr(config, "head_matmul", "fp32"))   # "fp32" | "bf16": ClassifierHead's matmul
         self.config = config
         self.frontend_impl = getattr(config, "frontend_impl", "torch")
         if self.frontend_impl not in ("torch", "hip"):

@@ -494,11 +494,19 @@ class ClassifierHead(_FlatBlock):
     ``state_dict()`` keys equal the model's (``dense_layer.*``, ``bili_layer_01.*``, ``classification_layer_01.*``).  The
     two embedding tables stay with the model (``ner_emb`` is also used by the encoder, ``dis_embed`` by the edge-feature
     producer) and are passed to ``forward``.  The hidden width of the pair features is 128 as in the reference (glove:234).
+
+    ``matmul="bf16"`` (opt-in; default ``"fp32"``: nothing changes) runs the four bilinear passes -- the forward pass, ``d eh``,
+    ``d et`` and the weight gradients of ``bili_layer_01`` / ``classification_layer_01`` -- with bf16 operands and fp32 accumulation
+    (``gcgcn_amd.functional.Bf16HeadBilinearFn`` is the definition).  Parameters, gradients and the ``state_dict`` stay fp32 and keep
+    their keys: a checkpoint moves freely between the two settings.
     """
 
     def __init__(self, hidden_size: int = 128, graph_hop: int = 2, entity_type_size: int = 20, dis_size: int = 20,
-                 relation_num: int = 97, dis_plus: int = 10):
+                 relation_num: int = 97, dis_plus: int = 10, matmul: str = "fp32"):
         super().__init__()
+        if matmul not in F_.HEAD_MATMUL:
+            raise ValueError(f"ClassifierHead: matmul must be 'fp32' or 'bf16', got {matmul!r}")
+        self.matmul = matmul
         self.hidden, self.nf, self.pt, self.pr, self.R, self.dis_plus = hidden_size, graph_hop + 1, entity_type_size, dis_size, \
             relation_num, dis_plus
         self.flat = nn.Parameter(torch.zeros(P_.head_layout(*self._dims())[-1]))
@@ -538,7 +546,7 @@ class ClassifierHead(_FlatBlock):
             node_feats = [f.unsqueeze(0) for f in node_feats]
             node_type, node_relative_pos = node_type.unsqueeze(0), node_relative_pos.unsqueeze(0)
         out = F_.classifier_head(node_feats, node_type, node_relative_pos, ner_emb_weight, dis_embed_weight, self.flat, self.R,
-                                 n_valid, self.dis_plus)
+                                 n_valid, self.dis_plus, matmul=self.matmul)
         return out if batched else out.squeeze(0)
 
 
@@ -633,12 +641,15 @@ class GraphModelTail(nn.Module):
     GCGCN_glove checkpoint loads with ``strict=True``.  The embeddings ``dis_embed`` / ``ner_emb`` stay with the encoder side
     of the model and are passed in.
 
+    ``head_matmul`` is the classifier head's ``matmul`` (``"fp32"`` | ``"bf16"``, :class:`ClassifierHead`).
+
     Reference behaviour kept: the model's ``node_feats`` list records the PRE-update features (glove:338), so the last hop's
     output never reaches the classifier -- it is still computed, as in the reference.
     """
 
     def __init__(self, hidden_size: int = 128, layer_num: int = 2, head_num: int = 8, graph_hop: int = 2, alpha: float = 1.0,
-                 dis_size: int = 20, entity_type_size: int = 20, relation_num: int = 97, dis_plus: int = 10, dropout: float = 0.2):
+                 dis_size: int = 20, entity_type_size: int = 20, relation_num: int = 97, dis_plus: int = 10, dropout: float = 0.2,
+                 head_matmul: str = "fp32"):
         super().__init__()
         self.graph_hop, self.alpha, self.p = graph_hop, float(alpha), float(dropout)
         self.producers = nn.ModuleList([EdgeFeatureProducer(hidden_size, dis_size) for _ in range(graph_hop)])
@@ -646,7 +657,7 @@ class GraphModelTail(nn.Module):
         self.get_adj_matrix = nn.ModuleList([MultiHeadAttention(head_num, hidden_size) for _ in range(graph_hop - 1)])
         self.graphcnn = nn.ModuleList([GraphConvolution(layer_num, hidden_size, hidden_size) if i == 0 else
                                        MultiGraphConvolution(layer_num, head_num, hidden_size, hidden_size) for i in range(graph_hop)])
-        self.head = ClassifierHead(hidden_size, graph_hop, entity_type_size, dis_size, relation_num, dis_plus)
+        self.head = ClassifierHead(hidden_size, graph_hop, entity_type_size, dis_size, relation_num, dis_plus, matmul=head_matmul)
         self._install_key_hooks()
 
     # ---- the model's key names: producers.{i}.<mod>.<rest> <-> <mod>.{i}.<rest>, head.<k> <-> <k> ---------------------------

@@ -41,7 +41,8 @@ const char* gcgcn_last_error(void); /* message of the last failing call on this 
  * up to fp32 summation order.  "head_v1" (-1 = by problem size), "head_bil3", "head_bil3_bwd", "head_dw3",
  * "head_compact", "chain_t", "chain_big" and "split_widen" select kernel generations (the five head options take effect in
  * csrc/head.hip head_plan and nowhere else: gcgcn_debug_head_plan shows the result; "split_widen" in csrc/gemm.hip gemm_plan and
- * nowhere else: gcgcn_debug_gemm_plan); "group_dump" (0 = off) prints what
+ * nowhere else: gcgcn_debug_gemm_plan); "head_matmul" is no switch but the matmul argument of the calling thread's NEXT
+ * classifier-head call (see gcgcn_head_fwd: taken by that call, no environment variable, nothing lasting); "group_dump" (0 = off) prints what
  * every GEMM launch is made of on stderr.  Each name also reads the environment variable GCGCN_<NAME> once when nobody set
  * it (GCGCN_CHAIN=0, GCGCN_HEAD_V1=1, ...: DESIGN.md section 6 lists them).  Any other name fails. */
 int gcgcn_set_option(const char* name, int value);
@@ -406,6 +407,20 @@ int gcgcn_head_bwd(int B, int N, int Hd, int nf, int Pt, int Pr, int R, int ND, 
                    const int64_t* node_type, const int64_t* node_relative_pos, const float* ner_emb, const float* dis_table,
                    const int32_t* n_valid, const float* flat, float* fbuf, int32_t* ibuf, float* bbuf, const float* dlogits,
                    float* const* dfeats, float* dner_emb, float* ddis_table, float* dflat, void* stream);
+/* Opt-in bf16 operands for the four bilinear passes (csrc/head_bf16.hip): the call takes one more
+ * argument, matmul (0 = fp32, 1 = bf16), which travels beside the argument list: gcgcn_set_option("head_matmul", v) hands v to the
+ * calling THREAD's next gcgcn_head_fwd / gcgcn_head_bwd / gcgcn_debug_head_plan call, which takes it (whatever it then returns) and
+ * leaves 0 behind.  A call that was not announced runs fp32, exactly as before: the value is per thread and per call, no environment
+ * variable is read, no other thread sees it and nothing lasting selects the arithmetic.  Any value but 0 and 1 is refused by the call
+ * that takes it, before a launch.  Both calls of a pair are announced with the same value.  The argument lists, the buffers and their
+ * sizes do not change.  (Entry points with matmul in their own argument list would be the plainer interface; none is added here.)
+ * With 1 the forward pass, d eh, d et and d W_b /
+ * d W_c run on v_mfma_f32_32x32x16_bf16 -- the generated operand (eh[p,a] et[p,b]; dout[p,r] et[p,b]; dout[p,r] eh[p,a]) is an fp32
+ * product rounded once to bf16 (nearest even), eh | et, dout and the weights are rounded once on their way into the instruction, every
+ * sum is fp32, the bias is added unrounded and its gradient is the column sum of the unrounded dlogits
+ * (gcgcn_amd.functional.Bf16HeadBilinearFn is the definition).  Everything else -- the dense layer, the tables, tanh and its backward,
+ * the compaction -- is the fp32 code; no bf16 copy of a weight exists in memory, the padding contract above holds, no float is added
+ * atomically and both calls are capturable. */
 
 /* ---- device-side tensorisation of packed documents  config/Config.py:162-233 -------------------------- */
 /* Expands the packed records of a batch (gcgcn_amd/data.py; all int32, device memory) into the dense inputs of the
@@ -445,7 +460,10 @@ int gcgcn_debug_chain_plan(int bwd, int B, int N, int D, int L, int H, int ragge
  * given.  out[6] = compact (the pair passes run on the pairs that exist), the forward pass and the d eh / d et passes (0
  * head_gemm_kernel, 1 head_bil2_kernel: 64-pair tiles, 2 head_bil3_kernel: 128-pair tiles), d W_b (0 head_gemm_kernel<4>, 1
  * head_dw_kernel), then for the forward and the d eh / d et passes whether both launch shapes are issued and the device-side
- * pair count selects one.  Host-only. */
+ * pair count selects one.  A call announced with gcgcn_set_option("head_matmul", 1) (see gcgcn_head_fwd; this call takes the
+ * announcement like a head call) answers 3, 3, 2 for the kernels (head_bf16_pass_kernel for the passes, head_bf16_dw_kernel for d W_b
+ * and d W_c; one launch of 128-pair tiles per pass, so the last two answers are 0); announced with any other value but 0 it fails.
+ * Not announced, its answers are what they were.  Host-only. */
 int gcgcn_debug_head_plan(int B, int N, int R, int ragged, int32_t* out);
 
 /* ---- test hook: which launch a pass over the edge tensor gets ----------------------------------------------------------
