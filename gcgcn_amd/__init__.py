@@ -11,10 +11,10 @@ from .functional import (TrainStats, TrainStatsResult, lstm_layer, manual_seed, 
 from .bert import BertConfig, BertModel, load_pretrained_state_dict  # noqa: F401
 from . import bert, evaluation, functional, models, optim, params, training  # noqa: F401
 from .evaluation import EvalResult, RelationEvaluator, evaluate  # noqa: F401
-from .optim import FusedAdam, GraphedTrainStep  # noqa: F401
+from .optim import FusedAdam, GraphedTrainStep, bert_param_groups  # noqa: F401
 from .training import TrainEpochResult, train_epoch  # noqa: F401
 
 __all__ = ["BertConfig", "BertModel", "load_pretrained_state_dict", "GraphConv", "GATAttention", "MultiHeadAttention", "GraphConvolution", "MultiGraphConvolution", "GraphHops",
            "EdgeFeatureProducer", "ClassifierHead", "GraphModelTail",
-           "manual_seed", "pair_bce_loss", "lstm_layer", "token_embed", "token_context", "FusedAdam", "GraphedTrainStep", "RelationEvaluator", "EvalResult", "evaluate", "TrainStats", "TrainStatsResult", "train_epoch", "TrainEpochResult",
+           "manual_seed", "pair_bce_loss", "lstm_layer", "token_embed", "token_context", "FusedAdam", "GraphedTrainStep", "bert_param_groups", "RelationEvaluator", "EvalResult", "evaluate", "TrainStats", "TrainStatsResult", "train_epoch", "TrainEpochResult",
            "bert", "evaluation", "functional", "models", "optim", "params", "training"]

@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # GCGCN_LIB=<path> loads another build of the same ABI (A/B timing of kernel variants)
 LIB_PATH = os.environ.get("GCGCN_LIB") or os.path.join(_HERE, "lib", "libgcgcn_hip.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcgcn.h")
+OPTIM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcgcn_optim.h")    # the optimiser extension, symbols gcopt_*
 
 ABI_VERSION = 7
 
@@ -45,10 +46,11 @@ class EdgeRide(ctypes.Structure):
 # ---- the header's declarations as ctypes ---------------------------------------------------------------------------------------
 _SCALARS = {"int": c_int, "int32_t": c_int, "int64_t": c_int64, "uint64_t": c_uint64, "float": c_float, "double": c_double}
 _DECL = re.compile(r"([\w\s*]+?)\b(gcgcn_\w+)\s*\(([^()]*)\)")                     # <ret> gcgcn_<name>(<args>)
+_DECL_OPTIM = re.compile(r"([\w\s*]+?)\b(gcopt_\w+)\s*\(([^()]*)\)")               # the same in gcgcn_optim.h
 _STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;")
 
 
-def _ctype(text: str, symbol: str, named: bool = True):
+def _ctype(text: str, symbol: str, named: bool = True, header: str = "include/gcgcn.h"):
     """One parameter or field ("const float* x", "int B"), or with named=False one return type ("int64_t", "void"), as ctypes.
     const char* is c_char_p, every other pointer c_void_p, a scalar what _SCALARS says; anything else raises."""
     toks = text.replace("*", " * ").split()
@@ -60,12 +62,14 @@ def _ctype(text: str, symbol: str, named: bool = True):
     if toks and toks[0] in _SCALARS and len(toks) <= 1 + named:
         return _SCALARS[toks[0]]
     bad = toks[0] if toks and toks[0] not in _SCALARS else " ".join(toks[1:]) or "an empty declaration"
-    raise RuntimeError(f"gcgcn_amd: cannot bind {symbol}: no ctypes type for {bad!r} in {text.strip()!r} (include/gcgcn.h)")
+    raise RuntimeError(f"gcgcn_amd: cannot bind {symbol}: no ctypes type for {bad!r} in {text.strip()!r} ({header})")
 
 
-def _parse_header(text: str):
+def _parse_header(text: str, pattern=_DECL, header: str = "include/gcgcn.h"):
     """The text of gcgcn.h -> (name -> (restype, argtypes), struct -> [(field, type)]), both in the header's order.  Comments,
-    preprocessor lines and the extern "C" braces are dropped; every statement left must be a typedef struct or a gcgcn_* declaration."""
+    preprocessor lines and the extern "C" braces are dropped; every statement left must be a typedef struct or a gcgcn_* declaration
+    (`pattern`: what a declaration looks like, and `header`: the file's name in error messages; gcgcn_optim.h's symbols are
+    gcopt_*)."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
     structs = {}
@@ -73,18 +77,19 @@ def _parse_header(text: str):
         structs[name] = []
         for decl in filter(str.strip, body.split(";")):
             first, *more = decl.split(",")                                          # "int32_t B, N, D": one type, several names
-            ctype = _ctype(first, name)
+            ctype = _ctype(first, name, header=header)
             if more and "*" in first:
-                raise RuntimeError(f"gcgcn_amd: cannot bind {name}: several names behind a pointer in {decl.strip()!r} (include/gcgcn.h)")
+                raise RuntimeError(f"gcgcn_amd: cannot bind {name}: several names behind a pointer in {decl.strip()!r} ({header})")
             structs[name] += [(n.replace("*", " ").split()[-1], ctype) for n in (first, *more)]
     sigs = {}
     for stmt in filter(str.strip, re.sub(r'extern\s+"C"\s*\{|\}', " ", _STRUCT.sub(" ", text)).split(";")):
-        m = _DECL.fullmatch(stmt.strip())
+        m = pattern.fullmatch(stmt.strip())
         if not m or m.group(2) in sigs:
-            raise RuntimeError(f"gcgcn_amd: cannot bind {m.group(2) if m else 'include/gcgcn.h'}: "
+            raise RuntimeError(f"gcgcn_amd: cannot bind {m.group(2) if m else header}: "
                                f"{'declared twice' if m else 'not a declaration'}: {' '.join(stmt.split())[:100]!r}")
         ret, name, args = m.groups()
-        sigs[name] = (_ctype(ret, name, named=False), [] if args.strip() == "void" else [_ctype(a, name) for a in args.split(",")])
+        sigs[name] = (_ctype(ret, name, named=False, header=header),
+                      [] if args.strip() == "void" else [_ctype(a, name, header=header) for a in args.split(",")])
     return sigs, structs
 
 
@@ -101,7 +106,18 @@ def _load_header():
     return sigs
 
 
+def _load_optim_header():
+    if not os.path.exists(OPTIM_HEADER_PATH):
+        raise RuntimeError(f"gcgcn_amd: {OPTIM_HEADER_PATH} not found. The binding is derived from the C headers of the source tree.")
+    with open(OPTIM_HEADER_PATH) as f:
+        sigs, structs = _parse_header(f.read(), _DECL_OPTIM, "include/gcgcn_optim.h")
+    if structs:
+        raise RuntimeError(f"gcgcn_amd: include/gcgcn_optim.h declares structs {list(structs)}; its tables travel as const void*")
+    return sigs
+
+
 SIGNATURES = _load_header()  # name -> (restype, argtypes), in the order of include/gcgcn.h
+OPTIM_SIGNATURES = _load_optim_header()  # the same for include/gcgcn_optim.h; a table of its own, so the core's stays what is recorded
 
 _lib = None
 
@@ -115,7 +131,7 @@ def lib() -> ctypes.CDLL:
                 f"gcgcn_amd: {LIB_PATH} not found. Build it with `make -C gcgcn_amd/csrc` "
                 "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args
