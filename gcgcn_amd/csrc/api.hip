@@ -142,9 +142,21 @@ int head_matmul_take() {
   g_head_matmul_next = 0;
   return v;
 }
+// "lstm_recurrent" travels the same way: the recurrent argument (0 = fp32, 1 = bf16 operands) of the calling thread's next
+// gcgcn_lstm_fwd / _fwd_len / _bwd / _bwd_len, which takes it first -- whatever it then returns -- and leaves 0 behind.
+static thread_local int g_lstm_recurrent_next = 0;
+int lstm_recurrent_take() {
+  const int v = g_lstm_recurrent_next;
+  g_lstm_recurrent_next = 0;
+  return v;
+}
 static bool set_opt(const char* name, int value) {
   if (strcmp(name, "head_matmul") == 0) {
     g_head_matmul_next = value;
+    return true;
+  }
+  if (strcmp(name, "lstm_recurrent") == 0) {
+    g_lstm_recurrent_next = value;
     return true;
   }
   for (Opt& o : g_opts)
@@ -1074,10 +1086,11 @@ int gcgcn_lstm_fwd(int B, int T, int I, int H, int nd, const float* x, const flo
 
 int gcgcn_lstm_fwd_len(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* bias,
                        const float* h0, const float* c0, float* out, float* gates, float* csave, const int* lens, void* stream) {
+  const int recurrent = lstm_recurrent_take();   // first: whatever this call returns, the announcement was for it
   GC_TRY(lstm_shape_ok("lstm_fwd", B, T, I, H, nd));
   GC_REQUIRE(x && w_ih && w_hh && bias && h0 && c0 && out && gates, "lstm_fwd: null pointer");
   GC_REQUIRE((((uintptr_t)w_hh) & 15) == 0, "lstm_fwd: w_hh must be 16-byte aligned");
-  return lstm_fwd(B, T, I, nd, x, w_ih, w_hh, bias, h0, c0, out, gates, csave, lens, (hipStream_t)stream);
+  return lstm_fwd(B, T, I, nd, x, w_ih, w_hh, bias, h0, c0, out, gates, csave, lens, recurrent, (hipStream_t)stream);
 }
 
 int gcgcn_lstm_bwd(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* h0,
@@ -1091,6 +1104,7 @@ int gcgcn_lstm_bwd_len(int B, int T, int I, int H, int nd, const float* x, const
                        const float* c0, const float* out, const float* gates, const float* csave, const float* dout, float* dgates,
                        float* dx, float* dw_ih, float* dw_hh, float* db, float* dh0, float* dc0, void* ws, int64_t ws_bytes,
                        const int* lens, void* stream) {
+  const int recurrent = lstm_recurrent_take();   // first: whatever this call returns, the announcement was for it
   GC_TRY(lstm_shape_ok("lstm_bwd", B, T, I, H, nd));
   GC_REQUIRE(x && w_ih && w_hh && h0 && c0 && out && gates && csave && dout && dgates && dx && dw_ih && dw_hh && db && dh0 && dc0 && ws,
              "lstm_bwd: null pointer");
@@ -1101,7 +1115,7 @@ int gcgcn_lstm_bwd_len(int B, int T, int I, int H, int nd, const float* x, const
   GC_REQUIRE(ws_bytes >= gcgcn_lstm_ws_bytes(B, T, I, H, nd), "lstm_bwd: workspace of %lld bytes needed (gcgcn_lstm_ws_bytes)",
              (long long)gcgcn_lstm_ws_bytes(B, T, I, H, nd));
   return lstm_bwd(B, T, I, nd, x, w_ih, w_hh, h0, c0, out, gates, csave, dout, dgates, dx, dw_ih, dw_hh, db, dh0, dc0, (float*)ws,
-                  ws_bytes / (int64_t)sizeof(float), lens, (hipStream_t)stream);
+                  ws_bytes / (int64_t)sizeof(float), lens, recurrent, (hipStream_t)stream);
 }
 
 // ---- the token front end (frontend.hip) ------------------------------------------------------------------------------------------

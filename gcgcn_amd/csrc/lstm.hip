@@ -24,18 +24,58 @@
 // Lane maps of the 16x16x4 form (lane l, c16 = l & 15, q = l >> 4): A[row c16][k q], B[k q][col c16], C/D [row 4 q + r][col c16].
 // The sum over k may run in any order as long as A and B agree, so k-step s of lane group q takes k = q * (K / 4) + s: a lane's A
 // values are then CONTIGUOUS in the LDS row (ds_read_b128) and the forward's weights contiguous in W_hh's rows.
+//
+// bf16 recurrence (recurrent = 1; DESIGN.md section 8.7, "bf16 recurrence").  The recurrence kernels are templates on BF as well;
+// BF = false is the code above, unchanged.  With BF the two recurrent products -- h_{t-1} W_hh^T forward, dgates_t W_hh backward --
+// take bf16 operands on v_mfma_f32_16x16x32_bf16 and accumulate in fp32: the wave's slice of W_hh is rounded once at load (64
+// registers instead of 128), the LDS image holds the rounding of h (of dgates_t) and nothing else is rounded -- the input
+// projection, the cell update, c, out, the saved gates, csave and the dgates that go to global memory are the fp32 values; the
+// cell update, the requests one step ahead and the length selects are the SAME statements for both formats.
+// Lane maps of the 16x16x32 form: A[row c16][k 8 q + j], B[k 8 q + j][col c16], j = 0 .. 7 (one ds_read_b128 per lane and
+// 32-deep k-block), C/D as above.  A and B use the instruction's own k order.
+// The bf16 LDS image (lstm_bf_row): rows of K bf16, K * 2 a multiple of 256 bytes.  ds_read_b128 is served in four groups of 16
+// lanes, {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32, i.e. rows {0-3, 12-15} of lane group q with rows {4-11} of
+// lane group q + 1, over 64 banks = 16 slots of 16 bytes; a lane reads slot (row's first slot + 4 kb + q) mod 16.  A constant
+// odd pitch cannot separate the two halves of such a group (row -> slot is then a permutation of all 16 slots, and the q + 1
+// rows land one slot further), so the pitch is K * 2 + 32 bytes (2 slots: rows 8 apart share a slot, rows {0-3, 12-15} take the
+// eight even slots, rows {4-11} + 1 the eight odd ones).  The 2-byte writes go to 32 banks in halves of 32 lanes: lane groups q
+// and q + 1 write rows 4 apart, 16 consecutive units each (8 banks).  Four pitches are a multiple of 32 banks, so rows 4 .. 11
+// start another 32 bytes later: the rows of a half are then 8 (q = 0, 1) and 24 (q = 2, 3) banks apart, and the reads keep
+// their even slots (2 more for all of rows 4 .. 11).  Neither access conflicts.
 #include "lstm.hpp"
 #include "gemm.hpp"
 
 namespace gc {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int LH = LSTM_H;
 constexpr int LROWS = 16;            // batch rows of a workgroup = rows of an MFMA tile
 constexpr int LHS = LH + 4;          // LDS row stride of the h image: rows 4 banks apart
 constexpr int LGS = 4 * LH + 4;      // ... of the dgates image
 static_assert(2 * LROWS * LGS * sizeof(float) <= 160 * 1024, "LDS of one compute unit");
+constexpr int LHB = LH + 16;         // bf16 images: elements per row of the h image (288 bytes) ...
+constexpr int LGB = 4 * LH + 16;     // ... and of the dgates image (1056 bytes); rows are placed by lstm_bf_row
+constexpr int LSTM_FP32 = 0, LSTM_BF16 = 1;   // the recurrent argument of a call (lstm.hpp)
+
+// element offset of row `row` of a bf16 image of pitch `pitch`: rows 4 .. 11 start 16 elements (32 bytes) later (top of the file)
+__device__ __forceinline__ int lstm_bf_row(int row, int pitch) { return row * pitch + 16 * (((row + 4) >> 3) & 1); }
+// one rounding to bf16, nearest even (what tensor.to(torch.bfloat16) does)
+__device__ __forceinline__ __bf16 lstm_bf(float x) { return static_cast<__bf16>(x); }
+// eight consecutive floats -> the eight bf16 of one operand fragment
+__device__ __forceinline__ bf16x8 lstm_bf8(const float4 lo, const float4 hi) {
+  const f32x2 a = {lo.x, lo.y}, b = {lo.z, lo.w}, c = {hi.x, hi.y}, d = {hi.z, hi.w};
+  const bf16x2 pa = __builtin_convertvector(a, bf16x2), pb = __builtin_convertvector(b, bf16x2);
+  const bf16x2 pc = __builtin_convertvector(c, bf16x2), pd = __builtin_convertvector(d, bf16x2);
+  return bf16x8{pa[0], pa[1], pb[0], pb[1], pc[0], pc[1], pd[0], pd[1]};
+}
+// The build's MFMA hazard check prices every low-precision matrix instruction as a 16-pass one (19 wait states before its result is
+// read); the compiler leaves what this shorter one needs.  Twenty wait states once per step satisfy the stricter count (a step is
+// thousands of cycles).  The accumulators are operands of the statement so that no read of them moves in front of it.
+__device__ __forceinline__ void lstm_settle(f32x4 (&a)[4]) { asm volatile("s_nop 15\n\ts_nop 3" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3])); }
 
 __device__ __forceinline__ float lstm_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 __device__ __forceinline__ int lstm_len(const int* __restrict__ lens, int b, int T) {
@@ -53,26 +93,43 @@ __device__ __forceinline__ int lstm_tile_len(const int* __restrict__ lens, int b
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
-template <bool LEN>
+template <bool LEN, bool BF>
 __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__ w_hh, const float* __restrict__ h0,
                                                        const float* __restrict__ c0, float* __restrict__ gates, float* __restrict__ out,
                                                        float* __restrict__ csave, const int* __restrict__ lens, const int B, const int T,
                                                        const int nd) {
-  __shared__ __attribute__((aligned(16))) float hbuf[2][LROWS * LHS];
+  // the h image, double-buffered: fp32 [2][16][LHS], or bf16 [2] x 16 rows placed by lstm_bf_row(., LHB)
+  constexpr int IMG = BF ? LROWS * LHB : LROWS * LHS;   // elements of one buffer
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * IMG * (BF ? sizeof(__bf16) : sizeof(float))];
+  float* const hbuf = reinterpret_cast<float*>(lds);
+  __bf16* const hbf = reinterpret_cast<__bf16*>(lds);
   const int dir = blockIdx.y, b0 = blockIdx.x * LROWS;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, c16 = l & 15, q = l >> 4;
   const int u = 16 * w + c16;   // the hidden unit of this lane's accumulator column
+  const int wrow = BF ? lstm_bf_row(4 * q, LHB) + u : 4 * q * LHS + u;   // the lane's first row in the image; its rows are
+  constexpr int wstep = BF ? LHB : LHS;                                  // 4 q + r, all on one side of lstm_bf_row's shift
 
-  // B operand: W_hh^T[k][g H + u] = W_hh[g H + u][k], k = 32 q + s
-  float wr[4][32];
+  // B operand: W_hh^T[k][g H + u] = W_hh[g H + u][k]; fp32: k = 32 q + s; bf16: k-block kb holds k = 32 kb + 8 q .. + 7, rounded here
+  float wr[BF ? 1 : 4][BF ? 1 : 32];
+  bf16x8 wb[BF ? 4 : 1][BF ? 4 : 1];
   const float* wd = w_hh + (long)dir * 4 * LH * LH;
+  if constexpr (BF) {
 #pragma unroll
-  for (int g = 0; g < 4; ++g)
+    for (int g = 0; g < 4; ++g)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float4 v = *reinterpret_cast<const float4*>(wd + (long)(g * LH + u) * LH + 32 * q + 4 * j);
-      wr[g][4 * j] = v.x, wr[g][4 * j + 1] = v.y, wr[g][4 * j + 2] = v.z, wr[g][4 * j + 3] = v.w;
-    }
+      for (int kb = 0; kb < 4; ++kb) {
+        const float* wp = wd + (long)(g * LH + u) * LH + 32 * kb + 8 * q;
+        wb[g][kb] = lstm_bf8(*reinterpret_cast<const float4*>(wp), *reinterpret_cast<const float4*>(wp + 4));
+      }
+  } else {
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float4 v = *reinterpret_cast<const float4*>(wd + (long)(g * LH + u) * LH + 32 * q + 4 * j);
+        wr[g][4 * j] = v.x, wr[g][4 * j + 1] = v.y, wr[g][4 * j + 2] = v.z, wr[g][4 * j + 3] = v.w;
+      }
+  }
 
   // the lane's four rows (C/D map): batch entries b0 + 4 q + r.  Rows past B read zeros (through a clamped address) and store nothing.
   bool valid[4];
@@ -90,7 +147,8 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
     const long s0 = ((long)dir * B + bc) * LH + u;
     c[r] = valid[r] ? c0[s0] : 0.f;
     hk[r] = valid[r] ? h0[s0] : 0.f;
-    hbuf[0][(4 * q + r) * LHS + u] = hk[r];
+    if constexpr (BF) hbf[wrow + r * wstep] = lstm_bf(hk[r]);
+    else hbuf[wrow + r * wstep] = hk[r];
     len[r] = LEN ? lstm_len(lens, bc, T) : T;
   }
   const long gstep = (long)nd * 4 * LH, ostep = (long)nd * LH;
@@ -118,18 +176,29 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
 #pragma unroll
       for (int r = 0; r < 4; ++r) gn[g][r] = gates[grow[r] + tn * gstep + g * LH];
 
-    const float* hp = hbuf[s & 1] + c16 * LHS + 32 * q;
+    if constexpr (BF) {   // 16 instructions; the four gates' chains interleaved, a dependent one three instructions later
+      const __bf16* hp = hbf + (s & 1) * IMG + lstm_bf_row(c16, LHB) + 8 * q;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float4 a = *reinterpret_cast<const float4*>(hp + 4 * j);
-      const float av[4] = {a.x, a.y, a.z, a.w};
+      for (int kb = 0; kb < 4; ++kb) {
+        const bf16x8 a = *reinterpret_cast<const bf16x8*>(hp + 32 * kb);
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
+        for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, wb[g][kb], acc[g], 0, 0, 0);
+      }
+      lstm_settle(acc);
+    } else {
+      const float* hp = hbuf + (s & 1) * IMG + c16 * LHS + 32 * q;
 #pragma unroll
-        for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], wr[g][4 * j + e], acc[g], 0, 0, 0);
+      for (int j = 0; j < 8; ++j) {
+        const float4 a = *reinterpret_cast<const float4*>(hp + 4 * j);
+        const float av[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], wr[g][4 * j + e], acc[g], 0, 0, 0);
+      }
     }
 
-    float* hn = hbuf[(s & 1) ^ 1];
+    const int hn = ((s & 1) ^ 1) * IMG + wrow;   // the lane's first row in the next buffer
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float gi = lstm_sigmoid(acc[0][r]), gf = lstm_sigmoid(acc[1][r]), gg = tanhf(acc[2][r]), go = lstm_sigmoid(acc[3][r]);
@@ -139,7 +208,8 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
         c[r] = act ? cn : c[r];
         const float h = go * tanhf(cn);
         hk[r] = act ? h : hk[r];
-        hn[(4 * q + r) * LHS + u] = hk[r];
+        if constexpr (BF) hbf[hn + r * wstep] = lstm_bf(hk[r]);
+        else hbuf[hn + r * wstep] = hk[r];
         if (valid[r]) {
           out[orow[r] + t * ostep] = act ? h : 0.f;
           if (csave && act) {
@@ -151,7 +221,8 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
       } else {
         c[r] = __builtin_fmaf(gf, c[r], gi * gg);
         const float h = go * tanhf(c[r]);
-        hn[(4 * q + r) * LHS + u] = h;
+        if constexpr (BF) hbf[hn + r * wstep] = lstm_bf(h);
+        else hbuf[hn + r * wstep] = h;
         if (valid[r]) {
           out[orow[r] + t * ostep] = h;
           if (csave) {
@@ -177,22 +248,37 @@ __global__ __launch_bounds__(512) void lstm_fwd_kernel(const float* __restrict__
 // nothing to the product, so the row keeps its old dh.  c_prev is c0 at the ROW's first step: t = lens[b] - 1 in the reverse
 // direction.  Whatever is read at an inactive step (the saved gates, csave, dout: possibly never written, possibly NaN) is
 // replaced by 0 through a select, never multiplied by a 0 / 1 flag.
-template <bool LEN>
+template <bool LEN, bool BF>
 __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__ w_hh, const float* __restrict__ c0,
                                                        const float* __restrict__ gates, const float* __restrict__ csave,
                                                        const float* __restrict__ dout, float* __restrict__ dgates, float* __restrict__ dh0,
                                                        float* __restrict__ dc0, const int* __restrict__ lens, const int B, const int T,
                                                        const int nd) {
-  __shared__ __attribute__((aligned(16))) float gbuf[2][LROWS * LGS];
+  // the dgates_t image, double-buffered: fp32 [2][16][LGS], or bf16 [2] x 16 rows placed by lstm_bf_row(., LGB)
+  constexpr int IMG = BF ? LROWS * LGB : LROWS * LGS;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[2 * IMG * (BF ? sizeof(__bf16) : sizeof(float))];
+  float* const gbuf = reinterpret_cast<float*>(lds);
+  __bf16* const gbf = reinterpret_cast<__bf16*>(lds);
   const int dir = blockIdx.y, b0 = blockIdx.x * LROWS;
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, c16 = l & 15, q = l >> 4;
   const int u = 16 * w + c16;
+  const int wrow = BF ? lstm_bf_row(4 * q, LGB) + u : 4 * q * LGS + u;   // as in the forward
+  constexpr int wstep = BF ? LGB : LGS;
 
-  // B operand of dh_rec = dgates W_hh: W_hh[k][u], k = 128 q + s over the 4H gate columns
-  float wr[128];
+  // B operand of dh_rec = dgates W_hh: W_hh[k][u] over the 4H gate columns; fp32: k = 128 q + s; bf16: k-block kb holds
+  // k = 32 kb + 8 q .. + 7, rounded here (a strided load, once per launch)
+  float wr[BF ? 1 : 128];
+  bf16x8 wb[BF ? 16 : 1];
   const float* wd = w_hh + (long)dir * 4 * LH * LH;
+  if constexpr (BF) {
 #pragma unroll
-  for (int s = 0; s < 128; ++s) wr[s] = wd[(long)(128 * q + s) * LH + u];
+    for (int kb = 0; kb < 16; ++kb)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) wb[kb][j] = lstm_bf(wd[(long)(32 * kb + 8 * q + j) * LH + u]);
+  } else {
+#pragma unroll
+    for (int s = 0; s < 128; ++s) wr[s] = wd[(long)(128 * q + s) * LH + u];
+  }
 
   bool valid[4];
   long grow[4], orow[4], srow[4];
@@ -229,7 +315,7 @@ __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__
 
   for (int s = 0; s < Lt; ++s) {
     const int fs = Lt - 1 - s, t = dir ? Lt - 1 - fs : fs;
-    float* gw = gbuf[s & 1];
+    const int gw = (s & 1) * IMG;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float gi, gf, gg, go, dyv, cv, cpv;
@@ -255,8 +341,13 @@ __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__
       } else {
         dc[r] = dcv * gf;
       }
-      float* lp = gw + (4 * q + r) * LGS + u;
-      lp[0] = da_i, lp[LH] = da_f, lp[2 * LH] = da_g, lp[3 * LH] = da_o;
+      if constexpr (BF) {   // the image holds the rounding; global memory (below) the fp32 values
+        __bf16* lp = gbf + gw + wrow + r * wstep;
+        lp[0] = lstm_bf(da_i), lp[LH] = lstm_bf(da_f), lp[2 * LH] = lstm_bf(da_g), lp[3 * LH] = lstm_bf(da_o);
+      } else {
+        float* lp = gbuf + gw + wrow + r * wstep;
+        lp[0] = da_i, lp[LH] = da_f, lp[2 * LH] = da_g, lp[3 * LH] = da_o;
+      }
       if (valid[r]) {
         float* gp = dgates + grow[r] + t * gstep;
         gp[0] = da_i, gp[LH] = da_f, gp[2 * LH] = da_g, gp[3 * LH] = da_o;
@@ -271,14 +362,24 @@ __global__ __launch_bounds__(512) void lstm_bwd_kernel(const float* __restrict__
     f32x4 acc[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) acc[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* ap = gw + c16 * LGS + 128 * q;
+    if constexpr (BF) {   // 16 instructions on the same four chains: k-block kb goes to chain kb & 3
+      const __bf16* ap = gbf + gw + lstm_bf_row(c16, LGB) + 8 * q;
 #pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      const float4 a = *reinterpret_cast<const float4*>(ap + 4 * j);
-      acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, wr[4 * j], acc[0], 0, 0, 0);       // four independent chains: the
-      acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, wr[4 * j + 1], acc[1], 0, 0, 0);   // instruction's dependent latency
-      acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, wr[4 * j + 2], acc[2], 0, 0, 0);   // exceeds its issue interval
-      acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, wr[4 * j + 3], acc[3], 0, 0, 0);
+      for (int kb = 0; kb < 16; ++kb) {
+        const bf16x8 a = *reinterpret_cast<const bf16x8*>(ap + 32 * kb);
+        acc[kb & 3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, wb[kb], acc[kb & 3], 0, 0, 0);
+      }
+      lstm_settle(acc);
+    } else {
+      const float* ap = gbuf + gw + c16 * LGS + 128 * q;
+#pragma unroll
+      for (int j = 0; j < 32; ++j) {
+        const float4 a = *reinterpret_cast<const float4*>(ap + 4 * j);
+        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, wr[4 * j], acc[0], 0, 0, 0);       // four independent chains: the
+        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, wr[4 * j + 1], acc[1], 0, 0, 0);   // instruction's dependent latency
+        acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, wr[4 * j + 2], acc[2], 0, 0, 0);   // exceeds its issue interval
+        acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, wr[4 * j + 3], acc[3], 0, 0, 0);
+      }
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -322,19 +423,19 @@ __global__ __launch_bounds__(256) void lstm_hprev_kernel(const float* __restrict
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
 int lstm_fwd(int B, int T, int I, int nd, const float* x, const float* w_ih, const float* w_hh, const float* bias, const float* h0,
-             const float* c0, float* out, float* gates, float* csave, const int* lens, hipStream_t st) {
+             const float* c0, float* out, float* gates, float* csave, const int* lens, int recurrent, hipStream_t st) {
   const long BT = (long)B * T;
   const int G = nd * 4 * LH;
+  GC_REQUIRE(recurrent == LSTM_FP32 || recurrent == LSTM_BF16, "lstm_fwd: lstm_recurrent = %d (0 = fp32, 1 = bf16)", recurrent);
   GemmArgs g = gemm_nt(x, I, w_ih, I, gates, G, (int)BT, G, I).tagged("lstm_gemm");   // gates = X W_ih^T + b, both directions
   g.bias = bias;
   GC_TRY(gemm(g, st, 0, 1));
-  if (lens)
-    GC_LAUNCH_TIMED("lstm_fwd", 2.0 * BT * G * LH, lstm_fwd_kernel<true>, dim3(cdiv(B, LROWS), nd), dim3(512), 0, st, w_hh, h0, c0, gates,
-                    out, csave, lens, B, T, nd);
-  else
-    GC_LAUNCH_TIMED("lstm_fwd", 2.0 * BT * G * LH, lstm_fwd_kernel<false>, dim3(cdiv(B, LROWS), nd), dim3(512), 0, st, w_hh, h0, c0, gates,
-                    out, csave, lens, B, T, nd);
-  return check_launch("lstm_fwd");
+  const bool bf = recurrent == LSTM_BF16;
+  const auto kernel = lens ? (bf ? lstm_fwd_kernel<true, true> : lstm_fwd_kernel<true, false>)
+                           : (bf ? lstm_fwd_kernel<false, true> : lstm_fwd_kernel<false, false>);
+  const char* tag = bf ? "lstm_fwd_bf16" : "lstm_fwd";
+  GC_LAUNCH_TIMED(tag, 2.0 * BT * G * LH, kernel, dim3(cdiv(B, LROWS), nd), dim3(512), 0, st, w_hh, h0, c0, gates, out, csave, lens, B, T, nd);
+  return check_launch(tag);
 }
 
 static long lstm_col_elems(int nd) { return (long)COL_RIDE_SLICES * nd * 4 * LH; }
@@ -344,22 +445,23 @@ long lstm_ws_elems(int B, int T, int I, int nd) { return (long)B * T * nd * LH +
 
 int lstm_bwd(int B, int T, int I, int nd, const float* x, const float* w_ih, const float* w_hh, const float* h0, const float* c0,
              const float* out, const float* gates, const float* csave, const float* dout, float* dgates, float* dx, float* dw_ih,
-             float* dw_hh, float* db, float* dh0, float* dc0, float* ws, long ws_elems, const int* lens, hipStream_t st) {
+             float* dw_hh, float* db, float* dh0, float* dc0, float* ws, long ws_elems, const int* lens, int recurrent, hipStream_t st) {
   const long BT = (long)B * T;
   const int G = nd * 4 * LH;
+  GC_REQUIRE(recurrent == LSTM_FP32 || recurrent == LSTM_BF16, "lstm_bwd: lstm_recurrent = %d (0 = fp32, 1 = bf16)", recurrent);
   GC_REQUIRE(ws_elems >= lstm_ws_elems(B, T, I, nd), "lstm_bwd: workspace of %ld floats needed", lstm_ws_elems(B, T, I, nd));
   float* hprev = ws;
   float* split = ws + BT * nd * LH;
   const long split_elems = lstm_split_elems(I, nd);
   float* part = split + split_elems;
 
-  if (lens)
-    GC_LAUNCH_TIMED("lstm_bwd", 2.0 * BT * G * LH, lstm_bwd_kernel<true>, dim3(cdiv(B, LROWS), nd), dim3(512), 0, st, w_hh, c0, gates, csave,
-                    dout, dgates, dh0, dc0, lens, B, T, nd);
-  else
-    GC_LAUNCH_TIMED("lstm_bwd", 2.0 * BT * G * LH, lstm_bwd_kernel<false>, dim3(cdiv(B, LROWS), nd), dim3(512), 0, st, w_hh, c0, gates, csave,
-                    dout, dgates, dh0, dc0, lens, B, T, nd);
-  GC_TRY(check_launch("lstm_bwd"));
+  const bool bf = recurrent == LSTM_BF16;
+  const auto kernel = lens ? (bf ? lstm_bwd_kernel<true, true> : lstm_bwd_kernel<true, false>)
+                           : (bf ? lstm_bwd_kernel<false, true> : lstm_bwd_kernel<false, false>);
+  const char* tag = bf ? "lstm_bwd_bf16" : "lstm_bwd";
+  GC_LAUNCH_TIMED(tag, 2.0 * BT * G * LH, kernel, dim3(cdiv(B, LROWS), nd), dim3(512), 0, st, w_hh, c0, gates, csave, dout, dgates, dh0, dc0,
+                  lens, B, T, nd);
+  GC_TRY(check_launch(tag));
   {
     ProfScope ps("lstm_hprev", st);
     hipLaunchKernelGGL(lstm_hprev_kernel, dim3(cdiv(BT * nd * (LH / 4), 256)), dim3(256), 0, st, out, h0, hprev, lens, B, T, nd);

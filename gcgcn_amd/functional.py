@@ -1304,21 +1304,30 @@ def pair_bce_loss(logits, labels, n_valid=None, stats=None):
 class LstmFn(torch.autograd.Function):
     """(x[B,T,I], w_ih[nd*4H,I], w_hh[nd*4H,H], bias[nd*4H], h0[nd,B,H], c0[nd,B,H]) -> out[B,T,nd*H]: one ``nn.LSTM`` layer over
     all T steps with the directions' parameters stacked and ``bias = b_ih + b_hh`` (``lstm_layer`` stacks and splits them).
-    ``lens``: ``None`` or the rows' lengths, int32 ``[B]`` on the device (saved for the backward)."""
+    ``lens``: ``None`` or the rows' lengths, int32 ``[B]`` on the device (saved for the backward).  ``recurrent``: 0 = fp32, 1 = bf16
+    operands for the recurrent products (``lstm_layer``); kept for the backward, announced before each of the two calls."""
 
     @staticmethod
-    def forward(ctx, x, w_ih, w_hh, bias, h0, c0, lens=None):
+    def _call(recurrent: int, name: str, *args):
+        """One LSTM entry point with the argument recurrent.  0: the call alone, as always.  1: announced to the library on this
+        thread right before the call, which takes the announcement (include/gcgcn.h, the LSTM block)."""
+        if recurrent:
+            call("gcgcn_set_option", b"lstm_recurrent", recurrent)
+        call(name, *args)
+
+    @staticmethod
+    def forward(ctx, x, w_ih, w_hh, bias, h0, c0, lens=None, recurrent=0):
         B, T, I = x.shape
         nd, H = h0.shape[0], h0.shape[2]
         need_grad = any(ctx.needs_input_grad)
         out = torch.empty(B, T, nd * H, device=x.device)
         gates = torch.empty(B * T, nd * 4 * H, device=x.device)
         csave = torch.empty(B, T, nd * H, device=x.device) if need_grad else None
-        call("gcgcn_lstm_fwd_len", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(bias), _p(h0), _p(c0), _p(out), _p(gates), _p(csave),
-             _p(lens), _stream())     # null lengths: every step of every row
+        LstmFn._call(recurrent, "gcgcn_lstm_fwd_len", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(bias), _p(h0), _p(c0), _p(out),
+                     _p(gates), _p(csave), _p(lens), _stream())     # null lengths: every step of every row
         written = (out, gates) if csave is None else (out, gates, csave)
         torch.autograd.graph.increment_version(written)     # raw-pointer writes, as in optim._written
-        ctx.has_lens = lens is not None
+        ctx.has_lens, ctx.recurrent = lens is not None, recurrent
         if need_grad:
             ctx.save_for_backward(x, w_ih, w_hh, h0, c0, out, gates, csave, *(() if lens is None else (lens,)))
         return out
@@ -1338,10 +1347,11 @@ class LstmFn(torch.autograd.Function):
         db = torch.empty(nd * 4 * H, device=x.device)
         dh0, dc0 = torch.empty_like(h0), torch.empty_like(c0)
         ws = _f32_buf(_bytes_or_raise("gcgcn_lstm_ws_bytes", B, T, I, H, nd), x.device)
-        call("gcgcn_lstm_bwd_len", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(h0), _p(c0), _p(out), _p(gates), _p(csave), _p(dout),
-             _p(dgates), _p(dx), _p(dw_ih), _p(dw_hh), _p(db), _p(dh0), _p(dc0), _p(ws), ws.numel() * 4, _p(lens), _stream())
+        LstmFn._call(ctx.recurrent, "gcgcn_lstm_bwd_len", B, T, I, H, nd, _p(x), _p(w_ih), _p(w_hh), _p(h0), _p(c0), _p(out), _p(gates),
+                     _p(csave), _p(dout), _p(dgates), _p(dx), _p(dw_ih), _p(dw_hh), _p(db), _p(dh0), _p(dc0), _p(ws), ws.numel() * 4,
+                     _p(lens), _stream())
         torch.autograd.graph.increment_version((dx, dw_ih, dw_hh, db, dh0, dc0))
-        return dx, dw_ih, dw_hh, db, dh0, dc0, None
+        return dx, dw_ih, dw_hh, db, dh0, dc0, None, None
 
 
 def _lstm_lengths(lengths, B: int, T: int, dev) -> Tensor:
@@ -1358,7 +1368,67 @@ def _lstm_lengths(lengths, B: int, T: int, dev) -> Tensor:
     return lengths.to(torch.int32).contiguous()
 
 
-def lstm_layer(x, w_ih, w_hh, b_ih, b_hh, h0, c0, w_ih_r=None, w_hh_r=None, b_ih_r=None, b_hh_r=None, lengths=None):
+LSTM_RECURRENT = {"fp32": 0, "bf16": 1}     # lstm_layer's recurrent -> the library's lstm_recurrent (include/gcgcn.h)
+
+
+def _bf16_round(t: Tensor) -> Tensor:
+    """r(.): one rounding to bf16, nearest even, kept in ``t``'s own dtype."""
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
+class Bf16RecurrentFn(torch.autograd.Function):
+    """The recurrent product of ``recurrent="bf16"``, as plain PyTorch on any device in float32 / float64 -- the contract of the HIP
+    kernels ("bf16 recurrence").  ``(a[B,K], w[N,K]) -> r(a) r(w)^T`` with r = one rounding to bf16, sums in ``a``'s
+    dtype.  Backward: ``da = r(dy) r(w)`` -- the cotangent is rounded like any other operand -- and ``dw = dy^T a`` on the UNROUNDED
+    values: the weight gradient treats the rounding as the identity.  ``rounding=False`` switches every r off (then this is
+    ``a @ w.T`` and its ordinary gradients)."""
+
+    @staticmethod
+    def forward(ctx, a, w, rounding=True):
+        ctx.save_for_backward(a, w)
+        ctx.rounding = rounding
+        r = _bf16_round if rounding else (lambda t: t)
+        return r(a) @ r(w).t()
+
+    @staticmethod
+    def backward(ctx, dy):
+        a, w = ctx.saved_tensors
+        r = _bf16_round if ctx.rounding else (lambda t: t)
+        return r(dy) @ r(w), dy.t() @ a, None
+
+
+def lstm_layer_bf16_definition(x, w_ih, w_hh, b_ih, b_hh, h0, c0, w_ih_r=None, w_hh_r=None, b_ih_r=None, b_hh_r=None, lengths=None,
+                               rounding=True):
+    """What ``lstm_layer(..., recurrent="bf16")`` computes, written as a Python time loop (any device, float32 / float64; slow):
+
+        gates_t = (x_t W_ih^T + b_ih + b_hh) + Bf16RecurrentFn(h_{t-1}, W_hh)
+
+    the input projection, the sum and the cell update in the tensors' dtype, unrounded; ``h0`` is rounded like any other ``h`` when
+    it becomes an operand.  Gradients are autograd's through ``Bf16RecurrentFn``.  ``lengths`` (int tensor ``[B]``) as in
+    ``lstm_layer``: an inactive step is the identity on ``h`` and ``c``, the output is 0 there, and everything of an inactive step
+    goes through a select (``torch.where``), so NaN in the cotangent at a padded position reaches nothing."""
+    B, T, _ = x.shape
+    H = w_hh.shape[1]
+    outs = []
+    for d, (wi, wh, bi, bh) in enumerate(((w_ih, w_hh, b_ih, b_hh),) if w_ih_r is None else ((w_ih, w_hh, b_ih, b_hh), (w_ih_r, w_hh_r, b_ih_r, b_hh_r))):
+        xp = x @ wi.t() + (bi + bh)
+        h, c = h0[d].expand(B, H), c0[d].expand(B, H)
+        steps = [None] * T
+        for t in (range(T - 1, -1, -1) if d else range(T)):
+            gi, gf, gg, go = (xp[:, t] + Bf16RecurrentFn.apply(h, wh, rounding)).chunk(4, 1)
+            gi, gf, gg, go = torch.sigmoid(gi), torch.sigmoid(gf), torch.tanh(gg), torch.sigmoid(go)
+            cn = gf * c + gi * gg
+            hn = go * torch.tanh(cn)
+            if lengths is None:
+                c, h, steps[t] = cn, hn, hn
+            else:
+                act = (lengths > t)[:, None]
+                c, h, steps[t] = torch.where(act, cn, c), torch.where(act, hn, h), torch.where(act, hn, torch.zeros_like(hn))
+        outs.append(torch.stack(steps, 1))
+    return torch.cat(outs, 2)
+
+
+def lstm_layer(x, w_ih, w_hh, b_ih, b_hh, h0, c0, w_ih_r=None, w_hh_r=None, b_ih_r=None, b_hh_r=None, lengths=None, recurrent="fp32"):
     """One ``nn.LSTM(input_size, H, 1, batch_first=True)`` layer in HIP: ``x[B,T,I]``, ``h0``/``c0`` ``[nd,B,H]`` (a ``[nd,1,H]``
     state is broadcast over the batch) -> the output ``[B,T,nd*H]``.  Gate order i, f, g, o and all T padded steps, as torch runs
     it.  The four ``*_r`` parameters of the reverse direction make it bidirectional (all four or none).  ``H = 128`` is served;
@@ -1368,7 +1438,14 @@ def lstm_layer(x, w_ih, w_hh, b_ih, b_hh, h0, c0, w_ih_r=None, w_hh_r=None, b_ih
     read outside a capture).  The layer then computes what ``pack_padded_sequence`` -> ``nn.LSTM`` ->
     ``pad_packed_sequence(total_length=T)`` computes: row ``b`` runs its own ``lengths[b]`` steps (the reverse direction from
     ``t = lengths[b] - 1``), the output is exactly 0 at ``t >= lengths[b]``, and so is the gradient to ``x`` there, whatever the
-    output's gradient holds at those positions.  ``x`` itself must be finite there."""
+    output's gradient holds at those positions.  ``x`` itself must be finite there.
+
+    ``recurrent``: ``"fp32"`` (the default: the kernels and the bits of a call without the keyword) or ``"bf16"``: the two
+    recurrent products -- ``h W_hh^T`` forward, ``dgates W_hh`` backward -- take bf16 operands with fp32 accumulation
+    (``lstm_layer_bf16_definition`` / ``Bf16RecurrentFn`` is the definition).  The input projection, the cell update, the output,
+    the three gradient products and every parameter and gradient stay fp32."""
+    if recurrent not in LSTM_RECURRENT:
+        raise ValueError(f"lstm_layer: recurrent={recurrent!r} (\"fp32\" or \"bf16\")")
     rev = (w_ih_r, w_hh_r, b_ih_r, b_hh_r)
     if any(t is None for t in rev) and not all(t is None for t in rev):
         raise ValueError("lstm_layer: the reverse direction needs all of w_ih_r, w_hh_r, b_ih_r, b_hh_r")
@@ -1392,10 +1469,13 @@ def lstm_layer(x, w_ih, w_hh, b_ih, b_hh, h0, c0, w_ih_r=None, w_hh_r=None, b_ih
         bias = torch.cat([b_ih + b_hh, b_ih_r + b_hh_r], 0)
     else:
         W_ih, W_hh, bias = w_ih.contiguous(), w_hh.contiguous(), b_ih + b_hh
-    if lengths is None:
+    lens = None if lengths is None else _lstm_lengths(lengths, B, T, x.device)
+    if recurrent != "fp32":
+        return LstmFn.apply(x, W_ih, W_hh, bias, h0.expand(nd, B, H).contiguous(), c0.expand(nd, B, H).contiguous(), lens,
+                            LSTM_RECURRENT[recurrent])
+    if lens is None:
         return LstmFn.apply(x, W_ih, W_hh, bias, h0.expand(nd, B, H).contiguous(), c0.expand(nd, B, H).contiguous())
-    return LstmFn.apply(x, W_ih, W_hh, bias, h0.expand(nd, B, H).contiguous(), c0.expand(nd, B, H).contiguous(),
-                        _lstm_lengths(lengths, B, T, x.device))
+    return LstmFn.apply(x, W_ih, W_hh, bias, h0.expand(nd, B, H).contiguous(), c0.expand(nd, B, H).contiguous(), lens)
 
 
 # ---- the token front end either side of the BiLSTM (csrc/frontend.hip) -----------------------------------------------------------

@@ -12,6 +12,7 @@ What runs where.  Everything from the entity pooling on (glove:293-360: edge-fea
 classifier head) is :class:`gcgcn_amd.GraphModelTail`, i.e. the HIP kernels.  The token encoder in front of it -- embeddings,
 ``EncoderLSTM`` (glove:377-428), ``linear_re`` + tanh, or BERT in the second model -- is plain PyTorch by default, restated here
 so that the model is complete.  ``config.encoder_impl = "hip"`` opts the BiLSTM into ``functional.lstm_layer`` (DESIGN.md 8.7);
+``config.encoder_recurrent = "bf16"`` (needs ``encoder_impl``; a ``ValueError`` without it) gives its recurrent products bf16 operands;
 ``config.frontend_impl = "hip"``, independently, opts the embeddings with their locked dropout into ``functional.token_embed`` and
 ``linear_re`` + tanh + the entity pooling into ``functional.token_context``.
 
@@ -28,7 +29,7 @@ from torch import nn
 from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
 
 from .bert import BertModel as OwnBertModel
-from .functional import lstm_layer, token_context, token_embed
+from .functional import lstm_layer, lstm_layer_bf16_definition, token_context, token_embed
 from .modules import GraphModelTail
 
 Tensor = torch.Tensor
@@ -62,13 +63,20 @@ class EncoderLSTM(nn.Module):
 
     ``forward(input, input_lengths)``: a TENSOR ``input_lengths`` (int ``[B]``, values in ``[1, T]``) makes every layer run each
     row at its own length, as a packed sequence: ``impl="hip"`` hands it to ``lstm_layer``, ``impl="torch"`` packs and pads back to
-    ``T`` (the output is 0 past a row's length).  Anything else there (the reference passes ``doc.size(1)``) is ignored."""
+    ``T`` (the output is 0 past a row's length).  Anything else there (the reference passes ``doc.size(1)``) is ignored.
 
-    def __init__(self, input_size, num_units, nlayers, concat, bidir, dropout, return_last, impl="torch"):
+    ``recurrent="bf16"`` (default ``"fp32"``) gives the layers' two recurrent products bf16 operands with fp32 accumulation;
+    parameters, gradients and the ``state_dict`` stay fp32, so a checkpoint moves freely between the settings.  ``impl="hip"``
+    hands it to ``lstm_layer``; ``impl="torch"`` then runs ``functional.lstm_layer_bf16_definition``, the same contract as a Python
+    time loop (any device, tensor lengths honoured; slow)."""
+
+    def __init__(self, input_size, num_units, nlayers, concat, bidir, dropout, return_last, impl="torch", recurrent="fp32"):
         super().__init__()
         if impl not in ("torch", "hip"):
             raise ValueError(f"EncoderLSTM: impl={impl!r} (\"torch\" or \"hip\")")
-        self.impl = impl
+        if recurrent not in ("fp32", "bf16"):
+            raise ValueError(f"EncoderLSTM: recurrent={recurrent!r} (\"fp32\" or \"bf16\")")
+        self.impl, self.recurrent = impl, recurrent
         self.rnns = nn.ModuleList(nn.LSTM(input_size if i == 0 else (num_units * 2 if bidir else num_units), num_units, 1,
                                           bidirectional=bidir, batch_first=True) for i in range(nlayers))
         nd = 2 if bidir else 1
@@ -84,11 +92,16 @@ class EncoderLSTM(nn.Module):
         output, outputs = input, []
         for i in range(self.nlayers):
             drop = (lambda x: x) if i == 0 and input_dropped else self.dropout
-            if self.impl == "hip":
+            if self.impl == "hip" or self.recurrent == "bf16":
                 r = self.rnns[i]
                 rev = (r.weight_ih_l0_reverse, r.weight_hh_l0_reverse, r.bias_ih_l0_reverse, r.bias_hh_l0_reverse) if r.bidirectional else ()
-                output = lstm_layer(drop(output), r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0,
-                                    self.init_hidden[i], self.init_c[i], *rev, lengths=lengths)
+                if self.impl == "hip":
+                    output = lstm_layer(drop(output), r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0,
+                                        self.init_hidden[i], self.init_c[i], *rev, lengths=lengths,
+                                        **({} if self.recurrent == "fp32" else {"recurrent": self.recurrent}))
+                else:
+                    output = lstm_layer_bf16_definition(drop(output), r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0,
+                                                        self.init_hidden[i], self.init_c[i], *rev, lengths=lengths)
                 outputs.append(output)
                 continue
             h0 = self.init_hidden[i].expand(-1, bsz, -1).contiguous()
@@ -165,8 +178,11 @@ class GCGCN_glove(_GraphRelationModel):
         input_size = vec.shape[1] + config.entity_type_size + config.coref_size
         self.ner_emb = nn.Embedding(7, config.entity_type_size, padding_idx=0)               # glove:241
         self.entity_embed = nn.Embedding(config.max_length, config.coref_size, padding_idx=0)   # glove:246
+        recurrent = getattr(config, "encoder_recurrent", "fp32")
+        if recurrent == "bf16" and getattr(config, "encoder_impl", None) is None:
+            raise ValueError("config.encoder_recurrent selects the recurrent products of EncoderLSTM's impl: set config.encoder_impl too")
         self.rnn = EncoderLSTM(input_size, self.HIDDEN, 1, True, True, 1 - config.keep_prob, False,   # glove:248
-                               impl=getattr(config, "encoder_impl", "torch"))
+                               impl=getattr(config, "encoder_impl", "torch"), recurrent=recurrent)
         self.linear_re = nn.Linear(self.HIDDEN * 2, self.HIDDEN)                             # glove:264
         self.dis_embed = nn.Embedding(config.dis_num, config.dis_size)                       # glove:279
 

@@ -42,7 +42,7 @@ const char* gcgcn_last_error(void); /* message of the last failing call on this 
  * "head_compact", "chain_t", "chain_big" and "split_widen" select kernel generations (the five head options take effect in
  * csrc/head.hip head_plan and nowhere else: gcgcn_debug_head_plan shows the result; "split_widen" in csrc/gemm.hip gemm_plan and
  * nowhere else: gcgcn_debug_gemm_plan); "head_matmul" is no switch but the matmul argument of the calling thread's NEXT
- * classifier-head call (see gcgcn_head_fwd: taken by that call, no environment variable, nothing lasting); "group_dump" (0 = off) prints what
+ * classifier-head call (see gcgcn_head_fwd: taken by that call, no environment variable, nothing lasting), and "lstm_recurrent" likewise the recurrent argument of its NEXT LSTM call (see gcgcn_lstm_fwd); "group_dump" (0 = off) prints what
  * every GEMM launch is made of on stderr.  Each name also reads the environment variable GCGCN_<NAME> once when nobody set
  * it (GCGCN_CHAIN=0, GCGCN_HEAD_V1=1, ...: DESIGN.md section 6 lists them).  Any other name fails. */
 int gcgcn_set_option(const char* name, int value);
@@ -574,7 +574,16 @@ int gcgcn_adam_step_dev(int n_tensors, const void* table, int64_t total_blocks, 
  * a bad value cannot address out of bounds).  Written: EVERY element of out (exactly 0 at t >= lens[b]) and, in the backward, of
  * dgates (0 there, hence dx exactly 0 there), dx, the parameter gradients, dh0, dc0; no memset is needed.  gates and csave are NOT
  * written at inactive steps, and the backward lets neither them nor dout at those positions reach any result (NaN included).
- * x must be finite at padded positions (it is multiplied by the zero dgates).  Both calls of a pair take the same lens. */
+ * x must be finite at padded positions (it is multiplied by the zero dgates).  Both calls of a pair take the same lens.
+ * The four calls take one more argument, recurrent (0 = fp32, 1 = bf16), which travels beside the argument list as the head's
+ * matmul does: gcgcn_set_option("lstm_recurrent", v) hands v to the calling thread's NEXT gcgcn_lstm_fwd / _fwd_len / _bwd /
+ * _bwd_len, which takes it first -- whatever it then returns -- and leaves 0 behind: no environment variable, nothing lasting,
+ * another thread never sees it, and a call nobody announced runs fp32 exactly as before.  Any value but 0 and 1 is refused
+ * (gcgcn_last_error).  With 1 the two recurrent products take bf16 operands on the bf16 matrix cores and accumulate in fp32, r(.)
+ * being one rounding to bf16, nearest even:  forward  gates_t = (x_t W_ih^T + bias) + r(h_{t-1}) r(W_hh)^T  (h0 is rounded like any
+ * other h);  backward  dh_rec = r(dgates_t) r(W_hh).  Nothing stored is rounded: out, gates, csave and dgates are the fp32 values, the
+ * input projection and dw_ih / dw_hh / dx / db are the same fp32 products on them, and lens means what it means above.  Both calls
+ * of a pair take the same recurrent.  gcgcn_lstm_ws_bytes does not depend on it. */
 int64_t gcgcn_lstm_ws_bytes(int B, int T, int I, int H, int nd);
 int gcgcn_lstm_fwd(int B, int T, int I, int H, int nd, const float* x, const float* w_ih, const float* w_hh, const float* bias,
                    const float* h0, const float* c0, float* out, float* gates, float* csave, void* stream);

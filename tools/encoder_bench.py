@@ -3,6 +3,7 @@ same parameters, same input, same session.
 
     python tools/encoder_bench.py [--B 32 --T 512 --I 140 --reps 30 --warmup 5] [--out profiles/encoder_bench.json]
     python tools/encoder_bench.py --lengths [--lib-old build/ab_old.so] --out profiles/encoder_bench_lengths.json
+    python tools/encoder_bench.py --recurrent fp32 bf16 [--lengths]          (writes profiles/encoder_bench_bf16.json; ab_recurrent)
 
 --lengths: per-document lengths (a fixed-seed draw, uniform in [T/4, T], the first document at T as in a collated batch; kept on the
 device, written into the JSON) go to both implementations, and impl="hip" without them is timed in the same interleaved loop as
@@ -77,8 +78,104 @@ def ab_abi(a, _lib, enc, x, dy, event_ms):
     return res
 
 
+def ab_recurrent(a, _lib, H, dev):
+    """EncoderLSTM(impl="hip", recurrent=s) for every s of --recurrent in ONE process, same parameters and input, interleaved rep by
+    rep: HIP events per step, eager and hipGraph replay, and -- one step per (rep, setting, kernel) inside a window of the library's
+    per-launch timer -- the two recurrence kernels on their own.  The acceptance of the bf16 setting: each kernel's bf16 MEDIAN below
+    the fp32 kernel's MINIMUM over the same reps."""
+    from gcgcn_amd.models import EncoderLSTM
+    torch.manual_seed(7)
+    enc = {}
+    for s in a.recurrent:
+        enc[s] = EncoderLSTM(a.I, H, 1, True, True, 0.0, False, impl="hip", recurrent=s).to(dev).train()
+        if len(enc) == 1:
+            for p in enc[s].parameters():                      # the reference's reset_parameters: N(0, 0.1^2)
+                p.data.normal_(0, 0.1)
+        else:
+            enc[s].load_state_dict(enc[a.recurrent[0]].state_dict(), strict=True)
+    x = torch.randn(a.B, a.T, a.I, device=dev, requires_grad=True)
+    dy = torch.randn(a.B, a.T, 2 * H, device=dev)
+    lens = None
+    if a.lengths:
+        lens = torch.randint(max(1, a.T // 4), a.T + 1, (a.B,), generator=torch.Generator().manual_seed(11))
+        lens[0] = a.T
+        lens = lens.to(device=dev, dtype=torch.int32)
+
+    def step(s):
+        for p in enc[s].parameters():
+            p.grad = None
+        x.grad = None
+        enc[s](x, lens).backward(dy)
+
+    def event_ms(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        return e0, e1
+
+    graphs, dx = {}, {}
+    for s in a.recurrent:
+        for _ in range(a.warmup):
+            step(s)
+        torch.cuda.synchronize()
+        dx[s] = x.grad.clone()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            step(s)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graphs[s] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[s]):
+            step(s)
+        torch.cuda.synchronize()
+        for _ in range(a.warmup):
+            graphs[s].replay()
+    ev = {(s, how): [] for s in a.recurrent for how in ("eager", "hipGraph replay")}
+    for _ in range(a.reps):
+        for s in a.recurrent:
+            ev[s, "eager"].append(event_ms(lambda: step(s)))
+            ev[s, "hipGraph replay"].append(event_ms(graphs[s].replay))
+    torch.cuda.synchronize()
+    impl = {s: {how: stats([e0.elapsed_time(e1) for e0, e1 in ev[s, how]]) for how in ("eager", "hipGraph replay")} for s in a.recurrent}
+
+    tags = ("lstm_fwd", "lstm_bwd")                          # a prefix filter: the bf16 kernels' tags are lstm_fwd_bf16 / lstm_bwd_bf16
+    per = {(s, tag): [] for s in a.recurrent for tag in tags}
+    for _ in range(a.reps):
+        for s in a.recurrent:
+            for tag in tags:
+                _lib.call("gcgcn_prof_start", tag.encode(), 64)
+                step(s)
+                torch.cuda.synchronize()
+                ms, n, w = ctypes.c_double(0), ctypes.c_int(0), ctypes.c_double(0)
+                _lib.call("gcgcn_prof_stop", ctypes.byref(ms), ctypes.byref(n), ctypes.byref(w))
+                assert n.value == 1, (s, tag, n.value)
+                per[s, tag].append(ms.value)
+    T_run = a.T if lens is None else int(lens.max())
+    kernels = {s: {tag: dict(stats(per[s, tag]), us_per_time_step=round(1e3 * statistics.median(per[s, tag]) / T_run, 3)) for tag in tags}
+               for s in a.recurrent}
+    line = {"metric": "EncoderLSTM(impl=hip) forward + backward, one bidirectional layer, per recurrent setting", "unit": "ms",
+            "config": {"B": a.B, "T": a.T, "input": a.I, "H": H, "device": torch.cuda.get_device_name(0)},
+            "timing": "one process, settings interleaved rep by rep; HIP events per step; kernels: library timer, kernel begin to end",
+            "impl": impl, "recurrence_kernels": kernels,
+            "model": {"fp32 us_per_time_step": 3.4, "bf16 us_per_time_step": 0.2,
+                      "note": "MFMA issue only: 1024 v_mfma_f32_16x16x4_f32 (32 cycles) / 128 v_mfma_f32_16x16x32_bf16 (16 cycles) per "
+                              "step and compute unit over 4 SIMDs at 2.4 GHz"}}
+    if "fp32" in a.recurrent and "bf16" in a.recurrent:
+        line["bf16 against fp32"] = {
+            tag: {"median_ratio": round(kernels["bf16"][tag]["median_ms"] / kernels["fp32"][tag]["median_ms"], 4),
+                  "bf16 median below fp32 min": kernels["bf16"][tag]["median_ms"] < kernels["fp32"][tag]["min_ms"]} for tag in tags}
+        line["bf16 against fp32"]["max_abs_dx_difference"] = (dx["bf16"] - dx["fp32"]).abs().max().item()
+    if a.lengths:
+        line["lengths"] = lens.tolist()
+    return line
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--recurrent", nargs="+", choices=("fp32", "bf16"), default=None,
+                    help="time EncoderLSTM(impl='hip') under these recurrent settings instead (default --out: profiles/encoder_bench_bf16.json)")
     ap.add_argument("--B", type=int, default=32)
     ap.add_argument("--T", type=int, default=512)
     ap.add_argument("--I", type=int, default=140)
@@ -86,12 +183,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--lengths", action="store_true", help="hand per-document lengths (fixed seed) to the encoders")
     ap.add_argument("--lib-old", default=None, help="another revision's library: gcgcn_lstm_fwd + _bwd of both, interleaved")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "encoder_bench.json"), help="the JSON is also written there")
+    ap.add_argument("--out", default=None, help="the JSON is also written there (default: profiles/encoder_bench.json)")
     a = ap.parse_args()
     from gcgcn_amd import _lib
     from gcgcn_amd.models import EncoderLSTM
     dev = torch.device("cuda:0")
     H = 128
+    if a.recurrent:
+        line = ab_recurrent(a, _lib, H, dev)
+        print(json.dumps(line))
+        out = a.out or os.path.join(ROOT, "profiles", "encoder_bench_bf16.json")
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, "w") as f:
+            json.dump(line, f, indent=1)
+            f.write("\n")
+        return
+    a.out = a.out or os.path.join(ROOT, "profiles", "encoder_bench.json")
     torch.manual_seed(7)
     enc = {"torch": EncoderLSTM(a.I, H, 1, True, True, 0.0, False).to(dev).train()}
     for p in enc["torch"].parameters():                        # the reference's reset_parameters: N(0, 0.1^2)

@@ -98,6 +98,8 @@ def main():
                          "(collate stays on the host, outside the graph) and the replays timed; eager: launches from Python only")
     ap.add_argument("--encoder", default="torch", choices=["torch", "hip"],
                     help="the BiLSTM token encoder: torch.nn.LSTM (the default model) or config.encoder_impl = \"hip\" (csrc/lstm.hip)")
+    ap.add_argument("--encoder-recurrent", default="fp32", choices=["fp32", "bf16"],
+                    help="with --encoder hip: config.encoder_recurrent, the operand format of the BiLSTM's recurrent products")
     ap.add_argument("--frontend", default="torch", choices=["torch", "hip"],
                     help="embeddings + locked dropout and linear_re + tanh + entity pooling: PyTorch (the default model) or "
                          "config.frontend_impl = \"hip\" (csrc/frontend.hip)")
@@ -114,6 +116,8 @@ def main():
     cfg = Cfg(a.vocab)
     if a.encoder == "hip":
         cfg.encoder_impl = "hip"
+        if a.encoder_recurrent != "fp32":
+            cfg.encoder_recurrent = a.encoder_recurrent
     if a.frontend == "hip":
         cfg.frontend_impl = "hip"
     model = GCGCN_glove(cfg).to(dev).train()
@@ -211,7 +215,7 @@ def main():
         "metric": "docs/sec, full training step of GCGCN_glove (collate -> forward -> loss -> backward -> Adam)", "value": round(a.B / dt, 1),
         "unit": "docs/s", "ms_per_step": round(dt * 1e3, 3), "ms_per_step_by_mode": ms_mode, "graph_optimiser": graph_opt, "dtype": "f32", "data": "synthetic",
         "config": {"workload": f"B={a.B} DocRED-shaped documents (T=512, mean {nv:.1f} entities, padded per batch), vocabulary {a.vocab}, "
-                               f"encoder {a.encoder}, front end {a.frontend}, train mode, {'torch.optim.Adam' if a.torch_adam else 'FusedAdam(capturable=True)' if capturable else 'FusedAdam (one launch)'}, eager launches, "
+                               f"encoder {a.encoder}{' (recurrent ' + a.encoder_recurrent + ')' if a.encoder == 'hip' else ''}, front end {a.frontend}, train mode, {'torch.optim.Adam' if a.torch_adam else 'FusedAdam(capturable=True)' if capturable else 'FusedAdam (one launch)'}, eager launches, "
                                f"{a.batches} resident packed batches rotated" + (", dead last hop skipped" if a.skip_dead_hop else "")},
         "ms_per_step_by_stage (stream time between HIP events, includes launch gaps)": split,
         "gpu_ms_per_step_by_part (library kernels in forward + backward)": by_part,
