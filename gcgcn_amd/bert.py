@@ -6,7 +6,8 @@ core, LayerNorm with residual and dropout, erf GELU, forward and backward, the L
 ``matmul="bf16"``, on the bf16 matrix cores; the attention core's products there too with ``attention="bf16"``) and the
 embeddings' LayerNorm through ``functional.res_layer_norm`` (their dropout is the library's elementwise kernel); it raises on CPU tensors.  The three embedding gathers
 (word, position, token type) and the pooler (one ``[B, D] x [D, D]`` product and a tanh) stay PyTorch in both implementations:
-three gathers and one small product.  Parameters live in ordinary ``nn.Embedding`` / ``nn.Linear`` / ``nn.LayerNorm`` holders
+three gathers and one small product.  ``embeddings="fused"`` moves the gathers, their sum, the LayerNorm and the dropout of
+``impl="hip"`` into ``functional.bert_embeddings`` (csrc/bert_embed.hip), opt-in.  Parameters live in ordinary ``nn.Embedding`` / ``nn.Linear`` / ``nn.LayerNorm`` holders
 under the package's names, so both implementations share one ``state_dict``.  DESIGN.md section 8.9."""
 from __future__ import annotations
 
@@ -251,21 +252,33 @@ class BertModel(nn.Module):
     accumulation; softmax, ``lse``, ``delta`` and ``dS`` stay at full precision and the dropout mask is the one the fp32 core draws
     (``Bf16AttentionFn`` is the definition).  Independent of ``matmul``: all four combinations are valid, and a checkpoint moves
     freely between them.  ``impl="hip"``: csrc/bert_attn_bf16.hip.  After a training forward of ``impl="hip"``,
-    ``last_rng_snaps`` holds the snapshots it used: ``[0]`` for the embeddings, ``[1 + l]`` for layer ``l``."""
+    ``last_rng_snaps`` holds the snapshots it used: ``[0]`` for the embeddings, ``[1 + l]`` for layer ``l``.
 
-    def __init__(self, config: Optional[BertConfig] = None, impl: str = "torch", matmul: str = "fp32", attention: str = "fp32"):
+    ``embeddings``: ``"torch"`` (default; nothing changes, launch for launch) or ``"fused"``: with ``impl="hip"`` the stage in front
+    of the layers -- ``(word[ids] + position[t]) + type[token_type_ids]``, LayerNorm, dropout, zeros on padding rows -- is ONE launch
+    of ``functional.bert_embeddings`` (csrc/bert_embed.hip) that never stores the sum, and its backward computes the three tables'
+    gradients owner-computed, dense and bit-reproducible; ids at padding positions are not read.  The forward is bit for bit the
+    default's (the same two fp32 adds, the same LayerNorm row body, the same dropout mask).  ``impl="torch"`` accepts the value and
+    computes the same contract in plain PyTorch as it always did.  Independent of ``matmul`` and ``attention``; the ``state_dict`` is
+    untouched, so a checkpoint moves freely between the settings."""
+
+    def __init__(self, config: Optional[BertConfig] = None, impl: str = "torch", matmul: str = "fp32", attention: str = "fp32",
+                 embeddings: str = "torch"):
         super().__init__()
         config = BertConfig() if config is None else config
         if impl not in ("torch", "hip"):
             raise ValueError(f"BertModel: impl must be 'torch' or 'hip', got {impl!r}")
         bert_matmul_index(matmul, "BertModel")      # raises on anything but the allowed names
         bert_attention_index(attention, "BertModel")
+        if embeddings not in ("torch", "fused"):
+            raise ValueError(f"BertModel: embeddings must be 'torch' or 'fused', got {embeddings!r}")
         if config.hidden_size % config.num_attention_heads:
             raise ValueError(f"BertModel: hidden size {config.hidden_size} is no multiple of {config.num_attention_heads} heads")
         if impl == "hip" and config.hidden_size != 64 * config.num_attention_heads:
             raise ValueError(f"BertModel(impl='hip'): the attention kernels serve a head width of 64, not "
                              f"{config.hidden_size // config.num_attention_heads}")
         self.config, self.impl, self.matmul, self.attention = config, impl, matmul, attention
+        self.embeddings_impl = embeddings           # (self.embeddings is the parameters' holder: a state_dict key)
         self.embeddings = _Embeddings(config)
         self.encoder = _Encoder(config)
         self.pooler = _Dense(config.hidden_size, config.hidden_size)
@@ -293,6 +306,12 @@ class BertModel(nn.Module):
         if T > c.max_position_embeddings:
             raise ValueError(f"BertModel: {T} tokens exceed max_position_embeddings = {c.max_position_embeddings}")
         tt = torch.zeros_like(input_ids) if token_type_ids is None else token_type_ids
+        if self.impl == "hip" and self.embeddings_impl == "fused":      # the sum is formed inside the stage's kernel
+            dt = e.word_embeddings.weight.dtype
+            key_bias = None if attention_mask is None else (1.0 - attention_mask.to(dt)) * MASK_PENALTY
+            outs = self._encode_hip(None, key_bias, lengths, ids=input_ids, tt=tt)
+            pooled = torch.tanh(self.pooler.dense(outs[-1][:, 0]))
+            return (outs if output_all_encoded_layers else outs[-1]), pooled
         pos = torch.arange(T, device=input_ids.device)
         emb = e.word_embeddings(input_ids) + e.position_embeddings(pos)[None] + e.token_type_embeddings(tt)
         key_bias = None if attention_mask is None else (1.0 - attention_mask.to(emb.dtype)) * MASK_PENALTY
@@ -321,29 +340,37 @@ class BertModel(nn.Module):
         pooled = torch.tanh(self.pooler.dense(last[:, 0]))
         return (outs if output_all_encoded_layers else last), pooled
 
-    def _encode_hip(self, emb, key_bias, lengths=None):
+    def _encode_hip(self, emb, key_bias, lengths=None, ids=None, tt=None):
+        """``emb``: the embeddings' sum ``[B,T,D]``; or None with ``ids`` / ``tt`` ``[B,T]`` (``embeddings="fused"``)."""
         from . import _lib, functional as Fn
         c, e = self.config, self.embeddings
-        if not emb.is_cuda:
-            raise RuntimeError(f"BertModel(impl='hip') runs on MI355X only; got {emb.device} tensors (impl='torch' runs anywhere)")
+        src = ids if emb is None else emb
+        if not src.is_cuda:
+            raise RuntimeError(f"BertModel(impl='hip') runs on MI355X only; got {src.device} tensors (impl='torch' runs anywhere)")
+        dev, (B, T) = src.device, src.shape[:2]
         training = self.training
         n = len(self.encoder.layer)
         snaps = []
         tv = rowblk = None
         if lengths is not None:      # one list of live 16-row blocks for every layer and its backward, built on the device
-            tv = lengths.to(device=emb.device, dtype=torch.int32).contiguous()
-            rowblk = Fn.row_blocks(tv, emb.shape[0], emb.shape[1])
-        with Fn.rng_scope(emb.device, n + 1, enabled=training):
-            snap = Fn.rng_snapshot(emb.device) if training and c.hidden_dropout_prob > 0 else None
+            tv = lengths.to(device=dev, dtype=torch.int32).contiguous()
+            rowblk = Fn.row_blocks(tv, B, T)
+        with Fn.rng_scope(dev, n + 1, enabled=training):
+            snap = Fn.rng_snapshot(dev) if training and c.hidden_dropout_prob > 0 else None
             snaps.append(snap)
-            # the dropout follows the LayerNorm here; with lengths the LayerNorm zeroes the padding rows and the dropout keeps 0 at 0
-            x = Fn.res_layer_norm(emb, e.LayerNorm.weight, e.LayerNorm.bias, t_valid=tv)
-            if snap is not None:
-                x = Fn.DropoutFn.apply(x, c.hidden_dropout_prob, snap, _lib.SALT_BERT_EMB)
+            if emb is None:
+                x = Fn.bert_embeddings(ids, tt, e.word_embeddings.weight, e.position_embeddings.weight, e.token_type_embeddings.weight,
+                                       e.LayerNorm.weight, e.LayerNorm.bias, p=c.hidden_dropout_prob, training=snap is not None, snap=snap,
+                                       t_valid=tv)
+            else:
+                # the dropout follows the LayerNorm here; with lengths the LayerNorm zeroes the padding rows and the dropout keeps 0 at 0
+                x = Fn.res_layer_norm(emb, e.LayerNorm.weight, e.LayerNorm.bias, t_valid=tv)
+                if snap is not None:
+                    x = Fn.DropoutFn.apply(x, c.hidden_dropout_prob, snap, _lib.SALT_BERT_EMB)
             outs = []
             kb = None if key_bias is None else key_bias.contiguous()
             for layer in self.encoder.layer:
-                snap = Fn.rng_snapshot(emb.device) if training else None
+                snap = Fn.rng_snapshot(dev) if training else None
                 snaps.append(snap)
                 x = Fn.bert_layer(x, kb, *layer.tensors(), p_attn=c.attention_probs_dropout_prob, p_hidden=c.hidden_dropout_prob,
                                   training=training, snap=snap, t_valid=tv, rowblk=rowblk, matmul=self.matmul, attention=self.attention)

@@ -28,6 +28,7 @@
 // through a select, rows past T are not stored: what lies behind a buffer's end is never read and never reaches a result.
 #include "bert.hpp"
 #include "bert_attn.hpp"
+#include "ln_row.hpp"
 #include "gemm.hpp"
 #include "gemm_bf16.hpp"
 #include "rowops.hpp"
@@ -373,8 +374,7 @@ int bert_attn_bwd(int B, int T, int H, const float* qkv, const float* key_bias, 
 
 // ---- LayerNorm(dropout(x + bias) + res) ------------------------------------------------------------------------------------------
 // One wave per row; lane l holds columns l + 64 i, i < D / 64 <= 16, in registers.  Two-pass variance: a constant row has var = 0.
-constexpr int LNV = BERT_LN_MAX_D / 64;
-
+// The row arithmetic itself is ln_row.hpp's, shared with the fused embeddings stage (bert_embed.hip).
 __device__ __forceinline__ void ln_input(float (&v)[LNV], const float* __restrict__ x, const float* __restrict__ bias,
                                          const float* __restrict__ res, const long row, const int D, const int l, const Drop& drop,
                                          const uint64_t dk) {
@@ -413,20 +413,13 @@ __global__ __launch_bounds__(256) void res_ln_fwd_kernel(const float* __restrict
   const uint64_t dk = drop.snap ? drop_key(drop) : 0;
   float v[LNV];
   ln_input(v, x, bias, res, row, D, l, drop, dk);
-  float s = 0.f;
-#pragma unroll
-  for (int i = 0; i < LNV; ++i) s += v[i];
-  const float m = wave_sum(s) / (float)D;
-  float sq = 0.f;
-#pragma unroll
-  for (int i = 0; i < LNV; ++i)
-    if (i < n) sq += (v[i] - m) * (v[i] - m);
-  const float r = 1.f / sqrtf(wave_sum(sq) / (float)D + BERT_LN_EPS);
+  float m, r;
+  ln_row_stats(v, n, D, m, r);
 #pragma unroll
   for (int i = 0; i < LNV; ++i)
     if (i < n) {
       const int c = l + 64 * i;
-      y[row * D + c] = weight[c] * ((v[i] - m) * r) + lnb[c];
+      y[row * D + c] = ln_row_out(v[i], m, r, weight[c], lnb[c]);
     }
   if (l == 0 && mean) mean[row] = m, rstd[row] = r;
 }
@@ -454,40 +447,17 @@ __global__ __launch_bounds__(256) void res_ln_bwd_kernel(const float* __restrict
       }
       continue;
     }
-    float v[LNV], g[LNV];
+    float v[LNV];
     ln_input(v, x, bias, res, row, D, l, drop, dk);
     const float m = mean[row], r = rstd[row];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < LNV; ++i) {
-      g[i] = 0.f;
-      if (i < n) {
-        const int c = l + 64 * i;
-        const float d = dy[row * D + c];
-        v[i] = (v[i] - m) * r;   // xhat
-        g[i] = d * weight[c];
-        s1 += g[i], s2 += g[i] * v[i];
-        aw[i] += d * v[i], ab[i] += d;
-      }
-    }
-    s1 = wave_sum(s1) / (float)D, s2 = wave_sum(s2) / (float)D;
-#pragma unroll
-    for (int i = 0; i < LNV; ++i)
-      if (i < n) {
-        const long o = row * D + l + 64 * i;
-        const float dv = r * (g[i] - s1 - v[i] * s2);
-        if (dres) dres[o] = dv;
-        dx[o] = drop.snap ? (rng_u32(dk, (uint64_t)o) >= drop.thresh ? dv * drop.scale : 0.f) : dv;
-      }
+    const auto dstore = [&](const int i, const float dv) {
+      const long o = row * D + l + 64 * i;
+      if (dres) dres[o] = dv;
+      dx[o] = drop.snap ? (rng_u32(dk, (uint64_t)o) >= drop.thresh ? dv * drop.scale : 0.f) : dv;
+    };
+    ln_row_bwd(v, [&](const int i) { return dy[row * D + l + 64 * i]; }, dstore, weight, n, D, l, m, r, aw, ab);
   }
-#pragma unroll
-  for (int i = 0; i < LNV; ++i)
-    if (i < n) sh[wv][0][l + 64 * i] = aw[i], sh[wv][1][l + 64 * i] = ab[i];
-  __syncthreads();
-  for (int c = threadIdx.x; c < 2 * D; c += 256) {
-    const int k = c >= D, cc = c - k * D;
-    part[(long)blockIdx.x * 2 * D + c] = (sh[0][k][cc] + sh[1][k][cc]) + (sh[2][k][cc] + sh[3][k][cc]);
-  }
+  ln_part_store(sh, aw, ab, part, n, D, wv, l);
 }
 // Stage 2: the G row groups in order
 __global__ __launch_bounds__(256) void res_ln_bwd_reduce_kernel(const float* __restrict__ part, const int G, const int D,
@@ -498,6 +468,11 @@ __global__ __launch_bounds__(256) void res_ln_bwd_reduce_kernel(const float* __r
   for (int g = 0; g < G; ++g) s += part[(long)g * 2 * D + c];
   if (c < D) dweight[c] = s;
   else dlnb[c - D] = s;
+}
+
+int res_ln_bwd_reduce(const float* part, int G, int D, float* dweight, float* dlnb, hipStream_t st) {
+  hipLaunchKernelGGL(res_ln_bwd_reduce_kernel, dim3(cdiv(2 * D, 256)), dim3(256), 0, st, part, G, D, dweight, dlnb);
+  return check_launch("res_ln_bwd_reduce");
 }
 
 int res_ln_fwd(long rows, int D, const float* x, const float* bias, const float* res, const float* weight, const float* lnb, float* y,
@@ -516,8 +491,7 @@ int res_ln_bwd(long rows, int D, const float* dy, const float* x, const float* b
   hipLaunchKernelGGL(res_ln_bwd_kernel, dim3(G), dim3(256), 0, st, dy, x, bias, res, weight, mean, rstd, dx, dres, part, rows, D, drop,
                      t_valid, t_valid ? T : 1);
   GC_TRY(check_launch("res_ln_bwd"));
-  hipLaunchKernelGGL(res_ln_bwd_reduce_kernel, dim3(cdiv(2 * D, 256)), dim3(256), 0, st, part, G, D, dweight, dlnb);
-  return check_launch("res_ln_bwd_reduce");
+  return res_ln_bwd_reduce(part, G, D, dweight, dlnb, st);
 }
 
 // ---- erf GELU with the bias ----------------------------------------------------------------------------------------------------

@@ -54,6 +54,8 @@ inline long res_ln_ws_elems(int D) { return 2L * BERT_LN_PARTS * D; }
 int res_ln_bwd(long rows, int D, const float* dy, const float* x, const float* bias, const float* res, const float* weight,
                const float* mean, const float* rstd, float* dx, float* dres, float* dweight, float* dlnb, float* part, Drop drop,
                hipStream_t st, const int* t_valid = nullptr, int T = 0);
+// stage 2 alone: dweight / dlnb from part [G][2][D], the G row groups in order (the fused embeddings stage writes its own stage 1)
+int res_ln_bwd_reduce(const float* part, int G, int D, float* dweight, float* dlnb, hipStream_t st);
 
 // ---- y = gelu(x + bias[col]), gelu(z) = z * 0.5 * (1 + erf(z / sqrt 2)); n = rows * C elements, C % 4 == 0; bias optional.
 int bias_gelu_fwd(long rows, int C, const float* x, const float* bias, float* y, hipStream_t st, const int* t_valid = nullptr, int T = 0);

@@ -67,9 +67,12 @@ int embed_fwd(int B, int T, const EmbedTables& tb, const float* scale, float* x,
 }
 
 // ---- embeddings, backward --------------------------------------------------------------------------------------------------
-// grid (chunks, column tiles of 64, 3 tables), 512 threads = 8 waves x 32 sorted tokens
+// grid (chunks, column tiles of 64, tables), 512 threads = 8 waves x 32 sorted tokens.  LEN (t_valid [B]; the BERT embeddings stage):
+// a token at or past its document's length adds nothing, and neither its id nor its row of dx is read.
+template <bool LEN>
 __global__ __launch_bounds__(512) void embed_bwd_chunk_kernel(const EmbedTables tb, const EmbedWs ws, const float* __restrict__ dx,
-                                                              const float* __restrict__ scale, const long n, const int T, const int I) {
+                                                              const float* __restrict__ scale, const long n, const int T, const int I,
+                                                              const int* __restrict__ t_valid) {
   __shared__ __attribute__((aligned(16))) int s_id[FE_CHUNK];
   __shared__ int s_sid[FE_CHUNK], s_pos[FE_CHUNK], s_b[FE_CHUNK];
   const int ti = blockIdx.z, ct = blockIdx.y, t = threadIdx.x;
@@ -80,7 +83,7 @@ __global__ __launch_bounds__(512) void embed_bwd_chunk_kernel(const EmbedTables 
   int id = FE_NONE;
   if (t < FE_CHUNK) {
     const long pos = k * FE_CHUNK + t;
-    if (pos < n) {
+    if (pos < n && (!LEN || (int)(pos % T) < min(max(t_valid[pos / T], 0), T))) {
       const int64_t v = tab.ids[pos];
       if (v >= 0 && v < tab.rows && v != tab.pad) id = (int)v;
     }
@@ -126,7 +129,7 @@ __global__ __launch_bounds__(512) void embed_bwd_chunk_kernel(const EmbedTables 
   }
 }
 
-// grid (rows / 4, 1, 3 tables): one wave per table row
+// grid (rows / 4, 1, tables): one wave per table row
 __global__ __launch_bounds__(256) void embed_bwd_rows_kernel(const EmbedTables tb, const EmbedWs ws, const int chunks, const int I) {
   const int ti = blockIdx.z, lane = threadIdx.x & 63;
   const EmbedTable& tab = tb.t[ti];
@@ -195,24 +198,26 @@ long embed_ws_bytes(long n, const EmbedTables& tb) {
   return 4 * (ints + nsorted * tb.width());
 }
 
-int embed_bwd(int B, int T, const EmbedTables& tb, const float* dx, const float* scale, void* wsp, long ws_bytes, hipStream_t st) {
+int embed_bwd(int B, int T, const EmbedTables& tb, const float* dx, const float* scale, void* wsp, long ws_bytes, hipStream_t st,
+              const int* t_valid, int ntab) {
   const long n = (long)B * T;
   const int I = tb.width();
   GC_REQUIRE(ws_bytes >= embed_ws_bytes(n, tb), "embed_bwd: workspace of %ld bytes needed", embed_ws_bytes(n, tb));
   const EmbedWs ws = embed_ws(n, tb, wsp);
   const int chunks = (int)(ws.nsorted / FE_CHUNK);
   int wmax = 1, rmax = 1;
-  for (int i = 0; i < 3; ++i) wmax = tb.t[i].width > wmax ? tb.t[i].width : wmax, rmax = tb.t[i].rows > rmax ? tb.t[i].rows : rmax;
+  for (int i = 0; i < ntab; ++i) wmax = tb.t[i].width > wmax ? tb.t[i].width : wmax, rmax = tb.t[i].rows > rmax ? tb.t[i].rows : rmax;
   {
     ProfScope ps("fe_embed_flags", st);
     GC_REQUIRE(hipMemsetAsync(ws.touched, 0, (char*)ws.sid - (char*)ws.touched, st) == hipSuccess, "embed_bwd: memset failed");
   }
-  GC_LAUNCH_TIMED("fe_embed_chunk", 8.0 * n * I, embed_bwd_chunk_kernel, dim3(chunks, cdiv(wmax, 64), 3), dim3(512), 0, st, tb, ws, dx,
-                  scale, n, T, I);
+  const auto chunk_kernel = t_valid ? embed_bwd_chunk_kernel<true> : embed_bwd_chunk_kernel<false>;
+  GC_LAUNCH_TIMED("fe_embed_chunk", 8.0 * n * I, chunk_kernel, dim3(chunks, cdiv(wmax, 64), ntab), dim3(512), 0, st, tb, ws, dx, scale, n, T,
+                  I, t_valid);
   GC_TRY(check_launch("embed_bwd_chunk"));
   double bytes = 0;
-  for (int i = 0; i < 3; ++i) bytes += 4.0 * tb.t[i].rows * tb.t[i].width;
-  GC_LAUNCH_TIMED("fe_embed_rows", bytes + 4.0 * n * I, embed_bwd_rows_kernel, dim3(cdiv(rmax, 4), 1, 3), dim3(256), 0, st, tb, ws, chunks, I);
+  for (int i = 0; i < ntab; ++i) bytes += 4.0 * tb.t[i].rows * tb.t[i].width;
+  GC_LAUNCH_TIMED("fe_embed_rows", bytes + 4.0 * n * I, embed_bwd_rows_kernel, dim3(cdiv(rmax, 4), 1, ntab), dim3(256), 0, st, tb, ws, chunks, I);
   return check_launch("embed_bwd_rows");
 }
 

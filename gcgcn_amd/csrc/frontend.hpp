@@ -26,7 +26,10 @@ int embed_fwd(int B, int T, const EmbedTables& tb, const float* scale, float* x,
 // Bytes of workspace embed_bwd needs (touched flags per table row, the chunks' sorted ids, the chunks' partial rows).
 long embed_ws_bytes(long n, const EmbedTables& tb);
 // dw of every table, fully written, from dx [B * T][I] (times scale): each row summed by one owner in ascending token position.
-int embed_bwd(int B, int T, const EmbedTables& tb, const float* dx, const float* scale, void* ws, long ws_bytes, hipStream_t st);
+// t_valid (int32 [B] on the device, or nullptr): token (b, t) with t >= t_valid[b] adds nothing; its ids and its row of dx are not read.
+// ntab: the leading tables the launches visit (the BERT embeddings stage hands over its word table alone, the others with no rows).
+int embed_bwd(int B, int T, const EmbedTables& tb, const float* dx, const float* scale, void* ws, long ws_bytes, hipStream_t st,
+              const int* t_valid = nullptr, int ntab = 3);
 
 // pre [B * T][128] = h W^T + b (scratch the caller owns), ctx = tanh(pre), node_feat [B][N][128] = node_pos [B][N][T] ctx.
 int context_fwd(int B, int T, int N, int K, const float* h, const float* w, const float* bias, const float* node_pos, float* pre,

@@ -1649,6 +1649,87 @@ def res_layer_norm(x, weight, bias, lin_bias=None, res=None, p=0.0, training=Fal
                                 t_valid)
 
 
+class BertEmbeddingsFn(torch.autograd.Function):
+    """(word_w[V,D], pos_w[Pmax,D], type_w[Ty,D], ln_w[D], ln_b[D], input_ids, token_type_ids int64 [B,T]) -> y[B,T,D]
+    (include/gcgcn_bert_embed.h: gcbe_fwd / gcbe_bwd)."""
+
+    @staticmethod
+    def forward(ctx, word_w, pos_w, type_w, ln_w, ln_b, input_ids, token_type_ids, p, snap, t_valid):
+        B, T = input_ids.shape
+        dims = (B, T, word_w.shape[1], word_w.shape[0], pos_w.shape[0], type_w.shape[0])
+        dev = word_w.device
+        y = torch.empty(B, T, dims[2], device=dev)
+        mean, rstd = torch.empty(B * T, device=dev), torch.empty(B * T, device=dev)
+        call("gcbe_fwd", *dims, _p(input_ids), _p(token_type_ids), _p(word_w), _p(pos_w), _p(type_w), _p(ln_w), _p(ln_b), _p(t_valid), _p(y),
+             _p(mean), _p(rstd), _p(snap), float(p), _stream())
+        torch.autograd.graph.increment_version((y, mean, rstd))
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(word_w, pos_w, type_w, ln_w, input_ids, token_type_ids, mean, rstd)
+            ctx.dims, ctx.p, ctx.snap, ctx.t_valid = dims, float(p), snap, t_valid
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        word_w, pos_w, type_w, ln_w, input_ids, token_type_ids, mean, rstd = ctx.saved_tensors
+        dy = dy.contiguous()
+        dev = dy.device
+        dword, dpos, dtype = torch.empty_like(word_w), torch.empty_like(pos_w), torch.empty_like(type_w)
+        dw, db = torch.empty_like(ln_w), torch.empty_like(ln_w)
+        ws = _f32_buf(_bytes_or_raise("gcbe_ws_bytes", *ctx.dims), dev)
+        call("gcbe_bwd", *ctx.dims, _p(input_ids), _p(token_type_ids), _p(word_w), _p(pos_w), _p(type_w), _p(ln_w), _p(ctx.t_valid), _p(mean),
+             _p(rstd), _p(dy), _p(dword), _p(dpos), _p(dtype), _p(dw), _p(db), _p(ws), ws.numel() * 4, _p(ctx.snap), ctx.p, _stream())
+        torch.autograd.graph.increment_version((dword, dpos, dtype, dw, db))
+        return dword, dpos, dtype, dw, db, None, None, None, None, None
+
+
+def bert_embeddings(input_ids, token_type_ids, word_w, pos_w, type_w, ln_w, ln_b, p=0.0, training=False, snap=None, t_valid=None):
+    """The stage in front of the BERT encoder layers as ONE launch (csrc/bert_embed.hip)::
+
+        emb[b,t] = (word_w[input_ids[b,t]] + pos_w[t]) + type_w[token_type_ids[b,t]]      y = dropout(LayerNorm(emb))
+
+    with the contract's LayerNorm (biased variance, eps = 1e-12 inside the root; ``res_layer_norm``'s row arithmetic, bit for bit)
+    and, in training with ``p > 0``, the mask ``DropoutFn`` draws from ``snap`` (default: a fresh snapshot) with ``SALT_BERT_EMB``.
+    Ids are int64 ``[B,T]`` (``token_type_ids`` None: zeros); ``word_w[V,D]``, ``pos_w[Pmax,D]`` with ``T <= Pmax``, ``type_w[Ty,D]``,
+    ``ln_w`` / ``ln_b`` ``[D]``; ``D`` a multiple of 64, at most 1024.  ``emb`` is never stored.
+
+    ``t_valid``: token counts ``[B]`` (row ``(b, t)`` is live iff ``t < t_valid[b]``).  Padding rows of ``y`` are exactly zero, the
+    ids there are not read, a gradient arriving there is not read (NaN included) and nothing of them reaches any gradient.
+
+    The five gradients (three tables, LayerNorm weight and bias) come back dense, every row written, each element summed by one
+    owner in a fixed order: two backward passes are bitwise equal.  Nothing is read on the host (the id range check apart, which is
+    skipped under capture, as ``token_embed``'s is): capturable, and a captured stage follows new ids and lengths."""
+    tabs = [_chk(w, nm, 2) for nm, w in (("word_w", word_w), ("pos_w", pos_w), ("type_w", type_w))]
+    ln_w, ln_b = _chk(ln_w, "ln_w", 1), _chk(ln_b, "ln_b", 1)
+    if not isinstance(input_ids, torch.Tensor) or not input_ids.is_cuda or input_ids.dtype != torch.int64 or input_ids.dim() != 2:
+        raise ValueError("input_ids: expected a GPU int64 tensor of shape [B,T]")
+    if token_type_ids is None:
+        token_type_ids = torch.zeros_like(input_ids)
+    if (not isinstance(token_type_ids, torch.Tensor) or not token_type_ids.is_cuda or token_type_ids.dtype != torch.int64
+            or token_type_ids.shape != input_ids.shape):
+        raise ValueError("token_type_ids: expected a GPU int64 tensor of input_ids' shape")
+    input_ids, token_type_ids = input_ids.contiguous(), token_type_ids.contiguous()
+    B, T = input_ids.shape
+    D = tabs[0].shape[1]
+    if D % 64 != 0 or D < 64 or D > 1024:
+        raise ValueError(f"bert_embeddings: D = {D} (a multiple of 64, at most 1024)")
+    if any(w.shape[1] != D for w in tabs) or ln_w.shape != (D,) or ln_b.shape != (D,):
+        raise ValueError(f"bert_embeddings: tables {[tuple(w.shape) for w in tabs]} / LayerNorm {tuple(ln_w.shape)}, {tuple(ln_b.shape)} "
+                         f"do not share the width {D}")
+    if T > tabs[1].shape[0]:
+        raise ValueError(f"bert_embeddings: {T} tokens exceed the position table's {tabs[1].shape[0]} rows")
+    if B < 1 or T < 1:
+        raise ValueError(f"bert_embeddings: empty batch {tuple(input_ids.shape)}")
+    _check_id_range([("input_ids", input_ids, 0, tabs[0].shape[0] - 1), ("token_type_ids", token_type_ids, 0, tabs[2].shape[0] - 1)])
+    t_valid = _nv(t_valid, B, T, input_ids.device)
+    p = float(p) if training else 0.0
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"bert_embeddings: p = {p} out of [0, 1)")
+    if p > 0 and snap is None:
+        snap = rng_snapshot(input_ids.device)
+    return BertEmbeddingsFn.apply(*tabs, ln_w, ln_b, input_ids, token_type_ids, p, snap if p > 0 else None, t_valid)
+
+
 BERT_LAYER_TENSORS = ("query.weight", "query.bias", "key.weight", "key.bias", "value.weight", "value.bias", "attention.output.dense.weight",
                       "attention.output.dense.bias", "attention.output.LayerNorm.weight", "attention.output.LayerNorm.bias",
                       "intermediate.dense.weight", "intermediate.dense.bias", "output.dense.weight", "output.dense.bias",

@@ -243,7 +243,12 @@ class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
 
     ``config.bert_attention = "fp32" | "bf16"`` (needs ``bert_impl``; a ``ValueError`` without it) is that encoder's ``attention``:
     with ``"bf16"`` the attention core's four matrix products take bf16 operands as well (``gcgcn_amd.bert.Bf16AttentionFn`` is the
-    definition).  Independent of ``bert_matmul``.  Without ``bert_attention`` nothing changes."""
+    definition).  Independent of ``bert_matmul``.  Without ``bert_attention`` nothing changes.
+
+    ``config.bert_embeddings = "torch" | "fused"`` (needs ``bert_impl``; a ``ValueError`` without it) is that encoder's
+    ``embeddings``: with ``"fused"`` and ``bert_impl = "hip"`` the stage in front of the layers -- three gathers, their sum,
+    LayerNorm, dropout -- is one launch, with owner-computed, bit-reproducible table gradients (``functional.bert_embeddings``).
+    Independent of ``bert_matmul`` and ``bert_attention``.  Without ``bert_embeddings`` nothing changes."""
 
     WORD_VEC_SIZE = 768
     _KEY_ORDER = ("bert", "ner_emb", "entity_embed", "get_weighted_adj_matrix", "get_adj_matrix", "graphcnn", "linear_re",
@@ -265,12 +270,19 @@ class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
                 raise ValueError(f"config.bert_attention must be 'fp32' or 'bf16', got {attention!r}")
             if impl is None:
                 raise ValueError("config.bert_attention selects the attention core of this library's own encoder: set config.bert_impl too")
+        embeddings = getattr(config, "bert_embeddings", None)
+        if embeddings is not None:
+            if embeddings not in ("torch", "fused"):
+                raise ValueError(f"config.bert_embeddings must be 'torch' or 'fused', got {embeddings!r}")
+            if impl is None:
+                raise ValueError("config.bert_embeddings selects the embeddings stage of this library's own encoder: set config.bert_impl too")
         if bert is None and impl is not None:                                                # this library's own encoder (bert.py)
             from .bert import BertConfig, BertModel as OwnBert, load_pretrained_state_dict
             if impl not in ("torch", "hip"):
                 raise ValueError(f"config.bert_impl must be 'torch' or 'hip', got {impl!r}")
             bert = OwnBert(getattr(config, "bert_config", None) or BertConfig(), impl=impl, **({} if matmul is None else {"matmul": matmul}),
-                           **({} if attention is None else {"attention": attention}))
+                           **({} if attention is None else {"attention": attention}),
+                           **({} if embeddings is None else {"embeddings": embeddings}))
             if getattr(config, "bert_weights", None):
                 load_pretrained_state_dict(bert, config.bert_weights)
             if bert.config.hidden_size != self.WORD_VEC_SIZE:

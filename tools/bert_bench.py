@@ -8,6 +8,7 @@ layer's time split: each non-GEMM kernel timed on its own through the C ABI, the
     python tools/bert_bench.py --lengths {full,ragged} [--shape 4x512] [--layers 12] [--iters 20] [--json out.json]
     python tools/bert_bench.py --matmul fp32 bf16 [--lengths ragged] [--shape 4x512] [--layers 12] [--iters 10] [--json out.json]
     python tools/bert_bench.py --attention fp32 bf16 [--matmul fp32 bf16] [--shape 4x512] [--layers 12] [--iters 10] [--json out.json]
+    python tools/bert_bench.py --embeddings torch fused [--lengths {full,ragged}] [--shape 4x512] [--layers 12] [--iters 10] [--json out.json]
 
 With --lengths only the HIP encoder runs, as one replayed hipGraph, twice on the same token counts in the same process: the
 prefix-mask path (attention_mask = arange(T) < t_valid, every row computed) and the length path (lengths = t_valid, live tokens
@@ -23,6 +24,11 @@ bf16 kernel's, with the achieved TF/s.  With --lengths the bf16 setting runs twi
 With --attention the same graph-replay runs go over every listed combination of BertModel(matmul=..., attention=...) (--matmul
 defaults to fp32 alone), and the kernel-alone section times the attention core through gcgcn_bert_attn_fwd_mx / _bwd_mx at each
 listed setting, back to back in the same process on the same data, with the achieved TF/s (4 and 10 B H T^2 64 flop).
+
+With --embeddings only the HIP encoder runs, once per listed setting of BertModel(embeddings=...), in the same process on the same
+inputs with the settings INTERLEAVED rep by rep (median, min and max of --iters samples each), eager and as one replayed hipGraph:
+the embeddings stage alone (a model without encoder layers, forward + backward) and the --layers encoder; with --lengths on those
+token counts through lengths=.  The stage's device kernel count per forward + backward is read from torch's profiler.
 
 Prints one table and, with --json, writes the numbers.  DESIGN.md section 8.9 holds the tables of record."""
 import argparse
@@ -69,6 +75,42 @@ def timed_stats(fn, iters, warmup=3):
     return statistics.median(ms), min(ms), max(ms)
 
 
+def timed_interleaved(fns, iters, warmup=3):
+    """{name: (median, min, max) ms}: the functions take turns, rep by rep, so that drift of the machine hits every one alike."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in fns}
+    for _ in range(iters):
+        for k, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            torch.cuda.synchronize()
+            ms[k].append(a.elapsed_time(b))
+    return {k: (statistics.median(v), min(v), max(v)) for k, v in ms.items()}
+
+
+def kernel_count(step):
+    """Device kernels (memsets and copies included) of one call of `step`, from torch's profiler; None where it reports none.  The
+    wrappers' id range check (a host read, skipped under capture) is switched off for the count: it is no part of the stage."""
+    from torch.profiler import ProfilerActivity, profile
+    from gcgcn_amd import functional
+    was, functional.check_ids = functional.check_ids, False
+    try:
+        step()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            step()
+            torch.cuda.synchronize()
+    finally:
+        functional.check_ids = was
+    n = sum(1 for e in prof.events() if str(e.device_type).endswith("CUDA"))
+    return n or None
+
+
 LENGTH_SEED = 2024
 ROWS_OPTION = b"bf16_rows"      # 0: the bf16 products ignore the row-block list
 
@@ -81,11 +123,11 @@ def draw_lengths(kind, B, T):
     return torch.randint(T // 8, T + 1, (B,), generator=g).to(torch.int32)
 
 
-def model_step(layers, impl, B, T, dev, t_valid=None, by_lengths=False, matmul="fp32", attention="fp32"):
+def model_step(layers, impl, B, T, dev, t_valid=None, by_lengths=False, matmul="fp32", attention="fp32", embeddings="torch"):
     """t_valid None: the masks this tool has always used.  Otherwise the prefix mask of these counts, or (by_lengths) lengths=t_valid."""
     cfg = BertConfig(num_hidden_layers=layers, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
     torch.manual_seed(0)
-    model = BertModel(cfg, impl=impl, matmul=matmul, attention=attention).to(dev).train()
+    model = BertModel(cfg, impl=impl, matmul=matmul, attention=attention, embeddings=embeddings).to(dev).train()
     g = torch.Generator().manual_seed(1)
     ids = torch.randint(0, cfg.vocab_size, (B, T), generator=g).to(dev)
     counts = torch.tensor([T - 37 * (b % 3) for b in range(B)]) if t_valid is None else t_valid.cpu()
@@ -198,12 +240,35 @@ def main():
     ap.add_argument("--shape", help="BxT: this shape only (default: 4x512 and 8x256)")
     ap.add_argument("--matmul", nargs="+", choices=("fp32", "bf16"), help="the HIP encoder with these matmul settings, back to back")
     ap.add_argument("--attention", nargs="+", choices=("fp32", "bf16"), help="the HIP encoder with these attention settings (times --matmul)")
+    ap.add_argument("--embeddings", nargs="+", choices=("torch", "fused"), help="the HIP encoder with these embeddings settings, interleaved")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.backends.cuda.matmul.allow_tf32 = False
     rows = []
     shapes = ((4, 512), (8, 256)) if not a.shape else (tuple(int(v) for v in a.shape.lower().split("x")),)
-    if a.matmul or a.attention:
+    if a.embeddings:
+        for B, T in shapes:
+            tv = draw_lengths(a.lengths, B, T) if a.lengths else None
+            if tv is not None:
+                print(f"B={B} T={T} lengths={a.lengths} seed={LENGTH_SEED} t_valid={tv.tolist()} mean={tv.float().mean().item():.1f}", flush=True)
+            for layers in sorted({0, a.layers}):
+                r = {"B": B, "T": T, "layers": layers, "lengths": a.lengths, "t_valid": None if tv is None else tv.tolist()}
+                steps = {e: model_step(layers, "hip", B, T, dev, tv, tv is not None, embeddings=e) for e in a.embeddings}
+                if layers == 0:
+                    for e, step in steps.items():
+                        r[f"{e}_kernels"] = kernel_count(step)
+                for mode, fns in (("eager", steps), ("graph", {e: graphed(s) for e, s in steps.items()})):
+                    for e, (med, lo, hi) in timed_interleaved(fns, a.iters).items():
+                        r[f"{e}_{mode}_ms"], r[f"{e}_{mode}_min_ms"], r[f"{e}_{mode}_max_ms"] = med, lo, hi
+                    del fns
+                del steps
+                torch.cuda.empty_cache()
+                rows.append(r)
+                what = "embeddings stage alone" if layers == 0 else f"layers={layers:2d}"
+                print(f"B={B} T={T} {what} lengths={a.lengths}: " + "  ".join(f"{k}={v:.4f}" for k, v in r.items() if k.endswith("_ms"))
+                      + "".join(f"  {k}={v}" for k, v in r.items() if k.endswith("_kernels")), flush=True)
+        shapes = ()
+    elif a.matmul or a.attention:
         combos = [(mm, at) for mm in (a.matmul or ["fp32"]) for at in (a.attention or ["fp32"])]
         for B, T in shapes:
             tv = draw_lengths(a.lengths, B, T) if a.lengths else None
