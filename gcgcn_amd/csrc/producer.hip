@@ -958,22 +958,24 @@ __global__ __launch_bounds__(64 * PW) void prod_table_bwd_kernel(const float* __
     float sf[HC], ds[HC];
 #pragma unroll
     for (int cc = 0; cc < HC; ++cc) sf[cc] = (lane + 64 * cc) < Hd ? sentF[bt * Hd + lane + 64 * cc] : 0.f, ds[cc] = 0.f;
-    const float gl = lane < ND ? dtable[((long)b * ND + lane) * T + t] : 0.f;   // all ND ids at once
-    unsigned long long todo = __ballot(gl != 0.f);
-    while (todo) {
-      const int k = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const float g = lane_value(gl, k);
-      dbias += g;
+    for (int k0 = 0; k0 < ND; k0 += 64) {   // 64 ids per trip, ascending: one trip, and the same sums as ever, for ND <= 64
+      const float gl = k0 + lane < ND ? dtable[((long)b * ND + k0 + lane) * T + t] : 0.f;
+      unsigned long long todo = __ballot(gl != 0.f);
+      while (todo) {
+        const int kl = __ffsll((long long)todo) - 1, k = k0 + kl;
+        todo &= todo - 1;
+        const float g = lane_value(gl, kl);
+        dbias += g;
 #pragma unroll
-      for (int cc = 0; cc < HC; ++cc) {
-        const int c = lane + 64 * cc;
-        if (c < Hd) {
-          const float z = tanhf(sf[cc] + disF[(long)k * Hd + c]);
-          const float d = g * w[cc] * (1.f - z * z);
-          ds[cc] += d;
-          mine[k * Hd + c] += d;          // this wave's own LDS record, program order
-          dw[cc] = fmaf(g, z, dw[cc]);
+        for (int cc = 0; cc < HC; ++cc) {
+          const int c = lane + 64 * cc;
+          if (c < Hd) {
+            const float z = tanhf(sf[cc] + disF[(long)k * Hd + c]);
+            const float d = g * w[cc] * (1.f - z * z);
+            ds[cc] += d;
+            mine[k * Hd + c] += d;          // this wave's own LDS record, program order
+            dw[cc] = fmaf(g, z, dw[cc]);
+          }
         }
       }
     }

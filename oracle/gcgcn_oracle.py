@@ -364,11 +364,12 @@ def edge_features(ctx: Tensor, sen_matrix: Tensor, pos_h: Tensor, pos_t: Tensor,
 
 
 def edge_features_folded(ctx: Tensor, sen_matrix: Tensor, pos_h: Tensor, pos_t: Tensor, node_feat: Tensor,
-                         dis_table: Tensor, sd: Params, hop: int) -> Tensor:
+                         dis_table: Tensor, sd: Params, hop: int, trace: Optional[dict] = None) -> Tensor:
     """The same E without ever materialising [N,N,S,T,Hd]: the word score depends only on (token t,
     distance id k), so it is a [21, T] table gathered by the position matrices; the attended word context is then a
     [N*N*S, T] x [T, Hd] product, and the node terms of the sentence score are per-entity vectors.  This is the
-    algorithm a kernel would implement; it is pinned against :func:`edge_features`."""
+    algorithm a kernel would implement; it is pinned against :func:`edge_features`.  ``trace`` (a dict) receives the sentence
+    scores before the mask and the relu, ``score_h`` / ``score_t`` [N,N,S], detached."""
     n, _, s, t = sen_matrix.shape
     wa = sub(sd, f"word_attention.{hop}")
     sent = ctx @ wa["attention_sent.weight"].t() + wa["attention_sent.bias"]                       # [T,Hd]
@@ -388,12 +389,14 @@ def edge_features_folded(ctx: Tensor, sen_matrix: Tensor, pos_h: Tensor, pos_t: 
     spad = ~sen_matrix[:, :, :, 0]                                                                # [N,N,S]
     div = spad.sum(dim=2, keepdim=True) + 1e-10                                                   # padded slots, as the reference
 
-    def sentence(node_term):                                                                      # node_term [N,N,1,Hd]
+    def sentence(node_term, side):                                                                # node_term [N,N,1,Hd]
         score = (torch.tanh(sfeat + node_term) @ sa["attention_all.weight"].t() + sa["attention_all.bias"]).squeeze(-1)
+        if trace is not None:
+            trace[side] = score.detach()
         att = torch.relu(score.masked_fill(spad, -100000.0))
         return (att.unsqueeze(-1) * cwa).sum(dim=2) / div
-    cs_h = sentence(nterm.view(1, n, 1, -1))                                                       # head side: indexed by j
-    cs_t = sentence(nterm.view(n, 1, 1, -1))                                                       # tail side: indexed by i
+    cs_h = sentence(nterm.view(1, n, 1, -1), "score_h")                                                       # head side: indexed by j
+    cs_t = sentence(nterm.view(n, 1, 1, -1), "score_t")                                                       # tail side: indexed by i
     ls = sub(sd, f"linear_sentence_att.{hop}")
     return torch.cat([cs_h, cs_t], 2) @ ls["weight"].t() + ls["bias"]
 
