@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("GCGCN_LIB") or os.path.join(_HERE, "lib", "libgcgcn_h
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcgcn.h")
 OPTIM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcgcn_optim.h")    # the optimiser extension, symbols gcopt_*
 BERT_EMBED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcgcn_bert_embed.h")    # the embeddings stage, symbols gcbe_*
+PRODUCER_REC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcgcn_producer_rec.h")    # the producer's record route, symbols gcpr_*
 
 ABI_VERSION = 7
 
@@ -49,6 +50,7 @@ _SCALARS = {"int": c_int, "int32_t": c_int, "int64_t": c_int64, "uint64_t": c_ui
 _DECL = re.compile(r"([\w\s*]+?)\b(gcgcn_\w+)\s*\(([^()]*)\)")                     # <ret> gcgcn_<name>(<args>)
 _DECL_OPTIM = re.compile(r"([\w\s*]+?)\b(gcopt_\w+)\s*\(([^()]*)\)")               # the same in gcgcn_optim.h
 _DECL_BERT_EMBED = re.compile(r"([\w\s*]+?)\b(gcbe_\w+)\s*\(([^()]*)\)")          # and in gcgcn_bert_embed.h
+_DECL_PRODUCER_REC = re.compile(r"([\w\s*]+?)\b(gcpr_\w+)\s*\(([^()]*)\)")        # and in gcgcn_producer_rec.h
 _STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;")
 
 
@@ -128,9 +130,20 @@ def _load_bert_embed_header():
     return sigs
 
 
+def _load_producer_rec_header():
+    if not os.path.exists(PRODUCER_REC_HEADER_PATH):
+        raise RuntimeError(f"gcgcn_amd: {PRODUCER_REC_HEADER_PATH} not found. The binding is derived from the C headers of the source tree.")
+    with open(PRODUCER_REC_HEADER_PATH) as f:
+        sigs, structs = _parse_header(f.read(), _DECL_PRODUCER_REC, "include/gcgcn_producer_rec.h")
+    if structs:
+        raise RuntimeError(f"gcgcn_amd: include/gcgcn_producer_rec.h declares structs {list(structs)}; it takes plain arguments only")
+    return sigs
+
+
 SIGNATURES = _load_header()  # name -> (restype, argtypes), in the order of include/gcgcn.h
 OPTIM_SIGNATURES = _load_optim_header()  # the same for include/gcgcn_optim.h; a table of its own, so the core's stays what is recorded
 BERT_EMBED_SIGNATURES = _load_bert_embed_header()  # and for include/gcgcn_bert_embed.h
+PRODUCER_REC_SIGNATURES = _load_producer_rec_header()  # and for include/gcgcn_producer_rec.h
 
 _lib = None
 
@@ -144,7 +157,8 @@ def lib() -> ctypes.CDLL:
                 f"gcgcn_amd: {LIB_PATH} not found. Build it with `make -C gcgcn_amd/csrc` "
                 "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(BERT_EMBED_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(BERT_EMBED_SIGNATURES.items()) + \
+                list(PRODUCER_REC_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -25,101 +25,28 @@
 
 #include "gemm.hpp"
 #include "rowops.hpp"
+#include "producer_slots.hpp"   // ProdIdx, the slot sources and the per-row bodies shared with producer_rec.hip
 
 namespace gc {
 
-constexpr int PW = 4;      // waves per workgroup of the row kernels
-constexpr int PGRID = 2048;  // persistent grid of the row kernels (8 workgroups per CU)
-constexpr int HCLIM = 8;   // Hd <= 64 * HCLIM
-
-struct ProdIdx {           // compact index of the live slots / pairs (device memory, int32)
-  int* doc_counts;         // [B][2] live slots, live pairs per document
-  int* pair_bits;          // [B*N*N] bit s set: slot s of the pair is live
-  int* pair_row0;          // [B*N*N] first compact row of the pair (its live slots are consecutive rows)
-  int* pair_prow;          // [B*N*N] compact pair index, -1: no live slot
-  float* pair_div;         // [B*N*N] padded slots + 1e-10 (glove:205, 212); 0 for padding entities
-  int* row_slot;           // [cap_rows] flat slot index ((b*N + i)*N + j)*S + s of a compact row
-  int* prow_pair;          // [cap_pairs] flat pair index of a compact pair
-  int* counts;             // [4] rows, pairs, overflow flag, unused
-  int* doc_off;            // [B + 1] first compact row of each document (its live rows are consecutive)
-  int* row_rng;            // [cap_rows] token range of the row's slot, t0 | t1 << 16 (written by the forward's word kernel)
-  int* tmax;               // [B] one past the last token any live slot of the document covers
-};
-
-__device__ __forceinline__ int pos_at(const void* pos, int pos_bytes, long idx) {
-  return pos_bytes == 8 ? (int)((const long long*)pos)[idx] : (pos_bytes == 4 ? ((const int*)pos)[idx] : (int)((const unsigned char*)pos)[idx]);
-}
-
-// ---- index: pass A, one workgroup per document -------------------------------------------------------------------
-// (Round 5: one workgroup per document is 32 workgroups of pure latency -- per 256 pairs it ran S dependent byte loads and a
-// 16-barrier Hillis-Steele scan, 28 us per call and two calls per step of the model.  Now the liveness bytes of eight chunks of
-// pairs are requested together, and the scan is a wave prefix (shuffles) plus one hand-over between the four waves: two
-// barriers per chunk.  Same integers out.)
+// ---- index: pass A, one workgroup per document (body: producer_slots.hpp) ------------------------------------------
 __global__ __launch_bounds__(256) void prod_index_a_kernel(const unsigned char* __restrict__ sen, const int* __restrict__ n_valid,
                                                            ProdIdx ix, int N, int S, int T) {
-  __shared__ int wsum[2][4];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nv = n_valid ? min(max(n_valid[b], 0), N) : N;
-  const int NN = N * N;
-  auto wave_incl = [&](int v) {
+  prod_index_a_body(
+      [&](long pp) {
+        int bits = 0;
+        const long s0 = pp * S;
+        for (int sb = 0; sb < S; sb += 8) {
+          unsigned char v[8];
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int t = __shfl_up(v, d, 64);
-      if (lane >= d) v += t;
-    }
-    return v;
-  };
-  int run_s = 0, run_p = 0;
-  constexpr int CH = 8;   // chunks of 256 pairs whose loads are in flight together
-  for (int base0 = 0; base0 < NN; base0 += CH * 256) {
-    int bitsv[CH];
+          for (int u = 0; u < 8; ++u) v[u] = sen[(s0 + min(sb + u, S - 1)) * T];
 #pragma unroll
-    for (int ch = 0; ch < CH; ++ch) {
-      const int p = base0 + ch * 256 + tid;
-      int bits = 0;
-      if (p < NN) {
-        const int i = p / N, j = p - i * N;
-        if (i < nv && j < nv) {
-          const long s0 = ((long)b * NN + p) * S;
-          for (int sb = 0; sb < S; sb += 8) {
-            unsigned char v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = sen[(s0 + min(sb + u, S - 1)) * T];
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-              if (sb + u < S && v[u] != 0) bits |= 1 << (sb + u);
-          }
+          for (int u = 0; u < 8; ++u)
+            if (sb + u < S && v[u] != 0) bits |= 1 << (sb + u);
         }
-      }
-      bitsv[ch] = bits;
-    }
-#pragma unroll
-    for (int ch = 0; ch < CH; ++ch) {
-      const int base = base0 + ch * 256;
-      if (base >= NN) break;                       // (uniform)
-      const int p = base + tid, bits = bitsv[ch];
-      const int c = __popc(bits), live = c > 0;
-      const int ic = wave_incl(c), il = wave_incl(live);
-      if (lane == 63) wsum[0][wave] = ic, wsum[1][wave] = il;
-      __syncthreads();
-      int offc = 0, offl = 0, totc = 0, totl = 0;
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const int a_ = wsum[0][w], q_ = wsum[1][w];
-        if (w < wave) offc += a_, offl += q_;
-        totc += a_, totl += q_;
-      }
-      if (p < NN) {
-        const long pp = (long)b * NN + p;
-        ix.pair_bits[pp] = bits;
-        ix.pair_row0[pp] = run_s + offc + ic - c;          // local to the document; pass B adds the document's offset
-        ix.pair_prow[pp] = live ? run_p + offl + il - 1 : -1;
-      }
-      run_s += totc, run_p += totl;
-      __syncthreads();
-    }
-  }
-  if (tid == 0) ix.doc_counts[2 * b] = run_s, ix.doc_counts[2 * b + 1] = run_p;
+        return bits;
+      },
+      n_valid, ix, N);
 }
 
 // ---- index: pass B, grid (ceil(N*N / 256), B): global rows + inverse maps ------------------------------------------
@@ -211,30 +138,6 @@ __global__ __launch_bounds__(64 * PW) void prod_table_fwd_kernel(const float* __
   }
 }
 
-// Gathered scores of one (slot, side) for the wave's tokens t = c0 + 64 u + lane, u < 8: the mask byte, the position id and
-// the table entry of all eight chunks are requested before the first one is used (clamped addresses, not guarded loads: a
-// load inside a branch is waited for at the branch's end).  sc[u] = -inf for masked / out-of-range tokens.
-__device__ __forceinline__ void slot_scores8(const unsigned char* __restrict__ m, const void* __restrict__ pos, int pos_bytes,
-                                             long slot_base, const float* __restrict__ tab, int T, int ND, int c0, int lane,
-                                             float (&sc)[8]) {
-  unsigned char mm[8];
-  int kk[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int tc = min(c0 + 64 * u + lane, T - 1);
-    mm[u] = m[tc];
-    kk[u] = pos_at(pos, pos_bytes, slot_base + tc);
-  }
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int tc = min(c0 + 64 * u + lane, T - 1);
-    sc[u] = tab[(long)min(max(kk[u], 0), ND - 1) * T + tc];
-  }
-#pragma unroll
-  for (int u = 0; u < 8; ++u)
-    if (c0 + 64 * u + lane >= T || !mm[u]) sc[u] = -INFINITY;
-}
-
 // ---- word attention of the live slots (glove:184-187): CW[row, side*Hd + c] = sum_t softmax_t(score)[t] ctx[b, t, c] -
 // dynamic LDS: PW * T floats (the un-normalised weights of the wave's slot)
 template <int HC>
@@ -244,110 +147,11 @@ __global__ __launch_bounds__(64 * PW) void prod_word_fwd_kernel(const float* __r
                                                                 float* __restrict__ CW, float* __restrict__ stats, int N, int S,
                                                                 int T, int Hd, int ND) {
   extern __shared__ float wsm[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float* ev = wsm + (long)wave * T;
-  const int nrows = ix.counts[0], total = 2 * nrows;
-  const long slots_per_doc = (long)N * N * S;
-  for (int r0 = blockIdx.x * PW; r0 < total; r0 += gridDim.x * PW) {
-    const int r = r0 + wave;
-    const bool on = r < total;
-    int t0 = T, t1 = 0;
-    float inv = 0.f;
-    long b = 0;
-    if (on) {
-      const int row = r >> 1, side = r & 1;
-      const long slot = ix.row_slot[row];
-      b = slot / slots_per_doc;
-      const unsigned char* m = sen + slot * T;
-      const void* pos = side ? pos_t : pos_h;
-      const float* tab = table + b * ND * T;
-      float mx = -INFINITY;
-      for (int c0 = 0; c0 < T; c0 += 512) {
-        float sc[8];
-        slot_scores8(m, pos, pos_bytes, slot * T, tab, T, ND, c0, lane, sc);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int t = c0 + 64 * u + lane;
-          if (t < T) {
-            ev[t] = sc[u];
-            if (sc[u] != -INFINITY) t0 = min(t0, t), t1 = max(t1, t + 1);
-            mx = fmaxf(mx, sc[u]);
-          }
-        }
-      }
-      mx = wave_max(mx);
-      t0 = -(int)wave_max((float)-t0), t1 = (int)wave_max((float)t1);   // exact for |t| < 2^24
-      float sum = 0.f;
-      for (int t = lane; t < T; t += 64) {
-        const float e = ev[t] == -INFINITY ? 0.f : expf(ev[t] - mx);   // masked tokens: exp(-100000 - max) == 0 in fp32
-        ev[t] = e;
-        sum += e;
-      }
-      sum = wave_sum(sum);
-      inv = 1.f / sum;
-      if (lane == 0) {
-        stats[2 * (long)r] = mx, stats[2 * (long)r + 1] = inv;
-        if (side == 0) ix.row_rng[row] = t0 | (t1 << 16);   // the slot's token range (T <= 2048): read again by the backward
-      }
-    }
-    __syncthreads();  // ev[] written lane-wise, read by every lane below (uniform trip count: every wave gets here)
-    if (on) {
-      const int row = r >> 1, side = r & 1;
-      const float* cb = ctx + b * T * Hd;
-      float acc[HC];
-#pragma unroll
-      for (int cc = 0; cc < HC; ++cc) acc[cc] = 0.f;
-      int t = t0;
-      for (; t + 3 < t1; t += 4) {  // four token rows in flight
-        float x[4][HC];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int cc = 0; cc < HC; ++cc) {
-            const int c = lane + 64 * cc;
-            x[u][cc] = c < Hd ? cb[(long)(t + u) * Hd + c] : 0.f;
-          }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const float e = ev[t + u];
-#pragma unroll
-          for (int cc = 0; cc < HC; ++cc) acc[cc] = fmaf(e, x[u][cc], acc[cc]);
-        }
-      }
-      for (; t < t1; ++t) {
-        const float e = ev[t];
-#pragma unroll
-        for (int cc = 0; cc < HC; ++cc) {
-          const int c = lane + 64 * cc;
-          if (c < Hd) acc[cc] = fmaf(e, cb[(long)t * Hd + c], acc[cc]);
-        }
-      }
-#pragma unroll
-      for (int cc = 0; cc < HC; ++cc) {
-        const int c = lane + 64 * cc;
-        if (c < Hd) CW[(long)row * 2 * Hd + side * Hd + c] = acc[cc] * inv;
-      }
-    }
-    __syncthreads();  // before the next slot overwrites ev[]
-  }
-  // rows [nrows, roundup64(nrows)) feed the K-dynamic GEMMs as zeros
-  if (blockIdx.x == 0) {
-    const int hi = (nrows + 63) & ~63;
-    for (long e = (long)nrows * 2 * Hd + threadIdx.x; e < (long)hi * 2 * Hd; e += 64 * PW) CW[e] = 0.f;
-  }
+  prod_word_fwd_body<HC>(DenseSlots{sen, pos_h, pos_t, pos_bytes}, wsm, ctx, table, ix, CW, stats, N, S, T, Hd, ND);
 }
 
 // ---- tmax[b] = one past the last token any live slot of document b covers (bounds the backward's per-token work) -------
-__global__ __launch_bounds__(256) void prod_tmax_kernel(ProdIdx ix) {
-  __shared__ int red[4];
-  const int b = blockIdx.x;
-  int m = 0;
-  for (int row = ix.doc_off[b] + threadIdx.x; row < ix.doc_off[b + 1]; row += 256) m = max(m, ix.row_rng[row] >> 16);
-  m = (int)wave_max((float)m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0) ix.tmax[b] = max(max(red[0], red[1]), max(red[2], red[3]));
-}
+__global__ __launch_bounds__(256) void prod_tmax_kernel(ProdIdx ix) { prod_tmax_body(ix); }
 
 // ---- sentence attention of the live pairs (glove:201-212) ----------------------------------------------------------
 //   score_h[s] = w . tanh(sfeat[row] + nterm[b, j]) + c,  score_t[s] uses nterm[b, i];  att = relu(score)
@@ -728,7 +532,7 @@ __global__ __launch_bounds__(256) void prod_dwb_fin_kernel(const float* __restri
 // dctx[b, t, :] and dtable[b, :, t]): scans the document's live rows, and for those whose slot holds the token recomputes
 // att and g (a 128-wide dot with the token state it keeps in registers) and accumulates in a fixed order -- deterministic,
 // and ~20x faster than scatter-adding with fp32 atomics.
-// dynamic LDS pass 1: PW * T floats
+// dynamic LDS pass 1: PW * (T + Hd) floats.  Both bodies: producer_slots.hpp.
 template <int HC>
 __global__ __launch_bounds__(64 * PW) void prod_word_bwd_rows_kernel(const float* __restrict__ ctx, const unsigned char* __restrict__ sen,
                                                                      const void* __restrict__ pos_h, const void* __restrict__ pos_t,
@@ -737,87 +541,7 @@ __global__ __launch_bounds__(64 * PW) void prod_word_bwd_rows_kernel(const float
                                                                      ProdIdx ix, float* __restrict__ dots, int N, int S, int T, int Hd,
                                                                      int ND) {
   extern __shared__ float wsm[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float* av = wsm + (long)wave * T;  // att[t]
-  const int nrows = ix.counts[0], total = 2 * nrows;
-  const long slots_per_doc = (long)N * N * S;
-  for (int r0 = blockIdx.x * PW; r0 < total; r0 += gridDim.x * PW) {
-    const int r = r0 + wave;
-    const bool on = r < total;
-    int t0 = T, t1 = 0;
-    long b = 0;
-    if (on) {
-      const int row = r >> 1, side = r & 1;
-      const long slot = ix.row_slot[row];
-      b = slot / slots_per_doc;
-      const void* pos = side ? pos_t : pos_h;
-      const unsigned char* m = sen + slot * T;
-      const float* tab = table + b * ND * T;
-      const float mx = stats[2 * (long)r], inv = stats[2 * (long)r + 1];
-      for (int c0 = 0; c0 < T; c0 += 512) {
-        float sc[8];
-        slot_scores8(m, pos, pos_bytes, slot * T, tab, T, ND, c0, lane, sc);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int t = c0 + 64 * u + lane;
-          if (t < T) {
-            av[t] = sc[u] == -INFINITY ? 0.f : expf(sc[u] - mx) * inv;
-            if (sc[u] != -INFINITY) t0 = min(t0, t), t1 = max(t1, t + 1);
-          }
-        }
-      }
-      t0 = -(int)wave_max((float)-t0), t1 = (int)wave_max((float)t1);
-    }
-    float* dl = wsm + (long)PW * T + (long)wave * Hd;   // this (row, side)'s dCW row, broadcast to every lane below
-    if (on)
-      for (int c = lane; c < Hd; c += 64) dl[c] = dCW[(long)(r >> 1) * 2 * Hd + (r & 1) * Hd + c];
-    __syncthreads();
-    if (on && (Hd & 3) == 0) {
-      // lanes over TOKENS: g[t] = dcw . ctx[t] is a private 128-wide dot per lane (16-byte loads of the lane's own token row,
-      // dcw broadcast from LDS) -- one wave reduction per 64 tokens instead of one per token
-      const float* cb = ctx + b * T * Hd;
-      float dotsum = 0.f;
-      for (int tb = t0; tb < t1; tb += 64) {
-        const int t = tb + lane;
-        const float4* cr = reinterpret_cast<const float4*>(cb + (long)min(t, t1 - 1) * Hd);
-        float g0 = 0.f, g1 = 0.f;
-        for (int q = 0; q < Hd / 4; q += 2) {
-          const float4 x0 = cr[q], x1 = cr[q + 1 < Hd / 4 ? q + 1 : q];
-          const float4 d0 = *reinterpret_cast<const float4*>(dl + 4 * q), d1 = *reinterpret_cast<const float4*>(dl + 4 * (q + 1 < Hd / 4 ? q + 1 : q));
-          g0 = fmaf(x0.x, d0.x, fmaf(x0.y, d0.y, fmaf(x0.z, d0.z, fmaf(x0.w, d0.w, g0))));
-          if (q + 1 < Hd / 4) g1 = fmaf(x1.x, d1.x, fmaf(x1.y, d1.y, fmaf(x1.z, d1.z, fmaf(x1.w, d1.w, g1))));
-        }
-        if (t < t1) dotsum = fmaf(av[t], g0 + g1, dotsum);
-      }
-      dotsum = wave_sum(dotsum);
-      if (lane == 0) dots[r] = dotsum;
-    } else if (on) {
-      const int row = r >> 1, side = r & 1;
-      const float* cb = ctx + b * T * Hd;
-      float dcw[HC], dotsum = 0.f;
-#pragma unroll
-      for (int cc = 0; cc < HC; ++cc) dcw[cc] = (lane + 64 * cc) < Hd ? dCW[(long)row * 2 * Hd + side * Hd + lane + 64 * cc] : 0.f;
-      for (int t = t0; t < t1; t += 4) {  // four tokens at a time: independent loads, interleaved reductions
-        float p[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int tt = min(t + u, t1 - 1);
-#pragma unroll
-          for (int cc = 0; cc < HC; ++cc) {
-            const int c = lane + 64 * cc;
-            if (c < Hd) p[u] = fmaf(dcw[cc], cb[(long)tt * Hd + c], p[u]);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const float g = wave_sum(p[u]);
-          if (t + u < t1) dotsum = fmaf(av[t + u], g, dotsum);
-        }
-      }
-      if (lane == 0) dots[r] = dotsum;
-    }
-    __syncthreads();
-  }
+  prod_word_bwd_rows_body<HC>(DenseSlots{sen, pos_h, pos_t, pos_bytes}, wsm, ctx, table, stats, dCW, ix, dots, N, S, T, Hd, ND);
 }
 
 // pass 2: one workgroup per (document, token); LDS: PW * (Hd + ND) floats
@@ -830,94 +554,7 @@ __global__ __launch_bounds__(64 * PW) void prod_word_bwd_tok_kernel(const float*
                                                                     float* __restrict__ dtable, float* __restrict__ dctx, int T, int Hd,
                                                                     int ND) {
   extern __shared__ float sm[];  // [PW][Hd] partial dctx rows | [PW][ND] partial dtable columns
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long bt = blockIdx.x;
-  const int b = (int)(bt / T), t = (int)(bt - (long)b * T);
-  float* accs = sm;
-  float* dts = sm + (long)PW * Hd;
-  for (int e = threadIdx.x; e < PW * ND; e += 64 * PW) dts[e] = 0.f;
-  float acc[HC], cx[HC];
-#pragma unroll
-  for (int cc = 0; cc < HC; ++cc) acc[cc] = 0.f, cx[cc] = (lane + 64 * cc) < Hd ? ctx[bt * Hd + lane + 64 * cc] : 0.f;
-  __syncthreads();
-  if (t < ix.tmax[b]) {
-    const int r_lo = ix.doc_off[b], r_hi = ix.doc_off[b + 1];
-    const float* tab = table + (long)b * ND * T;
-    float* dtw = dts + wave * ND;
-    for (int base = r_lo + wave * 64; base < r_hi; base += PW * 64) {
-      // lane-parallel: everything a hit needs except the dCW rows -- one latency chain per 64 candidate rows, not per hit
-      const int row = base + lane;
-      bool hit = false;
-      float ah = 0.f, at = 0.f, dh = 0.f, dt = 0.f;
-      int kh = 0, kt = 0;
-      if (row < r_hi) {
-        const int rg = ix.row_rng[row];
-        if (t >= (rg & 0xffff) && t < (rg >> 16)) {
-          const long slot = ix.row_slot[row];
-          if (sen[slot * T + t]) {
-            hit = true;
-            kh = min(max(pos_at(pos_h, pos_bytes, slot * T + t), 0), ND - 1);
-            kt = min(max(pos_at(pos_t, pos_bytes, slot * T + t), 0), ND - 1);
-            const float4 st = *reinterpret_cast<const float4*>(stats + 4L * row);   // max / 1/sum of the head, of the tail side
-            ah = expf(tab[(long)kh * T + t] - st.x) * st.y;
-            at = expf(tab[(long)kt * T + t] - st.z) * st.w;
-            dh = dots[2L * row], dt = dots[2L * row + 1];
-          }
-        }
-      }
-      unsigned long long todo = __ballot(hit);
-      float nh[HC], nt[HC];   // dCW rows of the NEXT hit, requested one hit ahead
-      int l = todo ? __ffsll((long long)todo) - 1 : 0;
-#pragma unroll
-      for (int cc = 0; cc < HC; ++cc) {
-        const int c = lane + 64 * cc;
-        nh[cc] = (todo && c < Hd) ? dCW[(long)(base + l) * 2 * Hd + c] : 0.f;
-        nt[cc] = (todo && c < Hd) ? dCW[(long)(base + l) * 2 * Hd + Hd + c] : 0.f;
-      }
-      while (todo) {
-        const int cur = l;
-        todo &= todo - 1;
-        float ch[HC], ct[HC], ph = 0.f, pt = 0.f;
-#pragma unroll
-        for (int cc = 0; cc < HC; ++cc) ch[cc] = nh[cc], ct[cc] = nt[cc];
-        if (todo) {
-          l = __ffsll((long long)todo) - 1;
-#pragma unroll
-          for (int cc = 0; cc < HC; ++cc) {
-            const int c = lane + 64 * cc;
-            nh[cc] = c < Hd ? dCW[(long)(base + l) * 2 * Hd + c] : 0.f;
-            nt[cc] = c < Hd ? dCW[(long)(base + l) * 2 * Hd + Hd + c] : 0.f;
-          }
-        }
-#pragma unroll
-        for (int cc = 0; cc < HC; ++cc) ph = fmaf(ch[cc], cx[cc], ph), pt = fmaf(ct[cc], cx[cc], pt);
-        const float gh = wave_sum(ph), gt = wave_sum(pt);
-        const float a_h = lane_value(ah, cur), a_t = lane_value(at, cur);
-        if (lane == 0) {   // one lane, program order: deterministic
-          dtw[__builtin_amdgcn_readlane(kh, cur)] += a_h * (gh - lane_value(dh, cur));
-          dtw[__builtin_amdgcn_readlane(kt, cur)] += a_t * (gt - lane_value(dt, cur));
-        }
-#pragma unroll
-        for (int cc = 0; cc < HC; ++cc) acc[cc] = fmaf(a_h, ch[cc], fmaf(a_t, ct[cc], acc[cc]));
-      }
-    }
-  }
-#pragma unroll
-  for (int cc = 0; cc < HC; ++cc)
-    if ((lane + 64 * cc) < Hd) accs[wave * Hd + lane + 64 * cc] = acc[cc];
-  __syncthreads();
-  for (int c = threadIdx.x; c < Hd; c += 64 * PW) {
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < PW; ++w) v += accs[w * Hd + c];
-    dctx[bt * Hd + c] = v;
-  }
-  for (int k = threadIdx.x; k < ND; k += 64 * PW) {
-    float v = 0.f;
-#pragma unroll
-    for (int w = 0; w < PW; ++w) v += dts[w * ND + k];
-    dtable[((long)b * ND + k) * T + t] = v;
-  }
+  prod_word_bwd_tok_body<HC>(DenseSlots{sen, pos_h, pos_t, pos_bytes}, sm, ctx, table, stats, dCW, dots, ix, dtable, dctx, T, Hd, ND);
 }
 
 // ---- backward of the score table ------------------------------------------------------------------------------------
@@ -1053,15 +690,6 @@ __global__ __launch_bounds__(256) void prod_colsum_fin_kernel(const float* __res
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
-// kernels are instantiated for HC = ceil(Hd / 64) in {1, 2, 4, 8} column chunks per lane (the reference's Hd = 128: HC = 2)
-#define PROD_LAUNCH(kernel, Hd, grid, block, lds, st, ...)                                            \
-  do {                                                                                                \
-    const int _hc = ((Hd) + 63) / 64;                                                                 \
-    if (_hc <= 1) hipLaunchKernelGGL((kernel<1>), grid, block, lds, st, __VA_ARGS__);                 \
-    else if (_hc <= 2) hipLaunchKernelGGL((kernel<2>), grid, block, lds, st, __VA_ARGS__);            \
-    else if (_hc <= 4) hipLaunchKernelGGL((kernel<4>), grid, block, lds, st, __VA_ARGS__);            \
-    else hipLaunchKernelGGL((kernel<8>), grid, block, lds, st, __VA_ARGS__);                          \
-  } while (0)
 
 struct ProdLayout {  // offsets (floats) inside the block's flat parameter buffer; reference tensors keep their [out, in] layout
   long Ws, bs, Wp, bp, wa, ba;           // word_attention.{attention_sent, attention_pos, attention_all}
@@ -1087,7 +715,13 @@ static long up64(long v) { return (v + 63) & ~63L; }
 // The deterministic backward's extra workspace (gcgcn_producer_bwd_det): dnpair[up64(cap_pairs)][2][Hd] | dwpart[PGRID][Hd + 1],
 // each piece rounded to 16 bytes.
 static long prod_det_dnpair_elems(int Hd, long cap_pairs) { return (up64(cap_pairs) * 2 * Hd + 3) & ~3L; }
-static long prod_det_elems(int Hd, long cap_pairs) { return prod_det_dnpair_elems(Hd, cap_pairs) + (((long)PGRID * (Hd + 1) + 3) & ~3L); }
+long prod_det_elems(int Hd, long cap_pairs) { return prod_det_dnpair_elems(Hd, cap_pairs) + (((long)PGRID * (Hd + 1) + 3) & ~3L); }
+
+int prod_index_b(const int* n_valid, ProdIdx ix, int B, int N, int S, long cap_rows, long cap_pairs, hipStream_t st) {
+  hipLaunchKernelGGL(prod_index_b_kernel, dim3(cdiv((long)N * N, 256), B), dim3(256), 0, st, n_valid, ix, B, N, S, (int)cap_rows,
+                     (int)cap_pairs);
+  return check_launch("prod_index_b");
+}
 
 int prod_index(const unsigned char* sen, const int* n_valid, ProdIdx ix, int B, int N, int S, int T, long cap_rows, long cap_pairs,
                hipStream_t st) {
@@ -1096,9 +730,7 @@ int prod_index(const unsigned char* sen, const int* n_valid, ProdIdx ix, int B, 
   ProfScope ps("prod_index", st);
   hipLaunchKernelGGL(prod_index_a_kernel, dim3(B), dim3(256), 0, st, sen, n_valid, ix, N, S, T);
   if (int e = check_launch("prod_index_a")) return e;
-  hipLaunchKernelGGL(prod_index_b_kernel, dim3(cdiv((long)N * N, 256), B), dim3(256), 0, st, n_valid, ix, B, N, S, (int)cap_rows,
-                     (int)cap_pairs);
-  return check_launch("prod_index_b");
+  return prod_index_b(n_valid, ix, B, N, S, cap_rows, cap_pairs, st);
 }
 
 // The three products of one Linear layer over `rows` rows, W stored [Nout, K] -- described here, launched by their callers.
@@ -1146,15 +778,15 @@ static int linear_bwd_all(const float* dY, const float* X, long M, int Nout, int
   return gemm_group(gs, 2, st, &cr);
 }
 
-struct ProdBufs {  // caller-owned device memory (include/gcgcn.h lists the sizes)
-  float *sentF, *disF, *table, *CW, *stats, *cwa, *sfeat, *nterm, *score, *CS, *Ec;
-};
 
-int prod_fwd(int B, int N, int S, int T, int Hd, int P, int ND, const float* ctx, const unsigned char* sen, const void* pos_h,
-             const void* pos_t, int pos_bytes, const float* node, const float* dis_table, const int* n_valid, const float* flat,
-             ProdIdx ix, long cap_rows, long cap_pairs, ProdBufs w, float* E, float* ws, long wse, hipStream_t st) {
+int prod_fwd(int B, int N, int S, int T, int Hd, int P, int ND, const float* ctx, const ProdSrc& src, const float* node,
+             const float* dis_table, const int* n_valid, const float* flat, ProdIdx ix, long cap_rows, long cap_pairs, ProdBufs w, float* E,
+             float* ws, long wse, hipStream_t st) {
+  const unsigned char* const sen = src.sen;
+  const void *const pos_h = src.pos_h, *const pos_t = src.pos_t;
+  const int pos_bytes = src.pos_bytes;
   GC_REQUIRE(Hd >= 1 && Hd <= 64 * HCLIM, "producer: hidden width %d (1..%d supported)", Hd, 64 * HCLIM);
-  GC_REQUIRE(pos_bytes == 8 || pos_bytes == 4 || pos_bytes == 1, "producer: position ids must be int64, int32 or uint8");
+  GC_REQUIRE(src.rec || pos_bytes == 8 || pos_bytes == 4 || pos_bytes == 1, "producer: position ids must be int64, int32 or uint8");
   GC_REQUIRE((size_t)PW * 2 * T * sizeof(float) <= 64 * 1024, "producer: T=%d tokens exceed the LDS budget", T);
   const ProdLayout y = prod_layout(Hd, P);
   const long BT = (long)B * T;
@@ -1171,12 +803,17 @@ int prod_fwd(int B, int N, int S, int T, int Hd, int P, int ND, const float* ctx
                        flat + y.ba, w.table, BT, T, Hd, ND);
     GC_TRY(check_launch("prod_table_fwd"));
   }
-  GC_TRY(prod_index(sen, n_valid, ix, B, N, S, T, cap_rows, cap_pairs, st));
+  if (src.rec) GC_TRY(prod_rec_index(src, n_valid, ix, B, N, S, T, cap_rows, cap_pairs, st));
+  else GC_TRY(prod_index(sen, n_valid, ix, B, N, S, T, cap_rows, cap_pairs, st));
   {
     ProfScope ps("prod_word", st);
-    PROD_LAUNCH(prod_word_fwd_kernel, Hd, dim3(PGRID), dim3(64 * PW), (size_t)PW * T * sizeof(float), st, ctx, sen, pos_h, pos_t,
-                       pos_bytes, w.table, ix, w.CW, w.stats, N, S, T, Hd, ND);
-    GC_TRY(check_launch("prod_word_fwd"));
+    if (src.rec) {   // the same body on the records (csrc/producer_rec.hip)
+      GC_TRY(prod_rec_word_fwd(src, ctx, w.table, ix, w.CW, w.stats, N, S, T, Hd, ND, st));
+    } else {
+      PROD_LAUNCH(prod_word_fwd_kernel, Hd, dim3(PGRID), dim3(64 * PW), (size_t)PW * T * sizeof(float), st, ctx, sen, pos_h, pos_t,
+                         pos_bytes, w.table, ix, w.CW, w.stats, N, S, T, Hd, ND);
+      GC_TRY(check_launch("prod_word_fwd"));
+    }
     hipLaunchKernelGGL(prod_tmax_kernel, dim3(B), dim3(256), 0, st, ix);
     GC_TRY(check_launch("prod_tmax"));
   }
@@ -1202,9 +839,6 @@ int prod_fwd(int B, int N, int S, int T, int Hd, int P, int ND, const float* ctx
   return 0;
 }
 
-struct ProdGrads {  // caller-owned workspace of the backward pass
-  float *dEc, *dCS, *dcwa, *dsfeat, *dnterm, *dCW, *dtable, *dsentF, *ddisF, *dwb, *part, *wpair, *dots, *tpart;
-};
 
 static int colsum_dyn(const float* X, const int* cnt, int C, float* part, float* out, hipStream_t st) {
   ProfScope ps("prod_colsum", st);
@@ -1214,11 +848,13 @@ static int colsum_dyn(const float* X, const int* cnt, int C, float* part, float*
   return check_launch("prod_colsum_fin");
 }
 
-int prod_bwd(int B, int N, int S, int T, int Hd, int P, int ND, const float* ctx, const unsigned char* sen, const void* pos_h,
-             const void* pos_t, int pos_bytes, const float* node, const float* dis_table, const int* n_valid, const float* flat,
-             ProdIdx ix, long cap_rows, long cap_pairs, ProdBufs w, const float* dE, ProdGrads g, float* dctx, float* dnode,
-             float* ddis_table, float* dflat, float* ws, long wse, hipStream_t st, const float* dEc_in = nullptr, bool det = false,
-             float* detbuf = nullptr) {
+int prod_bwd(int B, int N, int S, int T, int Hd, int P, int ND, const float* ctx, const ProdSrc& src, const float* node,
+             const float* dis_table, const int* n_valid, const float* flat, ProdIdx ix, long cap_rows, long cap_pairs, ProdBufs w,
+             const float* dE, ProdGrads g, float* dctx, float* dnode, float* ddis_table, float* dflat, float* ws, long wse, hipStream_t st,
+             const float* dEc_in, bool det, float* detbuf) {
+  const unsigned char* const sen = src.sen;
+  const void *const pos_h = src.pos_h, *const pos_t = src.pos_t;
+  const int pos_bytes = src.pos_bytes;
   const ProdLayout y = prod_layout(Hd, P);
   const long BT = (long)B * T, BN = (long)B * N, BNN = BN * N;
   const int* nrows = ix.counts;
@@ -1288,12 +924,16 @@ int prod_bwd(int B, int N, int S, int T, int Hd, int P, int ND, const float* ctx
   // word attention -> score table and token states
   {
     ProfScope ps("prod_word", st);
-    PROD_LAUNCH(prod_word_bwd_rows_kernel, Hd, dim3(PGRID), dim3(64 * PW), (size_t)PW * (T + Hd) * sizeof(float), st, ctx, sen, pos_h,
-                       pos_t, pos_bytes, w.table, w.stats, g.dCW, ix, g.dots, N, S, T, Hd, ND);
-    GC_TRY(check_launch("prod_word_bwd_rows"));
-    PROD_LAUNCH(prod_word_bwd_tok_kernel, Hd, dim3((unsigned)BT), dim3(64 * PW), sizeof(float) * PW * (size_t)(Hd + ND), st, ctx, sen,
-                       pos_h, pos_t, pos_bytes, w.table, w.stats, g.dCW, g.dots, ix, g.dtable, dctx, T, Hd, ND);
-    GC_TRY(check_launch("prod_word_bwd_tok"));
+    if (src.rec) {   // the same two bodies on the records (csrc/producer_rec.hip)
+      GC_TRY(prod_rec_word_bwd(src, ctx, w.table, w.stats, g.dCW, ix, g.dots, g.dtable, dctx, B, N, S, T, Hd, ND, st));
+    } else {
+      PROD_LAUNCH(prod_word_bwd_rows_kernel, Hd, dim3(PGRID), dim3(64 * PW), (size_t)PW * (T + Hd) * sizeof(float), st, ctx, sen, pos_h,
+                         pos_t, pos_bytes, w.table, w.stats, g.dCW, ix, g.dots, N, S, T, Hd, ND);
+      GC_TRY(check_launch("prod_word_bwd_rows"));
+      PROD_LAUNCH(prod_word_bwd_tok_kernel, Hd, dim3((unsigned)BT), dim3(64 * PW), sizeof(float) * PW * (size_t)(Hd + ND), st, ctx, sen,
+                         pos_h, pos_t, pos_bytes, w.table, w.stats, g.dCW, g.dots, ix, g.dtable, dctx, T, Hd, ND);
+      GC_TRY(check_launch("prod_word_bwd_tok"));
+    }
   }
   {
     ProfScope ps("prod_table", st);
@@ -1364,10 +1004,9 @@ __global__ __launch_bounds__(256) void prod_count_kernel(const unsigned char* __
   }
 }
 
-struct ProdBound { ProdIdx ix; ProdBufs w; ProdGrads g; float* scratch; long n_int, n_fwd, n_bwd, counts_off, prow_off, ec_off; };
 // Carve the caller's three buffers (every piece starts 16-byte aligned); with null bases this only measures them.
-static ProdBound prod_bind(int32_t* ibuf, float* fwd, float* bwd, bool want_bwd, int B, int N, int S, int T, int Hd, int P, int ND,
-                           long cap_rows, long cap_pairs) {
+ProdBound prod_bind(int32_t* ibuf, float* fwd, float* bwd, bool want_bwd, int B, int N, int S, int T, int Hd, int P, int ND,
+                    long cap_rows, long cap_pairs) {
   const long R = up64(cap_rows), Q = up64(cap_pairs), BNN = (long)B * N * N;
   ProdBound o;
   memset(&o, 0, sizeof(o));
@@ -1380,6 +1019,7 @@ static ProdBound prod_bind(int32_t* ibuf, float* fwd, float* bwd, bool want_bwd,
   o.counts_off = at;
   o.ix.counts = ti(4);
   o.ix.doc_off = ti(B + 1), o.ix.row_rng = ti(R), o.ix.tmax = ti(B);
+  o.row_rec = ti(R);   // the record route's row -> record map (csrc/producer_rec.hip); last, so that every offset above stays
   o.n_int = at;
   float* base = fwd;
   at = 0;
@@ -1403,7 +1043,7 @@ static ProdBound prod_bind(int32_t* ibuf, float* fwd, float* bwd, bool want_bwd,
   return o;
 }
 
-static long prod_scratch_elems(int B, int N, int T, int Hd) {
+long prod_scratch_elems(int B, int N, int T, int Hd) {
   const long rows = (long)B * T > (long)B * N ? (long)B * T : (long)B * N;
   long a = gemm_ws_elems(rows, 2L * Hd), b = 64L * Hd * 2 * Hd + 16;   // split-K partials of the K-dynamic weight gradients
   long c = colsum_scratch_elems((long)B * N * N, Hd, 1);
@@ -1454,7 +1094,9 @@ int gcgcn_producer_fwd(int B, int N, int S, int T, int Hd, int P, int ND, const 
   GC_REQUIRE(ctx && sen && pos_h && pos_t && node && dis_table && flat && ibuf && fbuf, "producer_fwd: null pointer");   // E == NULL: compact
   GC_REQUIRE(cap_rows >= 0 && cap_pairs >= 0 && cap_rows < (1L << 30) && cap_pairs < (1L << 30), "producer_fwd: bad capacities");
   const ProdBound o = prod_bind(ibuf, fbuf, nullptr, false, B, N, S, T, Hd, P, ND, cap_rows, cap_pairs);
-  return prod_fwd(B, N, S, T, Hd, P, ND, ctx, sen, pos_h, pos_t, pos_bytes, node, dis_table, n_valid, flat, o.ix, cap_rows, cap_pairs,
+  ProdSrc src;
+  src.sen = sen, src.pos_h = pos_h, src.pos_t = pos_t, src.pos_bytes = pos_bytes;
+  return prod_fwd(B, N, S, T, Hd, P, ND, ctx, src, node, dis_table, n_valid, flat, o.ix, cap_rows, cap_pairs,
                   o.w, E, scratch, scratch ? scratch_elems : 0, (hipStream_t)stream);
 }
 
@@ -1469,7 +1111,9 @@ int gcgcn_producer_bwd(int B, int N, int S, int T, int Hd, int P, int ND, const 
              "producer_bwd: null pointer");
   const ProdBound o = prod_bind(ibuf, fbuf, bbuf, true, B, N, S, T, Hd, P, ND, cap_rows, cap_pairs);
   if (n_valid && dE) GC_TRY(prod_wpair(n_valid, o.g.wpair, B, N, st));
-  return prod_bwd(B, N, S, T, Hd, P, ND, ctx, sen, pos_h, pos_t, pos_bytes, node, dis_table, n_valid, flat, o.ix, cap_rows, cap_pairs,
+  ProdSrc src;
+  src.sen = sen, src.pos_h = pos_h, src.pos_t = pos_t, src.pos_bytes = pos_bytes;
+  return prod_bwd(B, N, S, T, Hd, P, ND, ctx, src, node, dis_table, n_valid, flat, o.ix, cap_rows, cap_pairs,
                   o.w, dE, o.g, dctx, dnode, ddis_table, dflat, o.scratch, prod_scratch_elems(B, N, T, Hd), st, dE ? nullptr : dEc);
 }
 
@@ -1500,7 +1144,9 @@ int gcgcn_producer_bwd_det(int B, int N, int S, int T, int Hd, int P, int ND, co
              (long)det_elems, prod_det_elems(Hd, cap_pairs));
   const ProdBound o = prod_bind(ibuf, fbuf, bbuf, true, B, N, S, T, Hd, P, ND, cap_rows, cap_pairs);
   if (n_valid && dE) GC_TRY(prod_wpair(n_valid, o.g.wpair, B, N, st));
-  return prod_bwd(B, N, S, T, Hd, P, ND, ctx, sen, pos_h, pos_t, pos_bytes, node, dis_table, n_valid, flat, o.ix, cap_rows, cap_pairs,
+  ProdSrc src;
+  src.sen = sen, src.pos_h = pos_h, src.pos_t = pos_t, src.pos_bytes = pos_bytes;
+  return prod_bwd(B, N, S, T, Hd, P, ND, ctx, src, node, dis_table, n_valid, flat, o.ix, cap_rows, cap_pairs,
                   o.w, dE, o.g, dctx, dnode, ddis_table, dflat, o.scratch, prod_scratch_elems(B, N, T, Hd), st, dE ? nullptr : dEc, true,
                   detbuf);
 }

@@ -4,24 +4,10 @@
 // All outputs are pre-zeroed by the caller; records of entities / tokens / slots beyond the batch's (N, S, T) are clipped
 // exactly as the reference's final slicing [:max_num, :max_length] does.
 #include "common.hpp"
+#include "producer_slots.hpp"   // dis2idx / pos_id: the record route of the producer computes the same ids in place
 #include "../../include/gcgcn.h"
 
 namespace gc {
-
-// config/Config.py:106-116: 0, 1, 2, 2, 3 x4, 4 x8, ... , 10 from 512 on (the table has 1024 entries)
-__device__ __forceinline__ int dis2idx(int d) {
-  d = min(max(d, 0), 1023);
-  return d == 0 ? 0 : min(10, 32 - __clz(d));
-}
-// Config.py:190-203: signed bucket of the token's distance to a mention span [a, b): left of it negative, right positive,
-// inside 0; then + dis_plus
-__device__ __forceinline__ int pos_id(int k, int a, int b, int dis_plus) {
-  const int dl = k - a, dr = k - b;
-  int v = 0;
-  if (dl < 0) v = -dis2idx(-dl);
-  else if (dr > 0) v = dis2idx(dr);
-  return v + dis_plus;
-}
 
 struct TensArgs {
   int B, N, S, T, R, dis_plus;

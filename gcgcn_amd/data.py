@@ -110,13 +110,39 @@ class PackedDocs:
         return cls(docs)
 
 
+def live_counts(docs: Sequence[PackedDoc], N: int, S: int, T: int):
+    """(live sentence slots, entity pairs with a live slot) of a batch, from the packed records alone -- host numpy, what
+    ``functional.producer_live_counts`` reads back from the dense ``sen_matrix`` of the same batch.  A record with ``u >= N``,
+    ``v >= N`` or ``j >= S`` is dropped (and one past the document's own entity count); its token range is ``[max(s0, 0), min(s1, T))``;
+    the slot is live iff token 0 lies in that range (the reference's padding test, glove:305)."""
+    if not len(docs):
+        return 0, 0
+    s = np.concatenate([np.asarray(d.slots).reshape(-1, SLOT_W) for d in docs], 0).astype(np.int64)
+    per = [np.asarray(d.slots).reshape(-1, SLOT_W).shape[0] for d in docs]
+    b = np.repeat(np.arange(len(docs), dtype=np.int64), per)
+    n = np.repeat(np.asarray([min(d.n, N) for d in docs], np.int64), per)      # entities past the document's own count are padding
+    u, v, j = s[:, 0], s[:, 1], s[:, 2]
+    r0, r1 = np.maximum(s[:, 3], 0), np.minimum(s[:, 4], T)
+    live = (u >= 0) & (u < n) & (v >= 0) & (v < n) & (j >= 0) & (j < S) & (r0 == 0) & (r1 > 0)
+    slot = np.unique(((b[live] * N + u[live]) * N + v[live]) * S + j[live])     # (doc, u, v, j) is unique; counted once anyway
+    rows, pairs = int(slot.size), int(np.unique(slot // S).size)
+    return rows, pairs
+
+
 def collate(docs: Sequence[PackedDoc], device, max_length: int = 512, max_num: int = 5, dis_plus: int = 10,
-            pad_nodes_to: Optional[int] = None) -> Dict[str, torch.Tensor]:
+            pad_nodes_to: Optional[int] = None, dense_slots: bool = True) -> Dict[str, object]:
     """Batch of documents -> the reference forward's inputs on ``device`` (config/Config.py:162-233, batched):
     ``document``, ``document_pos``, ``document_ner`` int64 ``[B,T]`` (0-padded), ``adj_matrix`` float ``[B,N,N]``, ``sen_matrix``
     bool ``[B,N,N,S,T]``, ``pos_matrix_h`` / ``pos_matrix_t`` uint8 ``[B,N,N,S,T]``, ``node_pos`` float ``[B,N,T]``, ``node_type``
     int64 ``[B,N]``, ``node_relative_pos`` int64 ``[B,N,N]``, ``label_matrix`` float ``[B,N,N,R]``, ``n_valid`` int32 ``[B]``,
-    ``t_valid`` int32 ``[B]``.  T = min(longest document, max_length), S = min(most sentence slots, max_num), N = most entities."""
+    ``t_valid`` int32 ``[B]``.  T = min(longest document, max_length), S = min(most sentence slots, max_num), N = most entities.
+
+    ``dense_slots=False``: the three ``[B,N,N,S,T]`` byte tensors are neither allocated nor written (3 x 144 MB at B = 32, N = 42,
+    S = 5, T = 512).  Instead of ``sen_matrix`` / ``pos_matrix_h`` / ``pos_matrix_t`` the dict holds ``slot_records`` (the int32
+    ``[n,10]`` table this function uploads anyway: ``doc, u, v, j, s0, s1, h0, h1, t0, t1``), ``S``, and ``max_live_slots`` /
+    ``max_live_pairs`` (Python ints, :func:`live_counts`): what ``functional.edge_features(slot_records=...)``, the modules and the
+    models take in their place.  Every other key is the same.  (Values are tensors, but for ``S`` and ``max_live_*`` -- ints -- and
+    ``_keep``.)"""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("collate: gcgcn_amd tensorises on the GPU (no CPU fallback)")
@@ -153,19 +179,28 @@ def collate(docs: Sequence[PackedDoc], device, max_length: int = 512, max_num: i
     slots, edges, labels = up(recs["slots"], SLOT_W + 1), up(recs["edges"], 3), up(recs["labels"], 4)
     mentions, mnode = up(recs["mentions"], 2), up(men_node, 4)
     tok_d = torch.from_numpy(tok).to(dev)
-    out = {"adj_matrix": torch.zeros(B, N, N, device=dev), "sen_matrix": torch.zeros(B, N, N, S, T, dtype=torch.uint8, device=dev),
-           "pos_matrix_h": torch.zeros(B, N, N, S, T, dtype=torch.uint8, device=dev),
-           "pos_matrix_t": torch.zeros(B, N, N, S, T, dtype=torch.uint8, device=dev),
+    # without dense slots the launch gets no slot record; its three outputs are one-byte stand-ins that it never touches
+    slot_shape = (B, N, N, S, T) if dense_slots else (1,)
+    out = {"adj_matrix": torch.zeros(B, N, N, device=dev), "sen_matrix": torch.zeros(slot_shape, dtype=torch.uint8, device=dev),
+           "pos_matrix_h": torch.zeros(slot_shape, dtype=torch.uint8, device=dev),
+           "pos_matrix_t": torch.zeros(slot_shape, dtype=torch.uint8, device=dev),
            "node_pos": torch.zeros(B, N, T, device=dev), "node_relative_pos": torch.zeros(B, N, N, dtype=torch.int64, device=dev),
            "label_matrix": torch.zeros(B, N, N, R, device=dev)}
     nv_d, first_d = torch.from_numpy(nvalid).to(dev), torch.from_numpy(first).to(dev)
     p = lambda t: None if t.numel() == 0 else t.data_ptr()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    call("gcgcn_tensorise", B, N, S, T, R, dis_plus, slots.shape[0], p(slots), edges.shape[0], p(edges), labels.shape[0], p(labels),
+    n_slots = slots.shape[0] if dense_slots else 0
+    call("gcgcn_tensorise", B, N, S, T, R, dis_plus, n_slots, p(slots) if n_slots else None, edges.shape[0], p(edges), labels.shape[0], p(labels),
          mentions.shape[0], p(mentions), p(mnode), nv_d.data_ptr(), first_d.data_ptr(), out["adj_matrix"].data_ptr(), out["sen_matrix"].data_ptr(),
          out["pos_matrix_h"].data_ptr(), out["pos_matrix_t"].data_ptr(), out["node_pos"].data_ptr(),
          out["node_relative_pos"].data_ptr(), out["label_matrix"].data_ptr(), stream)
-    out["sen_matrix"] = out["sen_matrix"].view(torch.bool)
+    if dense_slots:
+        out["sen_matrix"] = out["sen_matrix"].view(torch.bool)
+    else:
+        for k in ("sen_matrix", "pos_matrix_h", "pos_matrix_t"):
+            del out[k]
+        out["slot_records"], out["S"] = slots, S
+        out["max_live_slots"], out["max_live_pairs"] = live_counts(docs, N, S, T)
     out["document"], out["document_pos"], out["document_ner"] = (tok_d[:, :, k].long() for k in range(3))
     out["node_type"] = torch.from_numpy(ntype).to(dev).long()
     out["n_valid"], out["t_valid"] = nv_d, torch.from_numpy(tvalid).to(dev)

@@ -27,6 +27,18 @@ _SCORE_SHIFT, _SCORE_MAX = 34, 0x3FFFFFFF
 COUNTERS = ("top1_acc", "na_recall", "na_correct", "total_recall", "total_correct", "have_label")
 FORWARD_KEYS = ("document", "document_ner", "document_pos", "adj_matrix", "sen_matrix", "pos_matrix_h", "pos_matrix_t", "node_pos",
                 "node_type", "node_relative_pos")
+DENSE_SLOT_KEYS = ("sen_matrix", "pos_matrix_h", "pos_matrix_t")
+
+
+def forward_args(bt: dict):
+    """A batch dict of ``data.collate`` -> (positional arguments of the models' forward, keywords of the record route).  A batch of
+    ``collate(dense_slots=False)`` has ``slot_records`` instead of the three dense slot tensors: those positions are None, and the
+    records travel with ``slot_shape`` (S) and the host-side capacities ``max_live_slots`` / ``max_live_pairs``."""
+    if bt.get("slot_records") is None:
+        return [bt[k] for k in FORWARD_KEYS], {}
+    kw = dict(slot_records=bt["slot_records"], slot_shape=bt["S"])
+    kw.update({k: bt[k] for k in ("max_live_slots", "max_live_pairs") if bt.get(k) is not None})
+    return [None if k in DENSE_SLOT_KEYS else bt[k] for k in FORWARD_KEYS], kw
 
 
 @dataclass
@@ -247,7 +259,8 @@ def evaluate(model, batches: Iterable[dict], relation_num: int = 97, max_n: int 
     try:
         with torch.no_grad():
             for bt in batches:
-                logits = model(*[bt[k] for k in FORWARD_KEYS], n_valid=bt.get("n_valid"))
+                args, rec = forward_args(bt)
+                logits = model(*args, n_valid=bt.get("n_valid"), **rec)
                 ev.update(logits, bt["label_matrix"], n_valid=bt.get("n_valid"), in_train=bt.get("in_train"))
     finally:
         model.train(was_training)

@@ -715,6 +715,68 @@ class ProducerFn(torch.autograd.Function):
         return dtok, dnode, dtab, dflat, None, None, None, None, None, None, None, None
 
 
+class ProducerRecFn(torch.autograd.Function):
+    """ProducerFn on the packed slot records: (ctx[B,T,Hd], node[B,N,Hd], dis_table[ND,P], flat; records int32[n,10]) -> the same
+    outputs, bit for bit what ProducerFn gives on the tensors gcgcn_tensorise writes from those records (csrc/producer_rec.hip,
+    include/gcgcn_producer_rec.h).  The three [B,N,N,S,T] byte tensors are never built."""
+
+    @staticmethod
+    def forward(ctx_, tok, node, dis_table, flat, records, n_valid, S, dis_plus, cap_rows, cap_pairs, compact, deterministic):
+        B, T, Hd = tok.shape
+        N = node.shape[1]
+        ND, P = dis_table.shape
+        dev = tok.device
+        if compact:
+            cap_pairs = max(int(cap_pairs), 1)
+        sizes = (ctypes.c_int64 * 7)()
+        call("gcgcn_producer_sizes", B, N, S, T, Hd, P, ND, cap_rows, cap_pairs, ctypes.cast(sizes, ctypes.c_void_p))
+        ibuf = torch.empty(sizes[0], dtype=torch.int32, device=dev)
+        fbuf = torch.empty(sizes[1], device=dev)
+        E = None if compact else torch.empty(B, N, N, Hd, device=dev)
+        n = int(records.shape[0])
+        call("gcpr_producer_fwd", B, N, S, T, Hd, P, ND, _p(tok), n, _p(records) if n else None, dis_plus, _p(node), _p(dis_table),
+             _p(n_valid), _p(flat), cap_rows, cap_pairs, _p(ibuf), _p(fbuf), None, 0, _p(E), _stream())
+        ctx_.save_for_backward(tok, node, dis_table, flat, records, ibuf, fbuf)
+        ctx_.n_valid, ctx_.caps, ctx_.nbwd, ctx_.compact = n_valid, (cap_rows, cap_pairs), int(sizes[2]), bool(compact)
+        ctx_.S, ctx_.dis_plus = S, dis_plus
+        ctx_.ndet = None
+        if deterministic:
+            ndet = ctypes.c_int64()
+            call("gcgcn_producer_det_elems", B, N, Hd, cap_pairs, ctypes.cast(ctypes.pointer(ndet), ctypes.c_void_p))
+            ctx_.ndet = int(ndet.value)
+        counts = ibuf[int(sizes[3]):int(sizes[3]) + 4]      # {live rows, live pairs, over capacity, 0}, on the device
+        if not compact:
+            ctx_.mark_non_differentiable(counts)
+            return E, counts
+        rows = int(sizes[6])
+        Ec = fbuf[int(sizes[5]):int(sizes[5]) + rows * Hd].view(rows, Hd)
+        prow = ibuf[int(sizes[4]):int(sizes[4]) + B * N * N].view(B, N, N)
+        ctx_.mark_non_differentiable(counts, prow)
+        return Ec, counts, prow
+
+    @staticmethod
+    def backward(ctx_, dE, _dcounts=None, _dprow=None):
+        tok, node, dis_table, flat, records, ibuf, fbuf = ctx_.saved_tensors
+        B, T, Hd = tok.shape
+        N = node.shape[1]
+        ND, P = dis_table.shape
+        dev = tok.device
+        dE = dE.contiguous()
+        bbuf = torch.empty(ctx_.nbwd, device=dev)
+        dtok, dnode = torch.empty_like(tok), torch.empty_like(node)
+        dtab, dflat = torch.empty_like(dis_table), torch.zeros_like(flat)       # (zeros: the layout's alignment gaps)
+        n = int(records.shape[0])
+        args = (B, N, ctx_.S, T, Hd, P, ND, _p(tok), n, _p(records) if n else None, ctx_.dis_plus, _p(node), _p(dis_table),
+                _p(ctx_.n_valid), _p(flat), ctx_.caps[0], ctx_.caps[1], _p(ibuf), _p(fbuf), _p(bbuf),
+                None if ctx_.compact else _p(dE), _p(dE) if ctx_.compact else None, _p(dtok), _p(dnode), _p(dtab), _p(dflat))
+        if ctx_.ndet is None:
+            call("gcpr_producer_bwd", *args, _stream())
+        else:
+            detbuf = torch.empty(ctx_.ndet, device=dev)
+            call("gcpr_producer_bwd_det", *args, _p(detbuf), ctx_.ndet, _stream())
+        return dtok, dnode, dtab, dflat, None, None, None, None, None, None, None, None
+
+
 class CompactEdges:
     """A hop's edge tensor without the tensor: ``Ec[rows, Hd]`` (one row per entity pair with a live sentence slot), ``prow[B,N,N]``
     (row of a pair, -1 = none) and ``bias[Hd]`` -- every other real pair of ``context_sent_att`` equals the bias of
@@ -987,7 +1049,8 @@ class ProducerCapacityError(RuntimeError):
 
 
 def edge_features(tok, sen, pos_h, pos_t, node, dis_table, flat, n_valid=None, max_live_slots=None, max_live_pairs=None,
-                  check_capacity=False, return_counts=False, compact=False, deterministic=False):
+                  check_capacity=False, return_counts=False, compact=False, deterministic=False, slot_records=None, dis_plus=10,
+                  slot_shape=None):
     """E[B,N,N,Hd] of one hop from token states tok[B,T,Hd], sentence masks sen[B,N,N,S,T] (bool / uint8), distance ids
     pos_h / pos_t [B,N,N,S,T] (int64 as the reference passes them, or int32 / uint8), entity features node[B,N,Hd] and
     the distance-embedding table dis_table[ND,P].  Without ``max_live_*`` the live slots are counted first (one host
@@ -998,9 +1061,27 @@ def edge_features(tok, sen, pos_h, pos_t, node, dis_table, flat, n_valid=None, m
     the device tensor ``int32[4] = {live slots, live pairs, over capacity, 0}`` for a check of the caller's own timing.
     ``compact=True``: returns ``(Ec[rows,Hd], prow[B,N,N])`` instead of E -- E is never written (see CompactEdges).
     ``deterministic=True``: the backward sums the per-entity node-term gradient and the sentence attention's vector / bias gradient
-    by their owners instead of with fp32 atomics (two more launches, one more workspace): every gradient is bit-reproducible."""
+    by their owners instead of with fp32 atomics (two more launches, one more workspace): every gradient is bit-reproducible.
+    ``slot_records``: the packed records themselves -- int32 ``[n, 10]`` on the GPU, rows ``doc, u, v, j, s0, s1, h0, h1, t0, t1`` as
+    ``data.collate`` uploads them -- in place of ``sen`` / ``pos_h`` / ``pos_t``, which must then be None; ``slot_shape`` carries S
+    (an int, or anything whose last entry is S) and ``dis_plus`` the offset of the distance ids.  The result equals, bit for bit, what
+    the dense tensors ``gcgcn_tensorise`` writes from those records give; no ``[B,N,N,S,T]`` tensor exists.  ``(doc, u, v, j)`` must be
+    unique.  Pass ``max_live_slots`` / ``max_live_pairs`` from ``data.live_counts`` (``collate(dense_slots=False)`` returns both) or a
+    batch-independent bound of your data.  Without them the capacities fall back to the table's own bounds, ``min(n, B N N S)`` rows
+    and ``min(n, B N N)`` pairs: still no host read, but every per-row buffer (about ``7 Hd`` floats per row forward and as much
+    again backward) is sized for ALL records, live or not -- several times the live rows on DocRED-like batches, and at B = 32, N = 42,
+    S = 5, Hd = 128 with a full table hundreds of MB, more than the dense tensors this route avoids."""
+    if slot_records is not None and (sen is not None or pos_h is not None or pos_t is not None):
+        raise ValueError("edge_features: give either slot_records or sen_matrix / pos_matrix_h / pos_matrix_t, not both")
+    if slot_records is None and (sen is None or pos_h is None or pos_t is None):
+        raise ValueError("edge_features: sen_matrix / pos_matrix_h / pos_matrix_t are required without slot_records")
+    if slot_records is not None:
+        _check_slot_records(slot_records, slot_shape)
     tok, node, dis_table = _chk(tok, "context_output", 3), _chk(node, "node_feat", 3), _chk(dis_table, "dis_embed.weight", 2)
     B, T, Hd = tok.shape
+    if slot_records is not None:
+        return _edge_features_rec(tok, slot_records, node, dis_table, flat, n_valid, max_live_slots, max_live_pairs, check_capacity,
+                                  return_counts, compact, deterministic, dis_plus, slot_shape)
     if sen.dim() != 5 or sen.shape[0] != B or sen.shape[4] != T or sen.shape[1] != sen.shape[2]:
         raise ValueError(f"sen_matrix: expected [B={B}, N, N, S, T={T}], got {tuple(sen.shape)}")
     N, S = sen.shape[1], sen.shape[3]
@@ -1036,6 +1117,49 @@ def edge_features(tok, sen, pos_h, pos_t, node, dis_table, flat, n_valid=None, m
         if int(counts[2].item()) != 0:
             raise ProducerCapacityError(f"edge_features: max_live_slots={max_live_slots} / max_live_pairs={max_live_pairs} are "
                                         "smaller than the batch's live sentence slots / entity pairs (producer_live_counts "
+                                        "reports both); nothing was computed")
+    return (E, counts) if return_counts else E
+
+
+def _check_slot_records(records, slot_shape) -> int:
+    """The argument checks of the record route that need no GPU -> S."""
+    if slot_shape is None:
+        raise ValueError("edge_features: slot_records needs slot_shape (S, the sentence slots per pair; collate returns it)")
+    S = int(slot_shape if isinstance(slot_shape, int) else tuple(slot_shape)[-1])
+    if not 1 <= S <= 31:
+        raise ValueError(f"edge_features: slot_shape gives S={S} sentence slots per pair (1..31 supported)")
+    if not isinstance(records, Tensor) or records.dtype != torch.int32 or records.dim() != 2 or records.shape[1] != 10:
+        raise ValueError("slot_records: expected an int32 tensor of shape [n, 10] (doc, u, v, j, s0, s1, h0, h1, t0, t1), got "
+                         f"{getattr(records, 'dtype', type(records))} {tuple(getattr(records, 'shape', ()))}")
+    return S
+
+
+def _edge_features_rec(tok, records, node, dis_table, flat, n_valid, max_live_slots, max_live_pairs, check_capacity, return_counts,
+                       compact, deterministic, dis_plus, slot_shape):
+    """edge_features on the record table (ProducerRecFn)."""
+    B, T, Hd = tok.shape
+    S = _check_slot_records(records, slot_shape)
+    if not records.is_cuda:
+        raise RuntimeError("slot_records: gcgcn_amd runs on MI355X only (no CPU fallback)")
+    if node.dim() != 3 or node.shape[0] != B or node.shape[2] != Hd:
+        raise ValueError(f"node_feat: expected [B={B}, N, Hd={Hd}], got {tuple(node.shape)}")
+    N = node.shape[1]
+    nv = _nv(n_valid, B, N, tok.device)
+    n = int(records.shape[0])
+    if max_live_slots is None:
+        max_live_slots = min(n, B * N * N * S)            # no record, no row: bounds that need no read
+    if max_live_pairs is None:
+        max_live_pairs = min(n, B * N * N)
+    out = ProducerRecFn.apply(tok, node, dis_table, _chk(flat, "flat"), records.contiguous(), nv, S, int(dis_plus), int(max_live_slots),
+                              int(max_live_pairs), bool(compact), bool(deterministic))
+    if compact:
+        E, counts = (out[0], out[2]), out[1]
+    else:
+        E, counts = out
+    if check_capacity and not torch.cuda.is_current_stream_capturing():
+        if int(counts[2].item()) != 0:
+            raise ProducerCapacityError(f"edge_features: max_live_slots={max_live_slots} / max_live_pairs={max_live_pairs} are "
+                                        "smaller than the batch's live sentence slots / entity pairs (data.live_counts "
                                         "reports both); nothing was computed")
     return (E, counts) if return_counts else E
 

@@ -446,7 +446,8 @@ class EdgeFeatureProducer(_FlatBlock):
     def forward(self, context_output: Tensor, sen_matrix: Tensor, pos_matrix_h: Tensor, pos_matrix_t: Tensor,
                 node_feat: Tensor, dis_embed_weight: Tensor, n_valid: Optional[Tensor] = None,
                 max_live_slots: Optional[int] = None, max_live_pairs: Optional[int] = None,
-                check_capacity: Optional[bool] = None, compact: bool = False, deterministic: Optional[bool] = None):
+                check_capacity: Optional[bool] = None, compact: bool = False, deterministic: Optional[bool] = None,
+                slot_records: Optional[Tensor] = None, slot_shape=None, dis_plus: int = 10):
         """context_output ``[T,H]`` / ``[1,T,H]`` (the reference's shapes, glove:292) or ``[B,T,H]``; sen_matrix / pos_matrix_*
         ``[N,N,S,T]`` or ``[B,N,N,S,T]``; node_feat ``[N,H]`` / ``[B,N,H]``; dis_embed_weight = ``model.dis_embed.weight``.
         Returns ``context_sent_att``: ``[N,N,H]`` or ``[B,N,N,H]``.
@@ -459,7 +460,26 @@ class EdgeFeatureProducer(_FlatBlock):
         pairs with a live sentence slot, the pair index and the bias every other pair equals; the graph blocks take it wherever
         they take ``edge_feat`` and the ``[N,N,hidden]`` tensor (and its gradient) is never written.
 
-        ``deterministic`` (default: ``self.deterministic``, off): the bit-reproducible backward, see the class attribute."""
+        ``deterministic`` (default: ``self.deterministic``, off): the bit-reproducible backward, see the class attribute.
+
+        ``slot_records`` (int32 ``[n,10]``, ``data.collate(dense_slots=False)``) with ``slot_shape`` (S) and ``dis_plus``: the packed
+        records in place of sen_matrix / pos_matrix_h / pos_matrix_t, which are then None; batched inputs only.  Same bits out
+        (``functional.edge_features``)."""
+        if slot_records is not None:
+            if sen_matrix is not None or pos_matrix_h is not None or pos_matrix_t is not None:
+                raise ValueError("EdgeFeatureProducer: give either slot_records or sen_matrix / pos_matrix_h / pos_matrix_t, not both")
+            if context_output.dim() != 3 or node_feat.dim() != 3:
+                raise ValueError("EdgeFeatureProducer: slot_records takes batched inputs (context_output [B,T,H], node_feat [B,N,H])")
+            chk = self.check_capacity if check_capacity is None else check_capacity
+            e, self.last_counts = F_.edge_features(context_output, None, None, None, node_feat, dis_embed_weight, self.flat, n_valid,
+                                                   max_live_slots, max_live_pairs, check_capacity=chk, return_counts=True, compact=compact,
+                                                   deterministic=self.deterministic if deterministic is None else deterministic,
+                                                   slot_records=slot_records, dis_plus=dis_plus, slot_shape=slot_shape)
+            if compact:
+                o = P_.producer_layout(self.hidden, self.dis_size)[15]          # linear_sentence_att.bias inside flat
+                nv = None if n_valid is None else n_valid.to(device=context_output.device, dtype=torch.int32)
+                return F_.CompactEdges(e[0], e[1], self.flat[o:o + self.hidden], nv, True)
+            return e
         batched = sen_matrix.dim() == 5
         tok = context_output
         if tok.dim() == 2:
@@ -719,10 +739,14 @@ class GraphModelTail(nn.Module):
     def forward(self, context_output: Tensor, node_feat: Tensor, adj_matrix: Optional[Tensor], sen_matrix: Tensor,
                 pos_matrix_h: Tensor, pos_matrix_t: Tensor, node_type: Tensor, node_relative_pos: Tensor,
                 dis_embed_weight: Tensor, ner_emb_weight: Tensor, n_valid: Optional[Tensor] = None,
-                max_live_slots: Optional[int] = None, max_live_pairs: Optional[int] = None) -> Tensor:
+                max_live_slots: Optional[int] = None, max_live_pairs: Optional[int] = None,
+                slot_records: Optional[Tensor] = None, slot_shape=None) -> Tensor:
         """Shapes as in the reference (one document: context_output ``[T,H]`` or ``[1,T,H]``, node_feat ``[N,H]``, ...) or with a
         leading batch axis everywhere.  Returns ``relation_before_softmax_01``.  ``max_live_slots`` / ``max_live_pairs``: capacities
-        of the edge-feature producers given up front (no host synchronisation; see EdgeFeatureProducer.forward)."""
+        of the edge-feature producers given up front (no host synchronisation; see EdgeFeatureProducer.forward).  ``slot_records`` /
+        ``slot_shape``: the packed slot records of ``data.collate(dense_slots=False)`` in place of sen_matrix / pos_matrix_h /
+        pos_matrix_t (then None), handed to every producer; the distance ids use the head's ``dis_plus``."""
+        rec = {} if slot_records is None else dict(slot_records=slot_records, slot_shape=slot_shape, dis_plus=self.head.dis_plus)
         x = node_feat
         feats = [x]
         mask = None
@@ -736,7 +760,7 @@ class GraphModelTail(nn.Module):
                 e = self.producers[i](context_output, sen_matrix, pos_matrix_h, pos_matrix_t, x, dis_embed_weight, n_valid=n_valid,
                                       max_live_slots=max_live_slots, max_live_pairs=max_live_pairs,
                                       compact=self.compact_edges and not self.get_weighted_adj_matrix.apply_mask,
-                                      deterministic=True if self.deterministic else None)
+                                      deterministic=True if self.deterministic else None, **rec)
                 if i < 1:
                     if self.get_weighted_adj_matrix.apply_mask and adj_matrix is not None:
                         mask = torch.eq(adj_matrix, 0)                                          # glove:330

@@ -14,7 +14,7 @@ from typing import Iterable, Optional
 
 import torch
 
-from .evaluation import FORWARD_KEYS
+from .evaluation import forward_args
 from .functional import TrainStats, TrainStatsResult, pair_bce_loss
 
 LOG_FORMAT = "| epoch {:2d} | ms/b {:5.2f} | train loss {:5.3f} | NA acc: {:4.2f} | not NA acc: {:4.2f}  | tot acc: {:4.2f} "
@@ -60,7 +60,8 @@ def train_epoch(model, optimizer, batches: Iterable[dict], stats: Optional[Train
             for p in params:
                 p.grad = None
             extra = {k: bt[k] for k in ("n_valid", "t_valid") if bt.get(k) is not None}
-            logits = model(*[bt[k] for k in FORWARD_KEYS], **extra)
+            args, rec = forward_args(bt)
+            logits = model(*args, **extra, **rec)
             total = pair_bce_loss(logits, labels, n_valid=bt.get("n_valid"), stats=stats).sum()
             (total * (1.0 / B if loss_scale is None else loss_scale)).backward()
             optimizer.step()

@@ -6,8 +6,8 @@ set -e
 rev=${1:-HEAD}
 root=$(cd $(dirname $0)/.. && pwd)
 d=/tmp/ab_src
-rm -rf $d && mkdir -p $d/gcgcn_amd/csrc $d/include   # the tree's layout: the sources include "../../include/gcgcn.h"
-for f in $(git ls-tree --name-only $rev gcgcn_amd/csrc/ | grep -E '\.(hip|hpp)$') include/gcgcn.h; do
+rm -rf $d && mkdir -p $d/gcgcn_amd/csrc $d/include   # the tree's layout: the sources include "../../include/*.h"
+for f in $(git ls-tree --name-only $rev gcgcn_amd/csrc/ | grep -E '\.(hip|hpp)$') $(git ls-tree --name-only $rev include/ | grep -E '\.h$'); do
   git show $rev:$f > $d/$f
 done
 cd $d/gcgcn_amd/csrc

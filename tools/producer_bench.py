@@ -4,7 +4,7 @@ gcgcn_amd.EdgeFeatureProducer on DocRED-shaped synthetic batches, with per-kerne
 roofline of the kernel that bounds it.
 
     python tools/producer_bench.py [--B 32] [--N 42] [--S 5] [--T 512] [--H 128] [--live 0.15] [--steps 20] [--cpu]
-                                   [--deterministic [--reps 200]] [--lib-old build/ab_old.so] [--out FILE]
+                                   [--deterministic [--reps 200]] [--lib-old build/ab_old.so] [--records] [--out FILE]
 
 --live: fraction of sentence slots that contain token 0 -- the only slots the reference keeps (glove:305); DocRED-like
 ~0.1-0.2 (pairs that co-occur in the first sentence), 1.0 = the dense stress case.
@@ -144,6 +144,74 @@ def ab_abi(a, _lib, _graph_mode, prod, inputs, cot, rows, pairs):
     return res
 
 
+def peak_of(fn, dev):
+    """(result, HIP-event ms, peak allocated bytes above what was allocated before) of one call."""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(dev)
+    base = torch.cuda.memory_allocated(dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return out, e0.elapsed_time(e1), torch.cuda.max_memory_allocated(dev) - base
+
+
+def ab_records(a, _graph_mode, dev):
+    """The dense route against the record route (edge_features(slot_records=...)) on ONE batch of packed synthetic documents
+    (train_step_bench.synth_doc), both in this process: collate of either kind (median ms, peak allocated bytes), then the producer's
+    forward + backward of both routes interleaved rep by rep, eager and as hipGraph replays."""
+    import statistics
+    import numpy as np
+    import gcgcn_amd
+    from gcgcn_amd.data import collate
+    from train_step_bench import synth_doc
+    rs = np.random.RandomState(7)
+    docs = [synth_doc(rs, 20000, T=a.T, max_num=a.S) for _ in range(a.B)]
+    kinds = {"dense": lambda: collate(docs, dev, max_length=a.T, max_num=a.S, pad_nodes_to=a.N),
+             "records": lambda: collate(docs, dev, max_length=a.T, max_num=a.S, pad_nodes_to=a.N, dense_slots=False)}
+    coll, batch = {}, {}
+    for k, fn in kinds.items():
+        fn()                                                   # warm the allocator and the library
+        runs = [peak_of(fn, dev) for _ in range(max(3, a.reps // 20))]
+        batch[k] = runs[-1][0]
+        coll[k] = {"median_ms": round(statistics.median(r[1] for r in runs), 4), "min_ms": round(min(r[1] for r in runs), 4),
+                   "max_ms": round(max(r[1] for r in runs), 4), "peak_allocated_bytes": int(max(r[2] for r in runs)), "reps": len(runs)}
+        del runs
+    d, r = batch["dense"], batch["records"]
+    B, N, _, S, T = d["sen_matrix"].shape
+    g = torch.Generator(device=dev).manual_seed(3)
+    ctx = torch.tanh(torch.randn(B, T, a.H, generator=g, device=dev)).requires_grad_()
+    node = (torch.rand(B, N, a.H, generator=g, device=dev) * 2 - 1).requires_grad_()
+    table = (torch.randn(21, a.P, generator=g, device=dev) * 0.5).requires_grad_()
+    cot = torch.randn(B, N, N, a.H, generator=g, device=dev)
+    prod = gcgcn_amd.EdgeFeatureProducer(a.H, a.P).to(dev)
+    rows, pairs = r["max_live_slots"], r["max_live_pairs"]
+    kw = dict(n_valid=d["n_valid"], max_live_slots=rows, max_live_pairs=pairs)
+
+    def side(rec):
+        def fn():
+            ctx.grad = node.grad = table.grad = prod.flat.grad = None
+            if rec:
+                e = prod(ctx, None, None, None, node, table, slot_records=r["slot_records"], slot_shape=S, **kw)
+            else:
+                e = prod(ctx, d["sen_matrix"], d["pos_matrix_h"], d["pos_matrix_t"], node, table, **kw)
+            torch.autograd.backward(e, cot)
+            return e
+        return fn
+    sides = {"dense": side(False), "records": side(True)}
+    same = bool(torch.equal(sides["dense"](), sides["records"]()))
+    res = {"shape": f"B={B} N={N} S={S} T={T} hidden={a.H}, {rows} live slots, {pairs} live pairs, {r['slot_records'].shape[0]} records",
+           "timing": "HIP events, sides interleaved rep by rep, median (min, max)", "forward bitwise equal": same,
+           "collate": coll, "dense slot tensors, bytes": int(3 * d["sen_matrix"].numel()),
+           "producer fwd+bwd, eager": _graph_mode.interleaved(sides, a.reps)}
+    if a.mode != "eager":
+        graphs = {k: _graph_mode.capture(fn) for k, fn in sides.items()}
+        if all(g_ is not None for g_ in graphs.values()):
+            res["producer fwd+bwd, hipGraph replay"] = _graph_mode.interleaved({k: g_.replay for k, g_ in graphs.items()}, a.reps)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=32)
@@ -166,6 +234,10 @@ def main():
     ap.add_argument("--lib-old", default=None,
                     help="another revision's library (tools/ab_build.sh): gcgcn_producer_fwd + gcgcn_producer_bwd of both on the same "
                          "buffers, interleaved rep by rep")
+    ap.add_argument("--records", action="store_true",
+                    help="also time the record route (edge_features(slot_records=...), collate(dense_slots=False)) against the dense "
+                         "route on one batch of packed synthetic documents, interleaved rep by rep, with collate time and peak "
+                         "allocated bytes of both")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     a = ap.parse_args()
     import gcgcn_amd
@@ -233,6 +305,8 @@ def main():
     if a.lib_old:
         line["abi (gcgcn_producer_fwd + gcgcn_producer_bwd, this tree against --lib-old, interleaved)"] = ab_abi(
             a, _lib, _graph_mode, prod, (ctx, node, table, sen, ph, pt), cot, rows, pairs)
+    if a.records:
+        line["records_vs_dense"] = ab_records(a, _graph_mode, dev)
     if a.cpu:
         from oracle import gcgcn_oracle as O
         torch.set_num_threads(min(os.cpu_count() or 1, 16))

@@ -10,6 +10,7 @@ tokens, entity counts ~ clip(round(N(19.5, 6^2)), 2, 42), one to three mentions 
 of entities sharing a sentence (up to max_num = 5 sentence slots per pair), 3 % positive labels.
 
     python tools/train_step_bench.py [--B 32] [--steps 10] [--skip-dead-hop] [--torch-adam] [--capturable] [--max-grad-norm C]
+                                     [--records [--reps 20]]
 
 The graph mode replays gcgcn_amd.GraphedTrainStep objects over FusedAdam(capturable=True): the step counters and the learning
 rate are read on the device, so what is timed is a step that trains (the default FusedAdam, captured, would replay the bias
@@ -103,10 +104,16 @@ def main():
     ap.add_argument("--frontend", default="torch", choices=["torch", "hip"],
                     help="embeddings + locked dropout and linear_re + tanh + entity pooling: PyTorch (the default model) or "
                          "config.frontend_impl = \"hip\" (csrc/frontend.hip)")
+    ap.add_argument("--records", action="store_true",
+                    help="also time the whole step fed by collate(dense_slots=False) (the producers' record route) against the dense "
+                         "step in this process, interleaved rep by rep (HIP events, median and min - max), with collate time and peak "
+                         "allocated bytes of both")
+    ap.add_argument("--reps", type=int, default=20, help="repetitions per side of the --records timing")
     a = ap.parse_args()
     import gcgcn_amd
     from gcgcn_amd import _lib, functional as F_
     from gcgcn_amd.data import collate
+    from gcgcn_amd.evaluation import forward_args
     from gcgcn_amd.models import GCGCN_glove
     from gcgcn_amd.optim import FusedAdam
     dev = torch.device("cuda:0")
@@ -210,6 +217,53 @@ def main():
             _lib.call("gcgcn_prof_stop", ctypes.byref(ms), ctypes.byref(n), ctypes.byref(w))
             tot += ms.value / 2
         by_part[name] = round(tot, 3)
+    records = None
+    if a.records:
+        import statistics
+        import _graph_mode
+
+        def route_step(dense):
+            def fn():
+                k = route_step.k
+                bt = collate(batches[k % len(batches)], dev, dense_slots=dense)
+                args, rec = forward_args(bt)
+                logits = model(*args, n_valid=bt["n_valid"], **rec)
+                loss = gcgcn_amd.pair_bce_loss(logits, bt["label_matrix"], n_valid=bt["n_valid"]).sum() / a.B
+                opt.zero_grad(set_to_none=True)
+                loss.backward()
+                opt.step()
+                route_step.k += 1
+            return fn
+        route_step.k = 0
+        coll = {}
+        for name, dense in (("dense", True), ("records", False)):
+            runs = []
+            for k in range(max(3, a.reps // 4)):
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats(dev)
+                base = torch.cuda.memory_allocated(dev)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                bt = collate(batches[k % len(batches)], dev, dense_slots=dense)
+                e1.record()
+                torch.cuda.synchronize()
+                runs.append((e0.elapsed_time(e1), torch.cuda.max_memory_allocated(dev) - base))
+                del bt
+            coll[name] = {"median_ms": round(statistics.median(r_[0] for r_ in runs), 4), "min_ms": round(min(r_[0] for r_ in runs), 4),
+                          "max_ms": round(max(r_[0] for r_ in runs), 4), "peak_allocated_bytes": int(max(r_[1] for r_ in runs))}
+        peaks = {}
+        for name, dense in (("dense", True), ("records", False)):
+            fn = route_step(dense)
+            fn()
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(dev)
+            fn()
+            torch.cuda.synchronize()
+            peaks[name] = int(torch.cuda.max_memory_allocated(dev))
+        records = {"timing": "whole eager step (collate -> forward -> loss -> backward -> optimiser), HIP events, sides interleaved rep by "
+                             "rep, one model and optimiser trained by both",
+                   "step": _graph_mode.interleaved({"dense": route_step(True), "records": route_step(False)}, a.reps, warmup=2),
+                   "collate": coll, "peak_allocated_bytes_of_a_step": peaks}
     nv = np.mean([d.n for b in batches for d in b])
     print(json.dumps({
         "metric": "docs/sec, full training step of GCGCN_glove (collate -> forward -> loss -> backward -> Adam)", "value": round(a.B / dt, 1),
@@ -219,7 +273,8 @@ def main():
                                f"{a.batches} resident packed batches rotated" + (", dead last hop skipped" if a.skip_dead_hop else "")},
         "ms_per_step_by_stage (stream time between HIP events, includes launch gaps)": split,
         "gpu_ms_per_step_by_part (library kernels in forward + backward)": by_part,
-        "loss_first_last": [round(losses[0].item(), 5), round(losses[-1].item(), 5)]}))
+        "loss_first_last": [round(losses[0].item(), 5), round(losses[-1].item(), 5)],
+        **({"records_vs_dense": records} if records else {})}))
 
 
 if __name__ == "__main__":
