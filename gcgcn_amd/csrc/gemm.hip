@@ -858,4 +858,87 @@ int gcgcn_debug_gemm_plan(int form, const int64_t* prob_a, const int64_t* prob_b
   return 0;
 }
 
+// The run-side twin: n problems described by flat rows (layout: include/gcgcn.h), built with the constructors of gemm.hpp and handed to
+// the launchers the library itself calls.  form: 0 gemm() per problem, 1 gemm_group, 2 gemm_defer each into a queue local to this call
+// (a refused problem runs through gemm() at once, as the callers do) then gemm_flush_deferred, 5 / 6 / 7 the pairs on *cnt.  Allocates
+// nothing, reads no device memory.  Exposed for tests.
+int gcgcn_debug_gemm_run(int form, int n, const int64_t* probs, const float* scal, const void* const* ptrs, const int64_t* ride,
+                         const void* const* ride_ptrs, int tile, int splits, const int32_t* cnt, int64_t cap, int32_t* out, void* stream) {
+  using namespace gc;
+  constexpr int NI = 40, NF = 2, NP = 14, MAXN = 40;   // (MAXN: past DeferQueue::CAP)
+  GC_REQUIRE((form == 0 || form == 1 || form == 2 || (form >= 5 && form <= 7)) && n >= 0 && n <= MAXN && out, "debug_gemm_run: bad arguments");
+  GC_REQUIRE(n == 0 || (probs && scal && ptrs), "debug_gemm_run: problems without their rows");
+  GC_REQUIRE(form < 5 || (n == 2 && cnt && cap >= 0), "debug_gemm_run: a pair is two problems on a device-side count");
+  hipStream_t st = (hipStream_t)stream;
+  for (int i = 0; i < 2 + 2 * n; ++i) out[i] = -1;
+  GemmArgs g[MAXN];
+  for (int i = 0; i < n; ++i) {
+    const int64_t* d = probs + (long)NI * i;
+    const float* f = scal + NF * i;
+    const void* const* p = ptrs + NP * i;
+    GemmArgs& a = g[i];
+    a = gemm_stored((int)d[3], (int)d[4], (const float*)p[0], d[5], (const float*)p[1], d[6], (float*)p[2], d[7], (int)d[0], (int)d[1], (int)d[2]);
+    a.batch_z1((int)d[8], d[13], d[15], d[17]).batch_z2((int)d[9], d[14], d[16], d[18]);
+    if (p[12]) a.split_ws((float*)p[12], d[11]);
+    a.alpha = f[0];
+    a.add = (const float*)p[3], a.ldadd = d[19], a.sAdd1 = d[20], a.sAdd2 = d[21];
+    a.bias = (const float*)p[4];
+    a.rowadd = (const float*)p[5], a.sRa1 = d[22], a.sRa2 = d[23];
+    a.rowscale = (const float*)p[6], a.sRs1 = d[24], a.sRs2 = d[25];
+    a.C2 = (float*)p[7], a.ldc2 = d[26], a.sC21 = d[27], a.sC22 = d[28];
+    a.add2 = (const float*)p[8], a.ldadd2 = d[29], a.sAdd21 = d[30], a.sAdd22 = d[31];
+    a.relu = (int)d[32], a.accumulate = (int)d[33];
+    a.n_valid = (const int*)p[9], a.nv_rows = (int)d[34], a.nv_zdoc = (int)d[35];
+    GC_REQUIRE(!a.n_valid || a.nv_rows >= 1, "debug_gemm_run: n_valid with nv_rows %d", a.nv_rows);
+    if (d[10]) {
+      GC_REQUIRE(p[10] && p[11], "debug_gemm_run: row-block mode %d without a list", (int)d[10]);
+      a.rb = (const int*)p[10], a.rb_n = (const int*)p[11], a.rb_mode = (int)d[10], a.rb_zero = (int)d[36];
+    }
+    a.drop = make_drop(p[13], (uint64_t)d[38], f[1]);
+    a.drop_base = d[37];
+  }
+  if (form == 0) {
+    int rc = 0;
+    for (int i = 0; i < n; ++i) {
+      out[3 + 2 * i] = gemm(g[i], st, tile, splits);
+      if (!rc) rc = out[3 + 2 * i];
+    }
+    return out[0] = rc;
+  }
+  if (form == 1) {
+    ColRide c;
+    const ColRide* col = nullptr;
+    if (ride && ride[0]) {
+      GC_REQUIRE(ride[0] >= 1 && ride[0] <= 3 && ride_ptrs, "debug_gemm_run: ride kind %ld", (long)ride[0]);
+      const float* X = (const float*)ride_ptrs[0];
+      float* o = (float*)ride_ptrs[1];
+      float* part = (float*)ride_ptrs[2];
+      if (ride[0] == 3) c = head_sum(X, (int)ride[1], (int)ride[2], o);
+      else c = col_sum(X, ride[1], ride[2], (int)ride[3], o, part);
+      if (ride[0] == 2) c = c.stage2((int)ride[4]);
+      col = &c;
+    }
+    bool later = false;
+    out[0] = gemm_group(g, n, st, col, ride && ride[5] ? &later : nullptr);
+    out[1] = later;
+    return out[0];
+  }
+  if (form == 2) {
+    DeferQueue q;
+    int rc = 0;
+    for (int i = 0; i < n; ++i) {
+      out[2 + 2 * i] = gemm_defer(&q, g[i]);
+      if (!out[2 + 2 * i]) {
+        out[3 + 2 * i] = gemm(g[i], st);
+        if (!rc) rc = out[3 + 2 * i];
+      }
+    }
+    out[0] = gemm_flush_deferred(&q, st);
+    return rc ? rc : out[0];
+  }
+  out[0] = form == 5 ? gemm_dyn_pair(g[0], g[1], cnt, cap, st) : form == 6 ? gemm_dyn_pair_ww(g[0], g[1], cnt, cap, st)
+                                                                            : gemm_dyn_pair_xx(g[0], g[1], cnt, cap, st);
+  return out[0];
+}
+
 }  // extern "C"

@@ -25,7 +25,9 @@ namespace gc {
 //   v  = 0                   if the row is a padding row (n_valid given)
 //   C[row, col] = v
 //   C2[row, col] = dropout(v) + add2[row * ldadd2 + col]     if C2 (dropout index = element
-//                                                             offset inside the C2 buffer)
+//                                                             offset inside the C2 buffer, plus drop_base)
+//   C2[row, col] = 0         if the row is a padding row: add2 is NOT added there (C2 leaves the block, as api.hip's `out`:
+//                                                             its padding rows are zero like C's)
 struct GemmArgs {
   const float* A = nullptr;
   const float* B = nullptr;

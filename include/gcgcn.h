@@ -515,6 +515,28 @@ int gcgcn_debug_out_bwd_plan(int fuse, int B, int N, int D, int H, int scratch, 
 int gcgcn_debug_gemm_plan(int form, const int64_t* prob_a, const int64_t* prob_b, int splits, int64_t group_work, int64_t cap,
                           int32_t* out);
 
+/* ---- test hook: run what the GEMM launcher launches -------------------------------------------------------------------
+ * The run-side twin of gcgcn_debug_gemm_plan: n <= 40 problems are built from flat rows with the named constructors of csrc/gemm.hpp
+ * and handed to the launchers the library itself calls.  form: 0 gemm() on each problem with the caller's tile / splits; 1 one
+ * gemm_group launch over all n (n = 0 with a ride: the ride alone); 2 gemm_defer of each problem into a DeferQueue local to the
+ * call -- a problem that is refused runs through gemm() at once, as the library's callers do -- then gemm_flush_deferred; 5, 6, 7
+ * gemm_dyn_pair, _ww, _xx over problems 0 and 1 on the device-side count *cnt <= cap (the numbering of gcgcn_debug_gemm_plan).
+ * Problem i is
+ *   probs + 40 i, int64[40]: [0..12] the 13 integers of gcgcn_debug_gemm_plan in their order (M, N, K, a_kc, b_kc, lda, ldb, ldc,
+ *     batch1, batch2, row-block mode, workspace ELEMENTS, unused); [13..18] sA1, sA2, sB1, sB2, sC1, sC2; [19..21] ldadd, sAdd1,
+ *     sAdd2; [22..25] sRa1, sRa2, sRs1, sRs2; [26..28] ldc2, sC21, sC22; [29..31] ldadd2, sAdd21, sAdd22; [32] relu; [33] accumulate;
+ *     [34] nv_rows; [35] nv_zdoc; [36] rb_zero; [37] drop_base; [38] the dropout salt; [39] unused;
+ *   scal + 2 i, float[2]: alpha, dropout p (0: no dropout);
+ *   ptrs + 14 i, 14 device pointers: A, B, C, add, bias, rowadd, rowscale, C2, add2, n_valid, rb, rb_n, ws, rng_snap (all but the
+ *     first three may be NULL; rb / rb_n are gcgcn_row_blocks' out + 4 / out and are required when the row-block mode is not 0).
+ * ride (form 1; NULL or ride[0] = 0: nothing rides), int64[6]: kind (1 col_sum, 2 col_sum(...).stage2(slices), 3 head_sum), R (head_sum:
+ * H), ld (head_sum: D), C, slices, and whether gemm_group is given a col_later to report into; ride_ptrs: X (head_sum: W), out, part.
+ * out, int32[2 + 2 n]: out[0] the return code of the launch (form 0: the first failing gemm(); form 2: of the flush), out[1] whether
+ * col_later was set, and per problem out[2 + 2 i] whether gemm_defer accepted it and out[3 + 2 i] the return code of its own gemm()
+ * call; -1: does not apply.  Returns the first non-zero code.  Allocates nothing and reads no device memory on the host. */
+int gcgcn_debug_gemm_run(int form, int n, const int64_t* probs, const float* scal, const void* const* ptrs, const int64_t* ride,
+                         const void* const* ride_ptrs, int tile, int splits, const int32_t* cnt, int64_t cap, int32_t* out, void* stream);
+
 /* ---- raw batched GEMM (exposed for unit tests and benchmarks of the MFMA kernel) ----------- */
 /* C[z] = alpha * opA(A[z]) opB(B[z]);  a_kc: A stored [M][K] else [K][M];  b_kc: B stored [N][K]
  * else [K][N];  z < batch with element strides sA, sB, sC;  tile: 0 or 1 = 64x64 block tiles (the only body; other values are refused);
