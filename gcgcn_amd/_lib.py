@@ -1,7 +1,8 @@
 """ctypes binding of libgcgcn_hip.so (the C ABI declared in include/gcgcn.h).
 
 The header is the single source of the binding: SIGNATURES is parsed from it at import, so a new entry point is bound by declaring it
-there.  There is no CPU or eager-PyTorch fallback: if the shared library is missing this module raises, and every op raises when
+there (the extension headers -- gcgcn_optim.h, gcgcn_bert_embed.h, gcgcn_producer_rec.h, gcgcn_bert_frontend.h -- are parsed the same
+way into tables of their own).  There is no CPU or eager-PyTorch fallback: if the shared library is missing this module raises, and every op raises when
 handed a non-GPU tensor.
 """
 from __future__ import annotations
@@ -18,6 +19,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcgcn.h")
 OPTIM_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcgcn_optim.h")    # the optimiser extension, symbols gcopt_*
 BERT_EMBED_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcgcn_bert_embed.h")    # the embeddings stage, symbols gcbe_*
 PRODUCER_REC_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcgcn_producer_rec.h")    # the producer's record route, symbols gcpr_*
+BERT_FRONTEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gcgcn_bert_frontend.h")    # the BERT model's glue, symbols gcbf_*
 
 ABI_VERSION = 7
 
@@ -51,6 +53,7 @@ _DECL = re.compile(r"([\w\s*]+?)\b(gcgcn_\w+)\s*\(([^()]*)\)")                  
 _DECL_OPTIM = re.compile(r"([\w\s*]+?)\b(gcopt_\w+)\s*\(([^()]*)\)")               # the same in gcgcn_optim.h
 _DECL_BERT_EMBED = re.compile(r"([\w\s*]+?)\b(gcbe_\w+)\s*\(([^()]*)\)")          # and in gcgcn_bert_embed.h
 _DECL_PRODUCER_REC = re.compile(r"([\w\s*]+?)\b(gcpr_\w+)\s*\(([^()]*)\)")        # and in gcgcn_producer_rec.h
+_DECL_BERT_FRONTEND = re.compile(r"([\w\s*]+?)\b(gcbf_\w+)\s*\(([^()]*)\)")       # and in gcgcn_bert_frontend.h
 _STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\1\s*;")
 
 
@@ -140,10 +143,21 @@ def _load_producer_rec_header():
     return sigs
 
 
+def _load_bert_frontend_header():
+    if not os.path.exists(BERT_FRONTEND_HEADER_PATH):
+        raise RuntimeError(f"gcgcn_amd: {BERT_FRONTEND_HEADER_PATH} not found. The binding is derived from the C headers of the source tree.")
+    with open(BERT_FRONTEND_HEADER_PATH) as f:
+        sigs, structs = _parse_header(f.read(), _DECL_BERT_FRONTEND, "include/gcgcn_bert_frontend.h")
+    if structs:
+        raise RuntimeError(f"gcgcn_amd: include/gcgcn_bert_frontend.h declares structs {list(structs)}; it takes plain arguments only")
+    return sigs
+
+
 SIGNATURES = _load_header()  # name -> (restype, argtypes), in the order of include/gcgcn.h
 OPTIM_SIGNATURES = _load_optim_header()  # the same for include/gcgcn_optim.h; a table of its own, so the core's stays what is recorded
 BERT_EMBED_SIGNATURES = _load_bert_embed_header()  # and for include/gcgcn_bert_embed.h
 PRODUCER_REC_SIGNATURES = _load_producer_rec_header()  # and for include/gcgcn_producer_rec.h
+BERT_FRONTEND_SIGNATURES = _load_bert_frontend_header()  # and for include/gcgcn_bert_frontend.h
 
 _lib = None
 
@@ -158,7 +172,7 @@ def lib() -> ctypes.CDLL:
                 "(or `python -c 'import __graft_entry__ as g; g.build()'`). There is no CPU fallback.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(OPTIM_SIGNATURES.items()) + list(BERT_EMBED_SIGNATURES.items()) + \
-                list(PRODUCER_REC_SIGNATURES.items()):
+                list(PRODUCER_REC_SIGNATURES.items()) + list(BERT_FRONTEND_SIGNATURES.items()):
             fn = getattr(handle, name)  # AttributeError if the .so lacks a declared symbol
             fn.restype = res
             fn.argtypes = args

@@ -12,6 +12,9 @@
 //                                           visiting only the non-zeros of a node_pos row, in ascending t
 //   context_bwd:  context_bwd_kernel        dpre = (dctx + node_pos^T dnode_feat) (1 - ctx^2), each token's sum in ascending n
 //                 dW = dpre^T h, dh = dpre W, db = column sums of dpre: one gemm_group launch, the column sum riding
+//   context_fwd_ld / context_bwd_ld: the same two with the weight (and its gradient) at a leading dimension of its own, and
+//                 context_fwd_kernel<true> adding two gathered 128-wide fold rows in front of tanh: the BERT model's folded pair
+//                 (bert_frontend.hip), which reads W1 in place inside linear_re's [128][Dw + Dc + Dn] weight
 //
 // No workgroup reads what another one of the same launch writes (the pooling workgroups recompute tanh(pre) instead of reading
 // ctx), no float is added atomically and no order is handed out by an atomic: the only shared writes are the touched flags, every
@@ -222,14 +225,31 @@ int embed_bwd(int B, int T, const EmbedTables& tb, const float* dx, const float*
 }
 
 // ---- linear_re + tanh + entity pooling ---------------------------------------------------------------------------------------
-// the first `ew` workgroups: ctx = tanh(pre), four floats a thread; the others: one wave per entity row of node_pos
+// the first `ew` workgroups: ctx = tanh(pre), four floats a thread; the others: one wave per entity row of node_pos.
+// FOLD (the BERT model's folded pair, bert_frontend.hip): both read pre[b, t] + f2[pos_ids[b, t]] + f3[ner_ids[b, t]] in place of pre.
+__device__ __forceinline__ const float* fold_row(const int64_t* __restrict__ ids, const float* __restrict__ f, const int rows, const long tok,
+                                                 bool& ok) {
+  const int64_t id = ids[tok];
+  ok = id >= 0 && id < rows;
+  return f + (ok ? id : 0) * FE_HD;
+}
+template <bool FOLD>
 __global__ __launch_bounds__(256) void context_fwd_kernel(const float* __restrict__ pre, const float* __restrict__ node_pos,
                                                           float* __restrict__ ctx, float* __restrict__ node_feat, const int ew, const long BT,
-                                                          const int T, const int N, const long BN) {
+                                                          const int T, const int N, const long BN, const ContextFold fo) {
   if ((int)blockIdx.x < ew) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= BT * (FE_HD / 4)) return;
     float4 v = reinterpret_cast<const float4*>(pre)[i];
+    if constexpr (FOLD) {
+      const int c4 = (int)(i & (FE_HD / 4 - 1));
+      bool ok2, ok3;
+      const float* r2 = fold_row(fo.pos_ids, fo.f2, fo.P, i / (FE_HD / 4), ok2);
+      const float* r3 = fold_row(fo.ner_ids, fo.f3, fo.R, i / (FE_HD / 4), ok3);
+      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 a = ok2 ? reinterpret_cast<const float4*>(r2)[c4] : zero, b = ok3 ? reinterpret_cast<const float4*>(r3)[c4] : zero;
+      v.x = (v.x + a.x) + b.x, v.y = (v.y + a.y) + b.y, v.z = (v.z + a.z) + b.z, v.w = (v.w + a.w) + b.w;
+    }
     v.x = tanhf(v.x), v.y = tanhf(v.y), v.z = tanhf(v.z), v.w = tanhf(v.w);
     reinterpret_cast<float4*>(ctx)[i] = v;
     return;
@@ -248,22 +268,36 @@ __global__ __launch_bounds__(256) void context_fwd_kernel(const float* __restric
       mask &= mask - 1;
       const float wj = __shfl(wt, j);
       const float* r = rows + (long)(t0 + j) * FE_HD;
-      a0 += wj * tanhf(r[lane]), a1 += wj * tanhf(r[64 + lane]);
+      float p0 = r[lane], p1 = r[64 + lane];
+      if constexpr (FOLD) {
+        bool ok2, ok3;
+        const long tok = (pid / N) * T + t0 + j;
+        const float* r2 = fold_row(fo.pos_ids, fo.f2, fo.P, tok, ok2);
+        const float* r3 = fold_row(fo.ner_ids, fo.f3, fo.R, tok, ok3);
+        p0 = (p0 + (ok2 ? r2[lane] : 0.f)) + (ok3 ? r3[lane] : 0.f);
+        p1 = (p1 + (ok2 ? r2[64 + lane] : 0.f)) + (ok3 ? r3[64 + lane] : 0.f);
+      }
+      a0 += wj * tanhf(p0), a1 += wj * tanhf(p1);
     }
   }
   node_feat[pid * FE_HD + lane] = a0, node_feat[pid * FE_HD + 64 + lane] = a1;
 }
 
-int context_fwd(int B, int T, int N, int K, const float* h, const float* w, const float* bias, const float* node_pos, float* pre,
-                float* ctx, float* node_feat, hipStream_t st) {
+int context_fwd_ld(int B, int T, int N, int K, const float* h, const float* w, long ldw, const float* bias, const float* node_pos, float* pre,
+                   float* ctx, float* node_feat, hipStream_t st, const ContextFold* fold) {
   const long BT = (long)B * T, BN = (long)B * N;
-  GemmArgs g = gemm_nt(h, K, w, K, pre, FE_HD, (int)BT, FE_HD, K).tagged("fe_gemm");
+  GemmArgs g = gemm_nt(h, K, w, ldw, pre, FE_HD, (int)BT, FE_HD, K).tagged("fe_gemm");
   g.bias = bias;
   GC_TRY(gemm(g, st, 0, 1));
   const int ew = cdiv(BT * (FE_HD / 4), 256);
-  GC_LAUNCH_TIMED("fe_ctx_fwd", 8.0 * BT * FE_HD + 4.0 * BN * T, context_fwd_kernel, dim3(ew + cdiv(BN, 4)), dim3(256), 0, st, pre, node_pos,
-                  ctx, node_feat, ew, BT, T, N, BN);
+  const ContextFold fo = fold ? *fold : ContextFold{nullptr, nullptr, nullptr, nullptr, 0, 0};
+  GC_LAUNCH_TIMED("fe_ctx_fwd", 8.0 * BT * FE_HD + 4.0 * BN * T, (fold ? context_fwd_kernel<true> : context_fwd_kernel<false>),
+                  dim3(ew + cdiv(BN, 4)), dim3(256), 0, st, pre, node_pos, ctx, node_feat, ew, BT, T, N, BN, fo);
   return check_launch("context_fwd");
+}
+int context_fwd(int B, int T, int N, int K, const float* h, const float* w, const float* bias, const float* node_pos, float* pre,
+                float* ctx, float* node_feat, hipStream_t st) {
+  return context_fwd_ld(B, T, N, K, h, w, K, bias, node_pos, pre, ctx, node_feat, st);
 }
 
 // grid (tiles of 64 tokens, B), 256 threads: thread (half, col) owns the sums of the tile's tokens j with j % 2 == half at column col
@@ -297,8 +331,9 @@ __global__ __launch_bounds__(256) void context_bwd_kernel(const float* __restric
 static long context_col_elems() { return (long)COL_RIDE_SLICES * FE_HD; }
 long context_ws_elems(int K) { return gemm_ws_elems(FE_HD, K) + context_col_elems(); }
 
-int context_bwd(int B, int T, int N, int K, const float* h, const float* w, const float* node_pos, const float* ctx, const float* dctx,
-                const float* dnode, float* dpre, float* dh, float* dw, float* db, float* ws, long ws_elems, hipStream_t st) {
+int context_bwd_ld(int B, int T, int N, int K, const float* h, const float* w, long ldw, const float* node_pos, const float* ctx,
+                   const float* dctx, const float* dnode, float* dpre, float* dh, float* dw, float* db, float* ws, long ws_elems,
+                   hipStream_t st) {
   const long BT = (long)B * T;
   GC_REQUIRE(ws_elems >= context_ws_elems(K), "context_bwd: workspace of %ld floats needed", context_ws_elems(K));
   const long split_elems = gemm_ws_elems(FE_HD, K);
@@ -307,11 +342,15 @@ int context_bwd(int B, int T, int N, int K, const float* h, const float* w, cons
                   dctx, dnode, dpre, T, N);
   GC_TRY(check_launch("context_bwd"));
   GemmArgs gs[2] = {
-      gemm_tn(dpre, FE_HD, h, K, dw, K, FE_HD, K, (int)BT).split_ws(ws, split_elems).tagged("fe_gemm"),
-      gemm_nn(dpre, FE_HD, w, K, dh, K, (int)BT, K, FE_HD).split_ws(ws, split_elems).tagged("fe_gemm"),
+      gemm_tn(dpre, FE_HD, h, K, dw, ldw, FE_HD, K, (int)BT).split_ws(ws, split_elems).tagged("fe_gemm"),
+      gemm_nn(dpre, FE_HD, w, ldw, dh, K, (int)BT, K, FE_HD).split_ws(ws, split_elems).tagged("fe_gemm"),
   };
   const ColRide cr = col_sum(dpre, BT, FE_HD, FE_HD, db, part);
   return gemm_group(gs, 2, st, &cr);
+}
+int context_bwd(int B, int T, int N, int K, const float* h, const float* w, const float* node_pos, const float* ctx, const float* dctx,
+                const float* dnode, float* dpre, float* dh, float* dw, float* db, float* ws, long ws_elems, hipStream_t st) {
+  return context_bwd_ld(B, T, N, K, h, w, K, node_pos, ctx, dctx, dnode, dpre, dh, dw, db, ws, ws_elems, st);
 }
 
 }  // namespace gc

@@ -35,9 +35,27 @@ int embed_bwd(int B, int T, const EmbedTables& tb, const float* dx, const float*
 int context_fwd(int B, int T, int N, int K, const float* h, const float* w, const float* bias, const float* node_pos, float* pre,
                 float* ctx, float* node_feat, hipStream_t st);
 
+// The folded pair of the BERT model (bert_frontend.hip): the projection runs on the encoder states alone, and the two small tables
+// arrive folded through it, f2 [P][128] and f3 [R][128]: pre[b, t] + f2[pos_ids[b, t]] + f3[ner_ids[b, t]], in this association, is
+// what tanh sees.  An id outside its table adds nothing (callers validate their ids).
+struct ContextFold {
+  const int64_t* pos_ids;   // [B * T]
+  const int64_t* ner_ids;
+  const float* f2;
+  const float* f3;
+  int P, R;
+};
+// context_fwd with the weight read in place at leading dimension ldw >= K (its first K columns), and the fold rows where given
+int context_fwd_ld(int B, int T, int N, int K, const float* h, const float* w, long ldw, const float* bias, const float* node_pos, float* pre,
+                   float* ctx, float* node_feat, hipStream_t st, const ContextFold* fold = nullptr);
+
 long context_ws_elems(int K);
 // dpre [B * T][128] = (dctx + node_pos^T dnode_feat) (1 - ctx^2) (scratch the caller owns); dw = dpre^T h, dh = dpre W, db = column sums.
 int context_bwd(int B, int T, int N, int K, const float* h, const float* w, const float* node_pos, const float* ctx, const float* dctx,
                 const float* dnode, float* dpre, float* dh, float* dw, float* db, float* ws, long ws_elems, hipStream_t st);
+// ... with w and dw at leading dimension ldw >= K: the first K columns of a wider weight are read, and of its gradient written
+int context_bwd_ld(int B, int T, int N, int K, const float* h, const float* w, long ldw, const float* node_pos, const float* ctx,
+                   const float* dctx, const float* dnode, float* dpre, float* dh, float* dw, float* db, float* ws, long ws_elems,
+                   hipStream_t st);
 
 }  // namespace gc

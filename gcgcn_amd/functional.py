@@ -1703,6 +1703,117 @@ def token_context(h, weight, bias, node_pos):
     return TokenContextFn.apply(h, weight, bias, node_pos)
 
 
+# ---- the BERT graph model's glue either side of the tail (csrc/bert_frontend.hip, include/gcgcn_bert_frontend.h) -----------------
+class BertTokenContextFn(torch.autograd.Function):
+    """(states[B,T,Dw], coref_w[P,Dc], ner_w[R,Dn], weight[128,Dw+Dc+Dn], bias[128], document_pos, document_ner int64 [B,T],
+    node_pos[B,N,T]) -> (ctx[B,T,128], node_feat[B,N,128]) (gcbf_context_fwd / gcbf_context_bwd)."""
+
+    @staticmethod
+    def forward(ctx, states, coref_w, ner_w, weight, bias, document_pos, document_ner, node_pos, coref_pad, ner_pad):
+        B, T, Dw = states.shape
+        dims = (B, T, node_pos.shape[1], Dw, coref_w.shape[1], ner_w.shape[1], coref_w.shape[0], ner_w.shape[0])
+        dev, Hd = states.device, weight.shape[0]
+        fold = torch.empty(dims[6] + dims[7], Hd, device=dev)
+        pre, out = torch.empty(B, T, Hd, device=dev), torch.empty(B, T, Hd, device=dev)
+        node_feat = torch.empty(B, dims[2], Hd, device=dev)
+        call("gcbf_context_fwd", *dims, _p(states), _p(document_pos), _p(document_ner), _p(coref_w), _p(ner_w), _p(weight), _p(bias),
+             _p(node_pos), _p(fold), _p(pre), _p(out), _p(node_feat), _stream())
+        torch.autograd.graph.increment_version((out, node_feat))
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(states, coref_w, ner_w, weight, document_pos, document_ner, node_pos, out)
+            ctx.dims, ctx.pads = dims, (coref_pad, ner_pad)
+        return out, node_feat
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dctx, dnode):
+        states, coref_w, ner_w, weight, document_pos, document_ner, node_pos, out = ctx.saved_tensors
+        dctx, dnode = dctx.contiguous(), dnode.contiguous()
+        dev = states.device
+        dstates, dcoref, dner, dw = torch.empty_like(states), torch.empty_like(coref_w), torch.empty_like(ner_w), torch.empty_like(weight)
+        db = torch.empty(weight.shape[0], device=dev)
+        ws = _f32_buf(_bytes_or_raise("gcbf_context_ws_bytes", *ctx.dims), dev)
+        call("gcbf_context_bwd", *ctx.dims, _p(states), _p(document_pos), _p(document_ner), _p(coref_w), _p(ner_w), _p(weight), _p(node_pos),
+             _p(out), _p(dctx), _p(dnode), ctx.pads[0], ctx.pads[1], _p(dstates), _p(dw), _p(db), _p(dcoref), _p(dner), _p(ws),
+             ws.numel() * 4, _stream())
+        torch.autograd.graph.increment_version((dstates, dcoref, dner, dw, db))
+        return dstates, dcoref, dner, dw, db, None, None, None, None, None
+
+
+def bert_token_context(states, document_pos, document_ner, coref_w, ner_w, weight, bias, node_pos, coref_padding_idx=0, ner_padding_idx=0):
+    """The context pair of ``GraphCNN_multihead_bert_gate_cls`` (bert:278-283 and the pooling) without its concatenated tensor::
+
+        ctx[B,T,128] = tanh(F.linear(cat([states, coref_w[document_pos], ner_w[document_ner]], -1), weight, bias))
+        node_feat[B,N,128] = bmm(node_pos, ctx)
+
+    computed with ``weight = W1 | W2 | W3`` split by columns as ``states W1^T + bias + F2[document_pos] + F3[document_ner]``,
+    ``F2 = coref_w W2^T``, ``F3 = ner_w W3^T``: the large product runs at ``K = Dw`` with ``W1`` read in place, and no
+    ``[B,T,Dw+Dc+Dn]`` tensor exists in either direction.  ``states[B,T,Dw]``, ids int64 ``[B,T]``, ``coref_w[P,Dc]``,
+    ``ner_w[R,Dn]``, ``weight[128,Dw+Dc+Dn]``, ``bias[128]``, ``node_pos[B,N,T]``.
+
+    The five gradients (``states``, ``coref_w``, ``ner_w``, ``weight``, ``bias``) come back dense, fully written and bit-reproducible;
+    the row at a padding index (``None``: the table has none) of ``coref_w`` / ``ner_w`` is exactly zero, while ``weight``'s gradient
+    counts the padding tokens as torch's does.  Nothing is read on the host (the id range check apart, skipped under capture):
+    capturable.  ``node_pos`` gets no gradient.  A width other than 128 raises."""
+    states, weight, bias = _chk(states, "states", 3), _chk(weight, "weight", 2), _chk(bias, "bias", 1)
+    coref_w, ner_w, node_pos = _chk(coref_w, "coref_w", 2), _chk(ner_w, "ner_w", 2), _chk(node_pos.detach(), "node_pos", 3)
+    B, T, Dw = states.shape
+    ids = []
+    for nm, t in (("document_pos", document_pos), ("document_ner", document_ner)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or tuple(t.shape) != (B, T):
+            raise ValueError(f"{nm}: expected a GPU int64 tensor of shape [{B},{T}]")
+        ids.append(t.contiguous())
+    K = Dw + coref_w.shape[1] + ner_w.shape[1]
+    if weight.shape[0] != 128 or weight.shape[1] != K or bias.shape[0] != weight.shape[0]:
+        raise ValueError(f"bert_token_context: weight {tuple(weight.shape)} / bias {tuple(bias.shape)} do not project "
+                         f"{Dw} + {coref_w.shape[1]} + {ner_w.shape[1]} features onto 128")
+    if node_pos.shape[0] != B or node_pos.shape[2] != T:
+        raise ValueError(f"bert_token_context: node_pos {tuple(node_pos.shape)}, expected [{B}, N, {T}]")
+    _check_id_range([("document_pos", ids[0], 0, coref_w.shape[0] - 1), ("document_ner", ids[1], 0, ner_w.shape[0] - 1)])
+    pads = [-1 if p is None else int(p) for p in (coref_padding_idx, ner_padding_idx)]
+    return BertTokenContextFn.apply(states, coref_w, ner_w, weight, bias, *ids, node_pos, *pads)
+
+
+class PairLogitBiasFn(torch.autograd.Function):
+    """(logits[B,N,N,R], cls[B,R], n_valid int32 [B] or None) -> out[B,N,N,R] (gcbf_logit_bias_fwd / gcbf_logit_bias_bwd)."""
+
+    @staticmethod
+    def forward(ctx, logits, cls, n_valid):
+        B, N, _, R = logits.shape
+        out = torch.empty_like(logits)
+        call("gcbf_logit_bias_fwd", B, N, R, _p(logits), _p(cls), _p(n_valid), _p(out), _stream())
+        torch.autograd.graph.increment_version((out,))
+        ctx.n_valid = n_valid
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        dcls = None
+        if ctx.needs_input_grad[1]:
+            dout = dout.contiguous()
+            B, N, _, R = dout.shape
+            dcls = torch.empty(B, R, device=dout.device)
+            ws = _f32_buf(_bytes_or_raise("gcbf_logit_bias_ws_bytes", B, N, R), dout.device)
+            call("gcbf_logit_bias_bwd", B, N, R, _p(dout), _p(ctx.n_valid), _p(dcls), _p(ws), ws.numel() * 4, _stream())
+            torch.autograd.graph.increment_version((dcls,))
+        return dout, dcls, None                                  # the gradient of logits is the incoming one: no copy, no launch
+
+
+def pair_logit_bias(logits, cls_logits, n_valid=None):
+    """``out[b,i,j,:] = logits[b,i,j,:] + cls_logits[b,:]`` where ``i, j < n_valid[b]`` (everywhere without ``n_valid``), ``logits``
+    unchanged elsewhere: ``linear_cls`` of the [CLS] state added to every pair's logits (bert:345-346), in one launch instead of a
+    mask, a multiply and an add over ``[B,N,N,R]``.  Backward: the gradient of ``logits`` is the incoming gradient itself, and
+    ``dcls[b,:]`` is its sum over the live pairs in a fixed two-stage order (bit-reproducible, no atomics).  Capturable."""
+    logits, cls_logits = _chk(logits, "logits", 4), _chk(cls_logits, "cls_logits", 2)
+    B, N, N2, R = logits.shape
+    if N2 != N or tuple(cls_logits.shape) != (B, R):
+        raise ValueError(f"pair_logit_bias: logits {tuple(logits.shape)} / cls_logits {tuple(cls_logits.shape)}, expected [B,N,N,R] and [B,R]")
+    if B < 1 or N < 1 or R < 1:
+        raise ValueError(f"pair_logit_bias: empty logits {tuple(logits.shape)}")
+    return PairLogitBiasFn.apply(logits, cls_logits, _nv(n_valid, B, N, logits.device))
+
+
 # ---- the BERT encoder layer (csrc/bert.hip) --------------------------------------------------------------------------------------
 class ResLayerNormFn(torch.autograd.Function):
     """y = LayerNorm(dropout(x + bias) + res) over the last axis (eps = 1e-12, biased variance); bias, res, dropout optional."""

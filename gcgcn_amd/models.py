@@ -29,7 +29,7 @@ from torch import nn
 from torch.nn.utils.rnn import pack_padded_sequence, pad_packed_sequence
 
 from .bert import BertModel as OwnBertModel
-from .functional import lstm_layer, lstm_layer_bf16_definition, token_context, token_embed
+from .functional import bert_token_context, lstm_layer, lstm_layer_bf16_definition, pair_logit_bias, token_context, token_embed
 from .modules import GraphModelTail
 
 Tensor = torch.Tensor
@@ -248,7 +248,13 @@ class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
     ``config.bert_embeddings = "torch" | "fused"`` (needs ``bert_impl``; a ``ValueError`` without it) is that encoder's
     ``embeddings``: with ``"fused"`` and ``bert_impl = "hip"`` the stage in front of the layers -- three gathers, their sum,
     LayerNorm, dropout -- is one launch, with owner-computed, bit-reproducible table gradients (``functional.bert_embeddings``).
-    Independent of ``bert_matmul`` and ``bert_attention``.  Without ``bert_embeddings`` nothing changes."""
+    Independent of ``bert_matmul`` and ``bert_attention``.  Without ``bert_embeddings`` nothing changes.
+
+    ``config.bert_frontend = "cat" | "folded"`` (``"folded"`` needs ``config.frontend_impl = "hip"``; a ``ValueError`` without it) is
+    this model's own glue either side of the tail.  ``"folded"`` runs ``functional.bert_token_context`` -- the two small tables folded
+    through ``linear_re``, no ``[B,T,808]`` tensor in either direction, owner-computed bit-reproducible table gradients -- and adds
+    ``linear_cls`` of the [CLS] state with ``functional.pair_logit_bias`` (one launch; ``dcls`` in a fixed order).  Parameters and the
+    ``state_dict`` are the same either way.  ``"cat"``, or no ``bert_frontend``, changes nothing."""
 
     WORD_VEC_SIZE = 768
     _KEY_ORDER = ("bert", "ner_emb", "entity_embed", "get_weighted_adj_matrix", "get_adj_matrix", "graphcnn", "linear_re",
@@ -276,6 +282,11 @@ class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
                 raise ValueError(f"config.bert_embeddings must be 'torch' or 'fused', got {embeddings!r}")
             if impl is None:
                 raise ValueError("config.bert_embeddings selects the embeddings stage of this library's own encoder: set config.bert_impl too")
+        self.bert_frontend = getattr(config, "bert_frontend", "cat")
+        if self.bert_frontend not in ("cat", "folded"):
+            raise ValueError(f"config.bert_frontend must be 'cat' or 'folded', got {self.bert_frontend!r}")
+        if self.bert_frontend == "folded" and self.frontend_impl != "hip":
+            raise ValueError("config.bert_frontend='folded' selects kernels of the hip front end: set config.frontend_impl='hip' too")
         if bert is None and impl is not None:                                                # this library's own encoder (bert.py)
             from .bert import BertConfig, BertModel as OwnBert, load_pretrained_state_dict
             if impl not in ("torch", "hip"):
@@ -320,6 +331,14 @@ class GraphCNN_multihead_bert_gate_cls(_GraphRelationModel):
             mask = torch.arange(document.size(1), device=document.device) < t_valid.to(document.device)[:, None]
             doc, _ = self.bert(document, attention_mask=mask, output_all_encoded_layers=False)
         cls_feat = doc[:, 0, :]                                                              # bert:277
+        if self.bert_frontend == "folded":
+            ctx, node_feat = bert_token_context(doc, document_pos, document_ner, self.entity_embed.weight, self.ner_emb.weight,
+                                                self.linear_re.weight, self.linear_re.bias, node_pos if batched else node_pos.unsqueeze(0),
+                                                self.entity_embed.padding_idx, self.ner_emb.padding_idx)
+            logits = self._graph_forward(ctx, adj_matrix, sen_matrix, pos_matrix_h, pos_matrix_t, node_pos, node_type, node_relative_pos,
+                                         n_valid, batched, node_feat=node_feat if batched else node_feat[0], **caps)
+            cls = self.linear_cls(cls_feat)                                                  # bert:345
+            return pair_logit_bias(logits, cls, n_valid) if batched else pair_logit_bias(logits.unsqueeze(0), cls)[0]
         doc = torch.cat([doc, self.entity_embed(document_pos), self.ner_emb(document_ner)], dim=-1)
         node_feat = None
         if self.frontend_impl == "hip":
